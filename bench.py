@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the NVSM training hot path on MI355X (BASELINE.json metric: n-gram windows/sec, batch = 51 200).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run (one rank per GPU,
 rendezvous on 127.0.0.1, a free port), so both call forms work.
+
+A plain run measures the headline figure only: it sets up, runs W warm-up steps, times ONE region of exactly K steps with no
+events in it, writes what the steps computed if `--dump-outputs DIR` is given (dump_outputs), and prints a line with `metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload (PLAIN_KEYS). `--full` adds everything described
+below: the median of `--repeats` regions, event-timed kernels in them, the kernel breakdown and rooflines, rocprofv3 counter
+passes, the secondary legs and configurations, the other scaling figure, the collective model and the CPU baseline.
 
 One "step" = one pass of the hot path (compute_cost → compute_gradients → update, negatives sampled on
 device) over one synthetic batch that is already resident in HBM. Workload = BASELINE.json configs[1]:
@@ -735,12 +741,56 @@ def ms_stats(times, steps, leg=None, enqueue=None):
     return med, st
 
 
+# the line of a plain run (no --full): the headline figure and what it was measured on
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "dtype_detail", "engine", "data", "config", "timing", "final_cost")
+
+DUMP_TABLE_BYTES = 24 << 20      # --dump-outputs: an embedding table larger than this is written as a sample of its rows
+
+
+def dump_outputs(model, wl, cost, out_dir):
+    """--dump-outputs: what the timed steps computed, as the caller of the step reads it back — the loss of the last step
+    (cost.npy) and the four parameter tensors under their checkpoint names (Model.get_data(): word and document tables, projection
+    matrix, bias) — float32 .npy files in `out_dir`. A table above DUMP_TABLE_BYTES is written as a sample of its rows: the rows
+    RandomState(0) picks, sorted, the same in every run of a shape, so that two builds compare output for output (≈ 48 MB in all at
+    the metric's shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {"word_representations-representations": wl["word_dim"], "entity_representations-representations": wl["entity_dim"],
+            "word_entity_mapping-transform": wl["entity_dim"], "word_entity_mapping-bias": wl["entity_dim"]}
+    for name, flat in model.get_data().items():
+        a = flat.reshape(-1, cols[name])
+        if a.nbytes > DUMP_TABLE_BYTES:
+            k = DUMP_TABLE_BYTES // (a.shape[1] * a.itemsize)
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    np.save(os.path.join(out_dir, "cost.npy"), np.array([cost], dtype=np.float32))
+
+
+def emit(line):
+    """Prints a result line as the LAST line on stdout: what C code wrote to stdout before it (RCCL's version banner once a
+    communicator exists) sits in the C library's buffer, which a pipe would otherwise only see flushed at exit, behind the line."""
+    import ctypes
+    sys.stdout.flush()
+    try:
+        ctypes.CDLL(None).fflush(None)
+    except (OSError, AttributeError):
+        pass
+    print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median one is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each; the median one is reported "
+                    "(default: 1, so that a plain run times exactly --steps steps; 5 with --full)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: event-timed kernels in the timed "
+                    "regions, the kernel breakdown and rooflines, counter passes, the secondary legs and configurations, the other "
+                    "scaling figure, the collective model and the CPU baseline. Without it a run sets up, warms up, times --steps "
+                    "steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed (the loss "
+                    "and the parameter tensors, large tables as a fixed sample of rows: dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--config", default="nvsm", choices=sorted(PRESETS), help="nvsm = BASELINE configs[1] (the bench line)")
     ap.add_argument("--update-method", default=None, choices=["sgd", "adagrad", "sparse_adam", "dense_adam", "full_adam"])
     ap.add_argument("--batch", type=int, default=None, help="windows per step (default 51200): per GPU at N = 1 and for the weak "
@@ -781,6 +831,8 @@ def main():
                     "the steps behind it run back to back as in steady state")
     ap.add_argument("--read-cost-every", type=int, default=0, help="read the loss back every n steps (0 = never inside the timed region)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if (args.full or args.secondary_leg) else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))
@@ -835,11 +887,13 @@ def main():
     if args.secondary_leg:
         if world != 1:
             raise SystemExit("--secondary-leg is a single-GPU child mode")
-        print(json.dumps(secondary_leg(env, args, wl, method)), flush=True)
+        emit(secondary_leg(env, args, wl, method))
         return
     Bg = wl["batch"]                          # the metric's batch: per GPU at N = 1 / weak, global for the strong split
     w = wl["window"]
-    quick = args.no_extra_legs or args.sequential or bool(args.gate_us)
+    # a plain run measures the headline figure only: no events in its timed region, no pass or leg behind it (--full)
+    quick = not args.full or args.no_extra_legs or args.sequential or bool(args.gate_us)
+    profiling = args.full and not args.no_profile
     strong_ok = world > 1 and Bg % world == 0
     headline_strong = strong_ok and not args.weak_scaling
     # the leg behind `value` (roofline and kernel breakdown are taken on it) and, for N > 1, the other scaling figure
@@ -859,7 +913,7 @@ def main():
     # own launch). Events around every kernel group (~50 records per step) cost ≈5 % of the step, so the full per-kernel
     # breakdown comes from a second, untimed pass over the same batches (--profile-all puts it back into the timed regions).
     ROOFLINE_KERNEL, GATHER_KERNEL = "loss_fused", "gather_mean_words"
-    model.profile_enable(not args.no_profile)
+    model.profile_enable(profiling)
     # (only the roofline kernel carries events inside the timed regions: an event pair riding on a launch is not free — it costs
     #  the stream ~5 us per kernel, 1 % of this step with two kernels timed, 12 % of the batch-4096 LSE step: tools/ab_profile_cost.sh;
     #  the word gather's time for `roofline_gather` comes from the untimed pass below)
@@ -869,12 +923,14 @@ def main():
     times = main_leg.timed_repeats(args.steps, args.repeats, None, args.read_cost_every)
     main_enqueue = list(main_leg.enqueue_s)
     final_cost = model.get_cost()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, wl, final_cost, args.dump_outputs)
     prof_timed = model.profile()
     prof = prof_timed
     breakdown_steps = args.steps * len(times)
     prof_riding = {}
     RIDING = ("gemm_bwd_T", "gemm_bwd_T_reduce", GATHER_KERNEL)
-    if not args.no_profile and not args.profile_all:
+    if profiling and not args.profile_all:
         breakdown_steps = min(args.steps, 20)
         # kernels timed by events that ride on their own launch (no records around them), in a pass with no other records: the dT
         # product's execution time inside an otherwise undisturbed step. Its whole-CU workgroups and the documents pass become
@@ -895,10 +951,10 @@ def main():
         env.sync_all(model)
         prof = model.profile()
     model.profile_enable(False)
-    touched = main_leg.touched_rows() if rank == 0 and not args.no_profile else None
+    touched = main_leg.touched_rows() if rank == 0 and profiling else None
     roofline_update = None
     dt_alone = None
-    if world == 1 and not args.no_profile and not args.sequential and not args.gate_us:
+    if world == 1 and profiling and not args.sequential and not args.gate_us:
         UPD = "row_pass_entities"
         tin = None
         if prof_timed.get(UPD, (0, 0))[1] > 0:
@@ -961,7 +1017,7 @@ def main():
             main_leg.model.close()
             torch.cuda.empty_cache()
             # HBM counter bytes of the headline workload, measured in this run (two rocprofv3 passes of this script's bare form)
-            if not args.no_pmc and not args.no_profile:
+            if not args.no_pmc and profiling:
                 pmc_flags = ["--config", args.config, "--batch", str(B), "--update-method", method] + base_flags
                 counter = pmc_in_run(pmc_flags)
             base = (["--uniform-words"] if args.uniform_words else [])
@@ -1058,7 +1114,7 @@ def main():
                 leg.model.close()
                 del leg
 
-    if counter is None and world == 1:
+    if counter is None and world == 1 and args.full:
         counter = pmc_committed_step(sig_main)
     if rank == 0:
         ms_per_step, tstats = ms_stats(times, args.steps, enqueue=main_enqueue)
@@ -1295,13 +1351,15 @@ def main():
                                                                  "none of them hidden; tables rank-local (DESIGN.md 6)")
             except Exception as e:            # noqa: BLE001  (no librccl: the line says so instead of failing the bench)
                 out["config"]["collectives_dp"] = {"error": str(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             os.sched_setaffinity(0, env.cpu_mask)      # every CPU the process was given, not only the GPU's node
             out["cpu_baseline"] = cpu_baseline(args, wl, method)
             out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
         else:
             out["cpu_baseline"] = None
-        print(json.dumps(out), flush=True)
+        if not args.full:
+            out = {k: v for k, v in out.items() if k in PLAIN_KEYS or k == scaling}
+        emit(out)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

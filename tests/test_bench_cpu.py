@@ -62,3 +62,46 @@ def test_collective_model_is_the_stated_formula():
     t8 = bench.collective_model_us(8, 307200, 2.5)
     wire = 14 / 8 * 307200 / (bench.XGMI_LINK_GBS * bench.XGMI_RING_EFFICIENCY * 1e3)
     assert abs(t8 - (2.5 + 14 * bench.XGMI_HOP_US + wire)) < 1e-9 and 25 < t8 < 40
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs at the metric's shape: the tables are larger than the cap, so a fixed sample of their rows is written — the same
+    rows from run to run — and all files together stay within 64 MB."""
+    import numpy as np
+    wl = dict(num_words=50000, num_entities=100000, word_dim=300, entity_dim=256)
+    shapes = {"word_representations-representations": (50000, 300), "entity_representations-representations": (100000, 256),
+              "word_entity_mapping-transform": (300, 256), "word_entity_mapping-bias": (1, 256)}
+
+    class FakeModel:
+        def get_data(self):
+            # row i of every tensor holds i, so that the rows a file holds can be read back from it
+            return {n: np.repeat(np.arange(r, dtype=np.float32), c) for n, (r, c) in shapes.items()}
+
+    rows = []
+    for i in range(2):
+        out = str(tmp_path / ("run%d" % i))
+        bench.dump_outputs(FakeModel(), wl, 12.5, out)
+        files = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+        assert set(files) == set(shapes) | {"cost"} and files["cost"].tolist() == [12.5]
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64 << 20
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert files["word_entity_mapping-transform"].shape == (300, 256) and files["word_entity_mapping-bias"].shape == (1, 256)
+        ids = {}
+        for n in ("word_representations-representations", "entity_representations-representations"):
+            a = files[n]
+            assert a.shape[1] == shapes[n][1] and 0 < a.shape[0] < shapes[n][0] and a.nbytes <= bench.DUMP_TABLE_BYTES
+            assert (a == a[:, :1]).all() and (np.diff(a[:, 0]) > 0).all()          # whole rows, sorted, no repeats
+            ids[n] = a[:, 0]
+        rows.append(ids)
+    for n in rows[0]:
+        assert np.array_equal(rows[0][n], rows[1][n])
+
+
+def test_result_line_is_printed_after_c_level_output(tmp_path):
+    """emit(): what C code wrote to a piped stdout before the line (RCCL's version banner) comes out before it, not at exit."""
+    import subprocess
+    code = ("import ctypes, sys; sys.path.insert(0, %r); import bench; "
+            "ctypes.CDLL(None).printf(b'banner from C\\n'); bench.emit({'value': 1})" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.splitlines() == ["banner from C", '{"value": 1}']

@@ -41,7 +41,7 @@ def roof_ok(roof):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-steps", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--cpu-steps", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -134,7 +134,7 @@ def test_bench_single_gpu_line():
 def test_bench_two_ranks_control_flow():
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--test-shared-gpu", "--exact-tables-leg"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -152,3 +152,32 @@ def test_bench_two_ranks_control_flow():
     assert "comm_ranks" in d["config"] and "gloo" in d["config"]["collectives"] and d["config"]["collectives_per_step"] == 3
     ps = d["per_shard_batch_norm"]
     assert ps["collectives_per_step"] == 1 and ps["batch_per_rank"] == 25600 and ps["value"] > 0 and ps["scaling"] == "strong"
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full): ONE timed region of exactly --steps steps, the headline fields only, the result line last on stdout;
+    --dump-outputs writes what the steps computed (float32 .npy), the same arrays from two runs with the same arguments."""
+    import numpy as np
+    import bench
+    runs = []
+    for i in range(2):
+        out = str(tmp_path / ("run%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "4096",
+                            "--num-words", "5000", "--num-entities", "4000", "--dump-outputs", out],
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert r.stdout.strip().splitlines()[-1].startswith("{")
+        d = _last_json(r.stdout)
+        assert set(d) == set(bench.PLAIN_KEYS)
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["timing"]["repeats"] == 1 and d["timing"]["ms_per_step_all"] == [d["ms_per_step"]]
+        assert d["higher_is_better"] is True and d["unit"] == "windows/s" and d["dtype"] == "f32"
+        assert abs(d["value"] - 4096 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+        runs.append({f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))})
+    a, b = runs
+    assert set(a) == {"cost", "word_representations-representations", "entity_representations-representations",
+                      "word_entity_mapping-transform", "word_entity_mapping-bias"}
+    assert a["word_representations-representations"].shape == (5000, 300) and a["entity_representations-representations"].shape == (4000, 256)
+    assert abs(float(a["cost"][0]) - d["final_cost"]) <= 1e-6 * abs(d["final_cost"])
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k

@@ -43,13 +43,13 @@ def test_bench_under_an_external_launcher_does_not_relaunch():
 def test_bench_two_ranks_on_one_gpu_reports_weak_and_strong():
     """The whole N = 2 control flow of bench.py on the 1-GPU box (both ranks on device 0, all-reduces through the gloo
     callback transport): self-launch, both legs, one JSON line. Not a measurement."""
-    out = _run(["--gpus", "2", "--test-shared-gpu", "--steps", "3", "--warmup", "1", "--batch", "2048", "--num-words", "5000",
+    out = _run(["--full", "--gpus", "2", "--test-shared-gpu", "--steps", "3", "--warmup", "1", "--batch", "2048", "--num-words", "5000",
                 "--num-entities", "4000", "--no-cpu-baseline"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 0
     assert out["weak"]["batch_per_rank"] == 2048 and out["weak"]["global_batch"] == 4096
     assert out["strong"]["batch_per_rank"] == 1024 and out["strong"]["global_batch"] == 2048 and out["strong"]["value"] == out["value"]
     assert out["strong"]["scaling"] == "strong" and out["weak"]["scaling"] == "weak"
-    weak = _run(["--gpus", "2", "--test-shared-gpu", "--steps", "3", "--warmup", "1", "--batch", "2048", "--num-words", "5000",
+    weak = _run(["--full", "--gpus", "2", "--test-shared-gpu", "--steps", "3", "--warmup", "1", "--batch", "2048", "--num-words", "5000",
                  "--num-entities", "4000", "--no-cpu-baseline", "--weak-scaling", "--repeats", "1"])
     assert weak["scaling"] == "weak" and weak["config"]["global_batch"] == 4096 and weak["strong"]["batch_per_rank"] == 1024
     assert out["roofline"]["traffic"] is None            # no PMC profile of THIS workload: no traffic claim
@@ -58,7 +58,7 @@ def test_bench_two_ranks_on_one_gpu_reports_weak_and_strong():
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_has_the_contract_fields():
-    out = _run(["--steps", "3", "--warmup", "1", "--batch", "4096", "--num-words", "5000", "--num-entities", "4000", "--cpu-steps", "1"])
+    out = _run(["--full", "--steps", "3", "--warmup", "1", "--batch", "4096", "--num-words", "5000", "--num-entities", "4000", "--cpu-steps", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "roofline_gather", "cpu_baseline", "value_readback_every_step", "value_host_batches"):
         assert k in out, k

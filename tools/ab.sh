@@ -7,7 +7,7 @@ export CUNVSM_AMD_LIB=${CUNVSM_AMD_LIB:-$(cd "$(dirname "$0")/.." && pwd)/cunvsm
 cd "$(dirname "$0")/.."
 for round in $(seq 1 ${ROUNDS:-3}); do
   for cfg in "$@"; do
-    r=$(env $cfg python bench.py --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --no-extra-legs ${PROFILE_FLAG---no-profile} $BENCH_FLAGS 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], 'ms  frac', (d.get('roofline') or {}).get('frac'), ' M/s', round(d['value']/1e6,2))")
+    r=$(env $cfg python bench.py --full --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline --no-extra-legs ${PROFILE_FLAG---no-profile} $BENCH_FLAGS 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], 'ms  frac', (d.get('roofline') or {}).get('frac'), ' M/s', round(d['value']/1e6,2))")
     echo "round $round  [$cfg]  $r"
   done
 done

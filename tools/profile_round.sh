@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp
-BENCH="python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs $*"
+BENCH="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra-legs $*"
 timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench -- $BENCH > $OUT/bench_stats.json 2> $OUT/bench_stats.err
 timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch -o bench -- $BENCH --steps 6 > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
 timeout 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/write -o bench -- $BENCH --steps 6 > $OUT/bench_write.json 2> $OUT/bench_write.err
