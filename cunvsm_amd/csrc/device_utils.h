@@ -93,8 +93,11 @@ __device__ __forceinline__ double ld_agent_f64(const double* p) {
     return __longlong_as_double(static_cast<long long>(
         __hip_atomic_load(reinterpret_cast<unsigned long long*>(const_cast<double*>(p)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
 }
+__device__ __forceinline__ void st_agent1(double* p, double x) { st_agent_f64(p, x); }
+__device__ __forceinline__ double ld_agent1(const double* p) { return ld_agent_f64(p); }
 
-// Ordered grid-wide sum: `total` workgroups each contribute a vector of n floats (val(i)); out(i, Σ) receives the sums.
+// Ordered grid-wide sum: `total` workgroups each contribute a vector of n values of type P (float or double: val(i)); out(i, Σ)
+// receives the sums.
 // Replaces one fp64 atomicAdd per value and workgroup (column statistics of the batch-norm / bias gradient, the loss word):
 // atomics add in arrival order, so the last bits differed from run to run, and a thousand workgroups adding to the same
 // 513 addresses serialise in the L2's atomic units (a quarter of the loss kernel's time at batch 6 400). Here a workgroup
@@ -119,8 +122,8 @@ __device__ __forceinline__ double ld_agent_f64(const double* p) {
 #define NVSM_GRID_SUM_IN_FLIGHT 16
 #endif
 constexpr int kGridSumInFlight = NVSM_GRID_SUM_IN_FLIGHT;
-template <int THREADS, class Val, class Out>
-__device__ __forceinline__ void grid_sum_ordered(float* part, double* part2, int* arrive, int fan, int n, int me, int total,
+template <int THREADS, class P, class Val, class Out>
+__device__ __forceinline__ void grid_sum_ordered(P* part, double* part2, int* arrive, int fan, int n, int me, int total,
                                                  Val val, Out out, int* flag) {
     const int tid = threadIdx.x;
     const int T = THREADS > 0 ? THREADS : static_cast<int>(blockDim.x);      // (THREADS = 0: the block size is a run-time value)
@@ -143,11 +146,11 @@ __device__ __forceinline__ void grid_sum_ordered(float* part, double* part2, int
     }
     __syncthreads();
     if (!*flag) return;
-    const float* gp = part + static_cast<size_t>(grp) * fan * n;
+    const P* gp = part + static_cast<size_t>(grp) * fan * n;
     for (int i = tid; i < n; i += T) {
         double s = 0.0;
         for (int j0 = 0; j0 < members; j0 += kGridSumInFlight) {        // members in flight, added in member order
-            float v[kGridSumInFlight];
+            P v[kGridSumInFlight];
 #pragma unroll
             for (int u = 0; u < kGridSumInFlight; ++u) v[u] = ld_agent1(gp + static_cast<size_t>(min(j0 + u, members - 1)) * n + i);
 #pragma unroll

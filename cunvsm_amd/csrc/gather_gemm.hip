@@ -358,11 +358,15 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(GemmArgs g) {
     // ---- epilogue: C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----
     // Interior tiles store unguarded: a per-row bounds branch would put an s_waitcnt vmcnt(0) (stores count in
     // vmcnt on CDNA4) between every pair of the 64 stores of a lane.
-    // With colstats the per-column Σ and Σ² of the stored values ride along: per-lane fp32 sums over the lane's 32
-    // rows, the two 32-lane halves folded by a cross-lane read, the two row-waves folded through LDS, then one fp64
-    // atomic per column per block (replaces the separate column-statistics pass over the GEMM output).
+    // With colstats the per-column Σ and Σ² of the stored values ride along, twice: plain fp32 sums over the lane's 32 rows,
+    // the two 32-lane halves folded by a cross-lane read, the two row-waves folded through LDS; and fp32 sums of the differences
+    // from a pivot (the lane's first value of the column), taken to fp64 in the lane and folded the same way. The tile hands the
+    // plain ones to the ordered sum over the m tiles where its values sit within four standard deviations of zero — as accurate
+    // there, and the bits the product formed before the pivot — and the pivoted ones elsewhere, where Σx² − (Σx)²/n from plain
+    // fp32 sums would lose about eps · (mean / std)² of the variance.
     const bool interior = (m0 + BM <= g.M) && (n0 + BN <= g.N);
-    float cs[2] = {0.f, 0.f}, cs2[2] = {0.f, 0.f};
+    float cs[2] = {0.f, 0.f}, cs2[2] = {0.f, 0.f}, ds[2] = {0.f, 0.f}, ds2[2] = {0.f, 0.f}, piv[2] = {0.f, 0.f};
+    int cnt[2] = {0, 0};
     if (interior) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -374,7 +378,11 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(GemmArgs g) {
                     const float v = g.alpha * acc[i][j][r] + bias[j];
                     cp[static_cast<size_t>((r & 3) + 8 * (r >> 2)) * g.ldc] = v;
                     cs[j] += v; cs2[j] += v * v;
+                    if (i == 0 && r == 0) piv[j] = v;
+                    const float d = v - piv[j];
+                    ds[j] += d; ds2[j] += d * d;
                 }
+                cnt[j] += 16;
             }
     } else {
 #pragma unroll
@@ -390,25 +398,45 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(GemmArgs g) {
                         const float v = g.alpha * acc[i][j][r] + bias[j];
                         C[static_cast<size_t>(row) * g.ldc + col] = v;
                         cs[j] += v; cs2[j] += v * v;
+                        if (i == 0 && r == 0) piv[j] = v;             // (the lane's smallest row: if it is outside, all are)
+                        const float d = v - piv[j];
+                        ds[j] += d; ds2[j] += d * d; ++cnt[j];
                     }
                 }
             }
     }
     if (g.colstats) {
-        float* red = lds;                 // [2 (Σ, Σ²)][2 (wr)][BN]; the operand tiles are dead (loop ended on a barrier)
+        // [2 (Σ, Σ²)][2 (wr)][BN] pivoted (fp64), then the same plain (fp32); the operand tiles are dead (loop ended on a barrier)
+        double* red = reinterpret_cast<double*>(lds);
+        float* red_plain = reinterpret_cast<float*>(red + 4 * BN);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             cs[j] += __shfl_xor(cs[j], 32);
             cs2[j] += __shfl_xor(cs2[j], 32);
+            // the lane's Σx = n p + Σd, Σx² = n p² + 2 p Σd + Σd², in fp64
+            const double p = piv[j], n = cnt[j], d1 = ds[j];
+            double s1 = n * p + d1, s2 = (n * p) * p + 2.0 * p * d1 + static_cast<double>(ds2[j]);
+            s1 += __shfl_xor(s1, 32);
+            s2 += __shfl_xor(s2, 32);
             if (lk == 0) {
-                red[(0 * 2 + wr) * BN + wc * 64 + j * 32 + l31] = cs[j];
-                red[(1 * 2 + wr) * BN + wc * 64 + j * 32 + l31] = cs2[j];
+                red[(0 * 2 + wr) * BN + wc * 64 + j * 32 + l31] = s1;
+                red[(1 * 2 + wr) * BN + wc * 64 + j * 32 + l31] = s2;
+                red_plain[(0 * 2 + wr) * BN + wc * 64 + j * 32 + l31] = cs[j];
+                red_plain[(1 * 2 + wr) * BN + wc * 64 + j * 32 + l31] = cs2[j];
             }
         }
         __syncthreads();
         // ordered sum over the m tiles of this n tile (device_utils.h grid_sum_ordered): the same bits every run
         const GridSumWs& ws = g.sums;
-        auto val = [&](int i) -> float { return i < BN ? red[i] + red[BN + i] : red[2 * BN + (i - BN)] + red[3 * BN + (i - BN)]; };
+        const double rows_tile = static_cast<double>(min(BM, g.M - m0));
+        auto val = [&](int i) -> double {
+            const int n = i < BN ? i : i - BN;
+            const double s1 = red[n] + red[BN + n], s2 = red[2 * BN + n] + red[3 * BN + n];
+            const double m = s1 / rows_tile, var = s2 / rows_tile - m * m;
+            if (m * m <= 16.0 * var) return static_cast<double>(i < BN ? red_plain[i] + red_plain[BN + i]
+                                                                       : red_plain[2 * BN + (i - BN)] + red_plain[3 * BN + (i - BN)]);
+            return i < BN ? s1 : s2;
+        };
         double* cs = g.colstats;
         const int N = g.N;
         auto out = [&](int i, double v) {
@@ -418,7 +446,7 @@ __global__ __launch_bounds__(256) void gemm_f32_mfma_kernel(GemmArgs g) {
         grid_sum_ordered<256>(ws.part + static_cast<size_t>(nt) * ws.contrib_cap * ws.width_cap,
                               ws.part2 + static_cast<size_t>(nt) * ws.groups_cap * ws.width_cap,
                               ws.arrive + nt * (ws.groups_cap + 1), ws.fan, 2 * BN, mt, g.mtiles, val, out,
-                              reinterpret_cast<int*>(red + 4 * BN));
+                              reinterpret_cast<int*>(red_plain + 4 * BN));
     }
 }
 

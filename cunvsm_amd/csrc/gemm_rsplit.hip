@@ -363,18 +363,36 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_rsplit_kernel(RsArgs g, typen
         }
     }
     if (g.colstats) {
+        const int nrow = min(SM, g.M - m0);              // (rows >= M: not summed)
         __syncthreads();
         for (int c = tid; c < NP; c += T) {
-            float s1 = 0.f, s2 = 0.f;
+            // Plain sums and sums of the differences from the column's value in the tile's first row (the pivot). Where the
+            // tile's values sit within four standard deviations of zero the plain ones are as accurate — and the bits the product
+            // formed before the pivot — and the tile keeps them (pivot 0); elsewhere Σx² − (Σx)²/n from plain fp32 sums would lose
+            // about eps · (mean / std)² of the variance, and the differences keep it at eps.
+            const float piv = tile[c];
+            float s1 = 0.f, s2 = 0.f, d1 = 0.f, d2 = 0.f;
 #pragma unroll 8
-            for (int r = 0; r < SM; ++r) { const float v = tile[r * TP + c]; s1 += v; s2 += v * v; }      // (rows >= M hold zeros)
-            red[c] = s1; red[NP + c] = s2;
+            for (int r = 0; r < SM; ++r) {
+                const float v = tile[r * TP + c], d = r < nrow ? v - piv : 0.f;      // (rows >= M hold zeros)
+                s1 += v; s2 += v * v; d1 += d; d2 += d * d;
+            }
+            const double n = nrow, m = piv + static_cast<double>(d1) / n;
+            const double var = (static_cast<double>(d2) - static_cast<double>(d1) * (static_cast<double>(d1) / n)) / n;
+            const bool plain = m * m <= 16.0 * var;
+            red[c] = plain ? s1 : d1; red[NP + c] = plain ? s2 : d2;
+            tile[c] = plain ? 0.f : piv;                                        // the pivot the tile's sums are taken from
         }
         __syncthreads();
         const int N = g.N;
         double* out = g.colstats;
         grid_sum_ordered<T>(g.sums.part, g.sums.part2, g.sums.arrive, g.sums.fan, 2 * N, static_cast<int>(blockIdx.x),
-                            static_cast<int>(gridDim.x), [&](int i) -> float { return i < N ? red[i] : red[NP + (i - N)]; },
+                            static_cast<int>(gridDim.x), [&](int i) -> double {
+                                // the tile's Σx = n p + Σd, Σx² = n p² + 2 p Σd + Σd², in fp64 (p = 0: the plain sums, exactly)
+                                const int c = i < N ? i : i - N;
+                                const double piv = tile[c], n = nrow, d1 = red[c];
+                                return i < N ? n * piv + d1 : (n * piv) * piv + 2.0 * piv * d1 + static_cast<double>(red[NP + c]);
+                            },
                             [&](int i, double v) { out[i] = v; }, flag);
     }
 }

@@ -60,8 +60,8 @@ __device__ __forceinline__ int split_slot(int r, int q) { return (q + 2 * ((r >>
 constexpr int kSplitWaves = 8;                                  // two per SIMD: 256 registers each, no AGPR shuffling
 constexpr int kSplitMaxWaves = kSplitWaves;
 // RBP = 16-row blocks per workgroup and pass: plane = 16 RBP rows, an image = three planes, two images
-constexpr size_t split_lds_bytes(int rbp) {      // two images | column sums [2][np <= 320] | row sums of squares [waves][16 rbp] | batch-norm constants
-    return static_cast<size_t>(2) * 3 * rbp * 16 * kSplitPitch + 2 * 320 * 4 + static_cast<size_t>(kSplitWaves) * rbp * 16 * 4 + 4 * 320 * 4;      // | PRE constants [4][K <= 320]
+constexpr size_t split_lds_bytes(int rbp) {      // two images | column sums [2][np <= 320] fp64 + fp32 | row sums of squares [waves][16 rbp] | batch-norm constants
+    return static_cast<size_t>(2) * 3 * rbp * 16 * kSplitPitch + 2 * 320 * 12 + static_cast<size_t>(kSplitWaves) * rbp * 16 * 4 + 4 * 320 * 4;      // | PRE constants [4][K <= 320]
 }
 constexpr int kSplitMaxDevices = 64;
 
@@ -176,13 +176,15 @@ __device__ __forceinline__ void split_body(const SplitArgs& g) {
     const unsigned a_last = static_cast<unsigned>((static_cast<size_t>(g.M - 1) * g.lda + g.K) * 4 - 16);      // last float4 of A
 
     SPLIT_STAMP(0);
-    // LDS: two images of a tile of A (three planes each) | column sums [2][np <= 320] | row sums of squares [WAVES][kRows]
-    float* st = reinterpret_cast<float*>(split_lds + 2 * kStage);
-    float* rs_lds = st + 2 * 320;
+    // LDS: two images of a tile of A (three planes each) | column sums [2][np <= 320]: pivoted (fp64), plain (fp32) | row sums of
+    // squares [WAVES][kRows]
+    double* st = reinterpret_cast<double*>(split_lds + 2 * kStage);
+    float* st_plain = reinterpret_cast<float*>(st + 2 * 320);
+    float* rs_lds = st_plain + 2 * 320;
     float* consts = rs_lds + WAVES * kRows;                   // PRE: [4][K <= 320] μ, invσ, dβ, dγ
     int* sum_flag = reinterpret_cast<int*>(split_lds);
     if (EPI & kSplitEpiStats) {
-        for (int k = tid; k < 2 * g.np; k += T) st[k] = 0.f;       // (the barriers of the K loop order this before the first add)
+        for (int k = tid; k < 2 * g.np; k += T) { st[k] = 0.0; st_plain[k] = 0.f; }       // (the barriers of the K loop order this before the first add)
     }
 
     if (PRE) {
@@ -388,7 +390,8 @@ __device__ __forceinline__ void split_body(const SplitArgs& g) {
         if (ps == 0) SPLIT_STAMP(2);
         if (ps == npass - 1) SPLIT_STAMP(3);
         // ---- epilogue: acc[rb][c][r] = C[row0 + 16 rb + i][16 (cb0 + c) + 4 q + r] ----
-        float cs1[CBW][4], cs2[CBW][4];                             // column sums of this lane's values of this pass
+        // column sums of this lane's values of this pass, plain (fp32, as before the pivoted ones below)
+        float cs1[CBW][4], cs2[CBW][4];
 #pragma unroll
         for (int c = 0; c < CBW; ++c)
 #pragma unroll
@@ -443,8 +446,50 @@ __device__ __forceinline__ void split_body(const SplitArgs& g) {
                     const float s1 = split_row16_sum(cs1[c][r]);
                     const float s2 = split_row16_sum(cs2[c][r]);
                     if (i == 15 && c < ncb) {
-                        st[16 * (cb0 + c) + 4 * q + r] += s1;
-                        st[g.np + 16 * (cb0 + c) + 4 * q + r] += s2;
+                        st_plain[16 * (cb0 + c) + 4 * q + r] += s1;
+                        st_plain[g.np + 16 * (cb0 + c) + 4 * q + r] += s2;
+                    }
+                }
+            }
+            // The same sums as differences from a pivot: the column's value in the pass's first row (lane i = 0 of the lane group),
+            // the same for all sixteen lanes whose sums split_row16_sum adds in fp32; the pass's Σx = n p + Σd,
+            // Σx² = n p² + 2 p Σd + Σd² go to LDS in fp64. (A second walk over the accumulators rather than four sums in one:
+            // the registers of the product's 26 row blocks leave no room for them.)
+            float piv[CBW][4];
+#pragma unroll
+            for (int c = 0; c < CBW; ++c)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { cs1[c][r] = 0.f; cs2[c][r] = 0.f; piv[c][r] = 0.f; }
+#pragma unroll
+            for (int rb = 0; rb < RBP; ++rb) {
+                if (rb < nbb) {
+                    const bool row_ok = row0 + 16 * rb + i < g.M;
+#pragma unroll
+                    for (int c = 0; c < CBW; ++c) {
+                        if (c < ncb) {
+                            const bool ok = row_ok && 16 * (cb0 + c) + 4 * q < g.N;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float v = g.alpha * acc[rb][c][r];              // (kSplitEpiStats comes without the bias)
+                                if (rb == 0) piv[c][r] = __shfl(v, lane & 48);       // (row row0: always inside the matrix)
+                                const float x = ok ? v - piv[c][r] : 0.f;
+                                cs1[c][r] += x;
+                                cs2[c][r] += x * x;
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CBW; ++c) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float s1 = split_row16_sum(cs1[c][r]);
+                    const float s2 = split_row16_sum(cs2[c][r]);
+                    if (i == 15 && c < ncb) {
+                        const double p = piv[c][r], n = nrows, d1 = s1;
+                        st[16 * (cb0 + c) + 4 * q + r] += n * p + d1;
+                        st[g.np + 16 * (cb0 + c) + 4 * q + r] += (n * p) * p + 2.0 * p * d1 + static_cast<double>(s2);
                     }
                 }
             }
@@ -466,7 +511,15 @@ __device__ __forceinline__ void split_body(const SplitArgs& g) {
         const int np = g.np;
         __syncthreads();
         const GridSumWs& ws = g.sums;
-        auto val = [&](int k) -> float { return st[k]; };
+        // Per column, the workgroup's plain sums where its values sit within four standard deviations of zero — as accurate as
+        // the pivoted ones there, and the bits the products formed before the pivot — and the pivoted sums elsewhere, where the
+        // plain ones would lose about eps · (mean / std)² of the variance in Σx² − (Σx)²/n (the pivoted totals decide).
+        const double rows_wg = static_cast<double>(min(g.M - rb_begin * 16, nb * 16));
+        auto val = [&](int k) -> double {
+            const int n = k < np ? k : k - np;
+            const double m = st[n] / rows_wg, var = st[np + n] / rows_wg - m * m;
+            return m * m <= 16.0 * var ? static_cast<double>(st_plain[k]) : st[k];
+        };
         double* cs = g.colstats;
         const int N = g.N;
         auto out = [&](int k, double v) {

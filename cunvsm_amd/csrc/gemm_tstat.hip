@@ -137,7 +137,7 @@ __device__ __forceinline__ void tstat_mma_range(const float4* __restrict__ bp, c
 constexpr int kEpiStats = 1, kEpiRowsq = 2, kEpiBias = 4;
 template <int KG, int NTC, int NH, int EPI>
 __device__ __forceinline__ void tstat_block(const TstatArgs& g, const float4* __restrict__ Bs, int rb, int j0, int tile0,
-                                            float4 (&a)[KG], int rb_next, int li, int q, float* __restrict__ stat_slot) {
+                                            float4 (&a)[KG], int rb_next, int li, int q, float* __restrict__ stat_slot, int n_before) {
     constexpr int H = (KG + 1) / 2;
     f32x4 acc[NTC];
 #pragma unroll
@@ -175,18 +175,29 @@ __device__ __forceinline__ void tstat_block(const TstatArgs& g, const float4* __
             *((q == 0 && row_ok) ? g.rowsq + static_cast<size_t>(tile) * g.M + row : g.dump) = rsq * g.rowsq_scale;
         }
         if (EPI & kEpiStats) {
-            // column sums over the block's 16 rows (= the 16 lanes of a DPP row), added to this wave's private slot
+            // The block's 16 rows (= the 16 lanes of a DPP row) summed as differences from the column's value in its first row,
+            // then merged into this wave's private slot, which holds the mean and the sum of squared deviations of the n_before
+            // rows it has seen (Chan, Golub & LeVeque). Sums of x and x² themselves lose about eps · (mean / std)² of the
+            // variance in Σx² − (Σx)²/n; here the slot's fp32 mean is off by a few ulp at most, which moves the variance by
+            // their square. The slot is this wave's own, so the result is the same every run.
+            const float nb = static_cast<float>(min(16, g.M - rb * 16));
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float x = ok ? v[r] : 0.f;
+                const float piv = __shfl(v[r], 16 * q);                 // (row 16 rb: inside the matrix)
+                const float x = ok ? v[r] - piv : 0.f;
                 const float s1 = row16_sum_to_last(x);
                 const float s2 = row16_sum_to_last(x * x);
                 if (li == 15) {
-                    // ds_add_f32 without return: no wait for the LDS round trip; the slot is this wave's own and a wave's
-                    // LDS operations execute in order, so the sums are the same every run
                     float* sp = stat_slot + 16 * (j0 + j) + 4 * q + r;
-                    unsafeAtomicAdd(sp, s1);
-                    unsafeAtomicAdd(sp + NH, s2);
+                    const float d1 = s1 / nb, mb = piv + d1, m2b = s2 - s1 * d1;
+                    if (n_before == 0) {
+                        sp[0] = mb;
+                        sp[NH] = m2b;
+                    } else {
+                        const float na = static_cast<float>(n_before), n = na + nb, delta = mb - sp[0];
+                        sp[0] += delta * (nb / n);
+                        sp[NH] += m2b + delta * delta * (na * (nb / n));
+                    }
                 }
             }
         }
@@ -272,16 +283,33 @@ __global__ __launch_bounds__(kTstatThreads) void gemm_tstat_kernel(TstatArgs g) 
         for (int i = 0; i < 6; ++i) __builtin_amdgcn_s_sleep(32);
     }
     // one loop per block shape (each with a fixed number of loads and stores per iteration, see tstat_block)
+    // rows of block rb; rows a wave's slot holds for tile tt before its single-tile task t (EPI & kEpiStats: the slot's count)
+    auto block_rows = [&](int rb) { return min(16, g.M - rb * 16); };
+    auto rows_before = [&](int ww, int t, int tt) {
+        const int ub = (units * ww) / kTstatWaves;
+        int n = 0;
+        for (int f = 0; f < full; ++f) n += block_rows(rb_begin + ww + kTstatWaves * f);
+        for (int u = ub; u < ub + (t - full); ++u)
+            if (u % nt == tt) n += block_rows(rb_begin + kTstatWaves * full + u / nt);
+        return n;
+    };
+    int n_full = 0;
     if (!MIXED || nt == NT) {
-        for (int t = 0; t < full; ++t)
-            tstat_block<KG, NT, NH, EPI>(g, Bs, task_rb(t), 0, tile0, a, task_rb(t + 1 < total ? t + 1 : t), li, q, my_stats);
+        for (int t = 0; t < full; ++t) {
+            tstat_block<KG, NT, NH, EPI>(g, Bs, task_rb(t), 0, tile0, a, task_rb(t + 1 < total ? t + 1 : t), li, q, my_stats, n_full);
+            n_full += block_rows(task_rb(t));
+        }
     } else {
-        for (int t = 0; t < full; ++t)
-            tstat_block<KG, NT - 1, NH, EPI>(g, Bs, task_rb(t), 0, tile0, a, task_rb(t + 1 < total ? t + 1 : t), li, q, my_stats);
+        for (int t = 0; t < full; ++t) {
+            tstat_block<KG, NT - 1, NH, EPI>(g, Bs, task_rb(t), 0, tile0, a, task_rb(t + 1 < total ? t + 1 : t), li, q, my_stats, n_full);
+            n_full += block_rows(task_rb(t));
+        }
     }
-    for (int t = full; t < total; ++t)
-        tstat_block<KG, 1, NH, EPI>(g, Bs, task_rb(t), (u_begin + (t - full)) % nt, tile0, a, task_rb(t + 1 < total ? t + 1 : t),
-                                    li, q, my_stats);
+    for (int t = full; t < total; ++t) {
+        const int tt = (u_begin + (t - full)) % nt;
+        tstat_block<KG, 1, NH, EPI>(g, Bs, task_rb(t), tt, tile0, a, task_rb(t + 1 < total ? t + 1 : t), li, q, my_stats,
+                                    (EPI & kEpiStats) ? rows_before(w, t, tt) : 0);
+    }
 
     if (EPI & kEpiStats) {
         __syncthreads();
@@ -289,10 +317,15 @@ __global__ __launch_bounds__(kTstatThreads) void gemm_tstat_kernel(TstatArgs g) 
         // bits every run, where one fp64 atomic per column and workgroup added in arrival order
         int* sum_flag = reinterpret_cast<int*>(tstat_lds);      // (the image of B is dead behind the barrier; LDS is full)
         const GridSumWs& ws = g.sums;
-        auto val = [&](int i) -> float {
-            float s = 0.f;
-#pragma unroll
-            for (int ww = 0; ww < kTstatWaves; ++ww) s += stats[ww * 2 * NH + i];
+        // the wave slots' (mean, M2) as Σx = n·mean, Σx² = M2 + n·mean², in fp64
+        auto val = [&](int i) -> double {
+            const int c = i < NH ? i : i - NH, tt = c / 16;
+            double s = 0.0;
+            for (int ww = 0; ww < kTstatWaves; ++ww) {
+                const int tasks_w = full + ((units * (ww + 1)) / kTstatWaves - (units * ww) / kTstatWaves);
+                const double n = rows_before(ww, tasks_w, tt), m = stats[ww * 2 * NH + c];
+                s += i < NH ? n * m : static_cast<double>(stats[ww * 2 * NH + NH + c]) + (n * m) * m;
+            }
             return s;
         };
         double* cs = g.colstats;

@@ -51,9 +51,10 @@ struct LazyView {
 // Workspace of the ordered grid-wide sums (device_utils.h grid_sum_ordered): the batch-norm column statistics out of the
 // projection GEMM's epilogue and [loss | Σdy | Σdy·x̂] out of the loss kernel are added up in a fixed order — same bits
 // every run, no atomics on data. `colgroups` independent sums (column parts / tiles of a GEMM; 1 for the loss kernel), each
-// of up to `contrib_cap` contributions of up to `width_cap` floats.
+// of up to `contrib_cap` contributions of up to `width_cap` values: fp64 from the projection products (their tile sums are
+// fp64 — see the pivot in their epilogues), fp32 from the loss kernel (which uses the buffer as floats).
 struct GridSumWs {
-    float* part;        // [colgroups][contrib_cap][width_cap]
+    double* part;       // [colgroups][contrib_cap][width_cap]
     double* part2;      // [colgroups][groups_cap][width_cap]
     int* arrive;        // [colgroups][groups_cap + 1], zero between launches
     int colgroups, contrib_cap, groups_cap, width_cap, fan;

@@ -8,8 +8,14 @@ namespace cunvsm {
 // =============================================================================================
 // Batch normalisation, per-activation, γ ≡ 1, β = projection bias, batch statistics only
 // (replaces cudnnBatchNormalizationForwardTraining/Backward, cpp/cudnn_utils.cu:107-124,158-177).
-// The forward column sums Σx, Σx² come from the projection GEMM's epilogue (gather_gemm.hip): fp32 over a
-// 128-row tile, merged with native fp64 atomics, so var = E[x²] − E[x]² is formed in double.
+// The forward column sums Σx, Σx² come from the projection GEMM's epilogue. var = E[x²] − E[x]² is formed in double, and that
+// alone would not do: fp32 sums of x and x² carry an error of about eps · n · mean², so the variance would lose about
+// eps · (mean / std)² of itself — 1/σ of a constant column at 3.7 came out as 95 instead of 100. Each product tile therefore also
+// sums the DIFFERENCES from a pivot (an fp32 value of the column inside the tile) in fp32 and forms its Σx = n p + Σd,
+// Σx² = n p² + 2 p Σd + Σd² in fp64; a tile whose values sit within four standard deviations of zero hands over its plain sums,
+// which are as accurate there and the bits the products formed before (gemm_tstat, whose LDS has no room for both: a running
+// mean and sum of squared deviations per wave instead). The tile sums are added in fp64 in a fixed order (device_utils.h
+// grid_sum_ordered).
 // =============================================================================================
 // Batch statistics of V columns from the fp64 column sums Σx, Σx² the projection GEMM left (cudnn_utils.cu:107-124:
 // biased variance, 1/sqrt(σ² + ε)). Every wave of the loss kernel evaluates this for its own columns — a few dozen
@@ -116,7 +122,7 @@ __device__ __forceinline__ void loss_block_sums(const LossArgs& a, const float* 
         return (sp[0] + sp[de]) + (sp[2 * de] + sp[3 * de]);
     };
     double* dst = a.loss_acc;
-    grid_sum_ordered<256>(a.sums.part, a.sums.part2, a.sums.arrive, a.sums.fan, n, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x),
+    grid_sum_ordered<256>(reinterpret_cast<float*>(a.sums.part), a.sums.part2, a.sums.arrive, a.sums.fan, n, static_cast<int>(blockIdx.x), static_cast<int>(gridDim.x),
                           val, [&](int i, double v) { dst[i] = v; }, flag);
 }
 

@@ -260,7 +260,7 @@ class Model {
     DevBuf<float> phrase_, pre_, proj_, dy_, gphrase_, coef_, probs_, pp_, msq_w_, msq_parts_, U_, scale_w_, grad_entity_;
     DevBuf<double> stats_;                   // [2 de | 1 + 2 de] = Σx Σx² | loss Σdy Σdy·x̂ — written by the ordered grid sums
     // workspaces of those sums (kernels.h GridSumWs): projection GEMM epilogue / loss kernel
-    struct SumsBufs { DevBuf<float> part; DevBuf<double> part2; DevBuf<int> arrive; GridSumWs ws{}; };
+    struct SumsBufs { DevBuf<double> part; DevBuf<double> part2; DevBuf<int> arrive; GridSumWs ws{}; };
     SumsBufs sums_fwd_, sums_bwd_;
     // the projection matrix cut into bf16 planes for the split-bf16 GEMM (gemm_split.hip), in the forward and the backward
     // product's layout; `ready` is cleared by everything that writes T

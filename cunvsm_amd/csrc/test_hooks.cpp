@@ -71,8 +71,8 @@ int nvsm_debug_gemm(int variant, int M, int N, int K, const float* hostA, const 
 int nvsm_debug_gemm_time(int b_layout, int M, int N, int K, int extras, int repeats, float* avg_ms) {
     NVSM_REQUIRE(avg_ms);
     return guarded_hook([&] {
-        cunvsm::DevBuf<float> A, B, C, rowsq, part;
-        cunvsm::DevBuf<double> stats, part2;
+        cunvsm::DevBuf<float> A, B, C, rowsq;
+        cunvsm::DevBuf<double> stats, part, part2;
         cunvsm::DevBuf<int> arrive;
         A.alloc(static_cast<size_t>(M) * K); B.alloc(static_cast<size_t>(K) * N); C.alloc(static_cast<size_t>(M) * N);
         {   // operands with all 24 significant bits in use (zeros would flatter a kernel: less switching, higher clocks)
