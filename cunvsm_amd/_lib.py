@@ -15,6 +15,8 @@ TANH, HARD_TANH = 0, 1
 SGD, ADAGRAD, ADAM = 0, 1, 2
 ADAM_NONE, ADAM_SPARSE, ADAM_DENSE_UPDATE, ADAM_DENSE_UPDATE_DENSE_VARIANCE = 0, 1, 2, 3
 SAMPLER_HOST_MINSTD, SAMPLER_DEVICE = 0, 1
+SIM_COSINE, SIM_DOT = 0, 1
+ACT_MODEL, ACT_IDENTITY = -1, -2
 
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "DEVICE", 4: "STATE", 5: "NO_DEVICE"}
 
@@ -46,6 +48,18 @@ class NvsmBatch(C.Structure):
     _fields_ = [
         ("features", C.c_void_p), ("feature_weights", C.c_void_p), ("labels", C.c_void_p), ("weights", C.c_void_p),
         ("num_instances", C.c_int64), ("on_device", C.c_int32),
+    ]
+
+
+class NvsmQueries(C.Structure):
+    _fields_ = [("word_ids", C.c_void_p), ("word_weights", C.c_void_p), ("offsets", C.c_void_p), ("num_queries", C.c_int64)]
+
+
+class NvsmRankOptions(C.Structure):
+    _fields_ = [
+        ("bias_coefficient", C.c_float), ("activation", C.c_int32), ("similarity", C.c_int32), ("top_k", C.c_int32),
+        ("candidates", C.c_void_p), ("candidate_offsets", C.c_void_p),
+        ("reserved", C.c_int32 * 4),
     ]
 
 
@@ -154,6 +168,9 @@ def lib():
         "nvsm_step_deferred": (C.c_int, [vp, P(NvsmBatch), vp, C.c_float, P(i64)]),
         "nvsm_deferred_cost": (C.c_int, [vp, i64, P(C.c_float)]), "nvsm_wait_inputs": (C.c_int, [vp]),
         "nvsm_tensor_size": (C.c_int, [vp, cp, P(i64)]), "nvsm_get_tensor": (C.c_int, [vp, cp, vp, i64]),
+        "nvsm_rank_options_default": (None, [P(NvsmRankOptions)]),
+        "nvsm_infer": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp]),
+        "nvsm_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp, vp, vp]),
         "nvsm_set_stream": (C.c_int, [vp, vp]), "nvsm_synchronize": (C.c_int, [vp]),
         "nvsm_describe": (C.c_int, [vp, C.c_int64, C.c_char_p, C.c_int64]),
         "nvsm_comm_unique_id": (C.c_int, [vp]), "nvsm_comm_init": (C.c_int, [vp, vp]),

@@ -273,6 +273,20 @@ int nvsm_get_tensor(nvsm_model* m, const char* name, float* dst, int64_t count) 
     return guarded_on(m, [&] { m->impl.get_tensor(name, dst, count); });
 }
 
+void nvsm_rank_options_default(nvsm_rank_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->bias_coefficient = 1.f; o->activation = NVSM_ACT_MODEL; o->similarity = NVSM_SIM_COSINE; o->top_k = 1000;
+}
+int nvsm_infer(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* opt, float* out) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(opt); NVSM_REQUIRE(out);
+    return guarded_on(m, [&] { m->impl.infer(*queries, *opt, out); });
+}
+int nvsm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* opt, int64_t* doc_ids, float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(opt); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.rank(*queries, *opt, doc_ids, scores, counts); });
+}
+
 int nvsm_set_stream(nvsm_model* m, void* s) { NVSM_REQUIRE(m); return guarded_on(m, [&] { m->impl.set_stream(static_cast<hipStream_t>(s)); }); }
 int nvsm_describe(nvsm_model* m, int64_t batch, char* buf, int64_t buf_bytes) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(buf);

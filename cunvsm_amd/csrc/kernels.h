@@ -400,5 +400,30 @@ struct TransformUpdateArgs {
 };
 void launch_transform_update(const TransformUpdateArgs& a, hipStream_t s);
 
+// ---- ranking: query inference and top-k documents (rank.hip; Model::infer, cpp/model.cu:105-133; py/nvsm/base.py:297-430) ----
+// query side: ragged weighted gather-mean (ids / wts / offsets on the device; `lazy` as launch_gather_mean), then f(pre + c·b) in place
+void launch_rank_query_mean(const float* W, int dw, int64_t num_words, const int64_t* ids, const float* wts, const int64_t* offsets,
+                            int64_t Q, float* out, const LazyView& lazy, int* err_flag, hipStream_t s);
+void launch_rank_bias_act(float* y, const float* bias, float c, int act, int64_t Q, int de, hipStream_t s);      // act: NVSM_TANH, NVSM_HARD_TANH, else identity
+void launch_rank_query_norm(const float* P, int64_t Q, int de, float* inv, int cosine, hipStream_t s);            // 1 / |P[q]|, 0 for a zero row; cosine 0: ones
+// scan: scores[q][i] = similarity of query q < Q and document d_begin + i, i < S (cosine: the row norms out of the same pass)
+bool rank_scan_uses_mfma(int de);
+void launch_rank_scan(const float* E, int de, int64_t d_begin, int S, const float* P, int Q, const float* qinv, float* scores,
+                      int64_t ld_scores, int cosine, const LazyView& lazy, hipStream_t s);
+// candidate lists (distinct, ascending ids, concatenated; cand_off [Q + 1]): keys[q][j < npad] = sortable (score, id), 0 past the list
+void launch_rank_scan_candidates(const float* E, int de, const float* P, const float* qinv, const int* cand, const int64_t* cand_off,
+                                 int Q, int64_t npad, unsigned long long* keys, int cosine, const LazyView& lazy, hipStream_t s);
+// selection: the min(k, S) best documents of the slab per query as keys[q][key_off ...], in no particular order. ws:
+// rank_select_ws_bytes(Q, S) bytes. true: by radix select (k < S); false: every document of the slab (k >= S).
+size_t rank_select_ws_bytes(int Q, int S);
+bool launch_rank_select(const float* scores, int64_t ld_scores, int S, int64_t d_begin, int Q, int k, void* ws,
+                        unsigned long long* keys, int64_t ld_keys, int64_t key_off, hipStream_t s);
+void launch_rank_fill_keys(unsigned long long* keys, int64_t ld_keys, int64_t from, int64_t to, int Q, hipStream_t s);   // keys[q][from, to) = 0
+// keys[q][0 .. npad) (npad a power of two) descending = score descending, id ascending. true: npad needed the global-memory steps.
+bool launch_rank_sort(unsigned long long* keys, int64_t npad, int Q, hipStream_t s);
+// ids / scores [Q][k], counts [Q] from the sorted keys; a query has cand_off[q + 1] - cand_off[q] keys (cand_off null: n_all)
+void launch_rank_write(const unsigned long long* keys, int64_t npad, int Q, int k, const int64_t* cand_off, int64_t n_all,
+                       int64_t* ids, float* scores, int64_t* counts, hipStream_t s);
+
 
 }  // namespace cunvsm

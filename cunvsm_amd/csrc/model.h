@@ -144,6 +144,10 @@ class Model {
     int64_t tensor_size(const std::string& name);
     void get_tensor(const std::string& name, float* dst, int64_t count);
 
+    // Model::infer (cpp/model.cu:105-133) for ragged queries, and the ranking of py/nvsm/base.py:362-430 (rank.cpp)
+    void infer(const nvsm_queries& q, const nvsm_rank_options& opt, float* out);
+    void rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts);
+
     void set_stream(hipStream_t s);
     int64_t step_deferred(const nvsm_batch& batch, const int64_t* entity_ids, float lr);
     float deferred_cost(int64_t ticket);
@@ -294,6 +298,18 @@ class Model {
     static constexpr int64_t kDtMainMinBatch = 16384;      // eager tables, one rank: the dT product on the split-bf16 kernel, on the main stream, from here
     int chunk_entries(const TableState& t, int64_t n) const;      // entries per level-1 chunk of a long row for a batch of n entries of table t
     bool use_dt() const;               // this step's dT product runs on it (else: the exact-fp32 tiled / panel kernels)
+
+    // ranking scratch: allocated by the first infer / rank call (training-only handles never pay for it), grown on demand
+    struct RankScratch {
+        DevBuf<int64_t> ids, offsets, cand_off, out_ids, out_counts;
+        DevBuf<float> wts, phrase, proj, qinv, scores, out_scores;
+        DevBuf<int> cand;
+        DevBuf<unsigned long long> keys;
+        DevBuf<char> sel_ws;
+    };
+    RankScratch rank_;
+    void rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt);      // argument checks; the handle's streams joined
+    void rank_project(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, int64_t qn);      // rank_.proj [qn][de], on the main stream
 
     bool have_forward_ = false, have_grads_ = false;
     struct DeferredCost { double* host = nullptr; hipEvent_t ev = nullptr; double batch = 1.0; int64_t ticket = -1; };

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -120,6 +120,72 @@ class Batch:
                          self._ptr(self.weights), self.num_instances, int(self.on_device))
 
 
+def self_information_weights(term_frequencies, total_terms):
+    """-log(tf / total) per query term (py/nvsm/base.py:297-301): the weights py/query.py averages the word rows with."""
+    tf = np.asarray(term_frequencies, dtype=np.float64)
+    if tf.size and (tf <= 0).any():
+        raise ValueError("term frequencies must be positive")
+    if not total_terms > 0:
+        raise ValueError("total_terms must be positive")
+    return (-np.log(tf / float(total_terms))).astype(np.float32)
+
+
+ACTIVATIONS = dict(NONLINEARITIES, model=_lib.ACT_MODEL, identity=_lib.ACT_IDENTITY, linear=_lib.ACT_IDENTITY)
+SIMILARITIES = {"cosine": _lib.SIM_COSINE, "dot": _lib.SIM_DOT}
+
+
+class Queries:
+    """nvsm_queries: a list of word-id lists of any lengths (ragged), flattened to ids + offsets; optional per-word weights
+    of the same shape. The element counts the ABI will read are checked here, as Batch.check_shapes does; id RANGES are
+    checked on the device."""
+
+    def __init__(self, queries, weights=None):
+        rows = [np.asarray(q, dtype=np.int64).ravel() for q in queries]
+        for q, r in zip(queries, rows):
+            if np.asarray(q).ndim > 1:
+                raise ValueError("a query must be a flat list of word ids")
+        self.num_queries = len(rows)
+        self.offsets = np.zeros(self.num_queries + 1, dtype=np.int64)
+        if rows:
+            np.cumsum([r.size for r in rows], out=self.offsets[1:])
+        self.word_ids = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, np.int64), dtype=np.int64)
+        self.word_weights = None
+        if weights is not None:
+            wrows = [np.asarray(w, dtype=np.float32).ravel() for w in weights]
+            if len(wrows) != self.num_queries:
+                raise ValueError("weights holds %d lists, expected one per query = %d" % (len(wrows), self.num_queries))
+            for i, (r, w) in enumerate(zip(rows, wrows)):
+                if r.size != w.size:
+                    raise ValueError("weights[%d] holds %d values, query %d has %d words" % (i, w.size, i, r.size))
+                if r.size and not abs(float(w.astype(np.float64).sum())) > 0.0:
+                    raise ValueError("weights[%d] sum to zero" % i)
+            self.word_weights = np.ascontiguousarray(np.concatenate(wrows) if wrows else np.zeros(0, np.float32), dtype=np.float32)
+
+    def as_struct(self):
+        return NvsmQueries(self.word_ids.ctypes.data, None if self.word_weights is None else self.word_weights.ctypes.data,
+                           self.offsets.ctypes.data, self.num_queries)
+
+
+def rank_options(num_entities, top_k=None, bias_coefficient=1.0, activation="model", similarity="cosine"):
+    """nvsm_rank_options from keywords; raises ValueError for what the ABI would refuse (no device needed)."""
+    opt = NvsmRankOptions()
+    opt.bias_coefficient, opt.activation, opt.similarity, opt.top_k = 1.0, _lib.ACT_MODEL, _lib.SIM_COSINE, 1000
+    if isinstance(activation, str):
+        if activation not in ACTIVATIONS:
+            raise ValueError("unknown activation %r (one of %s)" % (activation, sorted(ACTIVATIONS)))
+        activation = ACTIVATIONS[activation]
+    if isinstance(similarity, str):
+        if similarity not in SIMILARITIES:
+            raise ValueError("unknown similarity %r (one of %s)" % (similarity, sorted(SIMILARITIES)))
+        similarity = SIMILARITIES[similarity]
+    opt.bias_coefficient, opt.activation, opt.similarity = float(bias_coefficient), int(activation), int(similarity)
+    if top_k is not None:
+        if not 1 <= int(top_k) <= int(num_entities):
+            raise ValueError("top_k = %d outside [1, num_entities = %d]" % (int(top_k), int(num_entities)))
+        opt.top_k = int(top_k)
+    return opt
+
+
 class Model:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -194,6 +260,46 @@ class Model:
         check(lib().nvsm_step(self._h, C.byref(st), None if ids is None else ids.ctypes.data, learning_rate,
                               C.byref(c) if want_cost else None))
         return c.value if want_cost else None
+
+    # -- Model::infer (cpp/model.cu:105-133) and the ranking of py/nvsm/base.py:362-430 ---------------
+    def infer(self, queries, weights=None, **opts):
+        """Projected query representations [Q, entity_repr_size] float32: f(T·mean + c·b), no batch normalisation.
+        queries: a list of word-id lists (any lengths >= 1); weights: per-word weights of the same shape or None.
+        opts: bias_coefficient (1), activation ("model" | "tanh" | "hard_tanh" | "identity")."""
+        q = queries if isinstance(queries, Queries) else Queries(queries, weights)
+        opt = rank_options(self.cfg.num_entities, None, **opts)
+        out = np.empty((q.num_queries, self.cfg.entity_repr_size), dtype=np.float32)
+        st = q.as_struct()
+        check(lib().nvsm_infer(self._h, C.byref(st), C.byref(opt), out.ctypes.data))
+        return out
+
+    def rank(self, queries, top_k=1000, weights=None, candidates=None, **opts):
+        """The top_k documents per query: (ids [Q, k] int64, scores [Q, k] float32, counts [Q] int64), by score descending,
+        ties by ascending id; slots beyond counts[q] hold (-1, -inf). candidates: optional per-query lists of document ids
+        (duplicates and any order allowed): only those are scored. opts: as infer, plus similarity ("cosine" | "dot")."""
+        q = queries if isinstance(queries, Queries) else Queries(queries, weights)
+        opt = rank_options(self.cfg.num_entities, top_k, **opts)
+        keep = None
+        if candidates is not None:
+            rows = [np.asarray(c, dtype=np.int64).ravel() for c in candidates]
+            if len(rows) != q.num_queries:
+                raise ValueError("candidates holds %d lists, expected one per query = %d" % (len(rows), q.num_queries))
+            off = np.zeros(q.num_queries + 1, dtype=np.int64)
+            if rows:
+                np.cumsum([r.size for r in rows], out=off[1:])
+            flat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, np.int64), dtype=np.int64)
+            if flat.size and (flat.min() < 0 or flat.max() >= self.cfg.num_entities):
+                raise ValueError("a candidate document id is outside [0, num_entities = %d)" % self.cfg.num_entities)
+            keep = (flat, off)
+            opt.candidates, opt.candidate_offsets = flat.ctypes.data if flat.size else None, off.ctypes.data
+        k = opt.top_k
+        ids = np.empty((q.num_queries, k), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        check(lib().nvsm_rank(self._h, C.byref(st), C.byref(opt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        del keep
+        return ids, scores, counts
 
     # -- parameters / tensors ----------------------------------------------------------------------
     def step_deferred(self, batch, learning_rate, entity_ids=None):

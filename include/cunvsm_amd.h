@@ -214,6 +214,62 @@ int nvsm_wait_inputs(nvsm_model* m);
 int nvsm_tensor_size(nvsm_model* m, const char* name, int64_t* count);
 int nvsm_get_tensor(nvsm_model* m, const char* name, float* host_dst, int64_t count);
 
+/*
+ * Query inference and top-k document ranking — what the reference does with a trained model (no counterpart in its
+ * training loop). Semantics, pinned by the reference:
+ *   query        a list of model word ids of any length >= 1 (ragged: the queries of one call differ in length) with optional
+ *                per-word weights. Representation = Σ wᵢ·W[idᵢ] / Σ wᵢ (np.average, py/nvsm/base.py:305-307); word_weights
+ *                NULL = the plain mean, which is Model::infer's gather-mean over a fixed window (cpp/model.cu:105-133,
+ *                cpp/params.cu:75-95). Mapping index term ids to model ids, dropping out-of-vocabulary terms and computing
+ *                self-information weights (-log(tf / total), base.py:297-301) are the caller's job.
+ *   projection   f(T·x + c·b). NO batch normalisation, even on a handle created with batch_normalization = 1: the reference
+ *                passes nullptr statistics (cpp/model.cu:125-128, cpp/params.cu:396-428) and so does base.py:311-323.
+ *                bias_coefficient c = 1 with the handle's nonlinearity is Model::infer (the default here); c = 0 with tanh is
+ *                what py/query.py computes by default — base.py:228-233 multiplies the bias by a coefficient that is 0 whenever
+ *                the bias is kept (a quirk of the reference, reproduced by passing 0, not "fixed"); NVSM_ACT_IDENTITY is --linear.
+ *                l2_normalize_phrase_reprs / l2_normalize_entity_reprs of the handle are ignored: the reference's normalisers
+ *                belong to the objective (cpp/objective.cu:99-107), not to Model::infer, and base.py has none.
+ *   score        NVSM_SIM_COSINE: cosine similarity of the projected query and a document row, larger is better (the reference
+ *                returns the cosine DISTANCE, base.py:362-430, and py/query.py negates it); NVSM_SIM_DOT: the plain dot
+ *                product. A document row or a projected query of norm 0 has inverse norm 0: score 0, never NaN.
+ *   ranking      the top_k best documents per query, 1 <= top_k <= num_entities, by score descending, ties by ASCENDING
+ *                document id: a pure function of the parameters and the query (a repeated call returns the same bits). With
+ *                candidates (base.py's document_set: re-ranking judged documents) only those rows are scored and
+ *                counts[q] = min(top_k, number of distinct candidates of q). A query without words has counts[q] = 0 (the
+ *                reference returns None). Slots beyond counts[q] hold id -1 and score -inf.
+ * Word ids follow the index contract above: an id out of range reads row 0 and the call (it waits for its own results)
+ * returns NVSM_ERR_INVALID_ARGUMENT. Candidate ids out of range, decreasing offsets, word weights that sum to 0, unknown
+ * enums and top_k outside [1, num_entities] are NVSM_ERR_INVALID_ARGUMENT before anything runs.
+ * Both calls are synchronous and return host results; they run behind everything earlier steps have queued (the side
+ * streams' tails included) and leave parameters, optimiser state and the lazy-decay bookkeeping untouched: lazily decayed
+ * tables are read through their view (the values nvsm_get_param would return), nothing is flushed. The number of queries is
+ * independent of max_batch_size (chunked internally); device scratch is allocated by the first call, not by nvsm_create.
+ */
+enum { NVSM_SIM_COSINE = 0, NVSM_SIM_DOT = 1 };
+enum { NVSM_ACT_MODEL = -1, NVSM_ACT_IDENTITY = -2 };   /* or NVSM_TANH / NVSM_HARD_TANH */
+typedef struct {
+    const int64_t* word_ids;      /* [offsets[num_queries]] host */
+    const float*   word_weights;  /* same length, or NULL */
+    const int64_t* offsets;       /* [num_queries + 1], non-decreasing, offsets[0] = 0 */
+    int64_t        num_queries;
+} nvsm_queries;
+typedef struct {
+    float   bias_coefficient;     /* 1 = Model::infer, 0 = py/query.py's default */
+    int32_t activation;           /* NVSM_ACT_MODEL, NVSM_ACT_IDENTITY, NVSM_TANH, NVSM_HARD_TANH */
+    int32_t similarity;           /* NVSM_SIM_* */
+    int32_t top_k;
+    const int64_t* candidates;         /* optional: concatenated per-query document ids (duplicates and any order allowed) */
+    const int64_t* candidate_offsets;  /* [num_queries + 1] when candidates != NULL */
+    int32_t reserved[4];
+} nvsm_rank_options;
+/* bias_coefficient 1, NVSM_ACT_MODEL, NVSM_SIM_COSINE, top_k 1000 (py/query.py --top_k), no candidates */
+void nvsm_rank_options_default(nvsm_rank_options* opt);
+/* out [num_queries][entity_repr_size] host; top_k, similarity and candidates are not looked at */
+int nvsm_infer(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* opt, float* out);
+/* doc_ids, scores [num_queries][top_k], counts [num_queries], all host */
+int nvsm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* opt,
+              int64_t* doc_ids, float* scores, int64_t* counts);
+
 /* Streams. A handle issues its work on FOUR HIP streams of its own device: the main stream (highest priority: the step's
  * critical chain), two side streams (lowest priority: the batch → row-order sorts, and — in nvsm_step — the documents
  * update and the ∂T GEMM + projection update, which keep running after nvsm_step has returned and are joined by the next

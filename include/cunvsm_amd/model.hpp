@@ -115,12 +115,45 @@ class Model {
     void increment_parameter(const std::string& name, int64_t index, float epsilon) { check(nvsm_increment_parameter(h_, name.c_str(), index, epsilon)); }
     double get_cost_f64() { double c = 0.0; check(nvsm_get_cost_f64(h_, &c)); return c; }
 
+    // Model::infer (cpp/model.cu:105-133) for ragged queries: word ids of query q are word_ids[offsets[q] .. offsets[q + 1]);
+    // returns [num_queries][entity_repr_size]. opt == nullptr: nvsm_rank_options_default (c = 1, the model's nonlinearity).
+    std::vector<float> infer(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets,
+                             const std::vector<float>* word_weights = nullptr, const nvsm_rank_options* opt = nullptr) {
+        nvsm_rank_options o;
+        if (opt) o = *opt; else nvsm_rank_options_default(&o);
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        std::vector<float> out(static_cast<size_t>(q.num_queries) * static_cast<size_t>(cfg_.entity_repr_size));
+        check(nvsm_infer(h_, &q, &o, out.data()));
+        return out;
+    }
+    // the ranking of py/nvsm/base.py:362-430: the opt.top_k best documents per query, score descending, ties by ascending id
+    struct Ranking { std::vector<int64_t> doc_ids; std::vector<float> scores; std::vector<int64_t> counts; int32_t top_k; };
+    Ranking rank(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                 const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        Ranking r;
+        r.top_k = opt.top_k;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        r.doc_ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_rank(h_, &q, &opt, r.doc_ids.data(), r.scores.data(), r.counts.data()));
+        r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+
     void synchronize() { check(nvsm_synchronize(h_)); }
     void comm_init(const char id[128]) { check(nvsm_comm_init(h_, id)); }
     nvsm_model* handle() { return h_; }
     const nvsm_config& config() const { return cfg_; }
 
  private:
+    static nvsm_queries queries_of(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const std::vector<float>* word_weights) {
+        if (offsets.empty() || offsets.back() != static_cast<int64_t>(word_ids.size()) || (word_weights && word_weights->size() != word_ids.size()))
+            throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries: offsets must end at word_ids.size(), weights must match word_ids");
+        nvsm_queries q;
+        q.word_ids = word_ids.data(); q.word_weights = word_weights ? word_weights->data() : nullptr;
+        q.offsets = offsets.data(); q.num_queries = static_cast<int64_t>(offsets.size()) - 1;
+        return q;
+    }
     static uint64_t state_of(const std::minstd_rand0& rng) { std::stringstream ss; ss << rng; uint64_t s = 0; ss >> s; return s; }
     nvsm_config cfg_;
     nvsm_model* h_ = nullptr;
