@@ -16,6 +16,7 @@ SGD, ADAGRAD, ADAM = 0, 1, 2
 ADAM_NONE, ADAM_SPARSE, ADAM_DENSE_UPDATE, ADAM_DENSE_UPDATE_DENSE_VARIANCE = 0, 1, 2, 3
 SAMPLER_HOST_MINSTD, SAMPLER_DEVICE = 0, 1
 SIM_COSINE, SIM_DOT = 0, 1
+SPACE_WORDS, SPACE_PROJECTED_WORDS, SPACE_ENTITIES = 0, 1, 2
 ACT_MODEL, ACT_IDENTITY = -1, -2
 
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "DEVICE", 4: "STATE", 5: "NO_DEVICE"}
@@ -60,6 +61,18 @@ class NvsmRankOptions(C.Structure):
         ("bias_coefficient", C.c_float), ("activation", C.c_int32), ("similarity", C.c_int32), ("top_k", C.c_int32),
         ("candidates", C.c_void_p), ("candidate_offsets", C.c_void_p),
         ("reserved", C.c_int32 * 4),
+    ]
+
+
+class NvsmNeighborQueries(C.Structure):
+    _fields_ = [("ids", C.c_void_p), ("vectors", C.c_void_p), ("num_queries", C.c_int64), ("source_space", C.c_int32), ("dim", C.c_int32)]
+
+
+class NvsmNeighborOptions(C.Structure):
+    _fields_ = [
+        ("space", C.c_int32), ("similarity", C.c_int32), ("top_k", C.c_int32), ("exclude_self", C.c_int32),
+        ("bias_coefficient", C.c_float), ("activation", C.c_int32),
+        ("reserved", C.c_int32 * 6),
     ]
 
 
@@ -116,6 +129,7 @@ class _Library:
             for hook, (res, args) in {
                 "nvsm_debug_delay": (C.c_int, [vp, C.c_int]),
                 "nvsm_debug_set_table_pass_form": (C.c_int, [C.c_int]),
+                "nvsm_debug_neighbors_force_plain": (C.c_int, [C.c_int]),
                 "nvsm_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
                 "nvsm_debug_gemm_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float)]),
                 "nvsm_debug_dt_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]),
@@ -171,6 +185,9 @@ def lib():
         "nvsm_rank_options_default": (None, [P(NvsmRankOptions)]),
         "nvsm_infer": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp]),
         "nvsm_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp, vp, vp]),
+        "nvsm_neighbor_options_default": (None, [P(NvsmNeighborOptions)]),
+        "nvsm_neighbors": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNeighborOptions), vp, vp, vp]),
+        "nvsm_similarity": (C.c_int, [vp, C.c_int32, vp, vp, i64, C.c_int32, vp]),
         "nvsm_set_stream": (C.c_int, [vp, vp]), "nvsm_synchronize": (C.c_int, [vp]),
         "nvsm_describe": (C.c_int, [vp, C.c_int64, C.c_char_p, C.c_int64]),
         "nvsm_comm_unique_id": (C.c_int, [vp]), "nvsm_comm_init": (C.c_int, [vp, vp]),

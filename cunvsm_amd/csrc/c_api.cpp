@@ -287,6 +287,21 @@ int nvsm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_option
     return guarded_on(m, [&] { m->impl.rank(*queries, *opt, doc_ids, scores, counts); });
 }
 
+void nvsm_neighbor_options_default(nvsm_neighbor_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->space = NVSM_SPACE_WORDS; o->similarity = NVSM_SIM_COSINE; o->top_k = 30; o->exclude_self = 0;
+    o->bias_coefficient = 1.f; o->activation = NVSM_ACT_MODEL;
+}
+int nvsm_neighbors(nvsm_model* m, const nvsm_neighbor_queries* queries, const nvsm_neighbor_options* opt, int64_t* ids, float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(opt); NVSM_REQUIRE(ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.neighbors(*queries, *opt, ids, scores, counts); });
+}
+int nvsm_similarity(nvsm_model* m, int32_t space, const int64_t* a, const int64_t* b, int64_t n, int32_t similarity, float* out) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(a); NVSM_REQUIRE(b); NVSM_REQUIRE(out);
+    return guarded_on(m, [&] { m->impl.similarity(space, a, b, n, similarity, out); });
+}
+
 int nvsm_set_stream(nvsm_model* m, void* s) { NVSM_REQUIRE(m); return guarded_on(m, [&] { m->impl.set_stream(static_cast<hipStream_t>(s)); }); }
 int nvsm_describe(nvsm_model* m, int64_t batch, char* buf, int64_t buf_bytes) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(buf);

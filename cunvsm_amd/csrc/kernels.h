@@ -426,4 +426,21 @@ void launch_rank_write(const unsigned long long* keys, int64_t npad, int Q, int 
                        int64_t* ids, float* scores, int64_t* counts, hipStream_t s);
 
 
+// ---- nearest neighbours in word, projected-word and document space (rank.hip; py/nvsm/base.py:106-162, 325-353, 362-430) ----
+// the scan of nvsm_neighbors: scores as launch_rank_scan; the MFMA kernel wherever dim % 4 == 0 && dim >= 32 (a zero-filled tail
+// chunk where dim % 32 != 0), else the plain kernel. set_nbr_scan_force_plain: the plain kernel for every dimension (test hook:
+// how tools/bench_neighbors.py holds the two against each other).
+bool nbr_scan_uses_mfma(int dim);
+void set_nbr_scan_force_plain(bool on);
+void launch_nbr_scan(const float* E, int dim, int64_t d_begin, int S, const float* P, int Q, const float* qinv, float* scores,
+                     int64_t ld_scores, int cosine, const LazyView& lazy, hipStream_t s);
+// out[q][dim] = row ids[q] (ids null: first + q) of `table` at its logical values
+void launch_rank_gather_rows(const float* table, int dim, const int64_t* ids, int64_t first, int64_t Q, float* out, const LazyView& lazy, hipStream_t s);
+// scores[q][self[q] - d_begin] = -inf where that lies in the slab (self[q] < 0: nothing)
+void launch_rank_exclude_self(float* scores, int64_t ld_scores, int64_t d_begin, int S, const int64_t* self, int Q, hipStream_t s);
+// out[i] = cosine similarity or dot product of rows a[i] and b[i] (device ids) of one table; one wave per pair
+void launch_rank_pair_sim(const float* table, int dim, const int64_t* a, const int64_t* b, int64_t n, float* out, int cosine,
+                          const LazyView& lazy, hipStream_t s);
+
+
 }  // namespace cunvsm

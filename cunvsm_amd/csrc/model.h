@@ -147,6 +147,10 @@ class Model {
     // Model::infer (cpp/model.cu:105-133) for ragged queries, and the ranking of py/nvsm/base.py:362-430 (rank.cpp)
     void infer(const nvsm_queries& q, const nvsm_rank_options& opt, float* out);
     void rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts);
+    // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
+    // 362-430), and the similarity of pairs of rows (ranking.cpp)
+    void neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts);
+    void similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out);
 
     void set_stream(hipStream_t s);
     int64_t step_deferred(const nvsm_batch& batch, const int64_t* entity_ids, float lr);
@@ -306,9 +310,15 @@ class Model {
         DevBuf<int> cand;
         DevBuf<unsigned long long> keys;
         DevBuf<char> sel_ws;
+        DevBuf<float> panel, pslab, pair_out;      // neighbours: the query panel [round][dim], one slab of the projected vocabulary
+        DevBuf<int64_t> self;                      //             ... the queries' own rows (exclude_self)
     };
     RankScratch rank_;
     void rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt);      // argument checks; the handle's streams joined
+    void rank_join();                       // the handle's four streams waited for on the host; the words table's pending stamps settled
+    struct RowSpace { const float* rows; int64_t count; int dim; const TableState* table; };      // rows null: the projected vocabulary
+    RowSpace row_space(int space) const;
+    void project_words(const int64_t* ids_dev, int64_t first, int64_t n, float c, int act, float* out);      // out [n][de] = f(T·W[id] + c·b)
     void rank_project(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, int64_t qn);      // rank_.proj [qn][de], on the main stream
 
     bool have_forward_ = false, have_grads_ = false;

@@ -15,6 +15,9 @@
 //                                        v_mfma_f32_32x32x2_f32; the row norms come out of the same registers
 //                rank_scan_plain_kernel  every other d_e
 //                rank_scan_cand_kernel   candidate lists: one wave per (query, candidate)
+//   neighbours   nvsm_neighbors scans word rows, the projected vocabulary or document rows with the same kernels (the MFMA scan with
+//                a zero-filled tail chunk where the dimension is not a multiple of 32: d_w = 300); rank_gather_rows_kernel makes
+//                the query panel from row ids, rank_exclude_self_kernel drops a query's own row, rank_pair_sim_kernel scores pairs
 //   selection    radix select on the order-preserving bits of the scores of one slab of documents (three histogram passes:
 //                11 + 11 + 10 bits), an ORDERED compaction of the survivors (per-part counts, then positions by prefix sums: no
 //                atomics decide where anything lands), and a bitonic sort of (score, ~id) keys: ties come out by ascending id.
@@ -116,7 +119,11 @@ __global__ __launch_bounds__(64) void rank_query_norm_kernel(const float* __rest
 // error of a score at that of a blocked float32 sum.
 constexpr int kScanDocs = 128, kScanKc = 32, kScanLd = kScanKc + 4;
 
-template <int NT>
+// TAIL (nvsm_neighbors only: d_w = 300 is nine chunks and a tail of 12): the reduction dimension is any multiple of 4 from 32
+// up, whole chunks plus one zero-filled tail chunk. A float4 of a row lies wholly in front of or wholly behind `de`; those
+// behind it — panel rows and document elements alike — are not loaded and count as 0, so the tail's MFMAs add zeros and the
+// norms still come out of the same registers. Without TAIL (de % 32 == 0) no such test is compiled.
+template <int NT, bool TAIL>
 __global__ __launch_bounds__(256, 2) void rank_scan_mfma_kernel(const float* __restrict__ E, int de, int64_t d_begin, int S,
                                                              const float* __restrict__ P, int Q, const float* __restrict__ qinv,
                                                              float* __restrict__ scores, int64_t ld_scores, int cosine, LazyView lazy) {
@@ -140,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void rank_scan_mfma_kernel(const float* __r
             const int f = threadIdx.x + it * 256, r = f >> 3, c4 = (f & 7) * 4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) pn[it][j] = 0.f;
-            if (q0 + r < Q) ldv<4>(P + static_cast<size_t>(q0 + r) * de + kc + c4, pn[it]);
+            if (q0 + r < Q && (!TAIL || kc + c4 < de)) ldv<4>(P + static_cast<size_t>(q0 + r) * de + kc + c4, pn[it]);
         }
     };
     auto store_panel = [&](int buf, const float (&pn)[NT][4]) {
@@ -152,7 +159,15 @@ __global__ __launch_bounds__(256, 2) void rank_scan_mfma_kernel(const float* __r
     };
     auto load_rows = [&](int kc, float (&e)[kScanKc / 8][4]) {
 #pragma unroll
-        for (int kb = 0; kb < kScanKc / 8; ++kb) ldv<4>(row + kc + 8 * kb, e[kb]);
+        for (int kb = 0; kb < kScanKc / 8; ++kb) {
+            if constexpr (TAIL) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) e[kb][j] = 0.f;
+                if (kc + 8 * kb + 4 * h < de) ldv<4>(row + kc + 8 * kb, e[kb]);
+            } else {
+                ldv<4>(row + kc + 8 * kb, e[kb]);
+            }
+        }
     };
     f32x16 tot[NT];
 #pragma unroll
@@ -166,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void rank_scan_mfma_kernel(const float* __r
     load_rows(0, e);
     store_panel(0, pn);
     __syncthreads();
-    const int chunks = de / kScanKc;
+    const int chunks = TAIL ? (de + kScanKc - 1) / kScanKc : de / kScanKc;
     for (int c = 0; c < chunks; ++c) {
         const bool more = c + 1 < chunks;
         if (more) { load_panel((c + 1) * kScanKc, pn); load_rows((c + 1) * kScanKc, en); }
@@ -556,6 +571,60 @@ __global__ __launch_bounds__(256) void rank_write_kernel(const unsigned long lon
     }
 }
 
+// ---- nearest neighbours (nvsm_neighbors / nvsm_similarity) --------------------------------------------------------
+// out[q] = row ids[q] of a table at its logical values (ids null: rows first, first + 1, ...); the [Q][dim] panel the scans read
+__global__ __launch_bounds__(256) void rank_gather_rows_kernel(const float* __restrict__ table, int dim, const int64_t* __restrict__ ids,
+                                                               int64_t first, float* __restrict__ out, LazyView lazy) {
+    __shared__ float hist[kLazyHistory];
+    if (lazy.stamp) {
+        for (int i = threadIdx.x; i < kLazyHistory; i += blockDim.x) hist[i] = lazy.decay[i];
+        __syncthreads();
+    }
+    const int q = blockIdx.x;
+    const int64_t id = ids ? ids[q] : first + q;
+    const int stamp = lazy.stamp ? lazy.stamp[id] : 0;
+    for (int t = threadIdx.x; t < dim; t += blockDim.x) {
+        float x = table[static_cast<size_t>(id) * dim + t];
+        if (lazy.stamp) x = rank_lazy(x, stamp, lazy.now, hist);
+        out[static_cast<size_t>(q) * dim + t] = x;
+    }
+}
+
+// exclude_self: the score of a query's own row becomes -inf behind the scan, below every score of another row, so the
+// selection and the sort leave it last and rank_write_kernel writes one slot fewer. self[q] < 0: nothing to leave out.
+__global__ __launch_bounds__(256) void rank_exclude_self_kernel(float* __restrict__ scores, int64_t ld_scores, int64_t d_begin, int S,
+                                                                const int64_t* __restrict__ self, int Q) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Q) return;
+    const int64_t i = self[q] - d_begin;
+    if (self[q] >= 0 && i >= 0 && i < S) scores[static_cast<size_t>(q) * ld_scores + i] = -__builtin_inff();
+}
+
+// out[i] = similarity of rows a[i] and b[i] of one table (term_similarity, base.py:344-353, batched); one wave per pair
+__global__ __launch_bounds__(64) void rank_pair_sim_kernel(const float* __restrict__ table, int dim, const int64_t* __restrict__ a,
+                                                           const int64_t* __restrict__ b, float* __restrict__ out, int cosine, LazyView lazy) {
+    __shared__ float hist[kLazyHistory];
+    if (lazy.stamp) {
+        for (int i = threadIdx.x; i < kLazyHistory; i += blockDim.x) hist[i] = lazy.decay[i];
+        __syncthreads();
+    }
+    const int64_t ia = a[blockIdx.x], ib = b[blockIdx.x];
+    const float* ra = table + static_cast<size_t>(ia) * dim;
+    const float* rb = table + static_cast<size_t>(ib) * dim;
+    const int sa = lazy.stamp ? lazy.stamp[ia] : 0, sb = lazy.stamp ? lazy.stamp[ib] : 0;
+    float d = 0.f, na = 0.f, nb = 0.f;
+    for (int t = threadIdx.x; t < dim; t += 64) {
+        float x = ra[t], y = rb[t];
+        if (lazy.stamp) { x = rank_lazy(x, sa, lazy.now, hist); y = rank_lazy(y, sb, lazy.now, hist); }
+        d += x * y; na += x * x; nb += y * y;
+    }
+    d = wave_sum(d); na = wave_sum(na); nb = wave_sum(nb);
+    if (threadIdx.x == 0) {
+        const float ainv = na > 0.f ? 1.f / sqrtf(na) : 0.f, binv = nb > 0.f ? 1.f / sqrtf(nb) : 0.f;
+        out[blockIdx.x] = (cosine ? d * ainv * binv : d) + 0.f;
+    }
+}
+
 inline int cdiv(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
 
 }  // namespace
@@ -588,14 +657,53 @@ void launch_rank_scan(const float* E, int de, int64_t d_begin, int S, const floa
         // from 48 queries on the pass is bound by the matrix pipe, not by HBM)
         const int nt = Q <= 32 ? 1 : (Q <= 64 ? 2 : 4);
         const dim3 grid(cdiv(S, kScanDocs), cdiv(Q, nt * 32));
-        if (nt == 1) NVSM_LAUNCH(rank_scan_mfma_kernel<1>, grid, dim3(256), 0, s, E, de, d_begin, S, P, Q, qinv, scores, ld_scores, cosine, lazy);
-        else if (nt == 2) NVSM_LAUNCH(rank_scan_mfma_kernel<2>, grid, dim3(256), 0, s, E, de, d_begin, S, P, Q, qinv, scores, ld_scores, cosine, lazy);
-        else NVSM_LAUNCH(rank_scan_mfma_kernel<4>, grid, dim3(256), 0, s, E, de, d_begin, S, P, Q, qinv, scores, ld_scores, cosine, lazy);
+        auto kernel = nt == 1 ? rank_scan_mfma_kernel<1, false> : (nt == 2 ? rank_scan_mfma_kernel<2, false> : rank_scan_mfma_kernel<4, false>);
+        NVSM_LAUNCH(kernel, grid, dim3(256), 0, s, E, de, d_begin, S, P, Q, qinv, scores, ld_scores, cosine, lazy);
     } else {
         const dim3 grid(cdiv(S, 256), cdiv(Q, kPlainQ));
         NVSM_LAUNCH(rank_scan_plain_kernel, grid, dim3(256), static_cast<size_t>(kPlainQ) * de * sizeof(float), s, E, de, d_begin, S, P, Q,
                     qinv, scores, ld_scores, cosine, lazy);
     }
+}
+
+// nvsm_neighbors' scan: the MFMA kernel for every dimension that is a multiple of 4 from 32 up (with the tail chunk where it is
+// not a multiple of 32), the plain kernel for the rest. nvsm_rank keeps rank_scan_uses_mfma (de % 64 == 0).
+namespace { bool g_nbr_force_plain = false; }
+void set_nbr_scan_force_plain(bool on) { g_nbr_force_plain = on; }
+bool nbr_scan_uses_mfma(int dim) { return dim % 4 == 0 && dim >= kScanKc && !g_nbr_force_plain; }
+
+void launch_nbr_scan(const float* E, int dim, int64_t d_begin, int S, const float* P, int Q, const float* qinv, float* scores,
+                     int64_t ld_scores, int cosine, const LazyView& lazy, hipStream_t s) {
+    if (Q <= 0 || S <= 0) return;
+    if (!nbr_scan_uses_mfma(dim)) {
+        const dim3 grid(cdiv(S, 256), cdiv(Q, kPlainQ));
+        NVSM_LAUNCH(rank_scan_plain_kernel, grid, dim3(256), static_cast<size_t>(kPlainQ) * dim * sizeof(float), s, E, dim, d_begin, S, P, Q,
+                    qinv, scores, ld_scores, cosine, lazy);
+        return;
+    }
+    const int nt = Q <= 32 ? 1 : (Q <= 64 ? 2 : 4);
+    const dim3 grid(cdiv(S, kScanDocs), cdiv(Q, nt * 32));
+    const bool tail = dim % kScanKc != 0;
+    auto kernel = rank_scan_mfma_kernel<1, false>;
+    if (tail) kernel = nt == 1 ? rank_scan_mfma_kernel<1, true> : (nt == 2 ? rank_scan_mfma_kernel<2, true> : rank_scan_mfma_kernel<4, true>);
+    else kernel = nt == 1 ? rank_scan_mfma_kernel<1, false> : (nt == 2 ? rank_scan_mfma_kernel<2, false> : rank_scan_mfma_kernel<4, false>);
+    NVSM_LAUNCH(kernel, grid, dim3(256), 0, s, E, dim, d_begin, S, P, Q, qinv, scores, ld_scores, cosine, lazy);
+}
+
+void launch_rank_gather_rows(const float* table, int dim, const int64_t* ids, int64_t first, int64_t Q, float* out, const LazyView& lazy, hipStream_t s) {
+    if (Q <= 0) return;
+    NVSM_LAUNCH(rank_gather_rows_kernel, dim3(static_cast<unsigned>(Q)), dim3(256), 0, s, table, dim, ids, first, out, lazy);
+}
+
+void launch_rank_exclude_self(float* scores, int64_t ld_scores, int64_t d_begin, int S, const int64_t* self, int Q, hipStream_t s) {
+    if (Q <= 0 || S <= 0) return;
+    NVSM_LAUNCH(rank_exclude_self_kernel, dim3(cdiv(Q, 256)), dim3(256), 0, s, scores, ld_scores, d_begin, S, self, Q);
+}
+
+void launch_rank_pair_sim(const float* table, int dim, const int64_t* a, const int64_t* b, int64_t n, float* out, int cosine,
+                          const LazyView& lazy, hipStream_t s) {
+    if (n <= 0) return;
+    NVSM_LAUNCH(rank_pair_sim_kernel, dim3(static_cast<unsigned>(n)), dim3(64), 0, s, table, dim, a, b, out, cosine, lazy);
 }
 
 void launch_rank_scan_candidates(const float* E, int de, const float* P, const float* qinv, const int* cand, const int64_t* cand_off,

@@ -51,6 +51,10 @@ void Model::rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt) {
     if (act != NVSM_ACT_MODEL && act != NVSM_ACT_IDENTITY && act != NVSM_TANH && act != NVSM_HARD_TANH)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown activation");
     if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
+    rank_join();
+}
+
+void Model::rank_join() {
     NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
     settle_words_stamp();      // (what the next step's prologue would do: the stamps of the last words update)
     synchronize();             // reports what earlier kernels have flagged, as every wait of the handle does
@@ -216,6 +220,209 @@ void Model::rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* d
         if (q.offsets[i + 1] > q.offsets[i]) continue;
         counts[i] = 0;
         for (int j = 0; j < k; ++j) { doc_ids[i * k + j] = -1; scores[i * k + j] = -INFINITY; }
+    }
+    raise_device_error();
+}
+
+// ---- nearest neighbours (include/cunvsm_amd.h nvsm_neighbors / nvsm_similarity) ---------------------------------
+// The searched matrix is a pointer, a row count and a dimension: W or E directly (through their LazyView), or, for the projected
+// vocabulary, a scratch slab that is produced with the query side's own kernels right before it is scanned. Rounds, slabs,
+// selection, sort and write are nvsm_rank's.
+namespace {
+constexpr int64_t kProjSlabBytes = int64_t(64) << 20;       // one slab of the projected vocabulary
+constexpr int64_t kProjChunk = 16384;                       // words gathered and projected per launch group
+constexpr int64_t kPairChunk = 2048;                        // pairs per round of nvsm_similarity
+bool known_space(int s) { return s == NVSM_SPACE_WORDS || s == NVSM_SPACE_PROJECTED_WORDS || s == NVSM_SPACE_ENTITIES; }
+}  // namespace
+
+Model::RowSpace Model::row_space(int space) const {
+    if (space == NVSM_SPACE_WORDS) return RowSpace{words_.P.p, cfg_.num_words, cfg_.word_repr_size, &words_};
+    if (space == NVSM_SPACE_ENTITIES) return RowSpace{ents_.P.p, cfg_.num_entities, cfg_.entity_repr_size, &ents_};
+    return RowSpace{nullptr, cfg_.num_words, cfg_.entity_repr_size, nullptr};
+}
+
+// out [n][de] = f(T·W[id] + c·b) for the words ids_dev[0 .. n) (null: first, first + 1, ...): the query side of nvsm_rank with
+// one word per query — launch_rank_query_mean (which applies the words table's lazy view), launch_gemm, launch_rank_bias_act
+void Model::project_words(const int64_t* ids_dev, int64_t first, int64_t n, float c, int act, float* out) {
+    const int dw = cfg_.word_repr_size, de = cfg_.entity_repr_size;
+    RankScratch& r = rank_;
+    grow(r.offsets, static_cast<size_t>(kProjChunk) + 1);
+    grow(r.phrase, static_cast<size_t>(kProjChunk) * dw);
+    std::vector<int64_t> iota(static_cast<size_t>(kProjChunk) + 1);
+    for (size_t i = 0; i < iota.size(); ++i) iota[i] = static_cast<int64_t>(i);
+    NVSM_HIP_CHECK(hipMemcpy(r.offsets.p, iota.data(), iota.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!ids_dev) grow(r.ids, static_cast<size_t>(kProjChunk));
+    for (int64_t i0 = 0; i0 < n; i0 += kProjChunk) {
+        const int64_t cn = std::min(kProjChunk, n - i0);
+        const int64_t* ids = ids_dev ? ids_dev + i0 : r.ids.p;
+        if (!ids_dev) {
+            for (int64_t i = 0; i < cn; ++i) iota[static_cast<size_t>(i)] = first + i0 + i;
+            NVSM_HIP_CHECK(hipMemcpyAsync(r.ids.p, iota.data(), static_cast<size_t>(cn) * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+            NVSM_HIP_CHECK(hipStreamSynchronize(stream_));      // (`iota` is rewritten by the next chunk)
+        }
+        RankProf scope(prof, "nbr_project", stream_);
+        launch_rank_query_mean(words_.P.p, dw, cfg_.num_words, ids, nullptr, r.offsets.p, cn, r.phrase.p, lazy_view(words_), err_host_, stream_);
+        float* y = out + static_cast<size_t>(i0) * de;
+        launch_gemm(0, 0, r.phrase.p, T_.p, y, static_cast<int>(cn), de, dw, dw, de, de, 1.f, nullptr, 1, 0, stream_);
+        launch_rank_bias_act(y, b_.p, c, act, cn, de, stream_);
+    }
+}
+
+void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts) {
+    if (!known_space(opt.space)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space");
+    if (opt.similarity != NVSM_SIM_COSINE && opt.similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
+    const int act_opt = opt.activation;
+    if (act_opt != NVSM_ACT_MODEL && act_opt != NVSM_ACT_IDENTITY && act_opt != NVSM_TANH && act_opt != NVSM_HARD_TANH)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown activation");
+    if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
+    const RowSpace sp = row_space(opt.space);
+    const int64_t R = sp.count, Q = q.num_queries;
+    const int dim = sp.dim;
+    if (Q < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_queries is negative");
+    if ((q.ids != nullptr) == (q.vectors != nullptr)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries: exactly one of ids and vectors must be given");
+    if (q.ids) {
+        if (!known_space(q.source_space)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown source space");
+        const RowSpace src = row_space(q.source_space);
+        if (src.dim != dim) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the source space's dimension differs from the searched space's");
+        for (int64_t i = 0; i < Q; ++i)
+            if (q.ids[i] < 0 || q.ids[i] >= src.count) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a query row id is outside the source space");
+    } else if (q.dim != dim) {
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->dim differs from the searched space's dimension");
+    }
+    if (opt.exclude_self && !(q.ids && q.source_space == opt.space))
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "exclude_self needs queries given as row ids of the searched space");
+    if (opt.top_k < 1 || opt.top_k > R) throw Error(NVSM_ERR_INVALID_ARGUMENT, "top_k must be in [1, rows of the searched space]");
+    if (R >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "neighbour search supports fewer than 2^31 rows");
+    const int k = opt.top_k;
+    const int cosine = opt.similarity == NVSM_SIM_COSINE;
+    const int act = act_opt == NVSM_ACT_MODEL ? cfg_.nonlinearity : act_opt;
+    const bool exclude = opt.exclude_self != 0;
+    const int64_t n_out = exclude ? R - 1 : R;               // rows a query can retrieve
+    const int64_t kScoreFloats = static_cast<int64_t>(tune_.rank_slab_mb) * (int64_t(1) << 18);
+    const int64_t proj_rows = std::max<int64_t>(kSlabAlign, kProjSlabBytes / (static_cast<int64_t>(dim) * 4) / kSlabAlign * kSlabAlign);
+    rank_join();
+    RankScratch& r = rank_;
+    LazyView none{};
+    none.stamp = nullptr;
+    const LazyView view = sp.table ? lazy_view(*sp.table) : none;
+
+    for (int64_t q0 = 0; q0 < Q;) {
+        int64_t qn = std::min(kRankChunk, Q - q0);
+        int64_t S = 0, npad = 1, n_keys = 0;
+        for (;;) {
+            S = std::min<int64_t>(R, std::max<int64_t>(kSlabAlign, kScoreFloats / qn / kSlabAlign * kSlabAlign));
+            if (!sp.rows) S = std::min(S, proj_rows);
+            n_keys = 0;
+            for (int64_t d0 = 0; d0 < R; d0 += S) n_keys += std::min<int64_t>(k, std::min(S, R - d0));
+            npad = pow2_at_least(n_keys);
+            if (qn * npad <= kKeyCount || qn == 1) break;
+            qn = (qn + 1) / 2;
+        }
+        // ---- the round's query panel [qn][dim]
+        grow(r.panel, static_cast<size_t>(kRankChunk) * dim);
+        grow(r.ids, static_cast<size_t>(kInferChunk));
+        grow(r.qinv, static_cast<size_t>(kInferChunk));
+        const int64_t* self = nullptr;
+        if (q.ids) NVSM_HIP_CHECK(hipMemcpy(r.ids.p, q.ids + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (exclude) {      // (a copy of its own: r.ids serves project_words' identity lists further down)
+            grow(r.self, static_cast<size_t>(2 * kPairChunk));
+            NVSM_HIP_CHECK(hipMemcpy(r.self.p, q.ids + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
+            self = r.self.p;
+        }
+        if (q.vectors) {
+            NVSM_HIP_CHECK(hipMemcpy(r.panel.p, q.vectors + q0 * dim, static_cast<size_t>(qn) * dim * sizeof(float), hipMemcpyHostToDevice));
+        } else if (q.source_space == NVSM_SPACE_PROJECTED_WORDS) {
+            project_words(r.ids.p, 0, qn, opt.bias_coefficient, act, r.panel.p);
+        } else {
+            const RowSpace src = row_space(q.source_space);
+            RankProf scope(prof, "nbr_gather", stream_);
+            launch_rank_gather_rows(src.rows, dim, r.ids.p, 0, qn, r.panel.p, lazy_view(*src.table), stream_);
+        }
+        { RankProf scope(prof, "nbr_gather", stream_); launch_rank_query_norm(r.panel.p, qn, dim, r.qinv.p, cosine, stream_); }
+        grow(r.keys, static_cast<size_t>(qn * npad));
+        grow(r.out_ids, static_cast<size_t>(qn) * k);
+        grow(r.out_scores, static_cast<size_t>(qn) * k);
+        grow(r.out_counts, static_cast<size_t>(kInferChunk));
+        const int64_t ld = (S + 3) / 4 * 4;
+        grow(r.scores, static_cast<size_t>(qn * ld));
+        grow(r.sel_ws, rank_select_ws_bytes(static_cast<int>(qn), static_cast<int>(S)));
+        if (!sp.rows) grow(r.pslab, static_cast<size_t>(S) * dim);
+        int64_t key_off = 0;
+        for (int64_t d0 = 0; d0 < R; d0 += S) {
+            const int Ss = static_cast<int>(std::min(S, R - d0));
+            const float* rows = sp.rows;
+            int64_t begin = d0;
+            if (!sp.rows) {      // this slab of the projected vocabulary, then scanned as rows 0 .. Ss of the scratch
+                project_words(nullptr, d0, Ss, opt.bias_coefficient, act, r.pslab.p);
+                rows = r.pslab.p;
+                begin = 0;
+            }
+            {
+                RankProf scope(prof, "nbr_scan", stream_);
+                prof.note(nbr_scan_uses_mfma(dim) ? "nbr_scan_mfma" : "nbr_scan_plain");
+                launch_nbr_scan(rows, dim, begin, Ss, r.panel.p, static_cast<int>(qn), r.qinv.p, r.scores.p, ld, cosine, view, stream_);
+                if (self) launch_rank_exclude_self(r.scores.p, ld, d0, Ss, self, static_cast<int>(qn), stream_);
+            }
+            {
+                RankProf scope(prof, "rank_select", stream_);
+                const bool radix = launch_rank_select(r.scores.p, ld, Ss, d0, static_cast<int>(qn), k, r.sel_ws.p, r.keys.p, npad, key_off, stream_);
+                prof.note(radix ? "rank_select_radix" : "rank_select_all");
+            }
+            key_off += std::min<int64_t>(k, Ss);
+        }
+        launch_rank_fill_keys(r.keys.p, npad, n_keys, npad, static_cast<int>(qn), stream_);
+        {
+            RankProf scope(prof, "rank_sort", stream_);
+            const bool global_steps = launch_rank_sort(r.keys.p, npad, static_cast<int>(qn), stream_);
+            prof.note(global_steps ? "rank_sort_global" : "rank_sort_lds");
+            launch_rank_write(r.keys.p, npad, static_cast<int>(qn), k, nullptr, std::min<int64_t>(n_keys, n_out), r.out_ids.p, r.out_scores.p,
+                              r.out_counts.p, stream_);
+        }
+        NVSM_HIP_CHECK(hipMemcpyAsync(ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        q0 += qn;
+    }
+    raise_device_error();
+}
+
+void Model::similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out) {
+    if (!known_space(space)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space");
+    if (similarity != NVSM_SIM_COSINE && similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
+    if (n < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "n is negative");
+    const RowSpace sp = row_space(space);
+    for (int64_t i = 0; i < n; ++i)
+        if (a[i] < 0 || a[i] >= sp.count || b[i] < 0 || b[i] >= sp.count) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a row id is outside the space");
+    rank_join();
+    RankScratch& r = rank_;
+    const int cosine = similarity == NVSM_SIM_COSINE;
+    LazyView none{};
+    none.stamp = nullptr;
+    grow(r.ids, static_cast<size_t>(kInferChunk));
+    grow(r.self, static_cast<size_t>(2 * kPairChunk));
+    grow(r.pair_out, static_cast<size_t>(kPairChunk));
+    if (!sp.rows) {      // where the projected rows of a round's pairs lie in the panel: a at i, b at cn + i
+        std::vector<int64_t> pos(static_cast<size_t>(2 * kPairChunk));
+        for (size_t i = 0; i < pos.size(); ++i) pos[i] = static_cast<int64_t>(i);
+        NVSM_HIP_CHECK(hipMemcpy(r.self.p, pos.data(), pos.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    for (int64_t i0 = 0; i0 < n; i0 += kPairChunk) {
+        const int64_t cn = std::min(kPairChunk, n - i0);
+        // r.ids = [a | b] of the round
+        NVSM_HIP_CHECK(hipMemcpy(r.ids.p, a + i0, static_cast<size_t>(cn) * sizeof(int64_t), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.ids.p + cn, b + i0, static_cast<size_t>(cn) * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (sp.rows) {
+            RankProf scope(prof, "nbr_pairs", stream_);
+            launch_rank_pair_sim(sp.rows, sp.dim, r.ids.p, r.ids.p + cn, cn, r.pair_out.p, cosine, lazy_view(*sp.table), stream_);
+        } else {      // both rows of every pair projected (nvsm_rank_options_default's c and activation), then scored where they lie
+            grow(r.panel, static_cast<size_t>(2 * kPairChunk) * sp.dim);
+            project_words(r.ids.p, 0, 2 * cn, 1.f, cfg_.nonlinearity, r.panel.p);
+            RankProf scope(prof, "nbr_pairs", stream_);
+            launch_rank_pair_sim(r.panel.p, sp.dim, r.self.p, r.self.p + cn, cn, r.pair_out.p, cosine, none, stream_);
+        }
+        NVSM_HIP_CHECK(hipMemcpyAsync(out + i0, r.pair_out.p, static_cast<size_t>(cn) * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
     }
     raise_device_error();
 }

@@ -20,6 +20,10 @@ extern "C" {
 int nvsm_debug_set_table_pass_form(int one_launch) { cunvsm::set_table_pass_one_launch(one_launch != 0); return NVSM_OK; }
 int nvsm_debug_delay(nvsm_model* m, int microseconds) { NVSM_REQUIRE(m); return guarded_on(m, [&] { m->impl.debug_delay(microseconds); }); }
 
+// nvsm_neighbors' scan through rank_scan_plain_kernel whatever the dimension (tools/bench_neighbors.py: the MFMA scan with the tail
+// chunk against the plain scan on the same table, call by call). Process-wide, like the table-pass form above.
+int nvsm_debug_neighbors_force_plain(int on) { cunvsm::set_nbr_scan_force_plain(on != 0); return NVSM_OK; }
+
 // ---- debug hooks (tests only) ----
 int nvsm_debug_gemm(int variant, int M, int N, int K, const float* hostA, const float* hostB, float* hostC) {
     NVSM_REQUIRE(hostA); NVSM_REQUIRE(hostB); NVSM_REQUIRE(hostC);

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmNeighborOptions, NvsmNeighborQueries, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -186,6 +186,64 @@ def rank_options(num_entities, top_k=None, bias_coefficient=1.0, activation="mod
     return opt
 
 
+SPACES = {"words": _lib.SPACE_WORDS, "projected_words": _lib.SPACE_PROJECTED_WORDS, "entities": _lib.SPACE_ENTITIES}
+
+
+def space_shape(cfg, space):
+    """(enum, rows, dimension) of a searched or source space of nvsm_neighbors: "words" | "projected_words" | "entities"."""
+    if isinstance(space, str):
+        if space not in SPACES:
+            raise ValueError("unknown space %r (one of %s)" % (space, sorted(SPACES)))
+        space = SPACES[space]
+    if space == _lib.SPACE_WORDS:
+        return space, int(cfg.num_words), int(cfg.word_repr_size)
+    if space == _lib.SPACE_PROJECTED_WORDS:
+        return space, int(cfg.num_words), int(cfg.entity_repr_size)
+    if space == _lib.SPACE_ENTITIES:
+        return space, int(cfg.num_entities), int(cfg.entity_repr_size)
+    raise ValueError("unknown space %r" % (space,))
+
+
+def neighbor_arguments(cfg, space, ids=None, vectors=None, source=None, top_k=30, exclude_self=False, similarity="cosine",
+                       bias_coefficient=1.0, activation="model"):
+    """(nvsm_neighbor_queries, nvsm_neighbor_options, arrays to keep alive) from keywords; raises ValueError for what the ABI
+    would refuse (no device needed)."""
+    space, rows, dim = space_shape(cfg, space)
+    if (ids is None) == (vectors is None):
+        raise ValueError("exactly one of ids and vectors must be given")
+    ropt = rank_options(rows, None, bias_coefficient=bias_coefficient, activation=activation, similarity=similarity)
+    q = NvsmNeighborQueries()
+    if ids is not None:
+        src, src_rows, src_dim = space_shape(cfg, space if source is None else source)
+        if src_dim != dim:
+            raise ValueError("the source space's dimension %d differs from the searched space's dimension %d" % (src_dim, dim))
+        if np.asarray(ids).ndim > 1:
+            raise ValueError("ids must be a flat list of row ids")
+        data = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).ravel())
+        if data.size and (data.min() < 0 or data.max() >= src_rows):
+            raise ValueError("a query row id is outside [0, %d)" % src_rows)
+        if exclude_self and src != space:
+            raise ValueError("exclude_self needs queries given as row ids of the searched space")
+        q.ids, q.vectors, q.num_queries, q.source_space, q.dim = data.ctypes.data, None, data.size, src, dim
+    else:
+        if source is not None:
+            raise ValueError("source names the space of ids; vectors have none")
+        if exclude_self:
+            raise ValueError("exclude_self needs queries given as row ids of the searched space")
+        data = np.ascontiguousarray(vectors, dtype=np.float32)
+        if data.ndim == 1:
+            data = data.reshape(1, -1)
+        if data.ndim != 2 or data.shape[1] != dim:
+            raise ValueError("vectors has shape %s, expected [num_queries][dimension of the searched space = %d]" % (data.shape, dim))
+        q.ids, q.vectors, q.num_queries, q.source_space, q.dim = None, data.ctypes.data, data.shape[0], space, dim
+    if not 1 <= int(top_k) <= rows:
+        raise ValueError("top_k = %d outside [1, rows of the searched space = %d]" % (int(top_k), rows))
+    opt = NvsmNeighborOptions()
+    opt.space, opt.similarity, opt.top_k, opt.exclude_self = space, ropt.similarity, int(top_k), int(bool(exclude_self))
+    opt.bias_coefficient, opt.activation = ropt.bias_coefficient, ropt.activation
+    return q, opt, data
+
+
 class Model:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -300,6 +358,60 @@ class Model:
         check(lib().nvsm_rank(self._h, C.byref(st), C.byref(opt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         del keep
         return ids, scores, counts
+
+    # -- nearest neighbours in word, projected-word and document space (py/nvsm/base.py:106-162, 325-353, 362-430) ----
+    def neighbors(self, space, ids=None, vectors=None, source=None, top_k=30, exclude_self=False, similarity="cosine",
+                  **projection_opts):
+        """The top_k rows of `space` ("words" | "projected_words" | "entities") nearest to each query:
+        (ids [Q, k] int64, scores [Q, k] float32, counts [Q] int64), by score descending, ties by ascending id; slots beyond
+        counts[q] hold (-1, -inf). Queries: `ids`, row ids of `source` (default: the searched space), or `vectors` [Q, dim]
+        float32. exclude_self (ids of the searched space only) leaves a query's own row out. projection_opts
+        (bias_coefficient, activation: as infer) apply where projected words are searched or are the source."""
+        q, opt, keep = neighbor_arguments(self.cfg, space, ids, vectors, source, top_k, exclude_self, similarity, **projection_opts)
+        k = opt.top_k
+        out_ids = np.empty((q.num_queries, k), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        check(lib().nvsm_neighbors(self._h, C.byref(q), C.byref(opt), out_ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        del keep
+        return out_ids, scores, counts
+
+    def similarity(self, space, a, b, similarity="cosine"):
+        """Scores of row a[i] against row b[i] of one space, float32 [n] (nvsm_similarity)."""
+        space, rows, _ = space_shape(self.cfg, space)
+        if isinstance(similarity, str):
+            if similarity not in SIMILARITIES:
+                raise ValueError("unknown similarity %r (one of %s)" % (similarity, sorted(SIMILARITIES)))
+            similarity = SIMILARITIES[similarity]
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.int64).ravel())
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.int64).ravel())
+        if a.size != b.size:
+            raise ValueError("a holds %d ids, b holds %d" % (a.size, b.size))
+        for x in (a, b):
+            if x.size and (x.min() < 0 or x.max() >= rows):
+                raise ValueError("a row id is outside [0, %d)" % rows)
+        out = np.empty(a.size, dtype=np.float32)
+        check(lib().nvsm_similarity(self._h, space, a.ctypes.data, b.ctypes.data, a.size, int(similarity), out.ctypes.data))
+        return out
+
+    def related_terms(self, word_ids, top_k=30):
+        """NVSM.related_terms (base.py:325-342): the cosine neighbours of words among the word rows, the word itself included."""
+        return self.neighbors("words", ids=word_ids, top_k=top_k)
+
+    def term_similarity(self, a, b):
+        """NVSM.term_similarity (base.py:344-353): cosine similarity of word rows a[i] and b[i]; a float for two scalars."""
+        out = self.similarity("words", a, b)
+        return float(out[0]) if np.ndim(a) == 0 and np.ndim(b) == 0 else out
+
+    def nearest_terms(self, entity_ids=None, vectors=None, top_k=20, **projection_opts):
+        """TermBruteforcer (base.py:106-162, cardinality 1): the words whose projection f(T·W[w] + c·b) lies closest to
+        document rows (entity_ids) or to vectors of document space."""
+        return self.neighbors("projected_words", ids=entity_ids, vectors=vectors, source=None if entity_ids is None else "entities",
+                              top_k=top_k, **projection_opts)
+
+    def related_documents(self, entity_ids, top_k=10, exclude_self=False):
+        """Documents near documents (query_using_projected_query, base.py:362-430, with document rows as the queries)."""
+        return self.neighbors("entities", ids=entity_ids, top_k=top_k, exclude_self=exclude_self)
 
     # -- parameters / tensors ----------------------------------------------------------------------
     def step_deferred(self, batch, learning_rate, entity_ids=None):

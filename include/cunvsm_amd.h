@@ -270,6 +270,60 @@ int nvsm_infer(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_optio
 int nvsm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* opt,
               int64_t* doc_ids, float* scores, int64_t* counts);
 
+/*
+ * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query
+ * library does with the same parameters (py/nvsm/base.py). Semantics, pinned by the reference:
+ *   space        NVSM_SPACE_WORDS: the rows of W, dimension word_repr_size — NVSM.related_terms (base.py:325-342) and
+ *                term_similarity (:344-353), cosine neighbours of a word among the word rows.
+ *                NVSM_SPACE_PROJECTED_WORDS: row w is f(T·W[w] + c·b), dimension entity_repr_size — the vocabulary projected
+ *                into document space, which TermBruteforcer (base.py:106-162, n-gram cardinality 1) searches for the terms
+ *                closest to a document vector ("which terms describe this document"). NO batch normalisation;
+ *                bias_coefficient and activation mean exactly what they mean in nvsm_rank_options, with the same defaults
+ *                and the same quirk (c = 0 is what py/query.py computes; not "fixed" here).
+ *                NVSM_SPACE_ENTITIES: the rows of E, dimension entity_repr_size — query_using_projected_query
+ *                (base.py:362-430) called with a vector that is not a projected query: documents near a document.
+ *   queries      one vector of the searched space's dimension per query, given EITHER as row ids of a source space (ids,
+ *                source_space; vectors NULL) OR as host floats [num_queries][dim] (vectors, dim; ids NULL). A source whose
+ *                dimension differs from the searched space's is NVSM_ERR_INVALID_ARGUMENT before anything runs, and so are
+ *                ids out of range, unknown enums, top_k outside [1, rows of the space], both or neither of ids / vectors.
+ *   exclude_self only with row ids of the searched space itself: the query's own row is left out and
+ *                counts[q] = min(top_k, rows - 1). Default 0: the reference does not exclude — related_terms returns the
+ *                term itself among its 30.
+ *   score        NVSM_SIM_COSINE or NVSM_SIM_DOT. A zero row or a zero query has inverse norm 0: score 0, never NaN.
+ *   result       as nvsm_rank: the top_k rows by score descending, ties by ASCENDING id; slots beyond counts[q] hold
+ *                (-1, -inf); a pure function of the parameters and the arguments (a repeated call returns the same bits).
+ * nvsm_neighbors is synchronous and returns host results; it runs behind everything earlier steps have queued (the side
+ * streams' tails included) and leaves parameters, optimiser state and the lazy-decay bookkeeping untouched: tables are read
+ * through their view, nothing is flushed. The projected vocabulary is produced one slab of at most 64 MB at a time, never as
+ * the whole [num_words][entity_repr_size] matrix. Device scratch is allocated by the first call, not by nvsm_create.
+ * nvsm_similarity: out[i] = the score of row a[i] against row b[i] of one space for n pairs (term_similarity batched), the
+ * same lazy view; in NVSM_SPACE_PROJECTED_WORDS the rows are projected with nvsm_rank_options_default's c and activation.
+ */
+enum { NVSM_SPACE_WORDS = 0, NVSM_SPACE_PROJECTED_WORDS = 1, NVSM_SPACE_ENTITIES = 2 };
+typedef struct {
+    const int64_t* ids;           /* [num_queries] host: row ids of source_space, or NULL */
+    const float*   vectors;       /* [num_queries][dim] host, or NULL */
+    int64_t        num_queries;
+    int32_t        source_space;  /* NVSM_SPACE_*: what ids index (ignored with vectors) */
+    int32_t        dim;           /* floats per vector (ignored with ids) */
+} nvsm_neighbor_queries;
+typedef struct {
+    int32_t space;                /* NVSM_SPACE_*: the rows searched */
+    int32_t similarity;           /* NVSM_SIM_* */
+    int32_t top_k;
+    int32_t exclude_self;
+    float   bias_coefficient;     /* projected words, searched or as the source: as nvsm_rank_options */
+    int32_t activation;
+    int32_t reserved[6];
+} nvsm_neighbor_options;
+/* NVSM_SPACE_WORDS, NVSM_SIM_COSINE, top_k 30 (related_terms' default), exclude_self 0, bias_coefficient 1, NVSM_ACT_MODEL */
+void nvsm_neighbor_options_default(nvsm_neighbor_options* opt);
+/* ids, scores [num_queries][top_k], counts [num_queries], all host */
+int nvsm_neighbors(nvsm_model* m, const nvsm_neighbor_queries* queries, const nvsm_neighbor_options* opt,
+                   int64_t* ids, float* scores, int64_t* counts);
+/* a, b [n] host row ids of `space`; out [n] host */
+int nvsm_similarity(nvsm_model* m, int32_t space, const int64_t* a, const int64_t* b, int64_t n, int32_t similarity, float* out);
+
 /* Streams. A handle issues its work on FOUR HIP streams of its own device: the main stream (highest priority: the step's
  * critical chain), two side streams (lowest priority: the batch → row-order sorts, and — in nvsm_step — the documents
  * update and the ∂T GEMM + projection update, which keep running after nvsm_step has returned and are joined by the next

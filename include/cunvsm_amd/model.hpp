@@ -140,12 +140,46 @@ class Model {
         return r;
     }
 
+    // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
+    // 362-430): queries are row ids of `source_space`, or vectors [n][dim] of the searched space (neighbors_of_vectors)
+    struct Neighbors { std::vector<int64_t> ids; std::vector<float> scores; std::vector<int64_t> counts; int32_t top_k; };
+    Neighbors neighbors(const std::vector<int64_t>& row_ids, int32_t source_space, const nvsm_neighbor_options& opt) {
+        nvsm_neighbor_queries q;
+        q.ids = row_ids.data(); q.vectors = nullptr; q.num_queries = static_cast<int64_t>(row_ids.size());
+        q.source_space = source_space; q.dim = 0;
+        return neighbors_of(q, opt);
+    }
+    Neighbors neighbors_of_vectors(const std::vector<float>& vectors, int32_t dim, const nvsm_neighbor_options& opt) {
+        if (dim < 1 || vectors.size() % static_cast<size_t>(dim) != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "vectors: a whole number of rows of dim floats");
+        nvsm_neighbor_queries q;
+        q.ids = nullptr; q.vectors = vectors.data(); q.num_queries = static_cast<int64_t>(vectors.size() / static_cast<size_t>(dim));
+        q.source_space = opt.space; q.dim = dim;
+        return neighbors_of(q, opt);
+    }
+    // NVSM.term_similarity (base.py:344-353) batched: the score of row a[i] against row b[i] of one space
+    std::vector<float> similarity(int32_t space, const std::vector<int64_t>& a, const std::vector<int64_t>& b, int32_t sim = NVSM_SIM_COSINE) {
+        if (a.size() != b.size()) throw Error(NVSM_ERR_INVALID_ARGUMENT, "similarity: a and b differ in length");
+        std::vector<float> out(a.size() + 1);
+        check(nvsm_similarity(h_, space, a.data(), b.data(), static_cast<int64_t>(a.size()), sim, out.data()));
+        out.resize(a.size());
+        return out;
+    }
+
     void synchronize() { check(nvsm_synchronize(h_)); }
     void comm_init(const char id[128]) { check(nvsm_comm_init(h_, id)); }
     nvsm_model* handle() { return h_; }
     const nvsm_config& config() const { return cfg_; }
 
  private:
+    Neighbors neighbors_of(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt) {
+        Neighbors r;
+        r.top_k = opt.top_k;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        r.ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_neighbors(h_, &q, &opt, r.ids.data(), r.scores.data(), r.counts.data()));
+        r.ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
     static nvsm_queries queries_of(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const std::vector<float>* word_weights) {
         if (offsets.empty() || offsets.back() != static_cast<int64_t>(word_ids.size()) || (word_weights && word_weights->size() != word_ids.size()))
             throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries: offsets must end at word_ids.size(), weights must match word_ids");

@@ -20,6 +20,9 @@ int nvsm_debug_delay(nvsm_model* m, int microseconds);
 /* table passes of the update in one launch (1, the default) or as the three launches chunk / level-2 / rows (0): the two
  * forms are bit-identical (tests/test_gpu_parity.py); process-wide */
 int nvsm_debug_set_table_pass_form(int one_launch);
+/* nvsm_neighbors' scan through the plain kernel whatever the dimension (1) or by its own dispatch (0, the default): how
+ * tools/bench_neighbors.py holds the MFMA scan with the tail chunk against the plain scan on the same table; process-wide */
+int nvsm_debug_neighbors_force_plain(int on);
 /* the stable (row, entry) radix sort alone: keys of `bits` significant bits in, sorted keys + their original positions out */
 /* average ms per launch of a batch-sized projection product on device operands (extras: 1 = column statistics, 2 = row sums of squares) */
 int nvsm_debug_gemm_time(int b_layout, int M, int N, int K, int extras, int repeats, float* avg_ms);
