@@ -52,6 +52,15 @@ class NvsmBatch(C.Structure):
     ]
 
 
+class NvsmPairBatch(C.Structure):
+    _fields_ = [("pairs", C.c_void_p), ("weights", C.c_void_p), ("num_pairs", C.c_int64), ("on_device", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class NvsmMixture(C.Structure):
+    _fields_ = [("text_weight", C.c_float), ("pair_weight", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
 class NvsmQueries(C.Structure):
     _fields_ = [("word_ids", C.c_void_p), ("word_weights", C.c_void_p), ("offsets", C.c_void_p), ("num_queries", C.c_int64)]
 
@@ -179,6 +188,8 @@ def lib():
         "nvsm_update": (C.c_int, [vp, C.c_float, C.c_float]), "nvsm_get_cost": (C.c_int, [vp, P(C.c_float)]), "nvsm_get_cost_f64": (C.c_int, [vp, P(C.c_double)]),
         "nvsm_scaled_regularization_lambda": (C.c_float, [vp]),
         "nvsm_step": (C.c_int, [vp, P(NvsmBatch), vp, C.c_float, P(C.c_float)]),
+        "nvsm_compute_cost_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture)]),
+        "nvsm_step_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture), C.c_float, P(C.c_float)]),
         "nvsm_step_deferred": (C.c_int, [vp, P(NvsmBatch), vp, C.c_float, P(i64)]),
         "nvsm_deferred_cost": (C.c_int, [vp, i64, P(C.c_float)]), "nvsm_wait_inputs": (C.c_int, [vp]),
         "nvsm_tensor_size": (C.c_int, [vp, cp, P(i64)]), "nvsm_get_tensor": (C.c_int, [vp, cp, vp, i64]),

@@ -228,6 +228,38 @@ void launch_loss(const LossArgs& a, hipStream_t s);
 bool loss_reads_lazily(int de, int R, bool l2_entity);
 bool loss_two_row_sets(int64_t table_rows, int de);      // the row-gathering loss kernel keeps two sets of rows in flight per wave (tables beyond the Infinity Cache)
 
+// ---- entity-entity similarity objective: forward + first half of the backward pass (pairs.hip; replaces
+// RepresentationSimilarity::Objective, cpp/objective.cu:485-696) -------------------------------------------------------------
+struct PairArgs {
+    const float* E;           // [nD][de]
+    int64_t E_rows;
+    LazyView lazyE;           // pending decay of E's rows, applied as they are read (stamp null: none)
+    const int* ids;           // [2M] interleaved a_p, b_p (narrowed: out-of-range ids are row 0)
+    const float* w;           // [M] pair weights or null (= all 1.0)
+    float* X;                 // [2M][de] OUT gradient source rows: row 2p = E[b_p], row 2p + 1 = E[a_p]
+    float* coef;              // OUT coefficient of entry i at coef[i * coef_stride]: mult_p x scale for i = 2p, 2p + 1
+    int coef_stride;
+    float* sq;                // [2M]  OUT mean of squares of the entry's source row
+    float* probs;             // [M]   OUT
+    float* mults;             // [M]   OUT mult_p x scale
+    double* loss_acc;         // [1]   Σ ω·log prob, written (not accumulated) by the ordered grid-wide sum
+    GridSumWs sums;           // its workspace: one column group, pair_loss_blocks(M, de) contributions of one double
+    int64_t M;
+    int de;
+    float sig_eps, sig_hi, d_eps;
+    double d_hi;
+    float inv_batch;          // exp(−log(M))
+    float scale;              // mixture scale w_ee / (w_te + w_ee); 1 for the pair objective alone
+    float inv_de;
+};
+int pair_loss_blocks(int64_t M, int de);      // workgroups launch_pair_loss uses (sizes GridSumWs::contrib_cap)
+void launch_pair_loss(const PairArgs& a, hipStream_t s);
+// the entry ids of the merged documents update: vals[i] = i for the n_text text entries, (first_src + j) * R for pair entry j —
+// the id whose quotient by R is the entry's source row behind the text objective's (model.cpp compute_cost)
+void launch_pair_entry_ids(int* vals, int64_t n_text, int64_t first_src, int R, int64_t n_pair, hipStream_t s);
+void launch_pair_scale_weights(const float* w, float scale, float* out, int64_t n, hipStream_t s);      // out[i] = (w ? w[i] : 1) · scale
+void launch_pair_materialize(const float* coef, int coef_stride, const float* X, int64_t n, int de, float* out, hipStream_t s);   // tests
+
 // per-row mean of squares: out[b] = Σ_t G[b][t]² · inv_dim  (cpp/updates_adam.cu:232-240)
 void launch_row_meansq(const float* G, int64_t rows, int dim, float inv_dim, float* out, hipStream_t s);
 // grad_entity[j][t] = coef[j] · proj[j/R][t]  (tests / gradient checker only)

@@ -355,17 +355,13 @@ bool Model::table_decays_lazily(bool documents, int64_t rows, int dim, int64_t m
            static_cast<double>(rows) * table_split_ratio() >= static_cast<double>(max_entries);
 }
 
-void Model::alloc_table(TableState& t, int64_t rows, int dim, int64_t max_entries) {
-    t.rows = rows; t.dim = dim; t.max_entries = max_entries;
-    t.P.alloc(rows * dim, true);
-    const int method = cfg_.update_method, mode = cfg_.adam_mode;
-    if (method == NVSM_ADAGRAD) {
-        t.sc[0].alloc(rows, true); t.sc[1].alloc(rows, true);
-    } else if (method == NVSM_ADAM) {
-        t.m.alloc(rows * dim, true);
-        if (mode == NVSM_ADAM_DENSE_UPDATE_DENSE_VARIANCE) t.vfull.alloc(rows * dim, true);
-        else { t.sc[0].alloc(rows, true); t.sc[1].alloc(rows, true); }
-    }
+// The per-step CSR workspace of a table for up to `max_entries` entries (alloc_table; again, larger, by the first pair call for the
+// documents table — whether the level-1 chunks get a batch order stays what the handle's text batches decided).
+void Model::alloc_table_csr(TableState& t, int64_t max_entries, bool chunk_order) {
+    const int64_t rows = t.rows;
+    const int dim = t.dim;
+    const int method = cfg_.update_method;
+    t.max_entries = max_entries;
     // (a long row of c entries has at most c / chunk + 1 chunks and there are fewer than n / chunk long rows: at most 2 n / chunk
     //  chunks; SGD / Adagrad handles cut the long rows of their small batches into shorter chunks — chunk_entries())
     {
@@ -385,14 +381,32 @@ void Model::alloc_table(TableState& t, int64_t rows, int dim, int64_t max_entrie
         // (batches of a few thousand windows are launch-latency chains: no extra launches there)
         // (from 60 x 4096 entries: the 2-GPU share of the metric's batch, 25 600 windows of ten words, 0.5428 -> 0.5363 ms with the order;
         //  16 384 windows: 0.425 -> 0.429 the other way; 12 800: nothing)
-        if (chunk_order_enabled() && max_entries >= 60 * 4096) x.chunk_order.alloc(t.max_chunks, true);
+        if (chunk_order) x.chunk_order.alloc(t.max_chunks, true);
     }
     if (t.idx[0].chunk_order.p) { t.chunk_key.alloc(t.max_chunks, true); t.chunk_key_sorted.alloc(t.max_chunks, true); }
     t.partial.alloc(static_cast<size_t>(t.max_chunks) * dim);
     t.partial_q.alloc(t.max_chunks, true);
     t.partial2.alloc(static_cast<size_t>(t.max_chunks2) * dim);
     t.partial2_q.alloc(t.max_chunks2, true);
-    t.arrive_row.alloc(rows, true); t.arrive2.alloc(t.max_chunks2, true);      // zero once: the last arriver resets its counter
+    t.arrive2.alloc(t.max_chunks2, true);      // zero once: the last arriver resets its counter
+    t.sort_bits = bits_for(rows);
+    t.sort_temp_bytes = sort_pairs_temp_bytes(max_entries, t.sort_bits);
+    t.sort_temp.alloc(t.sort_temp_bytes, true);      // zero once: the arrival counter only ever grows
+}
+
+void Model::alloc_table(TableState& t, int64_t rows, int dim, int64_t max_entries) {
+    t.rows = rows; t.dim = dim; t.max_entries = max_entries;
+    t.P.alloc(rows * dim, true);
+    const int method = cfg_.update_method, mode = cfg_.adam_mode;
+    if (method == NVSM_ADAGRAD) {
+        t.sc[0].alloc(rows, true); t.sc[1].alloc(rows, true);
+    } else if (method == NVSM_ADAM) {
+        t.m.alloc(rows * dim, true);
+        if (mode == NVSM_ADAM_DENSE_UPDATE_DENSE_VARIANCE) t.vfull.alloc(rows * dim, true);
+        else { t.sc[0].alloc(rows, true); t.sc[1].alloc(rows, true); }
+    }
+    alloc_table_csr(t, max_entries, chunk_order_enabled() && max_entries >= 60 * 4096);
+    t.arrive_row.alloc(rows, true);      // zero once: the last arriver resets its counter
     {
         const bool sparse_adam = method == NVSM_ADAM && mode <= NVSM_ADAM_SPARSE;
         // When lazy decay pays. The dense passes it saves must cost more than what it adds (a snapshot and a stamp launch per
@@ -407,9 +421,6 @@ void Model::alloc_table(TableState& t, int64_t rows, int dim, int64_t max_entrie
         if (t.lazy) t.stamp.alloc(rows, true);
         for (float& d : t.decay_hist) d = 1.f;
     }
-    t.sort_bits = bits_for(rows);
-    t.sort_temp_bytes = sort_pairs_temp_bytes(max_entries, t.sort_bits);
-    t.sort_temp.alloc(t.sort_temp_bytes, true);      // zero once: the arrival counter only ever grows
 }
 
 void Model::alloc_sums(SumsBufs& b, int colgroups, int contrib_cap, int width_cap) {
@@ -584,6 +595,7 @@ Model::~Model() {
     if (ev_csr_) (void)hipEventDestroy(ev_csr_);
     for (hipEvent_t e : {ev_loss_, ev_dx_, ev_bwdx_, ev_E_done_, ev_T_done_, ev_copied_, ev_step_begin_[0], ev_step_begin_[1],
                          ev_host_ids_[0], ev_host_ids_[1], ev_gathered_, ev_words_late_, ev_cost_ready_, ev_cost_copied_, ev_untouched_}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {ev_pair_, ev_pair_copied_}) if (e) (void)hipEventDestroy(e);
     if (cost_host_) (void)hipHostFree(cost_host_);
     for (int p = 0; p < 2; ++p) if (host_ids_pin_[p]) (void)hipHostFree(host_ids_pin_[p]);
     if (err_host_) (void)hipHostFree(err_host_);
@@ -637,8 +649,9 @@ void Model::raise_device_error() {
     //  the next stand-alone update() skip that decay or refuse to run)
     words_untouched_hoisted_ = false; words_untouched_pending_ = false; words_snapshot_early_ = false;
     settle_words_stamp();
-    for (DevBuf<int>* b : {&sums_fwd_.arrive, &sums_bwd_.arrive, &words_.arrive_row, &words_.arrive2, &ents_.arrive_row, &ents_.arrive2})
+    for (DevBuf<int>* b : {&sums_fwd_.arrive, &sums_bwd_.arrive, &words_.arrive_row, &words_.arrive2, &ents_.arrive_row, &ents_.arrive2, &sums_pair_.arrive})
         if (b->p) (void)hipMemset(b->p, 0, b->n * sizeof(int));
+    pair_pending_ = false;
     (void)hipDeviceSynchronize();      // (the fills are queued on the null stream, which the handle's streams do not follow)
     if (code == NVSM_BAD_WORD_ID) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a word id of the batch is outside [0, num_words)");
     if (code == NVSM_BAD_ENTITY_ID) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a document id of the batch is outside [0, num_entities)");
@@ -948,6 +961,12 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
     cost_valid_ = false;
     loss_reduced_ = false;
     loss_folded_ = false;
+    // a mixed forward pass (compute_cost_mixed): the pair objective rides along — its ids behind the document ids, its kernel on
+    // side stream 1 under the forward pass, its entries in the documents CSR. Nothing below differs for a text-only pass.
+    const bool mixed = pair_req_ != nullptr;
+    mode_ = mixed ? MODE_MIXED : MODE_TEXT;
+    M_ = mixed ? pair_req_->num_pairs : 0;
+    const int64_t M2 = 2 * M_;
     RangeScope range_cc("ComputeCost");                 // cpp/main.cu:409
     if (cfg_.l2_normalize_entity_reprs) join_E();      // that documents update still reads ids_, which the prologue rewrites
     // The previous step's CSR builds (radix sorts on the side streams) read ids_ / widx_, which this step's prologue is
@@ -963,6 +982,7 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
     }
 
     ids_p_ = (ids_p_ == ids_buf_[0].p) ? ids_buf_[1].p : ids_buf_[0].p;
+    if (mixed) stage_pairs(*pair_req_, ids_p_ + N);      // (in front of the prologue, whose completion event says "ids final")
     // device-sampler mode: zeroing the statistics, narrowing the word ids and drawing the document ids are one launch
     const bool fused_prologue = !entity_ids && cfg_.sampler != NVSM_SAMPLER_HOST_MINSTD;
     if (!fused_prologue) {
@@ -1090,6 +1110,11 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
     const int csr_after = tune_.csr_after;
     if (!fused_prologue || exact_) NVSM_HIP_CHECK(hipEventRecord(ev_inputs_, stream_));
     inputs_recorded_ = true;
+    // The pair kernel needs E and the pair ids only: side stream 1, behind the previous step's documents update (which ran there,
+    // or on the main stream in front of this event) and under this step's forward pass. Not where the generic loss kernel has the
+    // batch's rows of a lazily decayed table refreshed in place first (below): behind the loss kernel then.
+    const bool pair_on_main = mixed && (debug_ || (ents_.lazy && !loss_reads_lazily(de, static_cast<int>(R_), cfg_.l2_normalize_entity_reprs != 0)));
+    if (mixed && !pair_on_main) launch_pairs(aux_stream_, ev_inputs_);
     // two side streams: the sorts are latency-bound chains of small launches, so the two tables' builds run next to
     // each other (at batch 4096 one behind the other they were the longest chain of the whole step)
     // Which side stream builds which table's CSR. Side stream 1 still carries the PREVIOUS step's documents update when this
@@ -1116,7 +1141,7 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         if ((which & 1) && se != aux_stream_ && E_pending_ && ents_.idx_sets < 2) NVSM_HIP_CHECK(hipStreamWaitEvent(se, ev_E_done_, 0));
         if (which & 1) csr_joined_ents_ = false;
         if (which & 2) { csr_joined_words_ = false; words_csr_stream_ = sw; }
-        auto ents = [&] { { PROF_ON("csr_entities", se); build_csr(ents_, csr_ids, Bu * R_, se); } NVSM_HIP_CHECK(hipEventRecord(ev_csr_ents_, se)); };
+        auto ents = [&] { { PROF_ON("csr_entities", se); build_csr(ents_, csr_ids, Bu * R_ + M2, se, M2); } NVSM_HIP_CHECK(hipEventRecord(ev_csr_ents_, se)); };
         // (lazily decayed words table with a per-row scalar: the scalars of the rows this batch touches are brought up to date
         //  into the snapshot the moments pass reads right here, behind the build that lists those rows — it needs nothing the
         //  step computes, and in front of the words update it was a launch of 7 us on the critical stream)
@@ -1248,6 +1273,12 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         a.pre = pre_.p; a.bn_mean = bn_mean_.p; a.bn_inv_std = bn_inv_std_.p; a.bias = b_.p;
         a.bn_sums = stats_fwd_; a.bn_n = bn_n; a.bn_eps = 1e-4f;
         a.E = ents_.P.p; a.E_rows = ents_.rows; a.ids = ids_p_; a.inst_w = instw_;
+        if (mixed) {
+            // the text objective's share w_te / (w_te + w_ee) (MergeGradientsFn): dy and the multipliers are linear in the instance
+            // weights, so a scaled copy of them carries it; get_cost divides the loss word back
+            launch_pair_scale_weights(instw_, text_scale_, instw_scaled_.p, B, stream_);
+            a.inst_w = instw_scaled_.p;
+        }
         a.proj = proj_.p; a.dy = dy_.p; a.coef = coef_.p; a.probs = probs_.p; a.pp = pp_.p;
         a.loss_acc = stats_bwd_; a.colstats = stats_bwd_ + 1; a.sums = sums_bwd_.ws;
         a.B = B; a.de = de; a.R = R_; a.k = k;
@@ -1270,7 +1301,7 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
                 // the generic loss kernel (odd dimensions, entity normaliser) reads the rows as they are: the documents of
                 // this batch (the touched list of their CSR) are brought up to date first, behind the sort
                 NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_ents_, 0));
-                Csr ce = csr_of(ents_, Bu * R_);
+                Csr ce = csr_of(ents_, Bu * R_ + M2);
                 lazy_refresh(ents_, &ce, stream_);
             }
         }
@@ -1288,6 +1319,7 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         } else launch_loss(a, stream_);
         if (!prof_bound) prof.end(stream_);
     }
+    if (pair_on_main) launch_pairs(stream_, nullptr);
     if (csr_after == 3 && !csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(ev_gathered_); }
     if (words_csr_late) { NVSM_HIP_CHECK(hipEventRecord(ev_words_late_, stream_)); launch_csr_builds(ev_words_late_, 2); }
     NVSM_HIP_CHECK(hipGetLastError());      // a failed launch of any kernel above surfaces here, not at the next sync
@@ -1309,6 +1341,7 @@ void Model::compute_gradients() {
     if (!have_forward_) throw Error(NVSM_ERR_STATE, "compute_gradients requires compute_cost");
     NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
     RangeScope range_cg("ComputeGradients");            // cpp/main.cu:414
+    if (mode_ == MODE_PAIRS) { have_grads_ = true; return; }      // (the pair kernel left rows, coefficients and means of squares: nothing else has a gradient)
     backward_dx();
     backward_T(stream_);
     NVSM_HIP_CHECK(hipGetLastError());
@@ -1553,7 +1586,16 @@ void Model::backward_T(hipStream_t strm) {
     }
 }
 
+// ForwardResult::scaled_regularization_lambda: lambda / M for the pair objective (intermediate_results.cu:126-129), the mean of the
+// two for the mixed one (AverageFn over the forward results)
+float Model::scaled_lambda_for(int mode, int64_t B, int64_t M) const {
+    const float lam = cfg_.regularization_lambda;
+    if (mode == MODE_PAIRS) return lam / static_cast<float>(static_cast<double>(M));
+    return (lam / static_cast<float>(static_cast<double>(B)) + lam / static_cast<float>(static_cast<double>(M))) / 2.f;
+}
+
 float Model::scaled_regularization_lambda() const {
+    if (mode_ != MODE_TEXT) return scaled_lambda_for(mode_, B_, M_);
     const double Bg = static_cast<double>(B_ > 0 ? B_ : cfg_.max_batch_size) * (cfg_.world_size > 1 ? cfg_.world_size : 1);
     return cfg_.regularization_lambda / static_cast<float>(Bg);      // intermediate_results.cu:126-129
 }
@@ -1561,6 +1603,19 @@ float Model::scaled_regularization_lambda() const {
 // ForwardResult::get_cost (intermediate_results.cu:80-124): −(Σ mass)/B, one D2H + stream sync.
 float Model::get_cost() {
     if (!have_forward_) throw Error(NVSM_ERR_STATE, "get_cost requires compute_cost");
+    if (!cost_valid_ && mode_ != MODE_TEXT) {
+        // the pair objective's loss word (and the text objective's, whose instance weights carried the mixture scale)
+        if (pair_pending_) { NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_pair_, 0)); pair_pending_ = false; }
+        double st = 0.0, sp = 0.0;
+        if (mode_ == MODE_MIXED) NVSM_HIP_CHECK(hipMemcpyAsync(&st, stats_bwd_, sizeof(double), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(&sp, pair_loss_.p, sizeof(double), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        raise_device_error();
+        pair_cost_ = -(sp / static_cast<double>(M_));
+        text_cost_ = mode_ == MODE_MIXED ? -((st / static_cast<double>(text_scale_)) / static_cast<double>(B_)) : 0.0;
+        cost_ = mode_ == MODE_MIXED ? (text_cost_ + pair_cost_) / 2.0 : pair_cost_;      // AverageFn: an unweighted mean
+        cost_valid_ = true;
+    }
     if (!cost_valid_) {
         double s = 0.0;
         const double* src = stats_bwd_;
@@ -1617,11 +1672,18 @@ Csr Model::csr_of(TableState& t, int64_t n) {
     return c;
 }
 
-void Model::build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s) {
+void Model::build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s, int64_t n_pair_entries) {
     if (t.idx_sets > 1) t.idx_cur ^= 1;      // the other set may still be read by the previous step's update
     TableState::CsrIndex& x = t.idx[t.idx_cur];
+    // the merged documents update: the last n_pair_entries keys are pair ids, whose entries are numbered (B + i) * R (model.h)
+    const int* vals = nullptr;
+    if (n_pair_entries > 0) {
+        const int64_t n_text = n - n_pair_entries;
+        launch_pair_entry_ids(pair_vals_[t.idx_cur].p, n_text, n_text / R_, R_, n_pair_entries, s);
+        vals = pair_vals_[t.idx_cur].p;
+    }
     // (the sort's first launch also clears the CSR's per-step counters: no memset launch)
-    sort_pairs(t.sort_temp.p, t.sort_temp_bytes, &t.sort_epoch, keys, x.sorted_key.p, nullptr, x.sorted_entry.p, n, t.sort_bits, err_host_, s,
+    sort_pairs(t.sort_temp.p, t.sort_temp_bytes, &t.sort_epoch, keys, x.sorted_key.p, vals, x.sorted_entry.p, n, t.sort_bits, err_host_, s,
                x.csr_zeroed.p, csr_counter_ints(t.rows));
     launch_csr_build(csr_of(t, n), s, n > 0, x.chunk_order.p ? t.chunk_key.p : nullptr);
     if (x.chunk_order.p) launch_chunk_order(csr_of(t, n), t.chunk_key.p, t.chunk_key_sorted.p, t.sort_temp.p, t.sort_temp_bytes, s, /*keys_written=*/n > 0);
@@ -1734,9 +1796,13 @@ static void fill_adam_consts(RowPassArgs& a, float bc, float sl) {
 
 void Model::update_entities(float lr, float sl, hipStream_t strm, hipEvent_t row_pass_after) {
     const UpdateInputs u = update_inputs();
-    const int64_t N = u.B * R_;
+    const int64_t N = ents_entries(u.B);      // (with pairs: the text entries and the 2M pair entries in one CSR — one decay, one step counter)
     const int de = cfg_.entity_repr_size;
     TableState& t = ents_;
+    if (mode_ != MODE_TEXT && pair_stream_ != strm) {      // the pair kernel wrote the pair entries' rows and coefficients
+        NVSM_HIP_CHECK(hipStreamWaitEvent(strm, ev_pair_, 0));
+        if (strm == stream_) pair_pending_ = false;
+    }
     Csr c = csr_of(t, N);
     RowPassArgs a{};
     a.table = 1; a.X = u.proj; a.coefs = u.coef; a.sq_src = u.pp; a.div = static_cast<uint32_t>(R_);
@@ -1777,7 +1843,7 @@ void Model::update_entities(float lr, float sl, hipStream_t strm, hipEvent_t row
     int path;
     // (timed by an event pair that rides on the pass's own launch: the kernel's execution time in the step — bench.py
     //  roofline_update —, not the side stream's wait for it)
-    timed_launch(prof, "row_pass_entities", strm, /*single=*/true, [&] { path = launch_table_pass(c, a, strm); });
+    timed_launch(prof, mode_ != MODE_TEXT ? "row_pass_entities_mixed" : "row_pass_entities", strm, /*single=*/true, [&] { path = launch_table_pass(c, a, strm); });
     if (path == TABLE_PASS_ENTRY_WALK) prof.note("entry_walk_entities");
     if (swap_sc) t.sc_cur ^= 1;
     lazy_end_update(t, c, strm);
@@ -1939,6 +2005,14 @@ std::string Model::describe(int64_t batch) const {
     else out += " | loss loss_kernel (generic)";
     out += std::string(" | tables: words ") + (words_.lazy ? "lazy" : "eager") + " decay, documents " + (ents_.lazy ? "lazy" : "eager") + " decay";
     out += " | CSR stream layout " + std::to_string(tune_.sort_layout >= 0 ? tune_.sort_layout : (dt_main ? 2 : 4));
+    {
+        const bool multi_ok = !(cfg_.update_method == NVSM_ADAGRAD || (cfg_.update_method == NVSM_ADAM && cfg_.adam_mode <= NVSM_ADAM_SPARSE));
+        const bool pairs_ok = cfg_.world_size <= 1 && !cfg_.l2_normalize_entity_reprs;
+        out += std::string(" | pairs: ") + (!pairs_ok ? "refused (data parallel / entity normaliser)"
+               : std::string("pair_loss on side stream 1 under the forward pass, entries merged into the documents pass") +
+                 (multi_ok ? "" : "; the pair objective alone only (the mixed one is refused for this update method)") +
+                 (pairs_ready_ ? "" : "; workspaces not allocated yet"));
+    }
     char buf[2048];
     const char* sw = tuning_describe(tune_, buf, sizeof(buf));
     out += std::string(" | switches: ") + (sw[0] ? sw : "defaults");
@@ -2032,6 +2106,13 @@ void Model::update(float lr, float scaled_lambda) {
     NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_ents_, 0));     // join the side-stream CSR builds
     NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_, 0));
     csr_joined_ents_ = csr_joined_words_ = true;
+    if (mode_ == MODE_PAIRS) {
+        // only the documents table has a gradient: the other parameters are left alone (cpp/params.cu:304-307), their step counters too
+        update_entities(lr, scaled_lambda, stream_);
+        NVSM_HIP_CHECK(hipGetLastError());
+        have_grads_ = false;
+        return;
+    }
     gather_update_inputs();
     update_entities(lr, scaled_lambda, stream_);
     update_words(lr, scaled_lambda);
@@ -2069,6 +2150,7 @@ void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, f
         // lr and λ are known before the forward pass: parts of the update that depend on nothing else can be queued early (compute_cost)
         const double Bg = static_cast<double>(batch.num_instances > 0 ? batch.num_instances : 1) * (cfg_.world_size > 1 ? cfg_.world_size : 1);
         hoist_lr_ = lr; hoist_sl_ = cfg_.regularization_lambda / static_cast<float>(Bg);      // = scaled_regularization_lambda() behind compute_cost
+        if (pair_req_) hoist_sl_ = scaled_lambda_for(MODE_MIXED, batch.num_instances > 0 ? batch.num_instances : 1, pair_req_->num_pairs);
         hoist_untouched_ = tune_.hoist_untouched != 0 && lr >= 0.f && hoist_sl_ > 0.f;
     }
     try { compute_cost(batch, entity_ids); } catch (...) { loss_stop_event_ = nullptr; hoist_untouched_ = false; words_untouched_hoisted_ = false; throw; }
@@ -2078,7 +2160,8 @@ void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, f
     // stream 3 behind an event recorded here lets the host read it while the backward pass and the updates still run, and
     // queue the next step in the meantime (waiting for the whole step instead — get_cost() — left the GPU idle while the host
     // queued: 5 % of the NVSM step). Not under data parallelism, where the word is summed over the ranks in the backward pass.
-    const bool early_cost = cost && cfg_.world_size <= 1 && aux3_stream_ && cost_host_;
+    // (a mixed step's cost is two words, the pair objective's from side stream 1: read by get_cost below)
+    const bool early_cost = cost && cfg_.world_size <= 1 && aux3_stream_ && cost_host_ && mode_ == MODE_TEXT;
     if (early_cost) {
         NVSM_HIP_CHECK(hipEventRecord(ev_cost_ready_, stream_));
         NVSM_HIP_CHECK(hipStreamWaitEvent(aux3_stream_, ev_cost_ready_, 0));
@@ -2223,11 +2306,167 @@ float Model::deferred_cost(int64_t ticket) {
 }
 
 void Model::wait_inputs() {
+    if (pair_copy_pending_) { NVSM_HIP_CHECK(hipEventSynchronize(ev_pair_copied_)); pair_copy_pending_ = false; }
     // a host batch has been consumed once the copy stream is through with it; a device-resident one once the step's
     // prologue and gather have read it (ev_inputs_ sits behind the prologue; the feature weights are read later still,
     // but device-resident batches are the caller's to keep alive until the step has run)
     if (last_batch_on_host_) { if (copied_recorded_) NVSM_HIP_CHECK(hipEventSynchronize(ev_copied_)); }
     else if (inputs_recorded_) NVSM_HIP_CHECK(hipEventSynchronize(ev_inputs_));
+}
+
+// ---------------------------------------------------------------------------------------------
+// entity-entity pairs — RepresentationSimilarity::Objective on ENTITY_REPRS (cpp/objective.cu:485-696) and its mixture with the
+// text objective, TextEntityEntityEntity (:698-745). The arithmetic is pairs.hip's; what is here is where it sits in the step.
+// ---------------------------------------------------------------------------------------------
+void Model::check_pair_request(const nvsm_batch* text, const nvsm_pair_batch& pairs, const nvsm_mixture* mix) const {
+    if (pairs.num_pairs < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_pairs must be at least 1");
+    if (pairs.num_pairs > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_pairs must not exceed max_batch_size");
+    if (!pairs.pairs) throw Error(NVSM_ERR_INVALID_ARGUMENT, "pairs are required");
+    if (text) {
+        if (!mix) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: mix");
+        // CHECK_NE(text_entity_weight_, 0.0) / CHECK_NE(entity_entity_weight_, 0.0), cpp/objective.cu:708-709 (negative shares have no meaning)
+        if (!(mix->text_weight > 0.f) || !(mix->pair_weight > 0.f))
+            throw Error(NVSM_ERR_INVALID_ARGUMENT, "text_weight and pair_weight of a mixture must both be > 0");
+    }
+    if (cfg_.world_size > 1) throw Error(NVSM_ERR_UNSUPPORTED, "the entity-entity objective is not implemented under data parallelism (world_size > 1)");
+    if (cfg_.l2_normalize_entity_reprs) throw Error(NVSM_ERR_UNSUPPORTED, "the entity-entity objective is not implemented together with l2_normalize_entity_reprs");
+    if (text && cfg_.update_method == NVSM_ADAGRAD)
+        throw Error(NVSM_ERR_UNSUPPORTED, "Adagrad currently does not implement multiple gradients.");            // cpp/updates_adagrad.cu:108
+    if (text && cfg_.update_method == NVSM_ADAM && cfg_.adam_mode <= NVSM_ADAM_SPARSE)
+        throw Error(NVSM_ERR_UNSUPPORTED, "Sparse Adam currently does not implement multiple gradients.");        // cpp/updates_adam.cu:348
+    const int64_t rows = static_cast<int64_t>(cfg_.max_batch_size) * 3;      // B + 2M gradient source rows at most
+    if (rows * R_ >= (int64_t(1) << 26))
+        throw Error(NVSM_ERR_UNSUPPORTED, "pairs: 3 x max_batch_size x (num_random_entities + 1) must stay below 2^26 (entry ids of the merged update)");
+}
+
+// First pair call of a handle: room for 2M more gradient source rows, coefficients, means of squares and document ids behind the
+// text objective's, a documents CSR workspace for B·R + 2M entries, and the pair kernel's own buffers (M <= max_batch_size).
+void Model::ensure_pair_workspace() {
+    if (pairs_ready_) return;
+    synchronize();
+    settle_words_stamp();
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    have_forward_ = have_grads_ = false;      // (the forward result lived in the buffers replaced below)
+    const int64_t B = cfg_.max_batch_size, Mx = cfg_.max_batch_size;
+    const int de = cfg_.entity_repr_size;
+    const int64_t rows = B + 2 * Mx;
+    proj_.alloc(rows * de); coef_.alloc(rows * R_); pp_.alloc(rows);
+    ids_buf_[0].alloc(B * R_ + 2 * Mx); ids_buf_[1].alloc(B * R_ + 2 * Mx); ids_p_ = ids_buf_[0].p;
+    csr_joined_ents_ = csr_joined_words_ = true;
+    alloc_table_csr(ents_, B * R_ + 2 * Mx, ents_.idx[0].chunk_order.p != nullptr);
+    pair_vals_[0].alloc(B * R_ + 2 * Mx); pair_vals_[1].alloc(B * R_ + 2 * Mx);
+    pair_ids64_.alloc(2 * Mx); pair_w_.alloc(Mx); pair_probs_.alloc(Mx); pair_mults_.alloc(Mx); instw_scaled_.alloc(B);
+    pair_loss_.alloc(1, true);
+    alloc_sums(sums_pair_, 1, pair_loss_blocks(Mx, de), 1);
+    NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_, hipEventDisableTiming));
+    NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_copied_, hipEventDisableTiming));
+    pairs_ready_ = true;
+}
+
+void Model::stage_pairs(const nvsm_pair_batch& pairs, int* ids_dst) {
+    const int64_t M = pairs.num_pairs;
+    // the previous pair kernel may still be reading the staged weights
+    if (pair_pending_) { NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_pair_, 0)); pair_pending_ = false; }
+    const int64_t* ids64 = pairs.pairs;
+    pair_wdev_ = pairs.weights;
+    if (!pairs.on_device) {
+        NVSM_HIP_CHECK(hipMemcpyAsync(pair_ids64_.p, pairs.pairs, 2 * M * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+        ids64 = pair_ids64_.p;
+        if (pairs.weights) {
+            NVSM_HIP_CHECK(hipMemcpyAsync(pair_w_.p, pairs.weights, M * sizeof(float), hipMemcpyHostToDevice, stream_));
+            pair_wdev_ = pair_w_.p;
+        }
+        NVSM_HIP_CHECK(hipEventRecord(ev_pair_copied_, stream_));
+        pair_copy_pending_ = true;
+    }
+    launch_narrow_i64(ids64, ids_dst, 2 * M, cfg_.num_entities, err_host_, NVSM_BAD_ENTITY_ID, stream_);
+}
+
+void Model::launch_pairs(hipStream_t strm, hipEvent_t after) {
+    const int de = cfg_.entity_repr_size;
+    const int64_t B = mode_ == MODE_MIXED ? B_ : 0;      // the pair entries' rows / coefficients / ids sit behind the text objective's
+    if (after) NVSM_HIP_CHECK(hipStreamWaitEvent(strm, after, 0));
+    PairArgs a{};
+    a.E = ents_.P.p; a.E_rows = ents_.rows;
+    if (ents_.lazy) a.lazyE = lazy_view(ents_);
+    a.ids = ids_p_ + B * R_; a.w = pair_wdev_;
+    a.X = proj_.p + B * de; a.coef = coef_.p + B * R_; a.coef_stride = R_; a.sq = pp_.p + B;
+    a.probs = pair_probs_.p; a.mults = pair_mults_.p;
+    a.loss_acc = pair_loss_.p; a.sums = sums_pair_.ws;
+    a.M = M_; a.de = de;
+    a.sig_eps = cfg_.clip_sigmoid ? 1e-7f : 0.f;                                            // objective.cu:546-550
+    a.sig_hi = static_cast<float>(1.0 - static_cast<double>(a.sig_eps));
+    a.d_eps = cfg_.clip_sigmoid ? 1e-6f : 0.f;                                              // :622-623
+    a.d_hi = 1.0 - static_cast<double>(a.d_eps);
+    a.inv_batch = static_cast<float>(std::exp(-std::log(static_cast<double>(M_))));         // :609
+    a.scale = pair_scale_;
+    a.inv_de = static_cast<float>(std::exp(-std::log(static_cast<double>(de))));             // updates_adam.cu:238-240
+    timed_launch(prof, "pair_loss", strm, /*single=*/true, [&] { launch_pair_loss(a, strm); });
+    NVSM_HIP_CHECK(hipEventRecord(ev_pair_, strm));
+    pair_stream_ = strm;
+    pair_pending_ = strm != stream_;
+}
+
+void Model::compute_cost_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix) {
+    check_pair_request(text, pairs, mix);
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    ensure_pair_workspace();
+    if (text) {
+        text_scale_ = mix->text_weight / (mix->text_weight + mix->pair_weight);      // weight / summed_weight, intermediate_results.cu:19-36
+        pair_scale_ = mix->pair_weight / (mix->text_weight + mix->pair_weight);
+        pair_req_ = &pairs;
+        try { compute_cost(*text, entity_ids); } catch (...) { pair_req_ = nullptr; throw; }
+        pair_req_ = nullptr;
+        return;
+    }
+    // the pair objective alone: ids -> CSR -> kernel on the main stream; no other parameter is read or written
+    RangeScope range_cc("ComputeCost");
+    have_forward_ = have_grads_ = false;
+    cost_valid_ = false;
+    loss_reduced_ = false; loss_folded_ = false;
+    mode_ = MODE_PAIRS; M_ = pairs.num_pairs; B_ = 0;
+    text_scale_ = 1.f; pair_scale_ = 1.f;
+    if (inputs_recorded_) {      // the previous CSR builds read the id buffers (compute_cost)
+        if (!csr_joined_ents_) NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_ents_, 0));
+        if (!csr_joined_words_) NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_, 0));
+        csr_joined_ents_ = csr_joined_words_ = true;
+    }
+    join_E();      // the previous documents update: reads the rows / coefficients this pass rewrites, writes E
+    ids_p_ = (ids_p_ == ids_buf_[0].p) ? ids_buf_[1].p : ids_buf_[0].p;
+    stage_pairs(pairs, ids_p_);
+    NVSM_HIP_CHECK(hipEventRecord(ev_inputs_, stream_));
+    inputs_recorded_ = true;
+    last_batch_on_host_ = false;
+    ++step_count_;
+    { PROF("csr_entities"); build_csr(ents_, ids_p_, 2 * M_, stream_, 2 * M_); }
+    NVSM_HIP_CHECK(hipEventRecord(ev_csr_ents_, stream_));
+    launch_pairs(stream_, nullptr);
+    NVSM_HIP_CHECK(hipGetLastError());
+    have_forward_ = true;
+    if (debug_) { NVSM_HIP_CHECK(hipStreamSynchronize(stream_)); raise_device_error(); }
+}
+
+// compute_cost_mixed; compute_gradients; update(scaled lambda) — the mixed step through nvsm_step's streams: the pair kernel on side
+// stream 1 under the forward pass, the documents update (behind it on that stream) next to the backward products and the words
+// update. Same kernels on the same data in the same order per buffer as the three calls: the same bits.
+void Model::step_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix, float lr, float* cost) {
+    check_pair_request(text, pairs, mix);
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    ensure_pair_workspace();
+    if (!text) {
+        compute_cost_mixed(nullptr, nullptr, pairs, nullptr);
+        const float sl = scaled_regularization_lambda();
+        if (lr < 0.f || sl < 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "learning_rate and lambda must be >= 0");
+        compute_gradients();
+        update(lr, sl);
+        if (cost) *cost = get_cost();
+        return;
+    }
+    text_scale_ = mix->text_weight / (mix->text_weight + mix->pair_weight);
+    pair_scale_ = mix->pair_weight / (mix->text_weight + mix->pair_weight);
+    pair_req_ = &pairs;
+    try { step(*text, entity_ids, lr, cost); } catch (...) { pair_req_ = nullptr; throw; }
+    pair_req_ = nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2303,6 +2542,9 @@ int64_t Model::tensor_size(const std::string& name) {
     if (name == "grad_transform") return static_cast<int64_t>(de) * dw;
     if (name == "grad_entity") return N * de;
     if (name == "arrival_counters") return 6;
+    if (name == "pair_probs" || name == "pair_multipliers") return M_;
+    if (name == "grad_pair_entity") return 2 * M_ * de;
+    if (name == "pair_cost" || name == "text_cost") return 1;
     throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown tensor: " + name);
 }
 
@@ -2310,6 +2552,11 @@ void Model::get_tensor(const std::string& name, float* dst, int64_t count) {
     if (!have_forward_) throw Error(NVSM_ERR_STATE, "no forward result");
     if (count != tensor_size(name)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "size mismatch for " + name);
     const bool needs_grads = name.rfind("grad_", 0) == 0;
+    const bool pair_tensor = name.rfind("pair_", 0) == 0 || name == "grad_pair_entity";
+    if (pair_tensor && mode_ == MODE_TEXT) throw Error(NVSM_ERR_STATE, name + " requires a forward result with pairs (compute_cost_mixed)");
+    if (mode_ == MODE_PAIRS && !pair_tensor && name != "arrival_counters")
+        throw Error(NVSM_ERR_STATE, name + " does not exist in a forward result of the pair objective alone");
+    if (mode_ != MODE_MIXED && name == "text_cost") throw Error(NVSM_ERR_STATE, "text_cost requires a mixed forward result");
     if (needs_grads && !have_grads_) throw Error(NVSM_ERR_STATE, name + " requires compute_gradients (and no update since)");
     const float* src = nullptr;
     std::vector<float> tmp;
@@ -2330,6 +2577,19 @@ void Model::get_tensor(const std::string& name, float* dst, int64_t count) {
             launch_materialize_grad_entity_l2(coef_.p, proj_.p, ents_.P.p, ids_p_, B_ * R_, R_, cfg_.entity_repr_size, grad_entity_.p, nullptr, stream_);
         else
             launch_materialize_grad_entity(coef_.p, proj_.p, B_ * R_, R_, cfg_.entity_repr_size, grad_entity_.p, stream_);
+        src = grad_entity_.p;
+    } else if (name == "pair_probs") src = pair_probs_.p;
+    else if (name == "pair_multipliers") src = pair_mults_.p;
+    else if (name == "pair_cost" || name == "text_cost") {
+        (void)get_cost();
+        dst[0] = static_cast<float>(name == "pair_cost" ? pair_cost_ : text_cost_);
+        return;
+    } else if (name == "grad_pair_entity") {
+        // entry 2p: mult_p·E[b_p], entry 2p + 1: mult_p·E[a_p] (flip_adjacent_columns + apply_columnwise, objective.cu:643-661)
+        if (grad_entity_.n < static_cast<size_t>(count)) { synchronize(); grad_entity_.alloc(count); }
+        if (pair_pending_) { NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_pair_, 0)); pair_pending_ = false; }
+        const int64_t B = mode_ == MODE_MIXED ? B_ : 0;
+        launch_pair_materialize(coef_.p + B * R_, R_, proj_.p + B * cfg_.entity_repr_size, 2 * M_, cfg_.entity_repr_size, grad_entity_.p, stream_);
         src = grad_entity_.p;
     } else if (name == "arrival_counters") {
         // How many arrival counters of the last-arriver hand-overs (device_utils.h grid_sum_ordered, update.hip table passes) are NOT

@@ -136,6 +136,10 @@ class Model {
     double cost_f64() const { return cost_; }      // valid after get_cost()
     float scaled_regularization_lambda() const;
     void step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, float* cost);
+    // the entity-entity similarity objective alone (text null) or mixed into the text objective (TextEntityEntityEntity,
+    // cpp/objective.cu:698-745): see "entity-entity pairs" below
+    void compute_cost_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix);
+    void step_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix, float lr, float* cost);
 
     int64_t param_size(const std::string& name);
     void get_param(const std::string& name, float* dst, int64_t count);
@@ -176,7 +180,8 @@ class Model {
  private:
     struct ParamRef { float* p; int64_t n; };
     ParamRef find_param(const std::string& name);
-    void build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s);
+    void build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s, int64_t n_pair_entries = 0);
+    void alloc_table_csr(TableState& t, int64_t max_entries, bool chunk_order);
     Csr csr_of(TableState& t, int64_t n);
     void backward_dx();                                  // B5, B7, B9 on the main stream
     void backward_T(hipStream_t s);                      // B6 (+ its all-reduce)
@@ -302,6 +307,34 @@ class Model {
     static constexpr int64_t kDtMainMinBatch = 16384;      // eager tables, one rank: the dT product on the split-bf16 kernel, on the main stream, from here
     int chunk_entries(const TableState& t, int64_t n) const;      // entries per level-1 chunk of a long row for a batch of n entries of table t
     bool use_dt() const;               // this step's dT product runs on it (else: the exact-fp32 tiled / panel kernels)
+
+    // ---- entity-entity pairs (pairs.hip). The pair entries ride in the documents table's ONE sorted pass: the 2M gradient source
+    // rows sit behind the text objective's in proj_ (rows B .. B + 2M - 1), pair entry i carries the entry id (B + i) * R — so the
+    // pass's src = entry / R finds its row, coef_[entry] its coefficient, pp_[src] its mean of squares — and the CSR is built from the
+    // step's B * R document ids followed by the 2M pair ids. Everything here is allocated by the first pair call.
+    enum { MODE_TEXT = 0, MODE_PAIRS = 1, MODE_MIXED = 2 };
+    int mode_ = MODE_TEXT;                      // what the current forward result is
+    int64_t M_ = 0;                             // its pairs
+    float text_scale_ = 1.f, pair_scale_ = 1.f; // w / (w_te + w_ee) (MergeGradientsFn, cpp/intermediate_results.cu:19-38)
+    const nvsm_pair_batch* pair_req_ = nullptr; // set around compute_cost by compute_cost_mixed: this forward pass is a mixed one
+    bool pairs_ready_ = false;
+    DevBuf<int64_t> pair_ids64_;
+    DevBuf<float> pair_w_, pair_probs_, pair_mults_, instw_scaled_;
+    DevBuf<int> pair_vals_[2];                  // entry ids of the merged CSR, one per set of CSR arrays
+    DevBuf<double> pair_loss_;
+    const float* pair_wdev_ = nullptr;
+    SumsBufs sums_pair_;
+    hipEvent_t ev_pair_ = nullptr, ev_pair_copied_ = nullptr;
+    hipStream_t pair_stream_ = nullptr;         // the stream the last pair kernel ran on
+    bool pair_pending_ = false;                 // ... which the main stream has not followed yet
+    bool pair_copy_pending_ = false;
+    double pair_cost_ = 0.0, text_cost_ = 0.0;
+    void check_pair_request(const nvsm_batch* text, const nvsm_pair_batch& pairs, const nvsm_mixture* mix) const;
+    void ensure_pair_workspace();
+    void stage_pairs(const nvsm_pair_batch& pairs, int* ids_dst);      // ids narrowed into ids_dst, weights on the device (main stream)
+    void launch_pairs(hipStream_t s, hipEvent_t after);                // the pair kernel of the current forward result
+    int64_t ents_entries(int64_t text_windows) const { return text_windows * R_ + (mode_ != MODE_TEXT ? 2 * M_ : 0); }
+    float scaled_lambda_for(int mode, int64_t B, int64_t M) const;
 
     // ranking scratch: allocated by the first infer / rank call (training-only handles never pay for it), grown on demand
     struct RankScratch {

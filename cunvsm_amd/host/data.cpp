@@ -20,6 +20,8 @@ void set_batch_allocator(BatchAllocFn alloc, BatchFreeFn free_fn) {
     g_alloc = alloc ? alloc : default_alloc;
     g_free = free_fn ? free_fn : default_free;
 }
+void* batch_alloc(size_t bytes) { return g_alloc(bytes); }
+void batch_free(void* p) { g_free(p); }
 
 // ---- Batch: cpp/data.cu:8-92 ----
 Batch::Batch(size_t batch_size, size_t window_size)

@@ -1,8 +1,8 @@
 // Host data pipeline feeding the training step: the batch container handed to the C ABI (nvsm_batch) and the data
 // sources that fill it. Mirrors include/cuNVSM/data.h — BatchInterface / DataSourceInterface (:50-84),
 // TextEntity::Batch (:114-177) + cpp/data.cu:8-124, TextEntity::DataSource (:181-282), InMemoryDocumentSource
-// (:299-365), AsyncSource (cpp/data_async.cpp), RepeatingSource (cpp/data_repeating.cpp). The pair objectives'
-// sources (RepresentationSimilarity, MultiSource) are outside the hot-path scope.
+// (:299-365), AsyncSource (cpp/data_async.cpp), RepeatingSource (cpp/data_repeating.cpp). The entity-entity pair
+// source (RepresentationSimilarity) lives in pair_source.hpp; the term-term one is out of scope.
 #pragma once
 
 #include <atomic>
@@ -24,6 +24,8 @@ namespace nvsm_host {
 typedef void* (*BatchAllocFn)(size_t bytes);
 typedef void (*BatchFreeFn)(void* p);
 void set_batch_allocator(BatchAllocFn alloc, BatchFreeFn free_fn);
+void* batch_alloc(size_t bytes);       // through the installed allocator (pair_source.cpp's batches)
+void batch_free(void* p);
 
 typedef std::tuple<std::vector<WordIdxType>, std::vector<WeightType>, ObjectIdxType, WeightType> InstanceT;
 typedef std::deque<InstanceT> InstancesT;

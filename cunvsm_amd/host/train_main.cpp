@@ -6,8 +6,13 @@
 //   * <path to Indri index> is either an Indri 5.x repository directory, read without libindri (host/indri_index.hpp;
 //     --document_list resolves docnos through the repository's docno look-up files), or the TREC-text collection file itself, indexed
 //     in memory on start-up (host/trectext_index.hpp).
-//   * only TextEntity::Objective (LSE / NVSM) is accelerated: non-zero --entity_similarity_weight /
-//     --term_similarity_weight are refused with a clear message (the optional l2 normalisers are supported: untuned).
+//   * objectives: TextEntity::Objective (LSE / NVSM) and its mixture with the entity-entity similarity objective
+//     (TextEntityEntityEntity, cpp/main.cu:733-741): a second positional argument names the similarity file (lines of
+//     `docno docno weight`, cpp/main.cu:657-660) and --entity_similarity_weight w trains with the weights (1 - w, w). The pair source is
+//     built after the index source and before the model is initialised, so its shuffles sit where the reference's do in the one
+//     generator's stream. Refused: w = 1 (CHECK_NE(text_entity_weight_, 0.0), cpp/objective.cu:708), w != 0 without a similarity
+//     file, Adagrad and sparse Adam together with pairs (the reference's own refusal), pairs under data parallelism, with
+//     --l2_entity_normalization or with --check_gradients, and the term-term objective (--term_similarity_weight != 0).
 //   * extensions: --stopwords, --device, --sampler {host,device}, --allow_ragged_batches, and data parallelism over RCCL
 //     (--gpus N spawns one process per GPU; or --world_size / --rank [or WORLD_SIZE / RANK / LOCAL_RANK] under any launcher).
 #include <sys/stat.h>
@@ -30,6 +35,7 @@
 #include "hdf5_writer.hpp"
 #include "index_source.hpp"
 #include "indri_index.hpp"
+#include "pair_source.hpp"
 #include "rendezvous.hpp"
 #include "trectext_index.hpp"
 
@@ -152,6 +158,23 @@ class Trainer {
     Trainer(nvsm_model* model, const TrainConfig& tc, int64_t num_words, int64_t num_entities, int dw, int de, int world_size, int rank)
         : model_(model), tc_(tc), num_words_(num_words), num_entities_(num_entities), dw_(dw), de_(de), world_size_(world_size), rank_(rank) {}
 
+    // the mixed objective (TextEntityEntityEntity): every step also takes a batch of the repeating pair source; `rng` is the
+    // generator the pair source reshuffles with, shared with the model (handed over around every reshuffle)
+    void train_pairs(RepeatingPairSource* pair_source, RNG* rng, float text_weight, float pair_weight) {
+        pair_source_ = pair_source; pair_rng_ = rng;
+        pair_batch_.reset(new PairBatch(tc_.batch_size));
+        mix_.text_weight = text_weight; mix_.pair_weight = pair_weight;
+    }
+    // MultiSource::next for the pair half (cpp/data_multi.cpp:72-75): a pass that is over is reshuffled with the shared generator,
+    // whose live state is the model's while an epoch runs
+    void next_pairs() {
+        pair_batch_->clear();
+        const bool reshuffles = pair_source_->next_reshuffles();
+        if (reshuffles) { uint64_t st = 0; NVSM_CALL(nvsm_rng_get_state(model_, &st)); rng_set_state(pair_rng_, st); }
+        pair_source_->next(pair_batch_.get());
+        if (reshuffles) NVSM_CALL(nvsm_rng_set_state(model_, rng_state(*pair_rng_)));
+    }
+
     // DumpModelFn (cpp/main.cu:335-364) + write_to_hdf5 (include/cuNVSM/lse_hdf5_inl.h)
     void dump_model(size_t epoch, const std::string& identifier) {
         // data parallel: the replicas' tables have drifted apart (rank-local sparse updates): what is written is their mean,
@@ -202,8 +225,9 @@ class Trainer {
             const auto batch_start = std::chrono::steady_clock::now();
             NVSM_CALL(nvsm_wait_inputs(model_));        // the previous step has copied this host batch to the device
             batch->clear();
-            { Range fetch_range("FetchData"); data_source->next(batch); }                 // :388-390
-            const size_t n_global = batch->num_instances();
+            { Range fetch_range("FetchData"); data_source->next(batch); if (pair_source_) next_pairs(); }      // :388-390
+            // a step's instance count is the smaller of the two batches' (BatchHandler<tuple>::num_instances, cpp/main.cu:102-105)
+            const size_t n_global = pair_source_ ? std::min(batch->num_instances(), pair_batch_->num_instances()) : batch->num_instances();
             const size_t G = static_cast<size_t>(world_size_);
             if (n_global % 1024 != 0 && !FLAGS_allow_ragged_batches) {                        // maxThreadsPerBlock, :392-398
                 NVSM_LOG(ERROR) << "Skipping Batch #" << epoch_num_batches << " as it is not a multiple of " << 1024 << " (" << n_global << " instances).";
@@ -218,7 +242,20 @@ class Trainer {
                 b.labels = batch->labels() + lo; b.weights = batch->weights() + lo;
                 b.num_instances = static_cast<int64_t>(n); b.on_device = 0;
                 float cost = 0.f;
-                if (FLAGS_check_gradients) {
+                if (pair_source_) {
+                    // both batches as they are (the count above only decides whether the step is skipped, as in the reference)
+                    b.features = batch->features(); b.feature_weights = batch->feature_weights(); b.labels = batch->labels();
+                    b.weights = batch->weights(); b.num_instances = static_cast<int64_t>(batch->num_instances());
+                    nvsm_pair_batch pb{};
+                    pb.pairs = pair_batch_->features(); pb.weights = pair_batch_->weights();
+                    pb.num_pairs = static_cast<int64_t>(pair_batch_->num_instances()); pb.on_device = 0;
+                    if (backpropagate) {
+                        NVSM_CALL(nvsm_step_mixed(model_, &b, nullptr, &pb, &mix_, tc_.learning_rate, &cost));
+                    } else {
+                        NVSM_CALL(nvsm_compute_cost_mixed(model_, &b, nullptr, &pb, &mix_));
+                        NVSM_CALL(nvsm_get_cost(model_, &cost));
+                    }
+                } else if (FLAGS_check_gradients) {
                     NVSM_CALL(nvsm_compute_cost(model_, &b, nullptr));
                     NVSM_CALL(nvsm_compute_gradients(model_));
                     NVSM_CALL(nvsm_get_cost(model_, &cost));
@@ -360,6 +397,10 @@ class Trainer {
     int dw_, de_;
     int world_size_, rank_;
     uint64_t windows_ = 0;
+    RepeatingPairSource* pair_source_ = nullptr;
+    RNG* pair_rng_ = nullptr;
+    std::unique_ptr<PairBatch> pair_batch_;
+    nvsm_mixture mix_{};
 };
 
 void* pinned_alloc(size_t bytes) { void* p = nullptr; check_status(nvsm_host_alloc(bytes, &p), "nvsm_host_alloc"); return p; }
@@ -373,7 +414,7 @@ int run(int argc, char** argv) {
     log_to_stderr() = FLAGS_logtostderr || FLAGS_alsologtostderr;
 
     if (args.size() < 2) {
-        std::cerr << "Usage: " << args[0] << " [OPTIONS] <path to Indri index | TREC-text collection>\n" << flags.usage();
+        std::cerr << "Usage: " << args[0] << " [OPTIONS] <path to Indri index | TREC-text collection> [<path to document similarities>]\n" << flags.usage();
         NVSM_LOG(FATAL) << "Check failed: argc >= 2 Usage: " << args[0] << " [OPTIONS] <path to Indri index>";
     }
     static const std::map<std::string, std::pair<int, int>> UPDATE_METHODS = {                         // cpp/main.cu:479-485
@@ -487,9 +528,26 @@ int run(int argc, char** argv) {
     NVSM_CHECK(FLAGS_term_similarity_weight >= 0.0 && FLAGS_term_similarity_weight <= 1.0);
     NVSM_CHECK(FLAGS_seed > 0) << "Please specify a --seed value.";
     if (tc.learning_rate == 0.0f) tc.learning_rate = (tc.update_method == NVSM_ADAM) ? 0.001f : 0.01f;   // :710-721
-    if (FLAGS_entity_similarity_weight != 0.0 || FLAGS_term_similarity_weight != 0.0)
-        NVSM_LOG(FATAL) << "only the text-entity objective (LSE / NVSM) is implemented on this platform; "
-                           "--entity_similarity_weight and --term_similarity_weight must be 0.";
+    const std::string similarity_path = args.size() >= 3 ? args[2] : std::string();      // cpp/main.cu:657-660
+    if (FLAGS_term_similarity_weight != 0.0)
+        NVSM_LOG(FATAL) << "only the text-entity objective (LSE / NVSM) and its mixture with the entity-entity objective are implemented on "
+                           "this platform; --term_similarity_weight must be 0.";
+    const bool train_pairs = FLAGS_entity_similarity_weight != 0.0;                        // :733-741
+    if (train_pairs) {
+        if (similarity_path.empty())                                                      // CHECK(!data_config.similarity_path().empty()), :734
+            NVSM_LOG(FATAL) << "no similarity file given: only the text-entity objective can be trained without one "
+                               "(--entity_similarity_weight needs <path to document similarities> as the second argument).";
+        NVSM_CHECK(FLAGS_entity_similarity_weight < 1.0) << "--entity_similarity_weight must be below 1: the text-entity objective's weight "
+                                                            "1 - w must not be 0 (CHECK_NE(text_entity_weight_, 0.0)).";
+        if (tc.update_method == NVSM_ADAGRAD) NVSM_LOG(FATAL) << "Adagrad currently does not implement multiple gradients.";
+        if (tc.update_method == NVSM_ADAM && tc.adam_mode <= NVSM_ADAM_SPARSE) NVSM_LOG(FATAL) << "Sparse Adam currently does not implement multiple gradients.";
+        NVSM_CHECK(world_size == 1) << "the entity-entity objective is not implemented under data parallelism.";
+        NVSM_CHECK(!FLAGS_l2_entity_normalization) << "the entity-entity objective is not implemented together with --l2_entity_normalization.";
+        NVSM_CHECK(!FLAGS_check_gradients) << "--check_gradients covers the text-entity objective only.";
+        NVSM_CHECK(is_file(similarity_path)) << "cannot read the document similarities " << similarity_path;
+    } else if (!similarity_path.empty()) {
+        NVSM_LOG(WARNING) << "--entity_similarity_weight is 0: the document similarities in " << similarity_path << " are not used.";
+    }
 
     NVSM_LOG(INFO) << "Model descriptor: word_repr_size: " << FLAGS_word_repr_size << " entity_repr_size: " << FLAGS_entity_repr_size
                    << " transform_desc { batch_normalization: " << (FLAGS_batch_normalization ? "true" : "false") << " nonlinearity: "
@@ -500,7 +558,8 @@ int run(int argc, char** argv) {
                    << " include_oov: " << (FLAGS_include_oov ? "true" : "false");
     NVSM_LOG(INFO) << "Training configuration: num_epochs: " << tc.num_epochs << " batch_size: " << tc.batch_size << " window_size: "
                    << tc.window_size << " num_random_entities: " << tc.num_random_entities << " regularization_lambda: " << tc.regularization_lambda
-                   << " learning_rate: " << tc.learning_rate << " update_method: " << FLAGS_update_method << " no_shuffle: " << (tc.no_shuffle ? "true" : "false");
+                   << " learning_rate: " << tc.learning_rate << " update_method: " << FLAGS_update_method << " no_shuffle: " << (tc.no_shuffle ? "true" : "false")
+                   << " text_entity_weight: " << 1.0 - FLAGS_entity_similarity_weight << " entity_entity_weight: " << FLAGS_entity_similarity_weight;
     NVSM_LOG(INFO) << "FLOATING_POINT_TYPE=float32";
 
     RNG rng;
@@ -524,7 +583,21 @@ int run(int argc, char** argv) {
         index.release(), tc.window_size, &rng, FLAGS_max_vocabulary_size, FLAGS_min_document_frequency, max_document_frequency,
         FLAGS_document_cutoff, FLAGS_include_oov, false /* include_digits */, document_list.get(), term_blacklist.get(),
         !tc.no_shuffle, AUTOMATIC_SAMPLING, WEIGHTING_STRATEGIES.at(FLAGS_weighting), FEATURE_WEIGHTING_STRATEGIES.at(FLAGS_feature_weighting));
+    // construct_data_source<TextEntityEntityEntity::Objective> (:281-306): the docno -> model document id map of the index source,
+    // then the shuffled pair source (its first shuffle draws from `rng` HERE, behind the index source's and before the model's
+    // initialisation) inside RepeatingSource(-1)
+    std::unique_ptr<IdentifiersMapT> identifiers_map;
+    if (train_pairs) identifiers_map.reset(new IdentifiersMapT(index_source->build_document_identifiers_map()));
     std::unique_ptr<DataSourceInterface> data_source(new AsyncSource(10, tc.batch_size, tc.window_size, index_source));
+    std::unique_ptr<RepeatingPairSource> pair_source;
+    if (train_pairs) {
+        NVSM_LOG(INFO) << "Reading document similarities from " << similarity_path << ".";
+        PairSource* pairs = new PairSource(similarity_path, *identifiers_map, &rng);
+        NVSM_CHECK(pairs->size() > 0) << "no pair of " << similarity_path << " names two documents of the model.";
+        NVSM_LOG(INFO) << "Entity-entity objective: " << pairs->size() << " pairs, mixture weights text " << 1.0 - FLAGS_entity_similarity_weight
+                       << " / pairs " << FLAGS_entity_similarity_weight << ".";
+        pair_source.reset(new RepeatingPairSource(size_t(-1), pairs));
+    }
 
     Metadata meta;
     data_source->extract_metadata(&meta);
@@ -597,6 +670,8 @@ int run(int argc, char** argv) {
 
     Trainer trainer(model, tc, static_cast<int64_t>(vocabulary_size), static_cast<int64_t>(corpus_size),
                     static_cast<int>(FLAGS_word_repr_size), static_cast<int>(FLAGS_entity_repr_size), world_size, rank);
+    if (train_pairs)
+        trainer.train_pairs(pair_source.get(), &rng, static_cast<float>(1.0 - FLAGS_entity_similarity_weight), static_cast<float>(FLAGS_entity_similarity_weight));
     Batch batch(tc.batch_size, tc.window_size);
     std::vector<float> epoch_costs;
 
@@ -606,6 +681,7 @@ int run(int argc, char** argv) {
         NVSM_CALL(nvsm_rng_get_state(model, &s));
         rng_set_state(&rng, s);
         data_source->reset();
+        if (pair_source) pair_source->reset();                     // MultiSource::reset: every source in order (cpp/data_multi.cpp:48-51)
         NVSM_CALL(nvsm_rng_set_state(model, rng_state(rng)));
     };
 
@@ -642,6 +718,7 @@ int run(int argc, char** argv) {
     NVSM_VLOG(1) << "Training loop: " << num_batches << " batches in "
                  << std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count() << " seconds (incl. the model dumps)";
     data_source.reset();
+    pair_source.reset();
     nvsm_destroy(model);
     return 0;
 }

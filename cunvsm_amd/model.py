@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmNeighborOptions, NvsmNeighborQueries, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -118,6 +118,58 @@ class Batch:
     def as_struct(self):
         return NvsmBatch(self._ptr(self.features), self._ptr(self.feature_weights), self._ptr(self.labels),
                          self._ptr(self.weights), self.num_instances, int(self.on_device))
+
+
+class PairBatch:
+    """nvsm_pair_batch — the batch of the entity-entity similarity objective (RepresentationSimilarity::Batch,
+    cpp/data.cu:316-334): M pairs of document ids, given as an [M, 2] array (or flat, interleaved a_0 b_0 a_1 b_1 ...), and
+    optional weights [M]. Arrays may be numpy (host) or torch CUDA tensors. Element counts are checked here; id RANGES on the device."""
+
+    def __init__(self, pairs, weights=None):
+        self.on_device = hasattr(pairs, "data_ptr")
+        if self.on_device:
+            import torch
+            if pairs.dtype != torch.int64:
+                raise ValueError("pairs must be int64")
+            if weights is not None and weights.dtype != torch.float32:
+                raise ValueError("weights must be float32")
+            if not pairs.is_contiguous() or (weights is not None and not weights.is_contiguous()):
+                raise ValueError("device arrays must be contiguous")
+            shape, n = tuple(pairs.shape), int(pairs.numel())
+            wn = None if weights is None else int(weights.numel())
+            self.pairs, self.weights = pairs, weights
+        else:
+            a = np.asarray(pairs)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("pairs must hold integer document ids")
+            shape, n = a.shape, int(a.size)
+            self.pairs = np.ascontiguousarray(a, dtype=np.int64).ravel()
+            self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).ravel()
+            wn = None if weights is None else int(self.weights.size)
+        if len(shape) == 2 and shape[1] != 2:
+            raise ValueError("pairs has shape %s, expected [num_pairs][2]" % (shape,))
+        if len(shape) not in (1, 2) or n % 2 != 0:
+            raise ValueError("pairs must be [num_pairs][2] or a flat, interleaved list of 2 * num_pairs ids")
+        self.num_pairs = n // 2
+        if self.num_pairs < 1:
+            raise ValueError("pairs is empty: a pair batch needs at least one pair")
+        if wn is not None and wn != self.num_pairs:
+            raise ValueError("weights holds %d values, expected num_pairs = %d" % (wn, self.num_pairs))
+
+    def _ptr(self, a):
+        if a is None:
+            return None
+        return a.data_ptr() if self.on_device else a.ctypes.data
+
+    def as_struct(self):
+        return NvsmPairBatch(self._ptr(self.pairs), self._ptr(self.weights), self.num_pairs, int(self.on_device))
+
+
+def mixture(text_weight, pair_weight):
+    """nvsm_mixture; both weights must be > 0 (CHECK_NE(..., 0.0), cpp/objective.cu:708-709). No device needed."""
+    if not (float(text_weight) > 0.0 and float(pair_weight) > 0.0):
+        raise ValueError("text_weight and pair_weight of a mixture must both be > 0")
+    return NvsmMixture(float(text_weight), float(pair_weight))
 
 
 def self_information_weights(term_frequencies, total_terms):
@@ -318,6 +370,44 @@ class Model:
         check(lib().nvsm_step(self._h, C.byref(st), None if ids is None else ids.ctypes.data, learning_rate,
                               C.byref(c) if want_cost else None))
         return c.value if want_cost else None
+
+    # -- the entity-entity similarity objective, alone (batch None) or mixed into the text objective ----------------
+    def _checked_mixed(self, batch, pairs, entity_ids, weights):
+        if not isinstance(pairs, PairBatch):
+            pairs = PairBatch(pairs)
+        if pairs.num_pairs > self.cfg.max_batch_size:
+            raise ValueError("num_pairs = %d exceeds max_batch_size = %d" % (pairs.num_pairs, self.cfg.max_batch_size))
+        ids, st, mix = None, None, None
+        if batch is not None:
+            if entity_ids is not None:
+                ids = np.ascontiguousarray(entity_ids, dtype=np.int64)
+            st = self._checked(batch, ids)
+            mix = mixture(*weights)
+        self._keep = (batch, ids, pairs)
+        return st, ids, pairs.as_struct(), mix
+
+    def compute_cost_mixed(self, batch, pairs, weights=(0.5, 0.5), entity_ids=None):
+        """nvsm_compute_cost_mixed: `pairs` (a PairBatch) with the text `batch`, mixed with weights = (text, pairs); batch None:
+        the pair objective alone. compute_gradients / update / get_cost / get_tensor then act on that result."""
+        st, ids, ps, mix = self._checked_mixed(batch, pairs, entity_ids, weights)
+        check(lib().nvsm_compute_cost_mixed(self._h, None if st is None else C.byref(st), None if ids is None else ids.ctypes.data,
+                                            C.byref(ps), None if mix is None else C.byref(mix)))
+
+    def step_mixed(self, batch, pairs, learning_rate, weights=(0.5, 0.5), entity_ids=None, want_cost=False):
+        """nvsm_step_mixed: compute_cost_mixed + compute_gradients + update with the scaled lambda, as one multi-stream step."""
+        st, ids, ps, mix = self._checked_mixed(batch, pairs, entity_ids, weights)
+        c = C.c_float()
+        check(lib().nvsm_step_mixed(self._h, None if st is None else C.byref(st), None if ids is None else ids.ctypes.data,
+                                    C.byref(ps), None if mix is None else C.byref(mix), learning_rate, C.byref(c) if want_cost else None))
+        return c.value if want_cost else None
+
+    def get_cost_f64(self):
+        c = C.c_double()
+        check(lib().nvsm_get_cost_f64(self._h, C.byref(c)))
+        return c.value
+
+    def increment_parameter(self, name, index, delta):
+        check(lib().nvsm_increment_parameter(self._h, name.encode(), int(index), float(delta)))
 
     # -- Model::infer (cpp/model.cu:105-133) and the ranking of py/nvsm/base.py:362-430 ---------------
     def infer(self, queries, weights=None, **opts):

@@ -194,6 +194,56 @@ float nvsm_scaled_regularization_lambda(nvsm_model* m);
  * only. Errors flagged by the backward and update kernels of a step surface at the next call that waits. */
 int nvsm_step(nvsm_model* m, const nvsm_batch* batch, const int64_t* entity_ids, float learning_rate, float* cost);
 
+/*
+ * The entity-entity similarity objective (RepresentationSimilarity::Objective on ENTITY_REPRS, cpp/objective.cu:485-696) and its
+ * mixture with the text objective (TextEntityEntityEntity, cpp/objective.cu:698-745) — what the reference trains when
+ * cuNVSMTrainModel gets document-document similarities as its second argument (PRODUCT_SUBSTITUTABILITY.md).
+ *   pair objective   a batch is M pairs (a_p, b_p, ω_p) of document ids, interleaved as pairs[2p], pairs[2p + 1] (cpp/data.cu:316-334).
+ *                    s_p = E[a_p]·E[b_p]; prob_p = clip(σ(s_p), 1e-7, 1 − 1e-7) in float32 (objective.cu:546-550, the two-branch sigmoid
+ *                    of include/cuNVSM/cuda_utils.h:193-214); cost = −(1/M)·Σ ω_p·log prob_p (:553-567, intermediate_results.cu:81-124).
+ *                    No negative samples, no projection. mult_p = ω_p·d(prob_p)/M with d(x) = 0 for x ≥ 1 − 1e-6 or x ≤ 1e-6, else 1 − x
+ *                    (:607-626, cuda_utils.h:218-235); the gradient of entry 2p is mult_p·E[b_p], that of entry 2p + 1 mult_p·E[a_p]
+ *                    (flip_adjacent_columns, :643-661), both from the rows as they were at compute_cost (:519-521); window 1, no
+ *                    per-entry weights (intermediate_results.cu:300-307); gradient ascent. a_p == b_p and repeated pairs simply add.
+ *                    scaled lambda = lambda / M. Only the documents table is updated (the other parameters have no gradient:
+ *                    cpp/params.cu:304-307), with any of the five update methods.
+ *   mixed objective  cost = (cost_text + cost_pairs) / 2 — an unweighted mean (AverageFn) —; scaled lambda = (lambda/B + lambda/M) / 2;
+ *                    every text gradient is scaled by w_te / (w_te + w_ee), the pair gradient by w_ee / (w_te + w_ee)
+ *                    (MergeGradientsFn, intermediate_results.cu:3-60); the documents table is updated ONCE from both entry lists — one
+ *                    decay, both scatters (CompositeGradients, cpp/storage.cu:65-99), Adam's m from both lists (updates_adam.cu:196-200),
+ *                    dense_update's per-row v from the per-entry means of squares of both lists (:216-252), full Adam squares the summed
+ *                    gradient (:253-282). Exists for sgd, dense_update and full Adam; the reference refuses Adagrad
+ *                    (updates_adagrad.cu:108) and sparse Adam (updates_adam.cu:348) with more than one gradient list, and so does this.
+ * text == NULL: the pair objective alone (entity_ids and mix are ignored). Pair ids follow the index contract above (checked on the
+ * device, row 0, NVSM_ERR_INVALID_ARGUMENT at the next wait). on_device = 0: host arrays, copied by the call (nvsm_wait_inputs also
+ * covers them); 1: device arrays, which must stay untouched until nvsm_synchronize. weights NULL = all 1.0.
+ * nvsm_compute_gradients / nvsm_update / nvsm_get_cost / nvsm_get_cost_f64 / nvsm_scaled_regularization_lambda act on whichever
+ * forward result is current. nvsm_get_tensor additionally knows "pair_probs" [M], "pair_multipliers" [M] (mixture scale included),
+ * "grad_pair_entity" [2M][entity_repr_size], "pair_cost" and "text_cost" [1]; in a mixed result the text tensors carry the
+ * w_te / (w_te + w_ee) scale, as the reference's do after merging.
+ * NVSM_ERR_UNSUPPORTED (the handle stays usable): mixed with Adagrad or sparse Adam; world_size > 1; l2_normalize_entity_reprs.
+ * NVSM_ERR_INVALID_ARGUMENT: a mixture weight <= 0, num_pairs < 1 or > max_batch_size.
+ * The pair workspaces (and the larger CSR workspace of the documents table) are allocated by the first of these calls; a handle that
+ * never makes one allocates and launches exactly what it did before they existed. nvsm_step_mixed equals
+ * nvsm_compute_cost_mixed; nvsm_compute_gradients; nvsm_update(scaled lambda) bit for bit; cost may be NULL.
+ */
+typedef struct {
+    const int64_t* pairs;         /* [2 * num_pairs] document ids, interleaved */
+    const float*   weights;       /* [num_pairs] or NULL (= all 1.0) */
+    int64_t        num_pairs;
+    int32_t        on_device;
+    int32_t        reserved[3];
+} nvsm_pair_batch;
+typedef struct {
+    float   text_weight;          /* w_te: TrainConfig.text_entity_weight */
+    float   pair_weight;          /* w_ee: TrainConfig.entity_entity_weight */
+    int32_t reserved[2];
+} nvsm_mixture;
+int nvsm_compute_cost_mixed(nvsm_model* m, const nvsm_batch* text /* NULL: pairs only */, const int64_t* entity_ids,
+                            const nvsm_pair_batch* pairs, const nvsm_mixture* mix /* ignored when text is NULL */);
+int nvsm_step_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch* pairs,
+                    const nvsm_mixture* mix, float learning_rate, float* cost);
+
 /* The same step for training loops that want the loss of EVERY batch, as cpp/main.cu:427-444 does, without putting the
  * GPU behind the host: nvsm_step_deferred queues the step plus a device→host copy of its loss word and hands back a
  * ticket; nvsm_deferred_cost(ticket) waits for that copy only (not for the step's updates). At most

@@ -47,6 +47,15 @@ struct Batch {
     int64_t num_instances() const { return raw.num_instances; }
 };
 
+// RepresentationSimilarity::Batch (cpp/data.cu:316-334) — a view over the caller's interleaved pair ids and optional weights.
+struct PairBatch {
+    nvsm_pair_batch raw{};
+    PairBatch(const int64_t* pairs, const float* weights, int64_t num_pairs, bool on_device = false) {
+        raw.pairs = pairs; raw.weights = weights; raw.num_pairs = num_pairs; raw.on_device = on_device ? 1 : 0;
+    }
+    int64_t num_pairs() const { return raw.num_pairs; }
+};
+
 class Model {
  public:
     explicit Model(const nvsm_config& cfg) : cfg_(cfg) { check(nvsm_create(&cfg, &h_)); }
@@ -82,6 +91,23 @@ class Model {
     float step(const Batch& batch, float learning_rate, bool want_cost = true) {
         float c = 0.f;
         check(nvsm_step(h_, &batch.raw, nullptr, learning_rate, want_cost ? &c : nullptr));
+        return c;
+    }
+
+    // the entity-entity similarity objective mixed into the text objective with weights (text_weight, pair_weight)
+    // (TextEntityEntityEntity, cpp/objective.cu:698-745), or alone (text == nullptr): compute_gradients / update / get_cost follow
+    void compute_cost_mixed(const Batch* text, const PairBatch& pairs, float text_weight = 0.5f, float pair_weight = 0.5f,
+                            const int64_t* entity_ids = nullptr) {
+        nvsm_mixture mix{};
+        mix.text_weight = text_weight; mix.pair_weight = pair_weight;
+        check(nvsm_compute_cost_mixed(h_, text ? &text->raw : nullptr, entity_ids, &pairs.raw, &mix));
+    }
+    float step_mixed(const Batch* text, const PairBatch& pairs, float learning_rate, float text_weight = 0.5f, float pair_weight = 0.5f,
+                     bool want_cost = true) {
+        nvsm_mixture mix{};
+        mix.text_weight = text_weight; mix.pair_weight = pair_weight;
+        float c = 0.f;
+        check(nvsm_step_mixed(h_, text ? &text->raw : nullptr, nullptr, &pairs.raw, &mix, learning_rate, want_cost ? &c : nullptr));
         return c;
     }
 
