@@ -85,6 +85,19 @@ class NvsmNeighborOptions(C.Structure):
     ]
 
 
+class GemmEpilogueArgs(C.Structure):
+    """nvsm_debug_gemm_epilogue_args (include/cunvsm_amd_test_hooks.h)."""
+    _fields_ = [
+        ("kernel", C.c_int), ("b_layout", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+        ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("alpha", C.c_float), ("bias", C.c_void_p),
+        ("colstats", C.c_void_p), ("rowsq", C.c_void_p), ("rowsq_scale", C.c_float),
+        ("pre", C.c_void_p), ("mean", C.c_void_p), ("inv_std", C.c_void_p), ("sums", C.c_void_p), ("n_global", C.c_double),
+        ("dbeta", C.c_void_p), ("dgamma", C.c_void_p), ("grad_bias", C.c_void_p),
+        ("table", C.c_void_p), ("table_rows", C.c_int64), ("idx", C.c_void_p), ("wts", C.c_void_p), ("window", C.c_int),
+        ("A_out", C.c_void_p), ("launched", C.POINTER(C.c_int)),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_void_p)
 
 
@@ -140,6 +153,8 @@ class _Library:
                 "nvsm_debug_set_table_pass_form": (C.c_int, [C.c_int]),
                 "nvsm_debug_neighbors_force_plain": (C.c_int, [C.c_int]),
                 "nvsm_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+                "nvsm_debug_gemm_epilogue": (C.c_int, [P(GemmEpilogueArgs)]),
+                "nvsm_debug_gemm_plan": (C.c_int, [C.c_int] * 7 + [P(C.c_int), P(C.c_uint)]),
                 "nvsm_debug_gemm_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float)]),
                 "nvsm_debug_dt_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]),
                 "nvsm_debug_sort": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, P(C.c_float)]),

@@ -328,6 +328,10 @@ bool gemm_rows_covers(int b_layout, int M, int N, int K, bool colstats, bool row
     return rows_plan(b_layout, M, N, K, colstats, rowsq, bn, &t, &w) != 0;
 }
 
+bool gemm_rows_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bn, int* tpw, int* waves) {
+    return rows_plan(b_layout, M, N, K, colstats, rowsq, bn, tpw, waves) != 0;
+}
+
 // true: launched. A [M][K] row-major, 16 B aligned operands, leading dimensions multiples of 4.
 bool launch_gemm_rows(int b_layout, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                       float alpha, const float* bias_n, hipStream_t s, double* colstats, const GridSumWs* sums, float* rowsq,

@@ -500,6 +500,13 @@ bool gemm_rsplit_gather_covers(int M, int N, int K, bool colstats, int window) {
     return window >= 1 && gemm_split_products() != 0 && tuning().gemm_rsplit && rs_plan(0, M, N, K, colstats, false, false, &p, window);
 }
 
+bool gemm_rsplit_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bn, int gather_window, RsplitPlan* plan) {
+    RsPlan p;
+    if (gather_window < 0 || !gemm_split_products() || !tuning().gemm_rsplit || !rs_plan(b_layout, M, N, K, colstats, rowsq, bn, &p, gather_window)) return false;
+    plan->waves = p.waves; plan->rch = p.rch; plan->ks = (K + 15) / 16; plan->ksp = p.ksp; plan->nt = p.nt;
+    return true;
+}
+
 // true: launched. A [M][K] row-major, 16 B aligned operands, leading dimensions multiples of 4. ws: the planes of B in this
 // kernel's layout (GemmSplitWs::rplanes; cut here, on `s`, unless ws->rready says they are current).
 bool launch_gemm_rsplit(int b_layout, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,

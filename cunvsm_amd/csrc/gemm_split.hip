@@ -644,20 +644,35 @@ bool gemm_split_covers(int b_layout, int M, int N, int K, bool bn) {
     return b_layout == 0 ? cbs == 2 * kSplitWaves : (cbs > 2 * kSplitWaves && cbs <= 3 * kSplitWaves);
 }
 
+// ... and the epilogues split_launch has kernels for: the forward product (b_layout 0) carries column sums or a bias or nothing,
+// the backward one row sums of squares or nothing (with or without the batch-norm backward / bias gradient on the way in)
+bool gemm_split_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bias, bool bn, SplitPlan* plan) {
+    if (!gemm_split_covers(b_layout, M, N, K, bn)) return false;
+    if (b_layout == 0 ? (rowsq || (colstats && bias)) : (colstats || bias)) return false;
+    // (launch_gemm_split's deal: the column blocks over the eight waves as even as they go)
+    plan->cbs = (N + 15) / 16;
+    plan->ncb_min = plan->cbs / kSplitWaves;
+    plan->ncb_max = (plan->cbs + kSplitWaves - 1) / kSplitWaves;
+    return true;
+}
+
 // returns false when the shape is not one this kernel covers (nothing launched). rowsq: ONE complete value per row.
 // ws: the planes of B (cut here, on `s`, unless ws->ready says they are current).
 bool launch_gemm_split(int b_layout, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                        float alpha, const float* bias_n, hipStream_t s, double* colstats, const GridSumWs* sums, float* rowsq,
                        float rowsq_scale, GemmSplitWs* ws, const BnDxFused* bn) {
     const int nprod = gemm_split_products();
-    if (bn && (b_layout != 1 || K > 320 || (bn->pre && (bn->dy != A || reinterpret_cast<uintptr_t>(bn->pre) % 16)))) return false;
-    if (!nprod || M < 1024 || !ws || !ws->planes || ws->bytes < gemm_split_planes_bytes(N, K)) return false;
+    if (bn && bn->pre && (bn->dy != A || reinterpret_cast<uintptr_t>(bn->pre) % 16)) return false;
+    if (!ws || !ws->planes || ws->bytes < gemm_split_planes_bytes(N, K)) return false;
     // (the kernel addresses A — and pre — by 32-bit byte offsets from the base)
     if (static_cast<uint64_t>(M) * static_cast<uint64_t>(lda) * 4 >= (1ull << 32) || lda < K) return false;
-    if ((K % 4) || (N % 4) || (lda % 4) || (ldb % 4) || (ldc % 4) || K < 8) return false;
+    if ((lda % 4) || (ldb % 4) || (ldc % 4)) return false;
     if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) % 16) return false;
     if (bias_n && reinterpret_cast<uintptr_t>(bias_n) % 16) return false;
-    const int cbs = (N + 15) / 16;
+    // the shape and the epilogue (is there a kernel for it: split_launch) are gemm_split_plan's to decide — before anything is launched
+    SplitPlan plan;
+    if (!gemm_split_plan(b_layout, M, N, K, colstats != nullptr, rowsq != nullptr, bias_n != nullptr, bn != nullptr, &plan)) return false;
+    const int cbs = plan.cbs;
     static std::atomic<int> cus_of[kSplitMaxDevices];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kSplitMaxDevices) return false;
@@ -701,6 +716,7 @@ bool launch_gemm_split(int b_layout, const float* A, const float* B, float* C, i
     const int cbw = deal(kSplitWaves);
     const bool forward = b_layout == 0;
     if ((forward && (cbw != 2 || cbs % kSplitWaves)) || (!forward && (cbw != 3 || cbs < 2 * kSplitWaves))) return false;
+    if (cbw != plan.ncb_max) return false;
     if (!ws->ready) { launch_gemm_split_planes(b_layout, B, N, K, ldb, ws->planes, s); ws->ready = true; }
     if (forward) {
         // the forward product: 16 column blocks = two per wave, thirteen row blocks (the whole share of a CU) in one pass

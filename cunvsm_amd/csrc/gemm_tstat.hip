@@ -397,26 +397,13 @@ float* gemm_dump_buffer() {
 static bool g_gemm_tstat_enabled = true;
 void gemm_set_tstat_enabled(bool on) { g_gemm_tstat_enabled = on; }
 
-// returns false when the shape is not one this kernel covers (the caller falls back to the tiled kernel);
-// *rowsq_parts = number of [M]-sized parts written to rowsq (one per 16-column tile)
-bool launch_gemm_tstat(int a_layout, int b_layout, const float* A, const float* B, float* C, int M, int N, int K,
-                       int lda, int ldb, int ldc, float alpha, const float* bias_n, hipStream_t s, double* colstats,
-                       float* rowsq, float rowsq_scale, int* rowsq_parts, bool busy_chip, const GridSumWs* sums) {
+// The shape decision of launch_gemm_tstat, host arithmetic only (kernels.h TstatPlan): N in 1 to kTstatMaxParts column parts of 8 or
+// 10 tiles of 16 whose columns of B (+ the waves' statistics slots) fit in LDS, the first such split; then one of the four
+// compiled (KG, NT, layout, mixed) forms and an epilogue that form's layout carries — or false. From 1 024 rows, where the switch allows.
+bool gemm_tstat_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bias, TstatPlan* plan) {
     // NVSM_GEMM_TSTAT (A/B runs): bit 0 = the forward product (B as [K][N]), bit 1 = the backward one (B stored [N][K])
-    const int env_mask = tuning().gemm_tstat;
-    if (!g_gemm_tstat_enabled || !(env_mask & (b_layout ? 2 : 1)) || a_layout != 0 || M < 1024) return false;
-    // The forward product of a large batch starts while the previous step's documents update and this step's sorts still
-    // hold registers and LDS on most CUs, and a kernel that needs a whole CU per workgroup starts late on some of them; its
-    // static split has no slack for that. With round 1's step that cost more than the kernel gained (129 us against the
-    // tiled kernel's 127 us in-step, step 1.116 against 1.103 ms). Since the documents update's tail and the sorts got
-    // shorter it is the other way round at the NVSM shape (1.047 against 1.055 ms, interleaved) — but not where those are
-    // long, i.e. with tables much larger than the batch (configs[4]: 1.90 against 1.87 ms): the caller says which
-    // (busy_chip). NVSM_GEMM_TSTAT_FWD_ANY=0 / 1 overrides.
-    const int fwd_any = tuning().gemm_tstat_fwd_any;
-    if (b_layout == 0 && M > 16384 && (fwd_any >= 0 ? fwd_any == 0 : busy_chip)) return false;
-    if ((K % 4) || (N % 4) || (lda % 4) || (ldb % 4) || (ldc % 4)) return false;
-    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) % 16) return false;
-    if (bias_n && reinterpret_cast<uintptr_t>(bias_n) % 16) return false;
+    if (!(tuning().gemm_tstat & (b_layout ? 2 : 1)) || M < 1024) return false;
+    if (N <= 0 || K <= 0 || (K % 4) || (N % 4)) return false;
     const int KG = (K + 15) / 16;
     const int tiles = (N + 15) / 16;
     int parts = 0, NT = 0;
@@ -427,6 +414,45 @@ bool launch_gemm_tstat(int a_layout, int b_layout, const float* A, const float* 
         if (need <= kTstatLdsBytes) { parts = p; NT = nt; break; }
     }
     if (!parts) return false;
+    // the first `wide` parts have NT tiles, the others NT - 1
+    const int wide = tiles - parts * (NT - 1);
+    const bool mixed = wide < parts;
+    int inst = -1;
+    if (KG == 19 && NT == 8 && b_layout == 0 && !mixed) inst = 0;
+    else if (KG == 16 && NT == 10 && b_layout == 1 && mixed) inst = 1;
+    else if (KG == 8 && NT == 8 && b_layout == 0 && !mixed) inst = 2;
+    else if (KG == 16 && NT == 8 && b_layout == 1 && !mixed) inst = 3;
+    if (inst < 0) return false;
+    // (tstat_launch: the forward layout carries column sums or a bias, the backward one row sums of squares, or nothing)
+    const int epi = (colstats ? kEpiStats : 0) | (rowsq ? kEpiRowsq : 0) | (bias ? kEpiBias : 0);
+    if (b_layout == 0 ? !(epi == kEpiStats || epi == kEpiBias || epi == 0) : !(epi == kEpiRowsq || epi == 0)) return false;
+    plan->parts = parts; plan->NT = NT; plan->KG = KG; plan->wide = wide; plan->mixed = mixed; plan->inst = inst;
+    plan->lds = static_cast<size_t>(KG) * 4 * NT * 16 * 16 + (colstats ? static_cast<size_t>(kTstatWaves) * 2 * NT * 16 * 4 : 0);
+    return true;
+}
+
+// returns false when the shape is not one this kernel covers (the caller falls back to the tiled kernel);
+// *rowsq_parts = number of [M]-sized parts written to rowsq (one per 16-column tile)
+bool launch_gemm_tstat(int a_layout, int b_layout, const float* A, const float* B, float* C, int M, int N, int K,
+                       int lda, int ldb, int ldc, float alpha, const float* bias_n, hipStream_t s, double* colstats,
+                       float* rowsq, float rowsq_scale, int* rowsq_parts, bool busy_chip, const GridSumWs* sums) {
+    if (!g_gemm_tstat_enabled || a_layout != 0) return false;
+    // The forward product of a large batch starts while the previous step's documents update and this step's sorts still
+    // hold registers and LDS on most CUs, and a kernel that needs a whole CU per workgroup starts late on some of them; its
+    // static split has no slack for that. With round 1's step that cost more than the kernel gained (129 us against the
+    // tiled kernel's 127 us in-step, step 1.116 against 1.103 ms). Since the documents update's tail and the sorts got
+    // shorter it is the other way round at the NVSM shape (1.047 against 1.055 ms, interleaved) — but not where those are
+    // long, i.e. with tables much larger than the batch (configs[4]: 1.90 against 1.87 ms): the caller says which
+    // (busy_chip). NVSM_GEMM_TSTAT_FWD_ANY=0 / 1 overrides.
+    const int fwd_any = tuning().gemm_tstat_fwd_any;
+    if (b_layout == 0 && M > 16384 && (fwd_any >= 0 ? fwd_any == 0 : busy_chip)) return false;
+    if ((lda % 4) || (ldb % 4) || (ldc % 4)) return false;
+    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) % 16) return false;
+    if (bias_n && reinterpret_cast<uintptr_t>(bias_n) % 16) return false;
+    TstatPlan plan;
+    if (!gemm_tstat_plan(b_layout, M, N, K, colstats != nullptr, rowsq != nullptr, bias_n != nullptr, &plan)) return false;
+    const int tiles = (N + 15) / 16;
+    const int parts = plan.parts, NT = plan.NT;
     // per device ordinal: the CU count that sizes the grid
     static std::atomic<int> cus_of[kTstatMaxDevices];
     int dev = 0;
@@ -448,7 +474,7 @@ bool launch_gemm_tstat(int a_layout, int b_layout, const float* A, const float* 
     g.dbg = g_tstat_dbg;
 #endif
     // the first `wide` parts have NT tiles, the others NT - 1; workgroups in proportion to the tiles
-    const int wide = tiles - parts * (NT - 1);
+    const int wide = plan.wide;
     int wgs = num_cus < parts ? parts : num_cus;
     int t0 = 0, w0 = 0;
     for (int p = 0; p < parts; ++p) {
@@ -468,13 +494,15 @@ bool launch_gemm_tstat(int a_layout, int b_layout, const float* A, const float* 
         g.sums.fan = grid_sum_fan(wgs);
         if ((wgs + g.sums.fan - 1) / g.sums.fan > sums->groups_cap) return false;
     }
-    const size_t lds = static_cast<size_t>(KG) * 4 * NT * 16 * 16 + (colstats ? static_cast<size_t>(kTstatWaves) * 2 * NT * 16 * 4 : 0);
+    const size_t lds = plan.lds;
     bool ok = false;
-    const bool mixed = wide < parts;
-    if (KG == 19 && NT == 8 && b_layout == 0 && !mixed) ok = tstat_launch<19, 8, 0, false>(g, lds, wgs, s);
-    else if (KG == 16 && NT == 10 && b_layout == 1 && mixed) ok = tstat_launch<16, 10, 1, true>(g, lds, wgs, s);
-    else if (KG == 8 && NT == 8 && b_layout == 0 && !mixed) ok = tstat_launch<8, 8, 0, false>(g, lds, wgs, s);
-    else if (KG == 16 && NT == 8 && b_layout == 1 && !mixed) ok = tstat_launch<16, 8, 1, false>(g, lds, wgs, s);
+    switch (plan.inst) {
+    case 0: ok = tstat_launch<19, 8, 0, false>(g, lds, wgs, s); break;
+    case 1: ok = tstat_launch<16, 10, 1, true>(g, lds, wgs, s); break;
+    case 2: ok = tstat_launch<8, 8, 0, false>(g, lds, wgs, s); break;
+    case 3: ok = tstat_launch<16, 8, 1, false>(g, lds, wgs, s); break;
+    default: break;
+    }
     if (ok && rowsq_parts) *rowsq_parts = rowsq ? tiles : 0;
     return ok;
 }

@@ -148,6 +148,16 @@ bool launch_gemm_dt(const float* A, const float* B, float* partial, int M, int N
 bool gemm_dtw_covers(int M, int N, int rows);
 int gemm_dtw_slabs(int rows, int want);
 bool launch_gemm_dtw(const float* A, const float* B, float* partial, int M, int N, int rows, int lda, int ldb, int want_slabs, hipStream_t s);
+// What each of the four batch-sized kernels would do with a shape and an epilogue — host arithmetic only, no HIP call, the
+// functions the launchers themselves decide by (tests/test_gemm_plans.py reads them through nvsm_debug_gemm_plan). false: refused.
+struct TstatPlan { int parts, NT, KG, wide, inst; bool mixed; size_t lds; };      // inst: which compiled (KG, NT, layout, mixed) form
+bool gemm_tstat_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bias, TstatPlan* plan);
+struct RsplitPlan { int waves, rch, ks, ksp, nt; };                               // ks: k steps of 16; ksp: padded to an even number
+bool gemm_rsplit_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bn, int gather_window, RsplitPlan* plan);
+bool gemm_rows_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bn, int* tpw, int* waves);
+// (bn: a BnDxFused is passed, with or without `pre`; cbs: 16-column blocks, dealt to the eight waves ncb_min to ncb_max each)
+struct SplitPlan { int cbs, ncb_min, ncb_max; };
+bool gemm_split_plan(int b_layout, int M, int N, int K, bool colstats, bool rowsq, bool bias, bool bn, SplitPlan* plan);
 int gemm_split_products();               // NVSM_GEMM_SPLIT: 6 (default), 9, or 0 = exact-fp32 MFMA kernels only
 int gemm_rows_max_m();                   // largest M launch_gemm sends to the row-panel kernel (NVSM_GEMM_ROWS_MAX, default 8192; 0 = never): above it the split-bf16 kernel
 float* gemm_dump_buffer();               // 256 B per device nobody reads (gemm_tstat.hip): the target of masked-out stores

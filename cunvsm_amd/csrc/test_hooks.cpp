@@ -70,6 +70,168 @@ int nvsm_debug_gemm(int variant, int M, int N, int K, const float* hostA, const 
     });
 }
 
+// ONE named launcher of the batch-sized projection products with any of its fused epilogues (cunvsm_amd_test_hooks.h). Every
+// output starts as 0xFF bytes on the device — NaN as float and as double — so that the caller sees both "refused: nothing written"
+// and "launched: every element the kernel owns written"; the planes of B are cut fresh on every call.
+int nvsm_debug_gemm_epilogue(const nvsm_debug_gemm_epilogue_args* a) {
+    NVSM_REQUIRE(a); NVSM_REQUIRE(a->B); NVSM_REQUIRE(a->C); NVSM_REQUIRE(a->launched);
+    return guarded_hook([&] {
+        const int M = a->M, N = a->N, K = a->K, bl = a->b_layout;
+        const bool gather = a->table != nullptr, bn = a->sums != nullptr;
+        if (M <= 0 || N <= 0 || K <= 0 || (bl != 0 && bl != 1)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "gemm_epilogue: bad shape");
+        if (!gather && !a->A) throw Error(NVSM_ERR_INVALID_ARGUMENT, "gemm_epilogue: A is required without the gather");
+        if (gather && (!a->idx || a->window < 1 || a->table_rows < 1)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "gemm_epilogue: the gather needs idx, window and table_rows");
+        if (bn && a->pre && (!a->mean || !a->inv_std)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "gemm_epilogue: the batch-norm backward needs mean and inv_std");
+        auto fill = [](void* p, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemset(p, 0xFF, bytes)); };
+        auto up = [](void* d, const void* h, size_t bytes) { NVSM_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice)); };
+        auto down = [](void* h, const void* d, size_t bytes) { NVSM_HIP_CHECK(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost)); };
+        const size_t MK = static_cast<size_t>(M) * K, MN = static_cast<size_t>(M) * N;
+        cunvsm::DevBuf<float> A, B, C, bias, rowsq, rparts, pre, mean, inv_std, dbeta, dgamma, gbias, table, wts;
+        cunvsm::DevBuf<double> stats, part, part2, bsums;
+        cunvsm::DevBuf<int> arrive, idx;
+        cunvsm::DevBuf<int64_t> idx64;
+        A.alloc(MK); B.alloc(static_cast<size_t>(K) * N); C.alloc(MN);
+        if (gather) fill(A.p, MK * sizeof(float)); else up(A.p, a->A, MK * sizeof(float));
+        up(B.p, a->B, B.n * sizeof(float));
+        fill(C.p, MN * sizeof(float));
+        if (a->bias) { bias.alloc(N); up(bias.p, a->bias, N * sizeof(float)); }
+        cunvsm::GridSumWs ws{};
+        if (a->colstats) {      // sized as nvsm_debug_gemm_time sizes it, the width for the split kernel's padded columns
+            ws.colgroups = 8; ws.contrib_cap = M / 16 + 512; ws.width_cap = 2 * std::max((N + 31) / 32 * 32, 160);
+            ws.groups_cap = ws.contrib_cap / 16 + 1; ws.fan = 16;
+            part.alloc(static_cast<size_t>(ws.colgroups) * ws.contrib_cap * ws.width_cap);
+            part2.alloc(static_cast<size_t>(ws.colgroups) * ws.groups_cap * ws.width_cap);
+            arrive.alloc(static_cast<size_t>(ws.colgroups) * (ws.groups_cap + 1), true);
+            stats.alloc(2 * static_cast<size_t>(N));
+            fill(stats.p, stats.n * sizeof(double));
+            ws.part = part.p; ws.part2 = part2.p; ws.arrive = arrive.p;
+        }
+        const int parts_cap = cunvsm::gemm_rowsq_parts(N);
+        if (a->rowsq) {
+            rparts.alloc(static_cast<size_t>(parts_cap) * M); rowsq.alloc(M);
+            fill(rparts.p, rparts.n * sizeof(float)); fill(rowsq.p, rowsq.n * sizeof(float));
+        }
+        cunvsm::BnDxFused bf{};
+        if (bn) {
+            bsums.alloc(2 * static_cast<size_t>(K)); up(bsums.p, a->sums, bsums.n * sizeof(double));
+            dbeta.alloc(K); dgamma.alloc(K); gbias.alloc(K);
+            fill(dbeta.p, K * sizeof(float)); fill(dgamma.p, K * sizeof(float)); fill(gbias.p, K * sizeof(float));
+            if (a->pre) {
+                pre.alloc(MK); mean.alloc(K); inv_std.alloc(K);
+                up(pre.p, a->pre, MK * sizeof(float)); up(mean.p, a->mean, K * sizeof(float)); up(inv_std.p, a->inv_std, K * sizeof(float));
+            }
+            bf = cunvsm::BnDxFused{A.p, a->pre ? pre.p : nullptr, mean.p, inv_std.p, bsums.p, dbeta.p, dgamma.p, gbias.p, a->n_global};
+        }
+        cunvsm::GatherFused gf{};
+        if (gather) {
+            const size_t nid = static_cast<size_t>(M) * a->window;
+            table.alloc(static_cast<size_t>(a->table_rows) * K); up(table.p, a->table, table.n * sizeof(float));
+            idx64.alloc(nid); idx.alloc(nid); up(idx64.p, a->idx, nid * sizeof(int64_t));
+            if (a->wts) { wts.alloc(nid); up(wts.p, a->wts, nid * sizeof(float)); }
+            cunvsm::launch_narrow_i64(idx64.p, idx.p, static_cast<int64_t>(nid), a->table_rows, nullptr, 0, nullptr);
+            gf = cunvsm::GatherFused{table.p, idx.p, a->wts ? wts.p : nullptr, a->window, nullptr};
+        }
+        cunvsm::DevBuf<char> planes, rplanes;
+        planes.alloc(cunvsm::gemm_split_planes_bytes(N, K));
+        rplanes.alloc(cunvsm::gemm_rsplit_planes_bytes(N, K));
+        cunvsm::GemmSplitWs sws{planes.p, planes.n, false, rplanes.p, rplanes.n, false};
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        const int lda = K, ldb = bl ? K : N, ldc = N;
+        const cunvsm::GridSumWs* wsp = a->colstats ? &ws : nullptr;
+        const cunvsm::BnDxFused* bnp = bn ? &bf : nullptr;
+        float* rq = a->rowsq ? rparts.p : nullptr;
+        int nparts = a->rowsq ? 1 : 0;
+        bool launched = false;
+        switch (a->kernel) {
+        case NVSM_DEBUG_GEMM_ROWS:
+            launched = !gather && cunvsm::launch_gemm_rows(bl, A.p, B.p, C.p, M, N, K, lda, ldb, ldc, a->alpha, bias.p, nullptr, stats.p, wsp, rq, a->rowsq_scale, bnp);
+            break;
+        case NVSM_DEBUG_GEMM_RSPLIT:
+            launched = cunvsm::launch_gemm_rsplit(bl, A.p, B.p, C.p, M, N, K, lda, ldb, ldc, a->alpha, bias.p, nullptr, stats.p, wsp, rq, a->rowsq_scale, &sws, bnp,
+                                                  gather ? &gf : nullptr);
+            break;
+        case NVSM_DEBUG_GEMM_SPLIT:
+            launched = !gather && cunvsm::launch_gemm_split(bl, A.p, B.p, C.p, M, N, K, lda, ldb, ldc, a->alpha, bias.p, nullptr, stats.p, wsp, rq, a->rowsq_scale, &sws, bnp);
+            break;
+        case NVSM_DEBUG_GEMM_TSTAT:
+            launched = !gather && !bn && cunvsm::launch_gemm_tstat(0, bl, A.p, B.p, C.p, M, N, K, lda, ldb, ldc, a->alpha, bias.p, nullptr, stats.p, rq, a->rowsq_scale,
+                                                                   &nparts, false, wsp);
+            break;
+        case NVSM_DEBUG_GEMM_TILED:
+            if (!gather && !bn) {      // launch_gemm with every other kernel switched off: no row-panel batch size, no planes, no LDS-stationary / panel kernel
+                cunvsm::Tuning t = cunvsm::tuning();
+                t.gemm_rows_max = 0;
+                cunvsm::TuningScope scope(&t);
+                struct Off { Off() { cunvsm::gemm_set_tstat_enabled(false); cunvsm::gemm_set_panel_enabled(false); }
+                             ~Off() { cunvsm::gemm_set_tstat_enabled(true); cunvsm::gemm_set_panel_enabled(true); } } off;
+                cunvsm::launch_gemm(0, bl, A.p, B.p, C.p, M, N, K, lda, ldb, ldc, a->alpha, bias.p, 1, 0, nullptr, stats.p, rq, a->rowsq_scale, &nparts, false, wsp, nullptr);
+                launched = true;
+            }
+            break;
+        default: throw Error(NVSM_ERR_INVALID_ARGUMENT, "gemm_epilogue: kernel 0 = rows, 1 = rsplit, 2 = split, 3 = tstat, 4 = tiled");
+        }
+        NVSM_HIP_CHECK(hipGetLastError());
+        if (launched && a->rowsq && nparts > 1) cunvsm::launch_sum_parts(rparts.p, nparts, M, rowsq.p, M, nullptr);
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        *a->launched = launched ? 1 : 0;
+        down(a->C, C.p, MN * sizeof(float));
+        if (a->A_out) down(a->A_out, A.p, MK * sizeof(float));
+        if (a->colstats) down(a->colstats, stats.p, stats.n * sizeof(double));
+        if (a->rowsq) down(a->rowsq, (launched && nparts > 1) ? rowsq.p : rparts.p, M * sizeof(float));
+        if (bn) {
+            if (a->dbeta) down(a->dbeta, dbeta.p, K * sizeof(float));
+            if (a->dgamma) down(a->dgamma, dgamma.p, K * sizeof(float));
+            if (a->grad_bias) down(a->grad_bias, gbias.p, K * sizeof(float));
+        }
+    });
+}
+
+// What a launcher of nvsm_debug_gemm_epilogue would do with (shape, epilogue) — host arithmetic only, no HIP call: *covers and the
+// plan word of cunvsm_amd_test_hooks.h. The answers come from the functions the launchers themselves decide by (kernels.h).
+int nvsm_debug_gemm_plan(int kernel, int b_layout, int M, int N, int K, int flags, int window, int* covers, unsigned* plan) {
+    NVSM_REQUIRE(covers); NVSM_REQUIRE(plan);
+    return guarded_hook([&] {
+        const bool colstats = flags & NVSM_DEBUG_EPI_COLSTATS, rowsq = flags & NVSM_DEBUG_EPI_ROWSQ, bn = flags & NVSM_DEBUG_EPI_BN;
+        const bool bias = flags & NVSM_DEBUG_EPI_BIAS, gather = flags & NVSM_DEBUG_EPI_GATHER, gb = flags & NVSM_DEBUG_EPI_BIAS_GRAD;
+        *covers = 0; *plan = 0;
+        if (M <= 0 || N <= 0 || K <= 0 || (b_layout != 0 && b_layout != 1) || (bn && gb)) return;
+        if (gather && kernel != NVSM_DEBUG_GEMM_RSPLIT) return;
+        switch (kernel) {
+        case NVSM_DEBUG_GEMM_ROWS: {
+            int tpw = 0, waves = 0;
+            if (!cunvsm::gemm_rows_plan(b_layout, M, N, K, colstats, rowsq, bn, &tpw, &waves)) return;
+            *plan = static_cast<unsigned>(waves | (tpw << 8));
+            break;
+        }
+        case NVSM_DEBUG_GEMM_RSPLIT: {
+            cunvsm::RsplitPlan p;
+            if (gather && window < 1) return;
+            if (!cunvsm::gemm_rsplit_plan(b_layout, M, N, K, colstats, rowsq, bn, gather ? window : 0, &p)) return;
+            *plan = static_cast<unsigned>(p.waves | (p.rch << 8) | ((p.ksp != p.ks ? 1 : 0) << 16) | ((N - 32 * (p.nt - 1)) << 24));
+            break;
+        }
+        case NVSM_DEBUG_GEMM_SPLIT: {
+            cunvsm::SplitPlan p;
+            if (!cunvsm::gemm_split_plan(b_layout, M, N, K, colstats, rowsq, bias, bn || gb, &p)) return;
+            *plan = static_cast<unsigned>(p.cbs | (p.ncb_min << 8) | (p.ncb_max << 16));
+            break;
+        }
+        case NVSM_DEBUG_GEMM_TSTAT: {
+            cunvsm::TstatPlan p;
+            if (bn || gb) return;          // (launch_gemm_tstat has no argument for either: nvsm_debug_gemm_epilogue does not call it then)
+            if (!cunvsm::gemm_tstat_plan(b_layout, M, N, K, colstats, rowsq, bias, &p)) return;
+            *plan = static_cast<unsigned>(p.parts | (p.NT << 8) | ((p.mixed ? 1 : 0) << 16) | (p.KG << 24));
+            break;
+        }
+        case NVSM_DEBUG_GEMM_TILED:
+            if (bn || gb) return;
+            break;
+        default: throw Error(NVSM_ERR_INVALID_ARGUMENT, "gemm_plan: kernel 0 = rows, 1 = rsplit, 2 = split, 3 = tstat, 4 = tiled");
+        }
+        *covers = 1;
+    });
+}
+
 // average milliseconds of one launch_gemm of the batch-sized products on device-resident operands (A [M][K], B per b_layout):
 // extras bit 0 = ordered column statistics (the forward product), bit 1 = row sums of squares (the backward one)
 int nvsm_debug_gemm_time(int b_layout, int M, int N, int K, int extras, int repeats, float* avg_ms) {

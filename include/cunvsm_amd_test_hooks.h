@@ -14,6 +14,38 @@ extern "C" {
 
 /* Debug / unit-test hooks for individual kernels (tests only; not part of the drop-in surface). */
 int nvsm_debug_gemm(int variant, int M, int N, int K, const float* hostA, const float* hostB, float* hostC);
+/* ONE of the batch-sized projection products C[M][N] = alpha * A[M][K] * B (+ bias) by its own launcher - not launch_gemm's
+ * dispatch - with any of the epilogues the kernels fuse into the product. Everything past B is optional (null / 0 = absent).
+ * Every output buffer starts as 0xFF bytes on the device (NaN as float and as double): a refused launch leaves all of them so,
+ * a launch must have written every element it owns. The planes of B are cut fresh on every call. */
+enum { NVSM_DEBUG_GEMM_ROWS = 0, NVSM_DEBUG_GEMM_RSPLIT = 1, NVSM_DEBUG_GEMM_SPLIT = 2, NVSM_DEBUG_GEMM_TSTAT = 3,
+       NVSM_DEBUG_GEMM_TILED = 4 /* the tiled kernel through launch_gemm, the four others switched off */ };
+typedef struct nvsm_debug_gemm_epilogue_args {
+    int kernel, b_layout, M, N, K;   /* b_layout 0: B is [K][N]; 1: B is stored [N][K] */
+    const float* A;                  /* host [M][K]; ignored with the gather (A is then made, not read) */
+    const float* B;
+    float* C;                        /* out [M][N] */
+    float alpha;
+    const float* bias;               /* [N] */
+    double* colstats;                /* out [2][N]: ordered column sums of C and of its squares */
+    float* rowsq; float rowsq_scale; /* out [M]: rowsq_scale * sum over the columns of C squared (parts added by launch_sum_parts) */
+    /* batch-norm backward on the rows of A on the way in; sums non-null alone (pre null) = the bias gradient only */
+    const float* pre; const float* mean; const float* inv_std; const double* sums; double n_global;
+    float* dbeta; float* dgamma; float* grad_bias;   /* out [K] */
+    /* word gather-mean on the staging of A (rsplit only): table [table_rows][K], idx [M][window], wts [M][window] or null */
+    const float* table; int64_t table_rows; const int64_t* idx; const float* wts; int window;
+    float* A_out;                    /* out [M][K]: A after the launch (dx with the batch-norm backward, the phrases with the gather) */
+    int* launched;                   /* out: 1 = the launcher launched, 0 = it refused */
+} nvsm_debug_gemm_epilogue_args;
+int nvsm_debug_gemm_epilogue(const nvsm_debug_gemm_epilogue_args* args);
+/* Host-only (never touches the GPU): whether that launcher covers (shape, epilogue flags, gather window), and its plan word:
+ *   rows    waves | tpw << 8
+ *   rsplit  waves | rch << 8 | (odd number of k steps: one step of padding) << 16 | columns of the last 32-column tile << 24
+ *   split   16-column blocks | fewest blocks of a wave << 8 | most blocks of a wave << 16
+ *   tstat   parts | NT << 8 | mixed << 16 | KG << 24 */
+enum { NVSM_DEBUG_EPI_COLSTATS = 1, NVSM_DEBUG_EPI_ROWSQ = 2, NVSM_DEBUG_EPI_BN = 4, NVSM_DEBUG_EPI_BIAS = 8, NVSM_DEBUG_EPI_GATHER = 16,
+       NVSM_DEBUG_EPI_BIAS_GRAD = 32 };
+int nvsm_debug_gemm_plan(int kernel, int b_layout, int M, int N, int K, int flags, int window, int* covers, unsigned* plan);
 /* Queues a kernel on the handle's stream that spins for `microseconds` of GPU wall clock: profiling runs put it in
  * front of a step so that the host has queued the whole step before the GPU starts it (tools/rocprof_summary.py timeline). */
 int nvsm_debug_delay(nvsm_model* m, int microseconds);

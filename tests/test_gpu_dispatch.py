@@ -67,6 +67,17 @@ LAZY = _spec(num_words=61440, num_entities=61440, word_dim=300, entity_dim=256, 
              nonlinearity="hard_tanh", batch_norm=True)
 LAZY_MAX_B = 40960
 
+# Dimensions users pick that are no recipe's: whole steps at the shapes tests/test_gpu_gemm_epilogues.py holds kernel by kernel — the same tail
+# tiles, padded k steps and planner choices as there, with the model's own workspaces and stream order. (d_w, d_e):
+#   (100, 36)   gemm_rsplit with four waves, a 4-column last tile both ways, an odd number of k steps; beyond 8 192 rows the tiled kernel
+#   (200, 100)  gemm_rsplit staging eight float4s per thread forward, eight waves with the fused batch-norm backward on the way back
+#   (316, 320)  ten waves; beyond 8 192 rows gemm_split's backward product at its largest K with the batch-norm backward, 20 column blocks
+#   (256, 512)  no row-panel forward (N = 512); the backward refused by gemm_rsplit (K = 512 with batch-norm) and taken by gemm_rows
+UNUSUAL = {"d%dx%d" % (dw, de): _spec(num_words=500, num_entities=300, word_dim=dw, entity_dim=de, window=10, num_random=16,
+                                      nonlinearity="hard_tanh", batch_norm=True)
+           for dw, de in ((100, 36), (200, 100), (316, 320), (256, 512))}
+UNUSUAL_CASES = [(fam, B, method) for fam in UNUSUAL for B in (1024, 8193) for method in ("sgd", "adagrad")]
+
 BATCHES = [63, 64, 511, 512, 1023, 1024, 8192, 8193, 16383, 16384, 40959, 40960]
 SMALL_ONLY = {"wide": 16384, "l2": 16384}       # (runtime: these two families stop at 16 384 windows)
 # rotated over the cases so that every batch size has an SGD case and a case with the rowsq epilogue (need_msq)
@@ -94,6 +105,8 @@ def expected(fam, B, split=True, lazy=False):
     Thresholds: gemm_rsplit / gemm_rows from 512 to NVSM_GEMM_ROWS_MAX = 8 192, gemm_split above; gemm_tstat from 1 024; gemm_dtw
     from 64 to 16 383; gemm_dt on the main stream from kDtMainMinBatch = 16 384 (eager tables), from dt_min_batch = 40 960 on side
     stream 2 (lazy tables)."""
+    if fam in UNUSUAL:
+        return expected_unusual(fam, B)
     small, rows = B < 512, 512 <= B <= 8192
     if fam in ("nvsm", "l2"):
         fwd = bwd = "f32" if small else ("rsplit" if rows else "split")
@@ -127,6 +140,21 @@ def expected(fam, B, split=True, lazy=False):
     return dict(forward=FWD[fwd], backward=BWD[bwd], fused=fused, dT=DT[dt], main=on_main, loss=LOSS[loss])
 
 
+def expected_unusual(fam, B):
+    """The UNUSUAL families at 512 <= B <= 16 383 (batch-norm on, eager tables): the row-panel kernels to 8 192 rows; above, gemm_split
+    only where d_w makes 17 to 24 column blocks of the backward product, else gemm_tstat or the tiled kernel."""
+    assert 512 <= B <= 16383
+    rows = B <= 8192
+    if fam == "d256x512":
+        fwd, bwd = "tstat" if B >= 1024 else "f32", "rows" if rows else "tstat"
+    elif fam == "d316x320":
+        fwd, bwd = ("rsplit", "rsplit") if rows else ("tstat", "split")
+    else:
+        fwd = bwd = "rsplit" if rows else "tstat"
+    loss = "rows" if UNUSUAL[fam]["entity_dim"] <= 256 else "generic"
+    return dict(forward=FWD[fwd], backward=BWD[bwd], fused=True, dT=DT["dtw"], main=False, loss=LOSS[loss])
+
+
 def fields(desc):
     """describe()'s ' | '-separated fields by their first word (forward / backward / dT / loss / tables / ...)."""
     out = {}
@@ -147,7 +175,7 @@ def assert_dispatch(desc, want):
 
 
 def fam_spec(fam, method):
-    return dict(LAZY if fam == "lazy" else FAMILIES[fam], update_method=method)
+    return dict(LAZY if fam == "lazy" else UNUSUAL[fam] if fam in UNUSUAL else FAMILIES[fam], update_method=method)
 
 
 def fp32_yardstick(err_hip, err_f32, bound):
@@ -248,6 +276,15 @@ def test_dispatch_matrix_reaches_every_kernel_describe_names(monkeypatch):
     want = set(FWD.values()) | set(BWD.values()) | set(DT.values()) | set(LOSS.values()) | {"fused", "unfused"}
     assert want <= seen, sorted(want - seen)
     assert main_dt and side_dt
+
+
+@pytest.mark.parametrize("fam,B,method", UNUSUAL_CASES, ids=["%s-B%d-%s" % c for c in UNUSUAL_CASES])
+def test_unusual_dimensions_match_fp64_oracle(fam, B, method):
+    """One step at dimensions no recipe uses (UNUSUAL), with SGD and with an optimiser that takes the row sums of squares."""
+    assert method == "sgd" or method in NEED_MSQ
+    desc = one_step_against_oracle(fam_spec(fam, method), B, seed=B + 11 * len(fam) + UNUSUAL[fam]["word_dim"])
+    assert_dispatch(desc, expected(fam, B))
+    assert "words eager decay, documents eager decay" in desc, desc
 
 
 # ---------------------------------------------------------------------------------------------
