@@ -98,6 +98,22 @@ class GemmEpilogueArgs(C.Structure):
     ]
 
 
+class TablePassArgs(C.Structure):
+    """nvsm_debug_table_pass_args (include/cunvsm_amd_test_hooks.h)."""
+    _fields_ = [
+        ("table", C.c_int), ("kind", C.c_int), ("rows", C.c_int64), ("dim", C.c_int),
+        ("n", C.c_int64), ("keys", C.c_void_p), ("div", C.c_int), ("num_src", C.c_int64),
+        ("X", C.c_void_p), ("coef", C.c_void_p), ("sq_src", C.c_void_p), ("src_scale", C.c_void_p),
+        ("P", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("sc_in", C.c_void_p), ("sc_out", C.c_void_p),
+        ("lr", C.c_float), ("lambda_", C.c_float), ("decay", C.c_float), ("bc", C.c_float), ("dense", C.c_int),
+        ("wide", C.c_int), ("nt", C.c_int), ("max_entries", C.c_int64), ("adam", C.c_int),
+        ("one_launch", C.c_int), ("chunk_order", C.c_int), ("fill_in_bounds", C.c_int), ("entry_walk_min", C.c_int64),
+        ("prev_n", C.c_int64), ("prev_keys", C.c_void_p),
+        ("path", C.POINTER(C.c_int)), ("chunk", C.POINTER(C.c_int)), ("num_chunks", C.POINTER(C.c_int)),
+        ("max_chunks", C.POINTER(C.c_int)), ("max_chunks2", C.POINTER(C.c_int)), ("arrive_left", C.POINTER(C.c_int)),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_void_p)
 
 
@@ -154,6 +170,7 @@ class _Library:
                 "nvsm_debug_neighbors_force_plain": (C.c_int, [C.c_int]),
                 "nvsm_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
                 "nvsm_debug_gemm_epilogue": (C.c_int, [P(GemmEpilogueArgs)]),
+                "nvsm_debug_table_pass": (C.c_int, [P(TablePassArgs)]),
                 "nvsm_debug_gemm_plan": (C.c_int, [C.c_int] * 7 + [P(C.c_int), P(C.c_uint)]),
                 "nvsm_debug_gemm_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float)]),
                 "nvsm_debug_dt_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]),

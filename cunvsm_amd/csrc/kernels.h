@@ -7,6 +7,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include <stdexcept>
 #include <string>
 
@@ -321,6 +323,20 @@ constexpr int kChunkSmall = 32;       // (48 / 20 / 16: LSE 0.1533 / 0.1506 / 0.
 constexpr int64_t kChunkSmallMaxEntries = 131072;
 constexpr int kFan = 32;      // level-1 partials per level-2 chunk (64 until round 5: a row of 33-64 chunks then ended in one sum of up to 64 partials;
                               //   32 / 128: batch 51 200 and 6 400 the same / +0.4 %, +1.2 %, LSE batch 4 096 0.1473 -> 0.1456 ms / the same)
+// Entries per level-1 chunk of a long row in a batch of n entries (Csr::chunk; why 32 for the small batches of SGD / Adagrad handles on
+// narrow rows: Model::chunk_entries) and the chunk slots of a workspace for up to max_entries entries. A long row of L > chunk entries
+// has ceil(L / chunk) <= 2 L / (chunk + 1) chunks — equality at L = chunk + 1 —, so a batch has fewer than 2 n / chunk of them; the
+// level-2 chunks, two at most per kFan · chunk + 1 entries, likewise. Shared by Model::alloc_table_csr and the table-pass test hook
+// (test_hooks.cpp), which must size its workspace as the product does: tests/test_gpu_table_pass.py builds the batch of chunk + 1 rows.
+inline int csr_chunk_entries(bool adam, int dim, int64_t n) {
+    return (!adam && n <= kChunkSmallMaxEntries && dim <= 128) ? kChunkSmall : kChunk;
+}
+inline void csr_chunk_caps(bool adam, int dim, int64_t max_entries, int* max_chunks, int* max_chunks2) {
+    int64_t c1 = 2 * max_entries / kChunk;
+    if (!adam && dim <= 128) c1 = std::max<int64_t>(c1, 2 * std::min<int64_t>(max_entries, kChunkSmallMaxEntries) / kChunkSmall);
+    *max_chunks = static_cast<int>(c1 + 2);
+    *max_chunks2 = static_cast<int>(c1 / kFan + 2);
+}
 
 // bounds + long-row chunk list, from sorted_key; counters_cleared: row_begin | row_end | num_chunks | num_touched (one
 // allocation of csr_counter_ints(rows) ints) are already zero (sort_pairs cleared them), otherwise a memset does it
@@ -421,6 +437,9 @@ bool launch_untouched_rows(const Csr& c, const RowPassArgs& a, hipStream_t s);
 enum TablePassPath { TABLE_PASS_DENSE = 0, TABLE_PASS_LIST_WALK = 1, TABLE_PASS_ENTRY_WALK = 2 };
 int launch_table_pass(const Csr& c, const RowPassArgs& a, hipStream_t s, hipStream_t untouched_s = nullptr);
 void set_table_pass_one_launch(bool on);      // tests / A-B runs: false = the three-launch form (also NVSM_MERGED_PASS=0)
+bool table_pass_one_launch();                 // what set_table_pass_one_launch last said (the table-pass test hook puts it back)
+// the constants of an Adam row pass (β₁ = 0.9, β₂ = 0.999, ε = 1e-6) for bias correction bc and scaled λ sl (model.cpp)
+void fill_adam_consts(RowPassArgs& a, float bc, float sl);
 
 // words, window > 1 (cpp/updates_adagrad.cu:83-97, cpp/updates_adam.cu:132-151)
 void launch_adagrad_scale(const float* acc, const int* idx, int window, int64_t B, float eps, float* scale, hipStream_t s);

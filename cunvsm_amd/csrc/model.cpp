@@ -364,12 +364,7 @@ void Model::alloc_table_csr(TableState& t, int64_t max_entries, bool chunk_order
     t.max_entries = max_entries;
     // (a long row of c entries has at most c / chunk + 1 chunks and there are fewer than n / chunk long rows: at most 2 n / chunk
     //  chunks; SGD / Adagrad handles cut the long rows of their small batches into shorter chunks — chunk_entries())
-    {
-        int64_t c1 = 2 * max_entries / kChunk;
-        if (method != NVSM_ADAM && dim <= 128) c1 = std::max<int64_t>(c1, 2 * std::min<int64_t>(max_entries, kChunkSmallMaxEntries) / kChunkSmall);
-        t.max_chunks = static_cast<int>(c1 + 2);
-        t.max_chunks2 = static_cast<int>(c1 / kFan + 2);
-    }
+    csr_chunk_caps(method == NVSM_ADAM, dim, max_entries, &t.max_chunks, &t.max_chunks2);
     for (int k = 0; k < t.idx_sets; ++k) {
         TableState::CsrIndex& x = t.idx[k];
         x.sorted_key.alloc(max_entries); x.sorted_entry.alloc(max_entries);
@@ -1653,7 +1648,7 @@ float Model::adam_bc(uint64_t t) const {
 // rows' groups (300-wide rows: twice the chunks are nearly twice the chunk workgroups next to the other pass — Adagrad at batch
 // 6 400 0.2384 -> 0.2457, the Adam modes +1...4 %) and not for large batches (the passes are bytes there).
 int Model::chunk_entries(const TableState& t, int64_t n) const {
-    return (cfg_.update_method != NVSM_ADAM && n <= kChunkSmallMaxEntries && t.dim <= 128) ? kChunkSmall : kChunk;
+    return csr_chunk_entries(cfg_.update_method == NVSM_ADAM, t.dim, n);
 }
 
 Csr Model::csr_of(TableState& t, int64_t n) {
@@ -1689,7 +1684,6 @@ void Model::build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s, 
     if (x.chunk_order.p) launch_chunk_order(csr_of(t, n), t.chunk_key.p, t.chunk_key_sorted.p, t.sort_temp.p, t.sort_temp_bytes, s, /*keys_written=*/n > 0);
 }
 
-static void fill_adam_consts(RowPassArgs& a, float bc, float sl);
 // Streaming (nt) loads / stores for state the row passes touch once per step, so that it does not displace the gradient
 // rows they gather (each read 10-17 times) from the caches: 1 = documents moments, 2 = documents rows, 4 = word moments,
 // 8 = word rows. Interleaved A/B at the bench shape: 0: 1.134, 1: 1.128, 3: 1.125, 5: 1.136, 9: 1.134, 15: 1.144 ms.
@@ -1783,7 +1777,7 @@ void Model::lazy_end_update(TableState& t, const Csr& c, hipStream_t s) {
     if (t.updates_done % kLazyHistory == 0) lazy_refresh(t, nullptr, s);
 }
 
-static void fill_adam_consts(RowPassArgs& a, float bc, float sl) {
+void fill_adam_consts(RowPassArgs& a, float bc, float sl) {
     const double b1 = static_cast<double>(0.9f), b2 = static_cast<double>(0.999f);
     a.one_m_b1 = static_cast<float>(1.0 - b1);
     a.one_m_b2 = static_cast<float>(1.0 - b2);

@@ -370,6 +370,161 @@ int nvsm_debug_sort(int64_t n, int bits, const int32_t* keys, int32_t* keys_out,
     });
 }
 
+// One table pass on caller-supplied inputs (cunvsm_amd_test_hooks.h): the workspace of Model::alloc_table_csr / alloc_table with one
+// index set, the launch sequence of Model::build_csr, the arguments of Model::update_words / update_entities.
+int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* a) {
+    NVSM_REQUIRE(a); NVSM_REQUIRE(a->X);
+    return cunvsm::guarded([&] {
+        using namespace cunvsm;
+        const int64_t rows = a->rows, n = a->n, prev_n = a->prev_keys ? a->prev_n : 0, cap = a->max_entries;
+        const int dim = a->dim, kind = a->kind;
+        const bool adam = a->adam != 0, order = a->chunk_order != 0;
+        const bool uses_m = kind == ROW_ADAM_MV || kind == ROW_ADAM_SPARSE_ENT || kind == ROW_ADAM_DENSE || kind == ROW_ADAM_FULL;
+        const bool uses_p = kind == ROW_SGD || kind == ROW_ADAGRAD_ENT || kind == ROW_ADAM_SPARSE_ENT || kind == ROW_ADAM_DENSE || kind == ROW_ADAM_FULL;
+        const bool uses_sc = kind == ROW_ADAGRAD_ENT || kind == ROW_SCALAR_ACC || kind == ROW_ADAM_MV || kind == ROW_ADAM_SPARSE_ENT || kind == ROW_ADAM_DENSE;
+        auto bad = [](const char* what) { throw Error(NVSM_ERR_INVALID_ARGUMENT, std::string("table_pass: ") + what); };
+        if ((a->table != 0 && a->table != 1) || kind < ROW_SGD || kind > ROW_SCALAR_ACC) bad("table 0 / 1, kind 0 .. 6");
+        if (rows < 1 || rows >= (int64_t(1) << 30) || dim < 1 || n < 0 || prev_n < 0 || cap < 1 || n > cap || prev_n > cap) bad("bad sizes");
+        if (cap >= (int64_t(1) << 26) || a->div < 1 || a->div > 2048 || a->num_src < 1 || std::max(n, prev_n) > a->num_src * a->div) bad("entries must map to source rows: e / div < num_src, e < 2^26");
+        if ((n > 0 && !a->keys) || (uses_p && !a->P) || (uses_m && !a->m) || (kind == ROW_ADAM_FULL && !a->v) || (uses_sc && (!a->sc_in || !a->sc_out))) bad("a state array the kind needs is null");
+        if (a->table == 1 && a->src_scale) bad("src_scale belongs to the words table");
+        for (int64_t i = 0; i < n; ++i) if (a->keys[i] < 0 || a->keys[i] >= rows) bad("key out of range");
+        for (int64_t i = 0; i < prev_n; ++i) if (a->prev_keys[i] < 0 || a->prev_keys[i] >= rows) bad("previous key out of range");
+
+        // the form of the pass: these fields and the defaults, whatever the environment says
+        Tuning t;
+        t.csr_fill_in_bounds = a->fill_in_bounds != 0;
+        t.entry_walk_min = a->entry_walk_min;
+        TuningScope scope(&t);
+        struct Form { bool was; explicit Form(bool on) : was(table_pass_one_launch()) { set_table_pass_one_launch(on); }
+                      ~Form() { set_table_pass_one_launch(was); } } form(a->one_launch != 0);
+
+        auto up = [](void* d, const void* h, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice)); };
+        auto down = [](void* h, const void* d, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost)); };
+        auto copy = [](void* d, const void* s, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemcpy(d, s, bytes, hipMemcpyDeviceToDevice)); };
+        const size_t RD = static_cast<size_t>(rows) * dim, nent = static_cast<size_t>(std::max(n, prev_n));
+
+        // ---- the workspace, as Model::alloc_table_csr / alloc_table size it ----
+        int max_chunks = 0, max_chunks2 = 0;
+        csr_chunk_caps(adam, dim, cap, &max_chunks, &max_chunks2);
+        DevBuf<int> sorted_key, sorted_entry, csr_zeroed, chunk_base, touched, chunk_desc, chunk2_base, chunk2_desc, chunk_order, chunk_key,
+            chunk_key_sorted, arrive_row, arrive2, keys, prev_keys;
+        DevBuf<float> partial, partial_q, partial2, partial2_q;
+        DevBuf<char> sort_temp;
+        sorted_key.alloc(cap); sorted_entry.alloc(cap);
+        csr_zeroed.alloc(csr_counter_ints(rows), true); chunk_base.alloc(rows, true);
+        touched.alloc(std::min<int64_t>(rows, cap));
+        chunk_desc.alloc(static_cast<size_t>(max_chunks) * 3, true);
+        chunk2_base.alloc(rows, true);
+        chunk2_desc.alloc(static_cast<size_t>(max_chunks2) * 2, true);
+        if (order) { chunk_order.alloc(max_chunks, true); chunk_key.alloc(max_chunks, true); chunk_key_sorted.alloc(max_chunks, true); }
+        partial.alloc(static_cast<size_t>(max_chunks) * dim); partial_q.alloc(max_chunks);
+        partial2.alloc(static_cast<size_t>(max_chunks2) * dim); partial2_q.alloc(max_chunks2);
+        NVSM_HIP_CHECK(hipMemset(partial.p, 0xFF, partial.n * sizeof(float))); NVSM_HIP_CHECK(hipMemset(partial_q.p, 0xFF, partial_q.n * sizeof(float)));
+        NVSM_HIP_CHECK(hipMemset(partial2.p, 0xFF, partial2.n * sizeof(float))); NVSM_HIP_CHECK(hipMemset(partial2_q.p, 0xFF, partial2_q.n * sizeof(float)));
+        arrive2.alloc(max_chunks2, true); arrive_row.alloc(rows, true);
+        int sort_bits = 1;
+        while ((int64_t(1) << sort_bits) < rows) ++sort_bits;
+        const size_t sort_temp_bytes = sort_pairs_temp_bytes(cap, sort_bits);
+        sort_temp.alloc(sort_temp_bytes, true);
+
+        // ---- inputs and state ----
+        DevBuf<float> X, coef, sq_src, src_scale, P, m, v, sc_in, sc_out, P2, m2, v2, sc2_in, sc2_out;
+        X.alloc(static_cast<size_t>(a->num_src) * dim); up(X.p, a->X, X.n * sizeof(float));
+        if (a->coef) { coef.alloc(nent); up(coef.p, a->coef, nent * sizeof(float)); }
+        if (a->sq_src) { sq_src.alloc(a->num_src); up(sq_src.p, a->sq_src, sq_src.n * sizeof(float)); }
+        if (a->src_scale) { src_scale.alloc(a->num_src); up(src_scale.p, a->src_scale, src_scale.n * sizeof(float)); }
+        const bool in_place = uses_sc && a->sc_out == a->sc_in;
+        if (a->P) { P.alloc(RD); up(P.p, a->P, RD * sizeof(float)); }
+        if (a->m) { m.alloc(RD); up(m.p, a->m, RD * sizeof(float)); }
+        if (a->v) { v.alloc(RD); up(v.p, a->v, RD * sizeof(float)); }
+        if (a->sc_in) { sc_in.alloc(rows); up(sc_in.p, a->sc_in, rows * sizeof(float)); }
+        if (a->sc_out && !in_place) { sc_out.alloc(rows); up(sc_out.p, a->sc_out, rows * sizeof(float)); }
+        if (n > 0) { keys.alloc(n); up(keys.p, a->keys, n * sizeof(int)); }
+        if (prev_n > 0) {
+            prev_keys.alloc(prev_n); up(prev_keys.p, a->prev_keys, prev_n * sizeof(int));
+            if (P.p) { P2.alloc(RD); copy(P2.p, P.p, RD * sizeof(float)); }
+            if (m.p) { m2.alloc(RD); copy(m2.p, m.p, RD * sizeof(float)); }
+            if (v.p) { v2.alloc(RD); copy(v2.p, v.p, RD * sizeof(float)); }
+            if (sc_in.p) { sc2_in.alloc(rows); copy(sc2_in.p, sc_in.p, rows * sizeof(float)); }
+            if (sc_out.p) { sc2_out.alloc(rows); copy(sc2_out.p, sc_out.p, rows * sizeof(float)); }
+        }
+
+        hipStream_t s;
+        NVSM_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        int* err = nullptr;
+        NVSM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err), sizeof(int), hipHostMallocDefault));
+        *err = 0;
+        uint64_t epoch = 0;
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+
+        auto run = [&](const int* k, int64_t cnt, float* tp, float* tm, float* tv, const float* si, float* so) {
+            Csr c{};
+            c.sorted_key = sorted_key.p; c.sorted_entry = sorted_entry.p;
+            c.row_begin = csr_zeroed.p; c.row_end = csr_zeroed.p + rows; c.chunk_base = chunk_base.p;
+            c.chunk_desc = chunk_desc.p; c.num_chunks = csr_zeroed.p + 2 * rows;
+            c.num_touched = c.num_chunks + 2; c.touched = touched.p;
+            c.partial = partial.p; c.partial_q = partial_q.p;
+            c.chunk2_base = chunk2_base.p; c.chunk2_desc = chunk2_desc.p; c.chunk_order = chunk_order.p;
+            c.partial2 = partial2.p; c.partial2_q = partial2_q.p;
+            c.arrive_row = arrive_row.p; c.arrive2 = arrive2.p;
+            c.n = cnt; c.rows = rows; c.max_chunks = max_chunks; c.max_chunks2 = max_chunks2;
+            c.chunk = csr_chunk_entries(adam, dim, cnt);
+            // Model::build_csr
+            sort_pairs(sort_temp.p, sort_temp_bytes, &epoch, k, sorted_key.p, nullptr, sorted_entry.p, cnt, sort_bits, err, s,
+                       csr_zeroed.p, csr_counter_ints(rows));
+            launch_csr_build(c, s, cnt > 0, chunk_order.p ? chunk_key.p : nullptr);
+            if (chunk_order.p) launch_chunk_order(c, chunk_key.p, chunk_key_sorted.p, sort_temp.p, sort_temp_bytes, s, /*keys_written=*/cnt > 0);
+            // Model::update_words / update_entities
+            RowPassArgs r{};
+            r.table = a->table; r.kind = kind; r.X = X.p;
+            if (a->table == 0) r.wts = coef.p; else r.coefs = coef.p;
+            r.sq_src = sq_src.p; r.src_scale = src_scale.p;
+            r.div = static_cast<uint32_t>(a->div);
+            r.div_magic = (uint64_t(1) << 37) / r.div + 1;
+            r.P = tp; r.m = tm; r.v = tv; r.sc_in = si; r.sc_out = so; r.dim = dim;
+            if (uses_m) fill_adam_consts(r, a->bc, a->lambda);
+            r.lr = a->lr; r.lambda = a->lambda; r.decay = a->decay; r.eps = 1e-6f;
+            r.dense = a->dense != 0; r.wide = a->wide != 0;
+            r.nt_m = a->nt & 1; r.nt_p = (a->nt >> 1) & 1;
+            const int path = launch_table_pass(c, r, s);
+            NVSM_HIP_CHECK(hipGetLastError());
+            NVSM_HIP_CHECK(hipStreamSynchronize(s));
+            return std::make_pair(path, c.chunk);
+        };
+        std::pair<int, int> res{0, 0};
+        try {
+            if (prev_n > 0) run(prev_keys.p, prev_n, P2.p, m2.p, v2.p, sc2_in.p, in_place ? sc2_in.p : sc2_out.p);
+            res = run(keys.p, n, P.p, m.p, v.p, sc_in.p, in_place ? sc_in.p : sc_out.p);
+        } catch (...) {
+            (void)hipStreamDestroy(s); (void)hipHostFree(err);
+            throw;
+        }
+        const int code = *err;
+        (void)hipStreamDestroy(s); (void)hipHostFree(err);
+        if (code) throw Error(NVSM_ERR_DEVICE, "sort reported an error");
+
+        if (a->path) *a->path = res.first;
+        if (a->chunk) *a->chunk = res.second;
+        if (a->num_chunks) down(a->num_chunks, csr_zeroed.p + 2 * rows, 2 * sizeof(int));
+        if (a->max_chunks) *a->max_chunks = max_chunks;
+        if (a->max_chunks2) *a->max_chunks2 = max_chunks2;
+        if (a->arrive_left) {      // the arrival counters of the one-launch pass are back at zero
+            std::vector<int> h(std::max<size_t>(rows, max_chunks2));
+            int left = 0;
+            down(h.data(), arrive_row.p, rows * sizeof(int));
+            for (int64_t i = 0; i < rows; ++i) left += h[i] != 0;
+            down(h.data(), arrive2.p, max_chunks2 * sizeof(int));
+            for (int i = 0; i < max_chunks2; ++i) left += h[i] != 0;
+            *a->arrive_left = left;
+        }
+        if (a->P) down(a->P, P.p, RD * sizeof(float));
+        if (a->m) down(a->m, m.p, RD * sizeof(float));
+        if (a->v) down(a->v, v.p, RD * sizeof(float));
+        if (uses_sc) down(a->sc_out, in_place ? sc_in.p : sc_out.p, rows * sizeof(float));
+    });
+}
+
 int nvsm_debug_gather_mean(int64_t num_rows, int dim, const float* table, const int64_t* idx, const float* wts,
                            int window, int64_t num_out, float* out) {
     NVSM_REQUIRE(table); NVSM_REQUIRE(idx); NVSM_REQUIRE(out);

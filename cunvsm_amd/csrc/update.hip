@@ -104,7 +104,9 @@ __global__ void csr_bounds_kernel(const int* __restrict__ key, int64_t n, int* _
 // Rows with more than kChunk entries (hot words) are cut into chunks of kChunk entries that are reduced in
 // parallel (level 1); rows with more than kFan level-1 chunks additionally get level-2 chunks, each the ordered
 // sum of kFan level-1 partials, so that no thread group ever walks more than max(kChunk, kFan) items serially
-// (until a row exceeds kChunk·kFan² entries) and every sum has a fixed order: results are run-to-run deterministic.
+// (until a row exceeds kChunk·kFan² entries: its final sum then runs over more than kFan level-2 partials, still in index order —
+// tests/test_gpu_table_pass.py pins rows of kFan²·chunk and kFan²·chunk + 1 entries, exact, for both chunk lengths) and every sum
+// has a fixed order: results are run-to-run deterministic.
 // csr_chunks_kernel (large batches) / csr_bounds_kernel itself (small ones: launch_csr_build) reserve the chunk ranges of the long
 // rows; the descriptors are written by
 // csr_chunk_fill_kernel, one thread per entry (a row-serial fill took 94 us for the Zipf head word).
@@ -1163,6 +1165,7 @@ static bool& merged_pass_flag() {      // (process-wide test hook: nvsm_debug_se
 }
 static bool merged_pass_enabled() { return merged_pass_flag() && tuning().merged_pass; }
 void set_table_pass_one_launch(bool on) { merged_pass_flag() = on; }
+bool table_pass_one_launch() { return merged_pass_flag(); }
 
 template <int V, int TABLE>
 static void table_pass_dispatch(const Csr& c, const RowPassArgs& a, int G, int nvec, int64_t row_items, hipStream_t s) {

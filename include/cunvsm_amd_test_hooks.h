@@ -52,6 +52,41 @@ int nvsm_debug_delay(nvsm_model* m, int microseconds);
 /* table passes of the update in one launch (1, the default) or as the three launches chunk / level-2 / rows (0): the two
  * forms are bit-identical (tests/test_gpu_parity.py); process-wide */
 int nvsm_debug_set_table_pass_form(int one_launch);
+/* ONE table pass of the update on caller-supplied inputs (tests/test_gpu_table_pass.py): the host arrays are uploaded, then the
+ * product's own launchers run in the order model.cpp calls them - sort_pairs, launch_csr_build, launch_chunk_order when the
+ * chunks get an order, launch_table_pass - on a workspace sized by the product's own arithmetic (csr_chunk_caps /
+ * csr_chunk_entries, kernels.h), and the state is copied back. Lazy decay stays out (RowPassArgs::pending is empty).
+ * The form of the pass comes from the fields below alone - a Tuning of the hook's own with every other switch at its default, and
+ * the process-wide launch form put back on exit -, never from the environment.
+ * Entry e (its position in `keys`) reads source row e / div of X and coefficient coef[e]: num_src * div >= max(n, prev_n), and
+ * coef, where given, has max(n, prev_n) elements. The partial sums of the chunk tree start as 0xFF bytes (NaN). */
+typedef struct nvsm_debug_table_pass_args {
+    int table;                       /* 0 words (q += coef * sq_src, src_scale applies), 1 entities (q += coef^2 * sq_src) */
+    int kind;                        /* RowKind (kernels.h): 0 SGD, 1 Adagrad, 2 Adam m/v, 3 sparse Adam, 4 dense Adam, 5 full Adam, 6 accumulator */
+    int64_t rows; int dim;
+    int64_t n; const int32_t* keys;  /* the table row of every entry, in batch order, each in [0, rows) */
+    int div; int64_t num_src;
+    const float* X;                  /* [num_src][dim] */
+    const float* coef;               /* per entry: wts (words) / coefs (entities); null = 1 */
+    const float* sq_src;             /* [num_src] or null */
+    const float* src_scale;          /* [num_src] or null (words only) */
+    float* P; float* m; float* v;    /* in / out [rows][dim]; m and v may be null for the kinds that do not use them */
+    const float* sc_in; float* sc_out;   /* per-row scalar [rows]: sc_out is uploaded too (rows the pass does not visit keep what it held);
+                                            sc_out == sc_in: updated in place, as the accumulator pass of Adagrad's words update does */
+    float lr, lambda, decay, bc; int dense;
+    int wide;                        /* RowPassArgs::wide (a ROW_SGD pass of an Adam update) */
+    int nt;                          /* bit 0: RowPassArgs::nt_m, bit 1: nt_p */
+    int64_t max_entries; int adam;   /* what the workspace is sized for (>= n, >= prev_n); the handle's update method is Adam */
+    int one_launch, chunk_order, fill_in_bounds; int64_t entry_walk_min;
+    int64_t prev_n; const int32_t* prev_keys;   /* optional: a batch run first through the same workspace, on scratch copies of the state */
+    /* out (each may be null) */
+    int* path;                       /* TablePassPath: 0 dense, 1 list walk, 2 entry walk */
+    int* chunk;                      /* entries per level-1 chunk */
+    int* num_chunks;                 /* [2]: level-1 / level-2 chunks the CSR build reserved */
+    int* max_chunks; int* max_chunks2;
+    int* arrive_left;                /* arrival counters of the one-launch pass that are not back at zero after it */
+} nvsm_debug_table_pass_args;
+int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* args);
 /* nvsm_neighbors' scan through the plain kernel whatever the dimension (1) or by its own dispatch (0, the default): how
  * tools/bench_neighbors.py holds the MFMA scan with the tail chunk against the plain scan on the same table; process-wide */
 int nvsm_debug_neighbors_force_plain(int on);
