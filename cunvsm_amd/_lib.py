@@ -73,6 +73,18 @@ class NvsmRankOptions(C.Structure):
     ]
 
 
+EVAL_MAX_CUTOFFS = 8
+# columns of a metric row (include/cunvsm_amd.h NVSM_EVAL_*); then per cutoff j: P, recall, ndcg at EVAL_FIXED + 3 j + {0, 1, 2}
+EVAL_NUM_RET, EVAL_NUM_REL, EVAL_NUM_REL_RET, EVAL_AP, EVAL_RPREC, EVAL_RECIP_RANK, EVAL_NDCG, EVAL_FIXED = range(8)
+
+
+class NvsmJudgments(C.Structure):
+    _fields_ = [
+        ("doc_ids", C.c_void_p), ("grades", C.c_void_p), ("offsets", C.c_void_p), ("cutoffs", C.c_void_p),
+        ("num_cutoffs", C.c_int32), ("reserved", C.c_int32 * 3),
+    ]
+
+
 class NvsmNeighborQueries(C.Structure):
     _fields_ = [("ids", C.c_void_p), ("vectors", C.c_void_p), ("num_queries", C.c_int64), ("source_space", C.c_int32), ("dim", C.c_int32)]
 
@@ -228,6 +240,7 @@ def lib():
         "nvsm_rank_options_default": (None, [P(NvsmRankOptions)]),
         "nvsm_infer": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp]),
         "nvsm_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp, vp, vp]),
+        "nvsm_evaluate": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmJudgments), vp, vp, vp, vp]),
         "nvsm_neighbor_options_default": (None, [P(NvsmNeighborOptions)]),
         "nvsm_neighbors": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNeighborOptions), vp, vp, vp]),
         "nvsm_similarity": (C.c_int, [vp, C.c_int32, vp, vp, i64, C.c_int32, vp]),

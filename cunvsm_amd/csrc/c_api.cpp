@@ -298,6 +298,11 @@ int nvsm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_option
     NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(opt); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
     return guarded_on(m, [&] { m->impl.rank(*queries, *opt, doc_ids, scores, counts); });
 }
+int nvsm_evaluate(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* opt, const nvsm_judgments* judgments,
+                  double* metrics, int64_t* doc_ids, float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(opt); NVSM_REQUIRE(judgments);
+    return guarded_on(m, [&] { m->impl.evaluate(*queries, *opt, *judgments, metrics, doc_ids, scores, counts); });
+}
 
 void nvsm_neighbor_options_default(nvsm_neighbor_options* o) {
     if (!o) return;

@@ -503,5 +503,18 @@ void launch_rank_exclude_self(float* scores, int64_t ld_scores, int64_t d_begin,
 void launch_rank_pair_sim(const float* table, int dim, const int64_t* a, const int64_t* b, int64_t n, float* out, int cosine,
                           const LazyView& lazy, hipStream_t s);
 
+// ---- retrieval metrics of a round's ranking (eval.hip; include/cunvsm_amd.h nvsm_evaluate) ----
+// One wave per query of the round. ids [Q][k] / counts [Q]: what launch_rank_write left. Judged documents of ALL queries of the
+// call: jids ascending per query (no -1 entries), jgrades next to them, joff [queries of the call + 1]; consts
+// [query][2 + kEvalMaxCutoffs] = R, idcg, idcg@cutoff; metrics [query][NVSM_EVAL_FIXED + 3 num_cutoffs]. q0: the round's first query.
+constexpr int kEvalMaxCutoffs = 8;
+struct EvalArgs {
+    const int64_t* ids; const int64_t* counts; int k;
+    const int* jids; const int* jgrades; const int64_t* joff; const double* consts;
+    int cutoffs[kEvalMaxCutoffs]; int num_cutoffs;
+    double* metrics; int64_t q0;
+};
+void launch_eval_metrics(const EvalArgs& a, int Q, hipStream_t s);
+
 
 }  // namespace cunvsm

@@ -151,6 +151,9 @@ class Model {
     // Model::infer (cpp/model.cu:105-133) for ragged queries, and the ranking of py/nvsm/base.py:362-430 (rank.cpp)
     void infer(const nvsm_queries& q, const nvsm_rank_options& opt, float* out);
     void rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts);
+    // the same ranking plus per-query retrieval metrics computed on the device (eval.hip); doc_ids / scores / counts may be null
+    void evaluate(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_judgments& j, double* metrics, int64_t* doc_ids,
+                  float* scores, int64_t* counts);
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
     // 362-430), and the similarity of pairs of rows (ranking.cpp)
     void neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts);
@@ -345,9 +348,17 @@ class Model {
         DevBuf<char> sel_ws;
         DevBuf<float> panel, pslab, pair_out;      // neighbours: the query panel [round][dim], one slab of the projected vocabulary
         DevBuf<int64_t> self;                      //             ... the queries' own rows (exclude_self)
+        DevBuf<int> jids, jgrades;                 // evaluate: the call's judged ids (ascending per query) and grades,
+        DevBuf<int64_t> joff;                      //           ... their offsets,
+        DevBuf<double> jconst, metrics;            //           ... R / idcg / idcg@c per query, and the metric rows
     };
     RankScratch rank_;
     void rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt);      // argument checks; the handle's streams joined
+    void rank_check(const nvsm_queries& q, const nvsm_rank_options& opt);      // ... the checks alone
+    struct EvalPlan;                        // evaluate: the judgments as the kernel reads them (ranking.cpp)
+    void eval_plan(EvalPlan& p, int64_t Q) const;                                 // checks, sorts, R / idcg / idcg@c
+    // the rounds of rank and evaluate (ev null: rank); null result pointers are not copied to
+    void rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts, EvalPlan* ev);
     void rank_join();                       // the handle's four streams waited for on the host; the words table's pending stamps settled
     struct RowSpace { const float* rows; int64_t count; int dim; const TableState* table; };      // rows null: the projected vocabulary
     RowSpace row_space(int space) const;

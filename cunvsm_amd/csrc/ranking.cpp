@@ -33,6 +33,11 @@ int64_t pow2_at_least(int64_t n) { int64_t p = 1; while (p < n) p <<= 1; return 
 }  // namespace
 
 void Model::rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt) {
+    rank_check(q, opt);
+    rank_join();
+}
+
+void Model::rank_check(const nvsm_queries& q, const nvsm_rank_options& opt) {
     if (q.num_queries < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_queries is negative");
     if (!q.offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->offsets");
     if (q.offsets[0] != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->offsets[0] must be 0");
@@ -51,7 +56,6 @@ void Model::rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt) {
     if (act != NVSM_ACT_MODEL && act != NVSM_ACT_IDENTITY && act != NVSM_TANH && act != NVSM_HARD_TANH)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown activation");
     if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
-    rank_join();
 }
 
 void Model::rank_join() {
@@ -101,6 +105,86 @@ void Model::infer(const nvsm_queries& q, const nvsm_rank_options& opt, float* ou
 }
 
 void Model::rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts) {
+    rank_rounds(q, opt, doc_ids, scores, counts, nullptr);
+}
+
+// ---- retrieval metrics (include/cunvsm_amd.h nvsm_evaluate; kernel: eval.hip) ------------------------------------
+// What the host prepares once per call: every query's judged list sorted by id with the -1 entries (judged documents the model
+// does not hold) dropped, and the constants of the formulas that do not depend on the ranking — R, idcg, idcg@c — in double.
+struct Model::EvalPlan {
+    const nvsm_judgments* request = nullptr;
+    double* metrics = nullptr;                  // host [Q][width]
+    int width = 0, num_cutoffs = 0;
+    int cutoffs[kEvalMaxCutoffs] = {};
+    std::vector<int> ids, grades;               // concatenated, per query ascending by id
+    std::vector<int64_t> off;                   // [Q + 1]
+    std::vector<double> consts;                 // [Q][2 + kEvalMaxCutoffs]
+};
+
+void Model::evaluate(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_judgments& j, double* metrics, int64_t* doc_ids,
+                     float* scores, int64_t* counts) {
+    EvalPlan plan;
+    plan.request = &j;      // (looked at by rank_rounds, behind nvsm_rank's own checks)
+    plan.metrics = metrics;
+    rank_rounds(q, opt, doc_ids, scores, counts, &plan);
+}
+
+void Model::eval_plan(EvalPlan& p, int64_t Q) const {
+    const nvsm_judgments& j = *p.request;
+    const int64_t D = cfg_.num_entities;
+    if (!p.metrics) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: metrics");
+    if (!j.offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: judgments->offsets");
+    if (j.offsets[0] != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "judgments->offsets[0] must be 0");
+    for (int64_t i = 0; i < Q; ++i)
+        if (j.offsets[i + 1] < j.offsets[i]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "judgments->offsets decrease");
+    if (j.offsets[Q] > 0 && !j.doc_ids) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: judgments->doc_ids");
+    if (j.offsets[Q] > 0 && !j.grades) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: judgments->grades");
+    if (j.num_cutoffs < 0 || j.num_cutoffs > NVSM_EVAL_MAX_CUTOFFS)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "judgments->num_cutoffs must be in [0, NVSM_EVAL_MAX_CUTOFFS]");
+    if (j.num_cutoffs > 0 && !j.cutoffs) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: judgments->cutoffs");
+    for (int c = 0; c < j.num_cutoffs; ++c) {
+        if (j.cutoffs[c] < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a cutoff is smaller than 1");
+        if (c > 0 && j.cutoffs[c] <= j.cutoffs[c - 1]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "judgments->cutoffs must ascend");
+        p.cutoffs[c] = j.cutoffs[c];
+    }
+    p.num_cutoffs = j.num_cutoffs;
+    p.width = NVSM_EVAL_FIXED + 3 * j.num_cutoffs;
+    p.off.assign(static_cast<size_t>(Q) + 1, 0);
+    p.consts.assign(static_cast<size_t>(Q) * (2 + kEvalMaxCutoffs), 0.0);
+    std::vector<std::pair<int, int>> one;       // (id, grade) of one query
+    std::vector<int> gains;
+    for (int64_t i = 0; i < Q; ++i) {
+        one.clear();
+        gains.clear();
+        int64_t R = 0;
+        for (int64_t t = j.offsets[i]; t < j.offsets[i + 1]; ++t) {
+            const int64_t id = j.doc_ids[t];
+            const int g = j.grades[t];
+            if (id < -1 || id >= D) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a judged document id is outside [-1, num_entities)");
+            if (g >= 1) { ++R; gains.push_back(g); }
+            if (id >= 0) one.emplace_back(static_cast<int>(id), g);
+        }
+        std::sort(one.begin(), one.end());
+        for (size_t t = 1; t < one.size(); ++t)
+            if (one[t].first == one[t - 1].first) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a document id is judged twice for one query");
+        for (const auto& e : one) { p.ids.push_back(e.first); p.grades.push_back(e.second); }
+        p.off[static_cast<size_t>(i) + 1] = static_cast<int64_t>(p.ids.size());
+        // idcg: the grades > 0 in descending order, gain g / log2(rank + 1), summed in rank order
+        std::sort(gains.begin(), gains.end(), [](int x, int y) { return x > y; });
+        double* c = p.consts.data() + static_cast<size_t>(i) * (2 + kEvalMaxCutoffs);
+        c[0] = static_cast<double>(R);
+        double sum = 0.0;
+        int next = 0;
+        for (size_t t = 0; t < gains.size(); ++t) {
+            while (next < p.num_cutoffs && static_cast<int64_t>(t) >= p.cutoffs[next]) c[2 + next++] = sum;
+            sum += static_cast<double>(gains[t]) / std::log2(static_cast<double>(t) + 2.0);
+        }
+        while (next < p.num_cutoffs) c[2 + next++] = sum;
+        c[1] = sum;
+    }
+}
+
+void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts, EvalPlan* ev) {
     const int64_t D = cfg_.num_entities, Q = q.num_queries;
     const int de = cfg_.entity_repr_size;
     if (opt.similarity != NVSM_SIM_COSINE && opt.similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
@@ -135,9 +219,30 @@ void Model::rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* d
     }
     const bool by_candidates = !cand_off.empty();
     const int64_t kScoreFloats = static_cast<int64_t>(tune_.rank_slab_mb) * (int64_t(1) << 18);      // score slab: 256 MB unless NVSM_RANK_SLAB_MB says otherwise
-    rank_begin(q, opt);
+    rank_check(q, opt);
+    if (ev) eval_plan(*ev, Q);      // (host work only: refusals come before anything runs)
+    rank_join();
     RankScratch& r = rank_;
     const LazyView view = lazy_view(ents_);
+    EvalArgs ea{};
+    if (ev) {      // the judgments and their constants go up once, not per round
+        grow(r.jids, std::max<size_t>(ev->ids.size(), 1));
+        grow(r.jgrades, std::max<size_t>(ev->ids.size(), 1));
+        grow(r.joff, static_cast<size_t>(Q) + 1);
+        grow(r.jconst, std::max<size_t>(ev->consts.size(), 1));
+        grow(r.metrics, std::max<size_t>(static_cast<size_t>(Q) * ev->width, 1));
+        if (!ev->ids.empty()) {
+            NVSM_HIP_CHECK(hipMemcpy(r.jids.p, ev->ids.data(), ev->ids.size() * sizeof(int), hipMemcpyHostToDevice));
+            NVSM_HIP_CHECK(hipMemcpy(r.jgrades.p, ev->grades.data(), ev->grades.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
+        NVSM_HIP_CHECK(hipMemcpy(r.joff.p, ev->off.data(), ev->off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (!ev->consts.empty()) NVSM_HIP_CHECK(hipMemcpy(r.jconst.p, ev->consts.data(), ev->consts.size() * sizeof(double), hipMemcpyHostToDevice));
+        ea.k = k;
+        ea.jids = r.jids.p; ea.jgrades = r.jgrades.p; ea.joff = r.joff.p; ea.consts = r.jconst.p;
+        for (int c = 0; c < kEvalMaxCutoffs; ++c) ea.cutoffs[c] = ev->cutoffs[c];
+        ea.num_cutoffs = ev->num_cutoffs;
+        ea.metrics = r.metrics.p;
+    }
 
     for (int64_t q0 = 0; q0 < Q;) {
         // ---- how many queries this round, and the layout of their scratch
@@ -209,17 +314,28 @@ void Model::rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* d
             prof.note(global_steps ? "rank_sort_global" : "rank_sort_lds");
             launch_rank_write(r.keys.p, npad, static_cast<int>(qn), k, cand_off_dev, n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
         }
-        NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        if (ev) {      // the round's metrics from the ranked ids where they lie: one wave per query
+            RankProf scope(prof, "rank_eval", stream_);
+            ea.ids = r.out_ids.p; ea.counts = r.out_counts.p; ea.q0 = q0;
+            launch_eval_metrics(ea, static_cast<int>(qn), stream_);
+        }
+        if (doc_ids) NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        if (scores) NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        if (counts) NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
         NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
         q0 += qn;
     }
+    if (ev && Q > 0)
+        NVSM_HIP_CHECK(hipMemcpy(ev->metrics, r.metrics.p, static_cast<size_t>(Q) * ev->width * sizeof(double), hipMemcpyDeviceToHost));
     // a query without words retrieves nothing (the reference returns None)
     for (int64_t i = 0; i < Q; ++i) {
         if (q.offsets[i + 1] > q.offsets[i]) continue;
-        counts[i] = 0;
-        for (int j = 0; j < k; ++j) { doc_ids[i * k + j] = -1; scores[i * k + j] = -INFINITY; }
+        if (counts) counts[i] = 0;
+        for (int j = 0; j < k; ++j) {
+            if (doc_ids) doc_ids[i * k + j] = -1;
+            if (scores) scores[i * k + j] = -INFINITY;
+        }
+        if (ev) std::fill(ev->metrics + i * ev->width, ev->metrics + (i + 1) * ev->width, 0.0);
     }
     raise_device_error();
 }

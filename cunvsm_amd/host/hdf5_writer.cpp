@@ -15,7 +15,8 @@ namespace {
 typedef int64_t hid_t;
 typedef int herr_t;
 typedef unsigned long long hsize_t;
-constexpr unsigned kH5F_ACC_EXCL = 0x0004u;
+constexpr unsigned kH5F_ACC_EXCL = 0x0004u, kH5F_ACC_RDONLY = 0x0000u;
+constexpr int kH5T_FLOAT = 1;          // H5T_class_t
 constexpr hid_t kH5P_DEFAULT = 0, kH5S_ALL = 0;
 constexpr int kH5T_ORDER_LE = 0;
 
@@ -34,6 +35,17 @@ struct Hdf5Api {
     herr_t (*Dwrite)(hid_t, hid_t, hid_t, hid_t, hid_t, const void*) = nullptr;
     herr_t (*Dclose)(hid_t) = nullptr;
     herr_t (*Eset_auto2)(hid_t, void*, void*) = nullptr;
+    // ... and what read_hdf5 needs
+    hid_t (*Fopen)(const char*, unsigned, hid_t) = nullptr;
+    int (*Lexists)(hid_t, const char*, hid_t) = nullptr;                  // htri_t
+    hid_t (*Dopen2)(hid_t, const char*, hid_t) = nullptr;
+    hid_t (*Dget_space)(hid_t) = nullptr;
+    hid_t (*Dget_type)(hid_t) = nullptr;
+    int (*Sget_simple_extent_ndims)(hid_t) = nullptr;
+    int (*Sget_simple_extent_dims)(hid_t, hsize_t*, hsize_t*) = nullptr;
+    int (*Tget_class)(hid_t) = nullptr;
+    size_t (*Tget_size)(hid_t) = nullptr;
+    herr_t (*Dread)(hid_t, hid_t, hid_t, hid_t, hid_t, void*) = nullptr;
     hid_t* native_float = nullptr;
 
     static Hdf5Api& get() {
@@ -59,6 +71,10 @@ struct Hdf5Api {
         NVSM_H5_SYM(Tcopy, "H5Tcopy") NVSM_H5_SYM(Tset_order, "H5Tset_order") NVSM_H5_SYM(Tclose, "H5Tclose")
         NVSM_H5_SYM(Dcreate2, "H5Dcreate2") NVSM_H5_SYM(Dwrite, "H5Dwrite") NVSM_H5_SYM(Dclose, "H5Dclose")
         NVSM_H5_SYM(Eset_auto2, "H5Eset_auto2") NVSM_H5_SYM(native_float, "H5T_NATIVE_FLOAT_g")
+        NVSM_H5_SYM(Fopen, "H5Fopen") NVSM_H5_SYM(Lexists, "H5Lexists") NVSM_H5_SYM(Dopen2, "H5Dopen2") NVSM_H5_SYM(Dget_space, "H5Dget_space")
+        NVSM_H5_SYM(Dget_type, "H5Dget_type") NVSM_H5_SYM(Sget_simple_extent_ndims, "H5Sget_simple_extent_ndims")
+        NVSM_H5_SYM(Sget_simple_extent_dims, "H5Sget_simple_extent_dims") NVSM_H5_SYM(Tget_class, "H5Tget_class")
+        NVSM_H5_SYM(Tget_size, "H5Tget_size") NVSM_H5_SYM(Dread, "H5Dread")
 #undef NVSM_H5_SYM
         unsigned maj = 0, min = 0, rel = 0;
         api.get_libversion(&maj, &min, &rel);
@@ -78,8 +94,8 @@ void write_hdf5(const std::string& filename, const std::vector<Hdf5Dataset>& dat
     const hid_t file = h5.Fcreate(filename.c_str(), kH5F_ACC_EXCL, kH5P_DEFAULT, kH5P_DEFAULT);
     if (file < 0) NVSM_LOG(FATAL) << "unable to create " << filename << " (H5F_ACC_EXCL: the file must not exist yet)";
     for (const Hdf5Dataset& d : datasets) {
-        const hsize_t dims[2] = {d.dim0, d.dim1};
-        const hid_t space = h5.Screate_simple(2, dims, nullptr);
+        const hsize_t dims[2] = {d.rank == 1 ? d.dim0 * d.dim1 : d.dim0, d.dim1};
+        const hid_t space = h5.Screate_simple(d.rank == 1 ? 1 : 2, dims, nullptr);
         const hid_t type = h5.Tcopy(*h5.native_float);
         bool ok = space >= 0 && type >= 0 && h5.Tset_order(type, kH5T_ORDER_LE) >= 0;
         hid_t dset = -1;
@@ -91,6 +107,42 @@ void write_hdf5(const std::string& filename, const std::vector<Hdf5Dataset>& dat
         if (!ok) { h5.Fclose(file); NVSM_LOG(FATAL) << "failed to write dataset " << d.name << " to " << filename; }
     }
     if (h5.Fclose(file) < 0) NVSM_LOG(FATAL) << "failed to close " << filename;
+}
+
+std::vector<Hdf5Array> read_hdf5(const std::string& filename, const std::vector<std::string>& names) {
+    Hdf5Api& h5 = Hdf5Api::get();
+    h5.Eset_auto2(0 /* H5E_DEFAULT */, nullptr, nullptr);
+    const hid_t file = h5.Fopen(filename.c_str(), kH5F_ACC_RDONLY, kH5P_DEFAULT);
+    if (file < 0) NVSM_LOG(FATAL) << "unable to open " << filename << " as an HDF5 file";
+    std::vector<Hdf5Array> out;
+    std::string error;
+    for (const std::string& name : names) {
+        if (h5.Lexists(file, name.c_str(), kH5P_DEFAULT) <= 0) { error = "holds no dataset " + name; break; }
+        const hid_t dset = h5.Dopen2(file, name.c_str(), kH5P_DEFAULT);
+        if (dset < 0) { error = "holds no dataset " + name; break; }
+        const hid_t space = h5.Dget_space(dset), type = h5.Dget_type(dset);
+        Hdf5Array a;
+        a.name = name;
+        hsize_t dims[2] = {0, 0};
+        if (space < 0 || type < 0) error = "dataset " + name + " cannot be described";
+        else if (h5.Sget_simple_extent_ndims(space) != 2) error = "dataset " + name + " is not two-dimensional";
+        else if (h5.Tget_class(type) != kH5T_FLOAT || h5.Tget_size(type) != sizeof(float)) error = "dataset " + name + " does not hold float32 values";
+        else if (h5.Sget_simple_extent_dims(space, dims, nullptr) != 2) error = "dataset " + name + " cannot be described";
+        else {
+            a.dim0 = dims[0]; a.dim1 = dims[1];
+            a.data.resize(static_cast<size_t>(dims[0]) * static_cast<size_t>(dims[1]));
+            if (!a.data.empty() && h5.Dread(dset, *h5.native_float, kH5S_ALL, kH5S_ALL, kH5P_DEFAULT, a.data.data()) < 0)
+                error = "dataset " + name + " cannot be read";
+        }
+        if (type >= 0) h5.Tclose(type);
+        if (space >= 0) h5.Sclose(space);
+        h5.Dclose(dset);
+        if (!error.empty()) break;
+        out.push_back(std::move(a));
+    }
+    h5.Fclose(file);
+    if (!error.empty()) NVSM_LOG(FATAL) << filename << " " << error;
+    return out;
 }
 
 }  // namespace nvsm_host

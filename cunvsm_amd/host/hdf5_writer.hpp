@@ -15,10 +15,20 @@ struct Hdf5Dataset {
     std::string name;
     unsigned long long dim0, dim1;   // as written: {cols, rows} of the reference matrix
     const float* data;               // dim0 * dim1 floats, row-major [dim0][dim1]
+    int rank = 2;                    // 1: the same floats as ONE dimension of dim0 * dim1 (what other writers produce; read_hdf5 refuses it)
 };
 
 // Throws FatalError (file exists, library missing, write error).
 void write_hdf5(const std::string& filename, const std::vector<Hdf5Dataset>& datasets);
+// The reader of what write_hdf5 wrote (py/nvsm/base.py:182-240 reads the same four datasets with h5py): every named dataset must
+// exist, be two-dimensional and hold 4-byte floats; they come back as float32 [dim0][dim1] in the order of `names`. Throws FatalError
+// (file or dataset missing, wrong rank or type, read error).
+struct Hdf5Array {
+    std::string name;
+    unsigned long long dim0 = 0, dim1 = 0;
+    std::vector<float> data;
+};
+std::vector<Hdf5Array> read_hdf5(const std::string& filename, const std::vector<std::string>& names);
 // Loads libhdf5 and initialises it now (the reference links it, so its loader pays this before main(); here it would otherwise
 // land inside the first model dump — on a cold box 0.9 s in the middle of the second epoch's batches-per-second figure).
 void hdf5_preload();

@@ -1,0 +1,363 @@
+// cuNVSMQuery — the reference's py/query.py on top of libcunvsm_amd.so's C ABI: from what cuNVSMTrainModel writes
+// ("<output>_meta", "<output>_<epoch>[_<batch>].hdf5") to one TREC run per topic file and, with --qrels, the retrieval metrics
+// that pick the epoch (rank-cranfield-collection.sh), computed on the device by nvsm_evaluate in the same call that ranks.
+//
+//   cuNVSMQuery --index <trectext file | Indri repository> --topics f1 [f2 ...] [OPTIONS] <model>_<epoch>.hdf5 <run_out>
+//
+// Differences from py/query.py, all forced by what exists on this platform:
+//   * the index is the one the trainer reads (host/trectext_index.hpp, host/indri_index.hpp); topics are tokenised with the
+//     trectext tokenizer. With a TREC-text collection the SAME --stopwords as at training time is needed, or the term ids differ.
+//   * the written score is the cosine similarity nvsm_rank returns; the reference writes cos - 1 through an external writer —
+//     the same ranking.
+//   * ties in a ranking are broken by ascending model document id, not by docno.
+//   * not offered: --rerank_exact_matching_documents, --num_workers, --l2norm_phrase (see --help).
+#include <sys/stat.h>
+
+#include <cmath>
+#include <cstdio>
+#include <fstream>
+#include <iomanip>
+#include <memory>
+#include <set>
+#include <sstream>
+
+#include "../../include/cunvsm_amd.h"
+#include "base.hpp"
+#include "flags.hpp"
+#include "hdf5_writer.hpp"
+#include "indri_index.hpp"
+#include "query_lib.hpp"
+#include "trectext_index.hpp"
+
+using namespace nvsm_host;
+
+namespace {
+
+std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs;
+bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
+    FLAGS_l2norm_phrase, FLAGS_help;
+double FLAGS_bias_coefficient;
+int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers;
+
+void define_flags(Flags* f) {
+    f->define_string("index", &FLAGS_index, "", "TREC-text collection file or Indri repository directory, as given to cuNVSMTrainModel.");
+    f->define_string("topics", &FLAGS_topics, "", "Topic file, one query per line: <topic id>;<text>. Further topic files follow as "
+                     "positional arguments in front of the model.");
+    f->define_string("stopwords", &FLAGS_stopwords, "", "Stop list applied while indexing a TREC-text collection. Must be the one used at "
+                     "training time: term ids are assigned while indexing, and the meta file maps THOSE ids to the model's.");
+    f->define_string("top_k", &FLAGS_top_k, "", "Documents per topic: a number (default 1000, clipped to the number of documents of the "
+                     "model), 'all', or qrel file names (blank-separated): each topic is then ranked among its judged documents only.");
+    f->define_bool("linear", &FLAGS_linear, false, "No nonlinearity behind the projection (default: tanh).");
+    f->define_double("bias_coefficient", &FLAGS_bias_coefficient, 0.0, "Accepted as by the reference, which never applies the bias: "
+                     "py/nvsm/base.py keeps the bias only where the coefficient is 0. Not fixed here.");
+    f->define_bool("self_information", &FLAGS_self_information, false, "Weight query terms by -log(term frequency / total terms).");
+    f->define_bool("strict", &FLAGS_strict, false, "Skip a topic when any of its terms is out of vocabulary (default: skip the term).");
+    f->define_int64("num_queries", &FLAGS_num_queries, 0, "Keep the first n topics of every topic file (default: all).");
+    f->define_string("qrels", &FLAGS_qrels, "", "Qrel file names (blank-separated, lines of <topic> <iteration> <docno> <grade>): evaluates "
+                     "every topic file's ranking on the device and prints the means in trec_eval's layout.");
+    f->define_string("cutoffs", &FLAGS_cutoffs, "5,10,20,100,1000", "Rank cutoffs of P, recall and ndcg_cut (ascending, at most 8).");
+    f->define_bool("per_query", &FLAGS_per_query, false, "With --qrels: also print every evaluated topic's metrics.");
+    f->define_int64("device", &FLAGS_device, 0, "HIP device ordinal.");
+    f->define_bool("rerank_exact_matching_documents", &FLAGS_rerank_exact_matching_documents, false, "NOT OFFERED: it needs Indri's TF-IDF "
+                   "query environment, which does not exist here.");
+    f->define_int64("num_workers", &FLAGS_num_workers, 0, "NOT OFFERED (accepted and ignored): every topic file is one GPU pass.");
+    f->define_bool("l2norm_phrase", &FLAGS_l2norm_phrase, false, "NOT OFFERED: py/nvsm/base.py has no such argument (the reference's "
+                   "py/query.py fails when it is given).");
+    f->define_bool("help", &FLAGS_help, false, "Print the options and exit.");
+    f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
+    f->define_int64("v", &FLAGS_v, 0, "Verbosity of VLOG messages.");
+}
+
+void check_status(int status, const char* what) {
+    if (status != NVSM_OK) NVSM_LOG(FATAL) << what << ": " << nvsm_last_error();
+}
+#define NVSM_CALL(expr) check_status((expr), #expr)
+
+bool is_directory(const std::string& path) { struct stat st; return stat(path.c_str(), &st) == 0 && S_ISDIR(st.st_mode); }
+bool is_file(const std::string& path) { struct stat st; return stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
+bool exists(const std::string& path) { struct stat st; return stat(path.c_str(), &st) == 0; }
+std::string basename_of(const std::string& path) { const size_t cut = path.rfind('/'); return cut == std::string::npos ? path : path.substr(cut + 1); }
+
+std::vector<std::string> split_blanks(const std::string& s) {
+    std::istringstream in(s);
+    std::vector<std::string> out;
+    for (std::string w; in >> w;) out.push_back(w);
+    return out;
+}
+
+Qrels read_qrels(const std::vector<std::string>& paths) {
+    Qrels qrels;
+    for (const std::string& path : paths) {
+        std::ifstream f(path);
+        NVSM_CHECK(f.good()) << "cannot read " << path;
+        parse_qrels(f, path, &qrels);
+    }
+    return qrels;
+}
+
+std::vector<int32_t> parse_cutoffs(const std::string& s) {
+    std::vector<int32_t> cutoffs;
+    std::istringstream in(s);
+    for (std::string item; std::getline(in, item, ',');) {
+        char* end = nullptr;
+        const long c = std::strtol(item.c_str(), &end, 10);
+        if (item.empty() || *end != '\0' || c < 1 || c > 2147483647L) NVSM_LOG(FATAL) << "--cutoffs: '" << item << "' is no rank cutoff";
+        if (!cutoffs.empty() && c <= cutoffs.back()) NVSM_LOG(FATAL) << "--cutoffs must ascend";
+        cutoffs.push_back(static_cast<int32_t>(c));
+    }
+    if (cutoffs.size() > NVSM_EVAL_MAX_CUTOFFS) NVSM_LOG(FATAL) << "--cutoffs: at most " << NVSM_EVAL_MAX_CUTOFFS;
+    return cutoffs;
+}
+
+std::vector<std::string> metric_names(const std::vector<int32_t>& cutoffs) {      // trec_eval's, in the order of a metric row
+    std::vector<std::string> names = {"num_ret", "num_rel", "num_rel_ret", "map", "Rprec", "recip_rank", "ndcg"};
+    for (const int32_t c : cutoffs)
+        for (const char* m : {"P_", "recall_", "ndcg_cut_"}) names.push_back(m + std::to_string(c));
+    return names;
+}
+
+void print_metric(const std::string& name, const std::string& topic, double value, bool integral) {      // "map<TAB>all<TAB>0.1234"
+    if (integral) std::printf("%s\t%s\t%lld\n", name.c_str(), topic.c_str(), static_cast<long long>(value));
+    else std::printf("%s\t%s\t%.4f\n", name.c_str(), topic.c_str(), value);
+}
+
+int run(int argc, char** argv) {
+    Flags flags;
+    define_flags(&flags);
+    const std::vector<std::string> args = flags.parse(argc, argv);
+    verbosity() = static_cast<int>(FLAGS_v);
+    log_to_stderr() = FLAGS_logtostderr;
+    const std::string usage = "Usage: " + args[0] + " --index <TREC-text collection | Indri repository> --topics <file> [<file> ...] [OPTIONS] "
+                              "<model>_<epoch>.hdf5 <run_out>\n" + flags.usage();
+    if (FLAGS_help) { std::cout << usage; return 0; }
+    if (args.size() < 3 || FLAGS_index.empty() || FLAGS_topics.empty()) {
+        std::cerr << usage;
+        NVSM_LOG(FATAL) << "--index, --topics, the model and the run's name are required.";
+    }
+    NVSM_CHECK(!FLAGS_rerank_exact_matching_documents) << "--rerank_exact_matching_documents is not offered: it needs Indri's TF-IDF query environment.";
+    NVSM_CHECK(!FLAGS_l2norm_phrase) << "--l2norm_phrase is not offered: py/nvsm/base.py has no such argument.";
+    if (FLAGS_num_workers != 0) NVSM_LOG(WARNING) << "--num_workers is ignored: every topic file is one GPU pass.";
+    if (FLAGS_bias_coefficient != 0.0)
+        NVSM_LOG(WARNING) << "--bias_coefficient " << FLAGS_bias_coefficient << ": as in the reference, the bias is never applied "
+                             "(py/nvsm/base.py:228-233 keeps it only where the coefficient is 0).";
+    NVSM_CHECK(FLAGS_num_queries >= 0) << "--num_queries must not be negative.";
+    std::vector<std::string> topic_paths = {FLAGS_topics};
+    for (size_t i = 1; i + 2 < args.size(); ++i) topic_paths.push_back(args[i]);
+    const std::string model_path = args[args.size() - 2], run_out = args[args.size() - 1];
+    for (const std::string& t : topic_paths) NVSM_CHECK(is_file(t)) << "cannot read the topic file " << t;
+    NVSM_CHECK(is_file(model_path)) << "cannot read the model " << model_path;
+    const std::vector<int32_t> cutoffs = parse_cutoffs(FLAGS_cutoffs);
+
+    // ---- --top_k (py/query.py:118-139)
+    int64_t top_k = 1000;
+    bool top_k_all = false;
+    std::unique_ptr<Qrels> candidate_qrels;
+    if (FLAGS_top_k == "all") {
+        top_k_all = true;
+    } else if (!FLAGS_top_k.empty() && FLAGS_top_k.find_first_not_of("0123456789") == std::string::npos) {
+        top_k = std::atoll(FLAGS_top_k.c_str());
+        NVSM_CHECK(top_k >= 1) << "--top_k must be at least 1.";
+    } else if (!FLAGS_top_k.empty()) {
+        const std::vector<std::string> paths = split_blanks(FLAGS_top_k);
+        for (const std::string& p : paths)
+            if (!exists(p)) NVSM_LOG(FATAL) << "--top_k: '" << FLAGS_top_k << "' is neither a number, nor 'all', nor existing qrel files (" << p << ").";
+        candidate_qrels.reset(new Qrels(read_qrels(paths)));
+    }
+    std::unique_ptr<Qrels> qrels;
+    if (!FLAGS_qrels.empty()) qrels.reset(new Qrels(read_qrels(split_blanks(FLAGS_qrels))));
+
+    // ---- the index
+    std::unique_ptr<IndexInterface> index;
+    if (is_directory(FLAGS_index)) {
+        if (!IndriDiskIndex::looks_like_repository(FLAGS_index)) NVSM_LOG(FATAL) << "Unable to open Indri parameters: " << FLAGS_index << " holds no manifest / index.";
+        if (!FLAGS_stopwords.empty()) NVSM_LOG(WARNING) << "--stopwords is not used with an Indri repository (its stop list was applied when it was built).";
+        index.reset(IndriDiskIndex::open(FLAGS_index));
+    } else {
+        NVSM_CHECK(is_file(FLAGS_index)) << "cannot read collection " << FLAGS_index;
+        NVSM_LOG(INFO) << "Indexing " << FLAGS_index << ".";
+        index.reset(TrectextIndex::from_file(FLAGS_index, FLAGS_stopwords));
+    }
+
+    // ---- the model (py/query.py:144-169, py/nvsm/base.py:165-240)
+    NVSM_LOG(INFO) << "Loading model.";
+    const ModelPath where = split_model_path(model_path);
+    Metadata meta;
+    {
+        std::ifstream f(where.meta_path, std::ios::binary);
+        std::stringstream wire;
+        wire << f.rdbuf();
+        NVSM_CHECK(f.good() && meta.ParseFromString(wire.str())) << "cannot parse " << where.meta_path;
+    }
+    static const char* kNames[4] = {"word_representations-representations", "entity_representations-representations",
+                                    "word_entity_mapping-transform", "word_entity_mapping-bias"};
+    const std::vector<Hdf5Array> arrays = read_hdf5(model_path, {kNames[0], kNames[1], kNames[2], kNames[3]});
+    const Hdf5Array &W = arrays[0], &E = arrays[1], &T = arrays[2], &b = arrays[3];
+    const int64_t num_words = static_cast<int64_t>(W.dim0), dw = static_cast<int64_t>(W.dim1);
+    const int64_t num_entities = static_cast<int64_t>(E.dim0), de = static_cast<int64_t>(E.dim1);
+    if (num_words < 1 || num_entities < 1 || dw < 1 || de < 1 || dw > 2147483647 || de > 2147483647) NVSM_LOG(FATAL) << model_path << " holds an empty table";
+    if (static_cast<int64_t>(T.dim0) != dw || static_cast<int64_t>(T.dim1) != de)
+        NVSM_LOG(FATAL) << model_path << ": the transform is " << T.dim0 << " x " << T.dim1 << ", expected " << dw << " x " << de;
+    if (b.dim0 * b.dim1 != static_cast<unsigned long long>(de)) NVSM_LOG(FATAL) << model_path << ": the bias holds " << b.dim0 * b.dim1 << " values, expected " << de;
+    const ModelMappings maps = build_mappings(meta, num_words, num_entities);
+    NVSM_LOG(INFO) << "<NVSM with " << num_words << " words (" << dw << "-dimensional) and " << num_entities << " entities (" << de
+                   << "-dimensional), epoch " << where.epoch << ">";
+    // docno -> model document id, of the documents the model holds (judged docnos the index or the model lacks find nothing here)
+    std::unordered_map<std::string, int64_t> model_doc_of_docno;
+    for (int64_t d = 0; d < num_entities; ++d)
+        if (maps.index_object_of[static_cast<size_t>(d)] >= 0) model_doc_of_docno.emplace(index->docno(maps.index_object_of[static_cast<size_t>(d)]), d);
+
+    if (nvsm_device_count() < 1) NVSM_LOG(FATAL) << "no HIP device visible: cuNVSMQuery has no CPU path.";
+    nvsm_config cfg;
+    nvsm_config_default(&cfg);      // a handle for ranking only: plain SGD (no optimiser state), a token batch capacity
+    cfg.num_words = num_words; cfg.num_entities = num_entities;
+    cfg.word_repr_size = static_cast<int32_t>(dw); cfg.entity_repr_size = static_cast<int32_t>(de);
+    cfg.window_size = 1; cfg.num_random_entities = 1; cfg.max_batch_size = 8;
+    cfg.update_method = NVSM_SGD; cfg.adam_mode = NVSM_ADAM_NONE; cfg.nonlinearity = NVSM_TANH; cfg.batch_normalization = 0;
+    cfg.device = static_cast<int32_t>(FLAGS_device);
+    nvsm_model* model = nullptr;
+    NVSM_CALL(nvsm_create(&cfg, &model));
+    for (int i = 0; i < 4; ++i)
+        NVSM_CALL(nvsm_set_param(model, kNames[i], arrays[static_cast<size_t>(i)].data.data(), static_cast<int64_t>(arrays[static_cast<size_t>(i)].data.size())));
+
+    nvsm_rank_options opt;
+    nvsm_rank_options_default(&opt);
+    opt.bias_coefficient = 0.f;                                           // (see --bias_coefficient)
+    opt.activation = FLAGS_linear ? static_cast<int32_t>(NVSM_ACT_IDENTITY) : static_cast<int32_t>(NVSM_TANH);
+    opt.similarity = NVSM_SIM_COSINE;
+    const std::vector<std::string> names = metric_names(cutoffs);
+    const size_t width = names.size();
+
+    for (const std::string& topic_path : topic_paths) {
+        const std::string run_out_path = run_out + "-" + basename_of(topic_path);
+        if (exists(run_out_path)) {
+            NVSM_LOG(WARNING) << "Run for topics " << topic_path << " already exists (" << run_out_path << "); skipping.";
+            continue;
+        }
+        std::vector<Topic> topics;
+        {
+            std::ifstream f(topic_path);
+            topics = parse_topics(f, topic_path);
+        }
+        if (FLAGS_num_queries > 0 && topics.size() > static_cast<size_t>(FLAGS_num_queries)) topics.resize(static_cast<size_t>(FLAGS_num_queries));
+
+        // ---- the topics that are ranked, in file order
+        std::vector<std::string> ranked;                                   // topic ids
+        std::vector<int64_t> word_ids, word_off = {0}, cand, cand_off = {0}, judged_ids, judged_off = {0};
+        std::vector<float> word_weights;
+        std::vector<int32_t> judged_grades;
+        std::vector<int64_t> terms;
+        int64_t most_candidates = 0;
+        for (const Topic& topic : topics) {
+            if (!query_terms(index.get(), maps, topic.text, FLAGS_strict, &terms)) {
+                NVSM_LOG(WARNING) << "Skipping topic " << topic.id << ": " << (terms.empty() ? "no term of it is in the model's vocabulary." : "a term is out of vocabulary (--strict).");
+                continue;
+            }
+            if (candidate_qrels) {
+                const auto hit = candidate_qrels->find(topic.id);
+                if (hit == candidate_qrels->end() || hit->second.empty()) {
+                    NVSM_LOG(WARNING) << "Skipping topic " << topic.id << " as there are no judged documents.";
+                    continue;
+                }
+                std::set<int64_t> docs;
+                for (const auto& j : hit->second) {
+                    const auto d = model_doc_of_docno.find(j.first);
+                    if (d != model_doc_of_docno.end()) docs.insert(d->second);
+                }
+                cand.insert(cand.end(), docs.begin(), docs.end());
+                cand_off.push_back(static_cast<int64_t>(cand.size()));
+                most_candidates = std::max<int64_t>(most_candidates, static_cast<int64_t>(hit->second.size()));
+            }
+            ranked.push_back(topic.id);
+            word_ids.insert(word_ids.end(), terms.begin(), terms.end());
+            word_off.push_back(static_cast<int64_t>(word_ids.size()));
+            if (FLAGS_self_information) {
+                const std::vector<float> w = self_information(maps, terms);
+                word_weights.insert(word_weights.end(), w.begin(), w.end());
+            }
+            if (qrels) {
+                const auto hit = qrels->find(topic.id);
+                if (hit != qrels->end())
+                    for (const auto& j : hit->second) {
+                        const auto d = model_doc_of_docno.find(j.first);
+                        judged_ids.push_back(d == model_doc_of_docno.end() ? -1 : d->second);
+                        judged_grades.push_back(j.second);
+                    }
+            }
+            judged_off.push_back(static_cast<int64_t>(judged_ids.size()));
+        }
+        const int64_t Q = static_cast<int64_t>(ranked.size());
+        // results_requested: --top_k clipped to the model's documents (py/nvsm/base.py:379-381); with qrel candidates the number of
+        // judged documents of the topic — one call ranks every topic, so it asks for the largest and counts[] cuts each topic's list
+        int64_t k = top_k_all ? num_entities : std::min(top_k, num_entities);
+        if (candidate_qrels) k = std::max<int64_t>(1, std::min(most_candidates, num_entities));
+        NVSM_CHECK(k <= 2147483647) << "--top_k is too large.";
+        opt.top_k = static_cast<int32_t>(k);
+        opt.candidates = candidate_qrels && !cand.empty() ? cand.data() : nullptr;
+        opt.candidate_offsets = candidate_qrels ? cand_off.data() : nullptr;
+        nvsm_queries queries;
+        queries.word_ids = word_ids.data(); queries.word_weights = FLAGS_self_information ? word_weights.data() : nullptr;
+        queries.offsets = word_off.data(); queries.num_queries = Q;
+        std::vector<int64_t> doc_ids(static_cast<size_t>(Q * k) + 1), counts(static_cast<size_t>(Q) + 1);
+        std::vector<float> scores(static_cast<size_t>(Q * k) + 1);
+        std::vector<double> metrics(static_cast<size_t>(Q) * width + 1);
+        if (qrels) {      // ranking and metrics in ONE call: the metrics are computed from each round's ranked ids where they lie
+            nvsm_judgments judgments{};
+            judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
+            judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());
+            NVSM_CALL(nvsm_evaluate(model, &queries, &opt, &judgments, metrics.data(), doc_ids.data(), scores.data(), counts.data()));
+        } else {
+            NVSM_CALL(nvsm_rank(model, &queries, &opt, doc_ids.data(), scores.data(), counts.data()));
+        }
+
+        // ---- the run: "<topic> Q0 <docno> <rank from 1> <score> cuNVSM"; %.9g round-trips a float32
+        {
+            std::ofstream run(run_out_path);
+            NVSM_CHECK(run.good()) << "cannot write " << run_out_path;
+            char score[32];
+            for (int64_t q = 0; q < Q; ++q)
+                for (int64_t r = 0; r < counts[static_cast<size_t>(q)]; ++r) {
+                    const size_t at = static_cast<size_t>(q * k + r);
+                    std::snprintf(score, sizeof(score), "%.9g", static_cast<double>(scores[at]));
+                    run << ranked[static_cast<size_t>(q)] << " Q0 " << index->docno(maps.index_object_of[static_cast<size_t>(doc_ids[at])]) << " " << r + 1
+                        << " " << score << " cuNVSM\n";
+                }
+            run.close();
+            NVSM_CHECK(run.good()) << "cannot write " << run_out_path;
+        }
+        NVSM_LOG(INFO) << "Run outputted to " << run_out_path << ".";
+
+        if (qrels) {      // means over the topics that are in the run and have relevant judged documents, in trec_eval's layout
+            std::vector<double> sums(width, 0.0);
+            int64_t num_q = 0;
+            for (int64_t q = 0; q < Q; ++q) {
+                const double* row = metrics.data() + static_cast<size_t>(q) * width;
+                if (counts[static_cast<size_t>(q)] < 1 || !(row[NVSM_EVAL_NUM_REL] > 0.0)) continue;
+                ++num_q;
+                for (size_t i = 0; i < width; ++i) {
+                    sums[i] += row[i];
+                    if (FLAGS_per_query) print_metric(names[i], ranked[static_cast<size_t>(q)], row[i], i < 3);
+                }
+            }
+            std::printf("runid\tall\tcuNVSM\n");
+            std::printf("topics\tall\t%s\n", basename_of(topic_path).c_str());
+            std::printf("num_q\tall\t%lld\n", static_cast<long long>(num_q));
+            for (size_t i = 0; i < width; ++i) print_metric(names[i], "all", i < 3 ? sums[i] : (num_q > 0 ? sums[i] / static_cast<double>(num_q) : 0.0), i < 3);
+            std::fflush(stdout);
+        }
+    }
+    nvsm_destroy(model);
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    try {
+        return run(argc, argv);
+    } catch (const FatalError&) {
+        return 1;                       // the message has been logged
+    } catch (const std::exception& e) {
+        std::cerr << "Exception: " << e.what() << std::endl;
+        return 1;
+    }
+}

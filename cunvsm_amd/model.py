@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -183,6 +183,7 @@ def self_information_weights(term_frequencies, total_terms):
 
 
 ACTIVATIONS = dict(NONLINEARITIES, model=_lib.ACT_MODEL, identity=_lib.ACT_IDENTITY, linear=_lib.ACT_IDENTITY)
+_EMPTY_F64 = np.zeros(1, dtype=np.float64)      # what a call without queries hands over as its (unwritten) metric rows
 SIMILARITIES = {"cosine": _lib.SIM_COSINE, "dot": _lib.SIM_DOT}
 
 
@@ -236,6 +237,83 @@ def rank_options(num_entities, top_k=None, bias_coefficient=1.0, activation="mod
             raise ValueError("top_k = %d outside [1, num_entities = %d]" % (int(top_k), int(num_entities)))
         opt.top_k = int(top_k)
     return opt
+
+
+def candidate_arrays(num_entities, num_queries, candidates):
+    """(flat ids, offsets) of per-query candidate lists as nvsm_rank_options reads them; raises ValueError for what the ABI
+    would refuse."""
+    rows = [np.asarray(c, dtype=np.int64).ravel() for c in candidates]
+    if len(rows) != num_queries:
+        raise ValueError("candidates holds %d lists, expected one per query = %d" % (len(rows), num_queries))
+    off = np.zeros(num_queries + 1, dtype=np.int64)
+    if rows:
+        np.cumsum([r.size for r in rows], out=off[1:])
+    flat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, np.int64), dtype=np.int64)
+    if flat.size and (flat.min() < 0 or flat.max() >= num_entities):
+        raise ValueError("a candidate document id is outside [0, num_entities = %d)" % num_entities)
+    return flat, off
+
+
+class Judgments:
+    """nvsm_judgments: per query a list of (model document id, grade) pairs, flattened to ids + grades + offsets. Id -1 is a
+    judged document the model does not hold (it counts towards num_rel and can never be retrieved); grade >= 1 is relevant.
+    What needs no device is checked here: pair shape, and an id >= 0 given twice for one query. The id RANGE is checked by
+    Model.evaluate, which knows num_entities."""
+
+    def __init__(self, lists):
+        ids, grades = [], []
+        for i, pairs in enumerate(lists):
+            a = np.asarray(list(pairs), dtype=np.int64)
+            if a.size == 0:
+                a = a.reshape(0, 2)
+            if a.ndim != 2 or a.shape[1] != 2:
+                raise ValueError("judgments[%d] must be a list of (document id, grade) pairs" % i)
+            if a.size and (np.abs(a[:, 1]) >= 2 ** 31).any():
+                raise ValueError("judgments[%d] holds a grade outside int32" % i)
+            held = np.sort(a[a[:, 0] >= 0, 0])
+            if held.size > 1 and (held[1:] == held[:-1]).any():
+                raise ValueError("judgments[%d] judges a document id twice" % i)
+            ids.append(a[:, 0])
+            grades.append(a[:, 1].astype(np.int32))
+        self.num_queries = len(ids)
+        self.offsets = np.zeros(self.num_queries + 1, dtype=np.int64)
+        if ids:
+            np.cumsum([r.size for r in ids], out=self.offsets[1:])
+        self.doc_ids = np.ascontiguousarray(np.concatenate(ids) if ids else np.zeros(0, np.int64), dtype=np.int64)
+        self.grades = np.ascontiguousarray(np.concatenate(grades) if grades else np.zeros(0, np.int32), dtype=np.int32)
+
+    def as_struct(self, cutoffs):
+        """cutoffs: a contiguous int32 array the caller keeps alive."""
+        j = NvsmJudgments()
+        j.doc_ids = self.doc_ids.ctypes.data if self.doc_ids.size else None
+        j.grades = self.grades.ctypes.data if self.grades.size else None
+        j.offsets = self.offsets.ctypes.data
+        j.cutoffs = cutoffs.ctypes.data if cutoffs.size else None
+        j.num_cutoffs = int(cutoffs.size)
+        return j
+
+
+def eval_cutoffs(cutoffs):
+    """The cutoffs of Model.evaluate as an int32 array; raises ValueError for what nvsm_evaluate would refuse."""
+    c = np.asarray(list(cutoffs), dtype=np.int64).ravel()
+    if c.size > _lib.EVAL_MAX_CUTOFFS:
+        raise ValueError("%d cutoffs, at most %d" % (c.size, _lib.EVAL_MAX_CUTOFFS))
+    if c.size and (c.min() < 1 or c.max() >= 2 ** 31):
+        raise ValueError("a cutoff is outside [1, 2^31)")
+    if c.size > 1 and (c[1:] <= c[:-1]).any():
+        raise ValueError("cutoffs must ascend")
+    return np.ascontiguousarray(c, dtype=np.int32)
+
+
+EVAL_FIXED_NAMES = ("num_ret", "num_rel", "num_rel_ret", "map", "Rprec", "recip_rank", "ndcg")
+
+
+def eval_metric_names(cutoffs):
+    """The columns of a metric row of nvsm_evaluate, by trec_eval's names."""
+    names = list(EVAL_FIXED_NAMES)
+    for c in cutoffs:
+        names += ["P_%d" % c, "recall_%d" % c, "ndcg_cut_%d" % c]
+    return names
 
 
 SPACES = {"words": _lib.SPACE_WORDS, "projected_words": _lib.SPACE_PROJECTED_WORDS, "entities": _lib.SPACE_ENTITIES}
@@ -429,16 +507,7 @@ class Model:
         opt = rank_options(self.cfg.num_entities, top_k, **opts)
         keep = None
         if candidates is not None:
-            rows = [np.asarray(c, dtype=np.int64).ravel() for c in candidates]
-            if len(rows) != q.num_queries:
-                raise ValueError("candidates holds %d lists, expected one per query = %d" % (len(rows), q.num_queries))
-            off = np.zeros(q.num_queries + 1, dtype=np.int64)
-            if rows:
-                np.cumsum([r.size for r in rows], out=off[1:])
-            flat = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, np.int64), dtype=np.int64)
-            if flat.size and (flat.min() < 0 or flat.max() >= self.cfg.num_entities):
-                raise ValueError("a candidate document id is outside [0, num_entities = %d)" % self.cfg.num_entities)
-            keep = (flat, off)
+            flat, off = keep = candidate_arrays(self.cfg.num_entities, q.num_queries, candidates)
             opt.candidates, opt.candidate_offsets = flat.ctypes.data if flat.size else None, off.ctypes.data
         k = opt.top_k
         ids = np.empty((q.num_queries, k), dtype=np.int64)
@@ -448,6 +517,41 @@ class Model:
         check(lib().nvsm_rank(self._h, C.byref(st), C.byref(opt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         del keep
         return ids, scores, counts
+
+    def evaluate(self, queries, judgments, top_k=1000, cutoffs=(5, 10, 20, 100, 1000), weights=None, candidates=None,
+                 return_ranking=False, **opts):
+        """Ranks as rank() does and computes every query's retrieval metrics on the device (nvsm_evaluate; the formulas are in
+        include/cunvsm_amd.h). judgments: a Judgments, or per query a list of (document id, grade) pairs. Returns a dict of
+        float64 arrays [Q] keyed num_ret, num_rel, num_rel_ret, map, Rprec, recip_rank, ndcg and, per cutoff c, P_<c>,
+        recall_<c>, ndcg_cut_<c>; with return_ranking also (ids, scores, counts) as rank() returns them. The ranking's ties
+        are broken by ascending document id, not by docno as trec_eval would."""
+        q = queries if isinstance(queries, Queries) else Queries(queries, weights)
+        j = judgments if isinstance(judgments, Judgments) else Judgments(judgments)
+        if j.num_queries != q.num_queries:
+            raise ValueError("judgments holds %d lists, expected one per query = %d" % (j.num_queries, q.num_queries))
+        if j.doc_ids.size and (j.doc_ids.min() < -1 or j.doc_ids.max() >= self.cfg.num_entities):
+            raise ValueError("a judged document id is outside [-1, num_entities = %d)" % self.cfg.num_entities)
+        cut = eval_cutoffs(cutoffs)
+        opt = rank_options(self.cfg.num_entities, top_k, **opts)
+        keep = None
+        if candidates is not None:
+            flat, off = keep = candidate_arrays(self.cfg.num_entities, q.num_queries, candidates)
+            opt.candidates, opt.candidate_offsets = flat.ctypes.data if flat.size else None, off.ctypes.data
+        k = opt.top_k
+        names = eval_metric_names(cut.tolist())
+        metrics = np.empty((q.num_queries, len(names)), dtype=np.float64)
+        ids = scores = counts = None
+        if return_ranking:
+            ids = np.empty((q.num_queries, k), dtype=np.int64)
+            scores = np.empty((q.num_queries, k), dtype=np.float32)
+            counts = np.empty(q.num_queries, dtype=np.int64)
+        st, js = q.as_struct(), j.as_struct(cut)
+        check(lib().nvsm_evaluate(self._h, C.byref(st), C.byref(opt), C.byref(js), metrics.ctypes.data if metrics.size else _EMPTY_F64.ctypes.data,
+                                  None if ids is None else ids.ctypes.data, None if scores is None else scores.ctypes.data,
+                                  None if counts is None else counts.ctypes.data))
+        del keep
+        result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}
+        return (result, ids, scores, counts) if return_ranking else result
 
     # -- nearest neighbours in word, projected-word and document space (py/nvsm/base.py:106-162, 325-353, 362-430) ----
     def neighbors(self, space, ids=None, vectors=None, source=None, top_k=30, exclude_self=False, similarity="cosine",

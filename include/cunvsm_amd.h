@@ -321,6 +321,50 @@ int nvsm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_option
               int64_t* doc_ids, float* scores, int64_t* counts);
 
 /*
+ * Ranking and retrieval metrics in one call: nvsm_evaluate ranks exactly as nvsm_rank does (same arguments, same checks with
+ * the same sentences, same ids / scores / counts bit for bit) and computes each query's metrics ON THE DEVICE from the ranked
+ * ids of every round, so that validation over thousands of topics at top_k = 1000 brings back a few doubles per query
+ * instead of num_queries x top_k ids and scores. doc_ids / scores / counts are still returned where the caller passes
+ * buffers (a run file needs them); each of the three may be NULL.
+ * The metrics are trec_eval's num_ret, num_rel, num_rel_ret, map, Rprec, recip_rank, ndcg, P_c, recall_c and ndcg_cut_c AS FAR AS
+ * WRITTEN HERE — these formulas are the contract. For one query, r_1 .. r_n is the ranking nvsm_rank returns, n = counts[q]; its
+ * order is the library's: score descending, ties by ASCENDING DOCUMENT ID (trec_eval would break ties by docno). g(d) is the
+ * judged grade of d, 0 if d is unjudged; rel(d) means g(d) >= 1; R is the number of judged entries with grade >= 1, entries with
+ * id -1 (judged documents the model does not hold) included: they can never be retrieved, as in trec_eval;
+ * c_i = sum over j <= i of rel(r_j). Then
+ *   num_ret = n, num_rel = R, num_rel_ret = c_n
+ *   ap         = (1 / R) · sum over i with rel(r_i) of c_i / i
+ *   rprec      = c_min(R, n) / R
+ *   recip_rank = 1 / min{i : rel(r_i)}, 0 if there is none
+ *   P@c        = c_min(c, n) / c          (always divided by c)
+ *   recall@c   = c_min(c, n) / R
+ *   dcg@c      = sum over i <= min(c, n) with g(r_i) > 0 of g(r_i) / log2(i + 1)
+ *   idcg@c     = the same sum over the query's judged grades > 0 sorted descending, the first c of them (-1 entries included)
+ *   ndcg@c     = dcg@c / idcg@c;  ndcg = ndcg@c with c = infinity
+ * Every ratio with a zero denominator is 0. A query without words gets all zeros. All arithmetic is fp64; sums are taken in a
+ * fixed order (a repeated call returns the same bits).
+ * Judgments: per query a list of (model document id, grade), ids in [-1, num_entities), an id >= 0 at most once per query, any
+ * order. Decreasing offsets or offsets[0] != 0, an id out of range, a repeated id, cutoffs that are not ascending, are < 1 or
+ * number more than NVSM_EVAL_MAX_CUTOFFS, and a NULL metrics are NVSM_ERR_INVALID_ARGUMENT before anything runs.
+ * Like nvsm_rank the call is synchronous, runs behind everything queued, reads lazily decayed tables through their view and
+ * leaves parameters, optimiser state and the lazy bookkeeping bit-identical.
+ */
+#define NVSM_EVAL_MAX_CUTOFFS 8
+typedef struct {
+    const int64_t* doc_ids;    /* concatenated per query: judged model document ids; -1 = a judged document the model does not hold */
+    const int32_t* grades;     /* same length; >= 1 relevant, <= 0 judged non-relevant */
+    const int64_t* offsets;    /* [num_queries + 1], offsets[0] = 0, non-decreasing */
+    const int32_t* cutoffs;    /* ascending, each >= 1 */
+    int32_t num_cutoffs;       /* 0 .. NVSM_EVAL_MAX_CUTOFFS */
+    int32_t reserved[3];
+} nvsm_judgments;
+enum { NVSM_EVAL_NUM_RET, NVSM_EVAL_NUM_REL, NVSM_EVAL_NUM_REL_RET, NVSM_EVAL_AP, NVSM_EVAL_RPREC, NVSM_EVAL_RECIP_RANK,
+       NVSM_EVAL_NDCG, NVSM_EVAL_FIXED };      /* then per cutoff j: P, recall, ndcg at NVSM_EVAL_FIXED + 3 j + {0, 1, 2} */
+/* metrics [num_queries][NVSM_EVAL_FIXED + 3 * num_cutoffs] doubles, host; doc_ids / scores / counts as nvsm_rank, each may be NULL */
+int nvsm_evaluate(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* opt, const nvsm_judgments* judgments,
+                  double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
+
+/*
  * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query
  * library does with the same parameters (py/nvsm/base.py). Semantics, pinned by the reference:
  *   space        NVSM_SPACE_WORDS: the rows of W, dimension word_repr_size — NVSM.related_terms (base.py:325-342) and

@@ -165,6 +165,25 @@ class Model {
         r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
         return r;
     }
+    // nvsm_evaluate: the same ranking plus, per query, NVSM_EVAL_FIXED + 3 * judgments.num_cutoffs metrics computed on the device
+    // (layout and formulas: cunvsm_amd.h). with_ranking false: only the metrics come back from the device.
+    struct Evaluation { std::vector<double> metrics; int32_t width; Ranking ranking; };
+    Evaluation evaluate(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                        const nvsm_judgments& judgments, const std::vector<float>* word_weights = nullptr, bool with_ranking = true) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        Evaluation e;
+        e.width = NVSM_EVAL_FIXED + 3 * (judgments.num_cutoffs > 0 ? judgments.num_cutoffs : 0);
+        e.ranking.top_k = opt.top_k;
+        const size_t Q = static_cast<size_t>(q.num_queries);
+        const size_t n = with_ranking ? Q * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0) : 0;
+        e.metrics.resize(Q * static_cast<size_t>(e.width) + 1);
+        if (with_ranking) { e.ranking.doc_ids.resize(n ? n : 1); e.ranking.scores.resize(n ? n : 1); e.ranking.counts.resize(Q + 1); }
+        check(nvsm_evaluate(h_, &q, &opt, &judgments, e.metrics.data(), with_ranking ? e.ranking.doc_ids.data() : nullptr,
+                            with_ranking ? e.ranking.scores.data() : nullptr, with_ranking ? e.ranking.counts.data() : nullptr));
+        e.metrics.resize(Q * static_cast<size_t>(e.width));
+        if (with_ranking) { e.ranking.doc_ids.resize(n); e.ranking.scores.resize(n); e.ranking.counts.resize(Q); }
+        return e;
+    }
 
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
     // 362-430): queries are row ids of `source_space`, or vectors [n][dim] of the searched space (neighbors_of_vectors)
