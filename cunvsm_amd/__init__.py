@@ -9,11 +9,11 @@ from ._lib import (  # noqa: F401
     ADAGRAD, ADAM, ADAM_DENSE_UPDATE, ADAM_DENSE_UPDATE_DENSE_VARIANCE, ADAM_NONE, ADAM_SPARSE, HARD_TANH,
     SAMPLER_DEVICE, SAMPLER_HOST_MINSTD, SGD, TANH, SIM_COSINE, SIM_DOT, ACT_MODEL, ACT_IDENTITY, NvsmBatch, NvsmConfig,
     SPACE_WORDS, SPACE_PROJECTED_WORDS, SPACE_ENTITIES, NvsmNeighborQueries, NvsmNeighborOptions,
-    NvsmQueries, NvsmRankOptions, NvsmJudgments, EVAL_MAX_CUTOFFS, NvsmPairBatch, NvsmMixture, NvsmError, abi_symbols, build_library,
+    NvsmQueries, NvsmRankOptions, NvsmJudgments, EVAL_MAX_CUTOFFS, NvsmPairBatch, NvsmMixture, NvsmCorpus, NvsmWindowBatch, NvsmError, abi_symbols, build_library,
     bind_host_thread, device_count, lib, library_path,
 )
 from . import dp  # noqa: F401
-from .model import Batch, Judgments, Model, PairBatch, Queries, UPDATE_METHODS, default_config, self_information_weights  # noqa: F401
+from .model import Batch, Corpus, WindowBatch, expand_windows, Judgments, Model, PairBatch, Queries, UPDATE_METHODS, default_config, self_information_weights  # noqa: F401
 
-__all__ = ["Model", "Batch", "PairBatch", "NvsmPairBatch", "NvsmMixture", "Queries", "Judgments", "self_information_weights", "NvsmQueries", "NvsmRankOptions", "NvsmJudgments", "NvsmNeighborQueries", "NvsmNeighborOptions", "default_config", "UPDATE_METHODS", "NvsmConfig", "NvsmBatch", "NvsmError", "lib",
+__all__ = ["Model", "Batch", "Corpus", "WindowBatch", "expand_windows", "NvsmCorpus", "NvsmWindowBatch", "PairBatch", "NvsmPairBatch", "NvsmMixture", "Queries", "Judgments", "self_information_weights", "NvsmQueries", "NvsmRankOptions", "NvsmJudgments", "NvsmNeighborQueries", "NvsmNeighborOptions", "default_config", "UPDATE_METHODS", "NvsmConfig", "NvsmBatch", "NvsmError", "lib",
            "library_path", "build_library", "device_count", "bind_host_thread", "abi_symbols"]

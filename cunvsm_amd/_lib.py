@@ -57,6 +57,15 @@ class NvsmPairBatch(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class NvsmCorpus(C.Structure):
+    _fields_ = [("tokens", C.c_void_p), ("doc_offsets", C.c_void_p), ("doc_weights", C.c_void_p), ("term_weights", C.c_void_p),
+                ("num_tokens", C.c_int64), ("num_documents", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class NvsmWindowBatch(C.Structure):
+    _fields_ = [("refs", C.c_void_p), ("num_instances", C.c_int64), ("on_device", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class NvsmMixture(C.Structure):
     _fields_ = [("text_weight", C.c_float), ("pair_weight", C.c_float), ("reserved", C.c_int32 * 2)]
 
@@ -234,6 +243,10 @@ def lib():
         "nvsm_step": (C.c_int, [vp, P(NvsmBatch), vp, C.c_float, P(C.c_float)]),
         "nvsm_compute_cost_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture)]),
         "nvsm_step_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture), C.c_float, P(C.c_float)]),
+        "nvsm_corpus_upload": (C.c_int, [vp, P(NvsmCorpus)]),
+        "nvsm_compute_cost_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp]),
+        "nvsm_step_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp, C.c_float, P(C.c_float)]),
+        "nvsm_step_windows_deferred": (C.c_int, [vp, P(NvsmWindowBatch), vp, C.c_float, P(i64)]),
         "nvsm_step_deferred": (C.c_int, [vp, P(NvsmBatch), vp, C.c_float, P(i64)]),
         "nvsm_deferred_cost": (C.c_int, [vp, i64, P(C.c_float)]), "nvsm_wait_inputs": (C.c_int, [vp]),
         "nvsm_tensor_size": (C.c_int, [vp, cp, P(i64)]), "nvsm_get_tensor": (C.c_int, [vp, cp, vp, i64]),

@@ -276,6 +276,23 @@ int nvsm_deferred_cost(nvsm_model* m, int64_t ticket, float* cost) {
 }
 int nvsm_wait_inputs(nvsm_model* m) { NVSM_REQUIRE(m); return guarded_on(m, [&] { m->impl.wait_inputs(); }); }
 
+int nvsm_corpus_upload(nvsm_model* m, const nvsm_corpus* corpus) {
+    NVSM_REQUIRE(m);
+    return guarded_on(m, [&] { m->impl.corpus_upload(corpus); });
+}
+int nvsm_compute_cost_windows(nvsm_model* m, const nvsm_window_batch* windows, const int64_t* entity_ids) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(windows);
+    return guarded_on(m, [&] { m->impl.compute_cost_windows(*windows, entity_ids); });
+}
+int nvsm_step_windows(nvsm_model* m, const nvsm_window_batch* windows, const int64_t* entity_ids, float learning_rate, float* cost) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(windows);
+    return guarded_on(m, [&] { m->impl.step_windows(*windows, entity_ids, learning_rate, cost); });
+}
+int nvsm_step_windows_deferred(nvsm_model* m, const nvsm_window_batch* windows, const int64_t* entity_ids, float learning_rate, int64_t* ticket) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(windows); NVSM_REQUIRE(ticket);
+    return guarded_on(m, [&] { *ticket = m->impl.step_windows_deferred(*windows, entity_ids, learning_rate); });
+}
+
 int nvsm_tensor_size(nvsm_model* m, const char* name, int64_t* count) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(name); NVSM_REQUIRE(count);
     return guarded_on(m, [&] { *count = m->impl.tensor_size(name); });

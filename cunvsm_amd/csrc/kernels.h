@@ -178,7 +178,7 @@ void launch_bn_dx(float* dy, const float* pre, const float* mean, const float* i
 void launch_colsum_finalize(const double* sums, int dim, float* out, hipStream_t s);   // no-BN grad_bias = Σdy
 
 // codes a kernel stores into the engine's error word (page-locked host memory, read at the next synchronisation point)
-enum { NVSM_BAD_WORD_ID = 1, NVSM_BAD_ENTITY_ID = 2, NVSM_SORT_TIMEOUT = 3, NVSM_NONFINITE_BASE = 16 };
+enum { NVSM_BAD_WORD_ID = 1, NVSM_BAD_ENTITY_ID = 2, NVSM_SORT_TIMEOUT = 3, NVSM_BAD_WINDOW_REF = 4, NVSM_NONFINITE_BASE = 16 };
 // ids outside [0, limit) become row 0 and raise `code` in *err_flag (err_flag may be null: tests of single kernels)
 void launch_narrow_i64(const int64_t* src, int* dst, int64_t n, int64_t limit, int* err_flag, int code, hipStream_t s);
 // stamp[list[i]] = value for i < *count (launch_stamp_rows' job, riding on the prologue: list == null: none)
@@ -198,6 +198,19 @@ void launch_host_pull(const HostPull& p, hipStream_t s);
 // gradient, and back (gather_gemm.hip)
 void launch_dp_pack_tail(const float* gb, const double* loss, float* tail, int de, hipStream_t s);
 void launch_dp_unpack_tail(const float* tail, float* gb, double* loss, int de, hipStream_t s);
+// Window references -> the four arrays of a device batch (corpus.hip; nvsm_step_windows). refs: [B] (document, first token inside
+// the document) as interleaved uint32; tokens / doc_offsets / doc_weights / term_weights: the corpus in HBM (the weight arrays may
+// be null: the matching output is then not written). A reference whose document is >= num_documents or whose window reaches beyond
+// its document becomes word 0 / label 0 and stores NVSM_BAD_WINDOW_REF into *err_flag; nothing is read out of bounds (tokens holds at
+// least one element, doc_offsets at least two, doc_weights at least one). words / wwts must be 16-byte aligned.
+struct WindowExpandArgs {
+    const uint32_t* refs; const int* tokens; const int64_t* doc_offsets; const float* doc_weights; const float* term_weights;
+    int64_t num_documents, B; int w;
+    int64_t* words; int64_t* labels; float* wwts; float* instw; int* err_flag;
+};
+void launch_window_expand(const WindowExpandArgs& a, hipStream_t s);
+// *bad = 1 if a token is outside [0, num_words) (nvsm_corpus_upload); *bad must be 0 before
+void launch_corpus_check_tokens(const int* tokens, int64_t n, int64_t num_words, int* bad, hipStream_t s);
 void launch_delay(int microseconds, hipStream_t s);      // one wave spinning on the 100 MHz wall clock (profiling aid)
 void launch_iota(int* dst, int64_t n, hipStream_t s);
 

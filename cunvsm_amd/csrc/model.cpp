@@ -591,6 +591,7 @@ Model::~Model() {
     for (hipEvent_t e : {ev_loss_, ev_dx_, ev_bwdx_, ev_E_done_, ev_T_done_, ev_copied_, ev_step_begin_[0], ev_step_begin_[1],
                          ev_host_ids_[0], ev_host_ids_[1], ev_gathered_, ev_words_late_, ev_cost_ready_, ev_cost_copied_, ev_untouched_}) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {ev_pair_, ev_pair_copied_}) if (e) (void)hipEventDestroy(e);
+    delete corpus_;
     if (cost_host_) (void)hipHostFree(cost_host_);
     for (int p = 0; p < 2; ++p) if (host_ids_pin_[p]) (void)hipHostFree(host_ids_pin_[p]);
     if (err_host_) (void)hipHostFree(err_host_);
@@ -650,6 +651,8 @@ void Model::raise_device_error() {
     (void)hipDeviceSynchronize();      // (the fills are queued on the null stream, which the handle's streams do not follow)
     if (code == NVSM_BAD_WORD_ID) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a word id of the batch is outside [0, num_words)");
     if (code == NVSM_BAD_ENTITY_ID) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a document id of the batch is outside [0, num_entities)");
+    if (code == NVSM_BAD_WINDOW_REF)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "a window reference of the batch names a document >= num_documents or reaches beyond its document's end");
     if (code == NVSM_SORT_TIMEOUT) throw Error(NVSM_ERR_DEVICE, "the row sort's grid-wide wait timed out (workgroups not co-resident?)");
     static const char* const names[] = {"phrase", "pre (projection)", "proj", "probs", "grad_proj", "grad_phrase", "grad_transform",
                                         "word_representations", "entity_representations", "transform"};
@@ -947,7 +950,7 @@ void Model::draw_reference_negatives(const int64_t* labels, int64_t B, int64_t* 
 void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
     const int64_t B = batch.num_instances;
     if (B <= 0 || B > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_instances must be in (0, max_batch_size]");
-    if (!batch.features || !batch.labels) throw Error(NVSM_ERR_INVALID_ARGUMENT, "features and labels are required");
+    if (!win_req_ && (!batch.features || !batch.labels)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "features and labels are required");
     NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
     const int dw = cfg_.word_repr_size, de = cfg_.entity_repr_size, w = cfg_.window_size, k = cfg_.num_random_entities;
     const int64_t N = B * R_;
@@ -989,7 +992,7 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
     const int64_t* words_dev;
     {
         PROF("h2d_batch");
-        if (batch.on_device) {
+        if (batch.on_device && !win_req_) {
             words_dev = batch.features;
             labels_dev_ = batch.labels;
             wwts_ = batch.feature_weights;
@@ -1000,6 +1003,15 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
             // ahead, has usually queued them by then) instead of sitting in front of step k on the main stream.
             // ev_step_begin_[p] was recorded on the main stream when the previous step's compute_cost started, i.e. behind
             // everything the step before that one — the last reader of this staging set — had queued there.
+            // (host sampler, device references: the host needs the labels. Read back NOW, in front of everything this step queues on
+            //  the copy stream — the wait for the staging set's last reader and the expansion — so that the host waits for these
+            //  2·B words only, exactly as device labels are read back in F2)
+            const bool refs_back = win_req_ && win_req_->on_device && !entity_ids && cfg_.sampler == NVSM_SAMPLER_HOST_MINSTD;
+            if (refs_back) {
+                host_refs_.resize(2 * B);
+                NVSM_HIP_CHECK(hipMemcpyAsync(host_refs_.data(), win_req_->refs, 2 * B * sizeof(uint32_t), hipMemcpyDeviceToHost, copy_stream_));
+                NVSM_HIP_CHECK(hipStreamSynchronize(copy_stream_));
+            }
             const int p = in_parity_ ^= 1;
             // When the copy stream is also the stream of the documents CSR build (the default layout), that order is there
             // already: this copy is queued behind the previous step's documents sort, which waited for that step's prologue,
@@ -1031,14 +1043,43 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
                     NVSM_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, copy_stream_));
                 }
             };
-            bring(in_words_[p].p, batch.features, B * w * sizeof(int64_t));
-            bring(in_labels_[p].p, batch.labels, B * sizeof(int64_t));
             words_dev = in_words_[p].p;
             labels_dev_ = in_labels_[p].p;
             wwts_ = nullptr; instw_ = nullptr;
-            if (batch.feature_weights) { bring(in_wwts_[p].p, batch.feature_weights, B * w * sizeof(float)); wwts_ = in_wwts_[p].p; }
-            if (batch.weights) { bring(in_instw_[p].p, batch.weights, B * sizeof(float)); instw_ = in_instw_[p].p; }
-            launch_host_pull(pull, copy_stream_);
+            if (win_req_) {
+                // Window references (nvsm_step_windows): the batch is not brought over, it is WRITTEN here — by a kernel that reads
+                // the references and the corpus in HBM — into the same staging set, on the same stream, behind the same wait: what
+                // is said above about the set's last reader holds word for word, and so does everything behind ev_copied_. Host
+                // references (8 B per window) come over first, by the pull or the copy engine like any array of a host batch
+                // (a slice of a page-locked plan at an odd instance offset is only 8-byte aligned: the copy engine's); device
+                // references are read in place.
+                const Corpus& c = *corpus_;
+                const uint32_t* refs_dev = win_req_->refs;
+                if (!win_req_->on_device) {
+                    bring(in_refs_[p].p, win_req_->refs, B * 2 * sizeof(uint32_t));
+                    launch_host_pull(pull, copy_stream_);
+                    refs_dev = in_refs_[p].p;
+                }
+                if (c.with_term_weights) wwts_ = in_wwts_[p].p;
+                if (c.with_doc_weights) instw_ = in_instw_[p].p;
+                WindowExpandArgs a{};
+                a.refs = refs_dev; a.tokens = c.tokens.p; a.doc_offsets = c.offsets.p;
+                a.doc_weights = c.with_doc_weights ? c.doc_weights.p : nullptr;
+                a.term_weights = c.with_term_weights ? c.term_weights.p : nullptr;
+                a.num_documents = c.num_documents; a.B = B; a.w = w;
+                a.words = in_words_[p].p; a.labels = in_labels_[p].p; a.wwts = in_wwts_[p].p; a.instw = in_instw_[p].p;
+                a.err_flag = err_host_;
+                // (timed, when the profiler is on, by an event pair that rides on the launch: the kernel's own time)
+                hipEvent_t t0 = nullptr, t1 = nullptr;
+                if (prof.bind("window_expand", &t0, &t1)) set_launch_events(t0, t1);
+                launch_window_expand(a, copy_stream_);
+            } else {
+                bring(in_words_[p].p, batch.features, B * w * sizeof(int64_t));
+                bring(in_labels_[p].p, batch.labels, B * sizeof(int64_t));
+                if (batch.feature_weights) { bring(in_wwts_[p].p, batch.feature_weights, B * w * sizeof(float)); wwts_ = in_wwts_[p].p; }
+                if (batch.weights) { bring(in_instw_[p].p, batch.weights, B * sizeof(float)); instw_ = in_instw_[p].p; }
+                launch_host_pull(pull, copy_stream_);
+            }
             NVSM_HIP_CHECK(hipEventRecord(ev_copied_, copy_stream_));
             NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_copied_, 0));
             copied_recorded_ = true;
@@ -1055,7 +1096,17 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
             launch_narrow_i64(in_ids64_.p, ids_p_, N, cfg_.num_entities, err_host_, NVSM_BAD_ENTITY_ID, stream_);
         } else if (cfg_.sampler == NVSM_SAMPLER_HOST_MINSTD) {
             host_labels_.resize(B);
-            if (batch.on_device) {
+            if (win_req_) {
+                // the labels are the references' documents (0 for a bad reference, as on the device); device references were read
+                // back in F1, in front of the expansion
+                const uint32_t* refs = win_req_->on_device ? host_refs_.data() : win_req_->refs;
+                const std::vector<int64_t>& off = corpus_->host_offsets;
+                for (int64_t i = 0; i < B; ++i) {
+                    const int64_t d = refs[2 * i], pos = refs[2 * i + 1];
+                    const bool ok = d < corpus_->num_documents && pos + w <= off[d + 1] - off[d];
+                    host_labels_[i] = ok ? d : 0;
+                }
+            } else if (batch.on_device) {
                 // device-resident labels: read back on the copy stream — the host waits for these B words only, not for
                 // whatever the main stream still has queued
                 NVSM_HIP_CHECK(hipMemcpyAsync(host_labels_.data(), batch.labels, B * sizeof(int64_t), hipMemcpyDeviceToHost, copy_stream_));
@@ -2007,6 +2058,8 @@ std::string Model::describe(int64_t batch) const {
                  (multi_ok ? "" : "; the pair objective alone only (the mixed one is refused for this update method)") +
                  (pairs_ready_ ? "" : "; workspaces not allocated yet"));
     }
+    if (corpus_) out += " | corpus=" + std::to_string(corpus_->bytes) + "B in HBM (" + std::to_string(corpus_->num_tokens) + " tokens, " +
+                        std::to_string(corpus_->num_documents) + " documents)";
     char buf[2048];
     const char* sw = tuning_describe(tune_, buf, sizeof(buf));
     out += std::string(" | switches: ") + (sw[0] ? sw : "defaults");
@@ -2306,6 +2359,108 @@ void Model::wait_inputs() {
     // but device-resident batches are the caller's to keep alive until the step has run)
     if (last_batch_on_host_) { if (copied_recorded_) NVSM_HIP_CHECK(hipEventSynchronize(ev_copied_)); }
     else if (inputs_recorded_) NVSM_HIP_CHECK(hipEventSynchronize(ev_inputs_));
+}
+
+// ---------------------------------------------------------------------------------------------
+// window references — training from an HBM-resident corpus (include/cunvsm_amd.h). The arithmetic is corpus.hip's and compute_cost's
+// F1; what is here is the upload and the argument checks.
+// ---------------------------------------------------------------------------------------------
+void Model::corpus_upload(const nvsm_corpus* corpus) {
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    if (corpus) {
+        const nvsm_corpus& c = *corpus;
+        if (c.num_tokens < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_tokens must not be negative");
+        if (c.num_documents < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_documents must not be negative");
+        if (c.num_documents > cfg_.num_entities) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_documents must not exceed num_entities (document i is document id i of the model)");
+        if (!c.doc_offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: doc_offsets");
+        if (!c.tokens && c.num_tokens > 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: tokens");
+        if (c.doc_offsets[0] != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "doc_offsets must start at 0");
+        for (int64_t d = 0; d < c.num_documents; ++d)
+            if (c.doc_offsets[d + 1] < c.doc_offsets[d]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "doc_offsets must not decrease");
+        if (c.doc_offsets[c.num_documents] != c.num_tokens) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the last of doc_offsets must be num_tokens");
+    }
+    if (!corpus) {
+        synchronize();      // whatever is queued may still read the corpus
+        Corpus* old = corpus_;
+        corpus_ = nullptr;
+        delete old;
+        in_refs_[0].release(); in_refs_[1].release();
+        return;
+    }
+    // The new corpus is built and checked next to the old one and takes its place only when every check has passed: a refused
+    // upload leaves the handle as it was.
+    const nvsm_corpus& c = *corpus;
+    Corpus* fresh = new Corpus();
+    const bool had_refs = in_refs_[0].p != nullptr;
+    try {
+        fresh->num_tokens = c.num_tokens; fresh->num_documents = c.num_documents;
+        fresh->with_doc_weights = c.doc_weights != nullptr; fresh->with_term_weights = c.term_weights != nullptr;
+        // (padded so that the clamped path of a bad reference — arena index 0, document 0 — has something to read: corpus.hip)
+        fresh->tokens.alloc(static_cast<size_t>(std::max<int64_t>(c.num_tokens, 1)), true);
+        fresh->offsets.alloc(static_cast<size_t>(std::max<int64_t>(c.num_documents + 1, 2)), true);
+        if (c.num_tokens > 0) NVSM_HIP_CHECK(hipMemcpy(fresh->tokens.p, c.tokens, c.num_tokens * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(fresh->offsets.p, c.doc_offsets, (c.num_documents + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (c.doc_weights) {
+            fresh->doc_weights.alloc(static_cast<size_t>(std::max<int64_t>(c.num_documents, 1)), true);
+            if (c.num_documents > 0) NVSM_HIP_CHECK(hipMemcpy(fresh->doc_weights.p, c.doc_weights, c.num_documents * sizeof(float), hipMemcpyHostToDevice));
+        }
+        if (c.term_weights) {
+            fresh->term_weights.alloc(static_cast<size_t>(cfg_.num_words));
+            NVSM_HIP_CHECK(hipMemcpy(fresh->term_weights.p, c.term_weights, cfg_.num_words * sizeof(float), hipMemcpyHostToDevice));
+        }
+        fresh->host_offsets.assign(c.doc_offsets, c.doc_offsets + c.num_documents + 1);
+        if (fresh->host_offsets.size() < 2) fresh->host_offsets.push_back(0);
+        DevBuf<int> bad;
+        bad.alloc(1, true);
+        launch_corpus_check_tokens(fresh->tokens.p, c.num_tokens, cfg_.num_words, bad.p, stream_);
+        int verdict = 0;
+        NVSM_HIP_CHECK(hipMemcpyAsync(&verdict, bad.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        if (verdict) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a token of the corpus is outside [0, num_words)");
+        if (!had_refs) for (int p = 0; p < 2; ++p) in_refs_[p].alloc(static_cast<size_t>(cfg_.max_batch_size) * 2);
+        fresh->bytes = (fresh->tokens.n + fresh->doc_weights.n + fresh->term_weights.n) * 4 + fresh->offsets.n * 8 + 2 * in_refs_[0].n * 4;
+        synchronize();      // whatever is queued may still read the corpus being replaced
+    } catch (...) {
+        delete fresh;
+        if (!had_refs) { in_refs_[0].release(); in_refs_[1].release(); }
+        throw;
+    }
+    delete corpus_;
+    corpus_ = fresh;
+}
+
+nvsm_batch Model::check_window_request(const nvsm_window_batch& wb) const {
+    if (!wb.refs) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: refs");
+    if (cfg_.world_size > 1) throw Error(NVSM_ERR_UNSUPPORTED, "window references are not implemented under data parallelism (world_size > 1)");
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "window references need a corpus: call nvsm_corpus_upload first");
+    if (wb.num_instances <= 0 || wb.num_instances > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_instances must be in (0, max_batch_size]");
+    nvsm_batch b{};      // (what compute_cost and step look at: the size, and where the references live)
+    b.num_instances = wb.num_instances;
+    b.on_device = wb.on_device;
+    return b;
+}
+
+void Model::compute_cost_windows(const nvsm_window_batch& wb, const int64_t* entity_ids) {
+    const nvsm_batch b = check_window_request(wb);
+    win_req_ = &wb;
+    try { compute_cost(b, entity_ids); } catch (...) { win_req_ = nullptr; throw; }
+    win_req_ = nullptr;
+}
+
+void Model::step_windows(const nvsm_window_batch& wb, const int64_t* entity_ids, float lr, float* cost) {
+    const nvsm_batch b = check_window_request(wb);
+    win_req_ = &wb;
+    try { step(b, entity_ids, lr, cost); } catch (...) { win_req_ = nullptr; throw; }
+    win_req_ = nullptr;
+}
+
+int64_t Model::step_windows_deferred(const nvsm_window_batch& wb, const int64_t* entity_ids, float lr) {
+    const nvsm_batch b = check_window_request(wb);
+    win_req_ = &wb;
+    int64_t ticket;
+    try { ticket = step_deferred(b, entity_ids, lr); } catch (...) { win_req_ = nullptr; throw; }
+    win_req_ = nullptr;
+    return ticket;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -141,6 +141,12 @@ class Model {
     void compute_cost_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix);
     void step_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix, float lr, float* cost);
 
+    // training from an HBM-resident corpus (include/cunvsm_amd.h; corpus.hip): see "window references" below
+    void corpus_upload(const nvsm_corpus* corpus);      // null: free it
+    void compute_cost_windows(const nvsm_window_batch& wb, const int64_t* entity_ids);
+    void step_windows(const nvsm_window_batch& wb, const int64_t* entity_ids, float lr, float* cost);
+    int64_t step_windows_deferred(const nvsm_window_batch& wb, const int64_t* entity_ids, float lr);
+
     int64_t param_size(const std::string& name);
     void get_param(const std::string& name, float* dst, int64_t count);
     void set_param(const std::string& name, const float* src, int64_t count);
@@ -338,6 +344,24 @@ class Model {
     void launch_pairs(hipStream_t s, hipEvent_t after);                // the pair kernel of the current forward result
     int64_t ents_entries(int64_t text_windows) const { return text_windows * R_ + (mode_ != MODE_TEXT ? 2 * M_ : 0); }
     float scaled_lambda_for(int mode, int64_t B, int64_t M) const;
+
+    // ---- window references (corpus.hip). The corpus lives in HBM from nvsm_corpus_upload on; a *_windows call is compute_cost / step
+    // on a batch that window_expand_kernel writes into a host batch's staging set (compute_cost F1). Everything here is allocated by
+    // the upload.
+    struct Corpus {
+        DevBuf<int> tokens;                 // at least one element
+        DevBuf<int64_t> offsets;            // at least two
+        DevBuf<float> doc_weights, term_weights;      // empty: none
+        std::vector<int64_t> host_offsets;  // host sampler: which references are bad (their label is 0, as on the device)
+        int64_t num_tokens = 0, num_documents = 0;
+        bool with_doc_weights = false, with_term_weights = false;
+        size_t bytes = 0;
+    };
+    Corpus* corpus_ = nullptr;
+    DevBuf<uint32_t> in_refs_[2];               // host references, one per staging set
+    std::vector<uint32_t> host_refs_;           // host sampler: device references read back
+    const nvsm_window_batch* win_req_ = nullptr;      // set around compute_cost by the *_windows calls: F1 expands these references
+    nvsm_batch check_window_request(const nvsm_window_batch& wb) const;      // the checks; the nvsm_batch that stands for it in compute_cost
 
     // ranking scratch: allocated by the first infer / rank call (training-only handles never pay for it), grown on demand
     struct RankScratch {

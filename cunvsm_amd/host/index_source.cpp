@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 
 namespace nvsm_host {
@@ -13,6 +14,7 @@ struct WindowRef {
     uint32_t doc;        // model document id (= the instance's label)
     uint32_t pos;        // first token of the window inside the document
 };
+static_assert(sizeof(WindowRef) == 8, "a window reference is the ABI's pair of uint32 (nvsm_window_batch)");
 
 // The permutation std::shuffle produced in libstdc++ up to GCC 6: element i (from the second on) is swapped with the
 // element at a position drawn uniformly from [0, i], one generator-backed draw per element. The reference's seed-pinned
@@ -69,14 +71,16 @@ class IndexSource::WindowFeeder {
         start_epoch();
     }
 
-    bool pending() const { return cursor_ < epoch_.size(); }
-    double fraction_done() const { return epoch_.empty() ? 1.0 : static_cast<double>(cursor_) / static_cast<double>(epoch_.size()); }
+    ~WindowFeeder() { if (held_) held_free_(held_); }
+
+    bool pending() const { return cursor_ < plan_size_; }
+    double fraction_done() const { return plan_size_ == 0 ? 1.0 : static_cast<double>(cursor_) / static_cast<double>(plan_size_); }
 
     void start_epoch() {
         if (pending()) NVSM_LOG(WARNING) << "Resetting instance generator while there are still instances to consume.";
         cursor_ = 0;
         if (order_ == DOCUMENT_ORDER) {
-            if (epoch_.empty()) plan_every_window(false);          // the same plan every epoch
+            if (!planned_) { plan_every_window(false); publish_plan(); }      // the same plan every epoch
             return;
         }
         epoch_.clear();
@@ -88,6 +92,44 @@ class IndexSource::WindowFeeder {
         }
         NVSM_LOG(INFO) << "Shuffling " << epoch_.size() << " instance pointers.";
         shuffle_pre_gcc7(&epoch_, rng_);                           // cpp/data_indri.cpp:404
+        publish_plan();
+    }
+
+    // the plan the cursor runs over: the vector it was made in, or — hold_in() — a copy in the caller's memory
+    void publish_plan() {
+        planned_ = true;
+        plan_size_ = epoch_.size();
+        if (!held_alloc_) { plan_ = epoch_.data(); return; }
+        if (plan_size_ > held_capacity_) {
+            if (held_) held_free_(held_);
+            held_ = static_cast<WindowRef*>(held_alloc_(std::max<size_t>(plan_size_, 1) * sizeof(WindowRef)));
+            held_capacity_ = plan_size_;
+        }
+        if (plan_size_) std::memcpy(held_, epoch_.data(), plan_size_ * sizeof(WindowRef));
+        plan_ = held_;
+        std::vector<WindowRef>().swap(epoch_);                     // (one copy of the plan, not two)
+    }
+    void hold_in(BatchAllocFn alloc, BatchFreeFn free_fn) {
+        NVSM_CHECK(!held_alloc_ && alloc && free_fn);
+        held_alloc_ = alloc; held_free_ = free_fn;
+        // (the plan made so far still lies in epoch_: plan_ points at its storage)
+        publish_plan();
+    }
+
+    void next_refs(size_t max, const uint32_t** refs, size_t* count) {
+        const size_t n = std::min(max, plan_size_ - cursor_);
+        *refs = reinterpret_cast<const uint32_t*>(plan_ + cursor_);
+        *count = n;
+        cursor_ += n;
+    }
+
+    IndexSource::CorpusView view() const {
+        IndexSource::CorpusView v;
+        v.tokens = arena_.data(); v.num_tokens = arena_.size();
+        v.first_token = first_token_.data(); v.num_documents = usable_.size();
+        v.instance_weight = instance_weight_.data();
+        v.term_weight = term_weight_.empty() ? nullptr : term_weight_.data(); v.num_term_weights = term_weight_.size();
+        return v;
     }
 
     // copies windows into the batch's free rows until it is full or the epoch is over
@@ -95,7 +137,7 @@ class IndexSource::WindowFeeder {
         std::vector<WordIdxType> ids(window_);
         std::vector<WeightType> per_term(term_weight_.empty() ? 0 : window_);
         while (!batch->full() && pending()) {
-            const WindowRef ref = epoch_[cursor_++];
+            const WindowRef ref = plan_[cursor_++];
             const int32_t* src = arena_.data() + first_token_[ref.doc] + ref.pos;
             for (size_t j = 0; j < window_; ++j) ids[j] = static_cast<WordIdxType>(src[j]);
             if (!term_weight_.empty())
@@ -204,7 +246,14 @@ class IndexSource::WindowFeeder {
     std::vector<WeightType> instance_weight_;  // per document
     std::vector<WeightType> term_weight_;      // per model term; empty = all 1
     double mean_tokens_ = 0.0;                 // in-vocabulary tokens per usable document (shuffled orders)
-    std::vector<WindowRef> epoch_;
+    std::vector<WindowRef> epoch_;             // where an epoch is planned and shuffled
+    const WindowRef* plan_ = nullptr;          // what the cursor runs over: epoch_'s storage, or held_
+    size_t plan_size_ = 0;
+    bool planned_ = false;
+    WindowRef* held_ = nullptr;                // hold_in(): the plan in the caller's memory
+    size_t held_capacity_ = 0;
+    BatchAllocFn held_alloc_ = nullptr;
+    BatchFreeFn held_free_ = nullptr;
     size_t cursor_ = 0;
 };
 
@@ -238,6 +287,16 @@ void IndexSource::next(Batch* batch) {
     DataSource::next(batch);               // nothing is ever parked in the base class's overflow queue by this source
     feeder_->feed(batch);
 }
+
+void IndexSource::next_refs(size_t max, const uint32_t** refs, size_t* count) {
+    NVSM_CHECK(!model_term_of_.empty());
+    NVSM_CHECK(DataSource::overflow_empty());
+    feeder_->next_refs(max, refs, count);
+}
+
+void IndexSource::hold_plan_in(BatchAllocFn alloc, BatchFreeFn free_fn) { feeder_->hold_in(alloc, free_fn); }
+
+IndexSource::CorpusView IndexSource::corpus_view() const { return feeder_->view(); }
 
 bool IndexSource::has_next() const { return DataSource::has_next() || feeder_->pending(); }
 

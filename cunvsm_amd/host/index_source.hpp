@@ -59,6 +59,26 @@ class IndexSource : public DataSource {
     std::map<std::string, int64_t> build_term_identifiers_map() const;
     std::map<std::string, int64_t> build_document_identifiers_map() const;
 
+    // ---- the collection as the GPU can train from it (nvsm_corpus_upload / nvsm_step_windows, include/cunvsm_amd.h) ----
+    // What next(Batch*) copies windows out of, read-only and valid as long as the source lives: the flat arena of model term
+    // ids, one offset per model document (+ 1), the instance weight of every window of a document, and the feature weight of
+    // every occurrence of a term (null under uniform term weighting: every weight is 1).
+    struct CorpusView {
+        const int32_t* tokens; size_t num_tokens;
+        const uint64_t* first_token; size_t num_documents;      // first_token[num_documents] == num_tokens
+        const WeightType* instance_weight;                      // [num_documents]
+        const WeightType* term_weight; size_t num_term_weights; // [num_term_weights] or null
+    };
+    CorpusView corpus_view() const;
+    // A second way to draw an epoch: the next at most `max` entries of the epoch plan as they lie in memory — (model document,
+    // first token inside the document) as interleaved uint32, *count of them at *refs, valid until the next reset(). The plan,
+    // the cursor and the shared generator are the ones next(Batch*) uses: has_next(), progress() and reset() behave the same,
+    // and an epoch drawn this way consumes the random stream exactly as one drawn through batches. hold_plan_in(alloc, free)
+    // moves the plan (this epoch's and every later one's) into memory from `alloc` — the trainer passes the page-locked
+    // allocator, so that slices of the plan are read by the GPU where they lie.
+    void next_refs(size_t max, const uint32_t** refs, size_t* count);
+    void hold_plan_in(BatchAllocFn alloc, BatchFreeFn free_fn);
+
     // −log(term frequency / total term occurrences) per term; empty under uniform term weighting (data.h:465-490)
     std::vector<WeightType> compute_term_weights(const std::vector<WordIdxType>& terms) const;
 

@@ -13,6 +13,10 @@
 //     generator's stream. Refused: w = 1 (CHECK_NE(text_entity_weight_, 0.0), cpp/objective.cu:708), w != 0 without a similarity
 //     file, Adagrad and sparse Adam together with pairs (the reference's own refusal), pairs under data parallelism, with
 //     --l2_entity_normalization or with --check_gradients, and the term-term objective (--term_similarity_weight != 0).
+//   * --device_corpus: the collection goes into HBM once (nvsm_corpus_upload) and every batch is handed over as window references —
+//     8 bytes per window, slices of the epoch plan in page-locked memory — instead of as a 132-byte-per-window host batch
+//     (nvsm_step_windows_deferred). The epochs, the random stream, the skip rule, the log lines and every number are those of the run
+//     without the flag. Refused together with a similarity file, with --check_gradients and under data parallelism.
 //   * extensions: --stopwords, --device, --sampler {host,device}, --allow_ragged_batches, and data parallelism over RCCL
 //     (--gpus N spawns one process per GPU; or --world_size / --rank [or WORLD_SIZE / RANK / LOCAL_RANK] under any launcher).
 #include <sys/stat.h>
@@ -51,7 +55,7 @@ double FLAGS_regularization_lambda, FLAGS_learning_rate, FLAGS_max_document_freq
     FLAGS_term_similarity_weight;
 bool FLAGS_bias_negative_samples, FLAGS_l2_phrase_normalization, FLAGS_l2_entity_normalization, FLAGS_batch_normalization,
     FLAGS_include_oov, FLAGS_compute_initial_cost, FLAGS_check_gradients, FLAGS_no_shuffle, FLAGS_dump_initial_model,
-    FLAGS_allow_ragged_batches, FLAGS_logtostderr, FLAGS_alsologtostderr, FLAGS_dp_exact_tables;
+    FLAGS_allow_ragged_batches, FLAGS_logtostderr, FLAGS_alsologtostderr, FLAGS_dp_exact_tables, FLAGS_device_corpus;
 int64_t FLAGS_dump_every, FLAGS_v, FLAGS_device, FLAGS_minloglevel, FLAGS_gpus, FLAGS_world_size, FLAGS_rank;
 std::string FLAGS_comm_id_file, FLAGS_comm_nonce;
 
@@ -109,6 +113,9 @@ void define_flags(Flags* f) {      // names, defaults and help strings of cpp/ma
                      "parent pid + MASTER_PORT; --gpus N hands its children a random one). A rendezvous file with another nonce is ignored.");
     f->define_string("sampler", &FLAGS_sampler, "host", "Negative sampler: host (minstd_rand0, draw-for-draw the reference) or device.");
     f->define_bool("allow_ragged_batches", &FLAGS_allow_ragged_batches, false, "Train on batches whose size is not a multiple of 1024 instead of skipping them as the reference does.");
+    f->define_bool("device_corpus", &FLAGS_device_corpus, false, "Put the collection into GPU memory once and train from window references (8 bytes per "
+                   "window) instead of host batches (132 bytes per window at window size 10). Same epochs, same random stream, same results. "
+                   "Single GPU, text-entity objective only.");
     // glog's own options that the reference's scripts pass
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
     f->define_bool("alsologtostderr", &FLAGS_alsologtostderr, true, "Accepted for compatibility.");
@@ -175,6 +182,10 @@ class Trainer {
         if (reshuffles) NVSM_CALL(nvsm_rng_set_state(model_, rng_state(*pair_rng_)));
     }
 
+    // --device_corpus: the epochs are drawn from `source` as window references into the corpus uploaded to the model; the data source
+    // handed to iterate_data is that same object (has_next / progress)
+    void train_from_refs(IndexSource* source) { ref_source_ = source; }
+
     // DumpModelFn (cpp/main.cu:335-364) + write_to_hdf5 (include/cuNVSM/lse_hdf5_inl.h)
     void dump_model(size_t epoch, const std::string& identifier) {
         // data parallel: the replicas' tables have drifted apart (rank-local sparse updates): what is written is their mean,
@@ -223,11 +234,18 @@ class Trainer {
         while (data_source->has_next()) {
             Range batch_range("Batch");                                                   // nvtxRangePush("Batch"), cpp/main.cu:386
             const auto batch_start = std::chrono::steady_clock::now();
-            NVSM_CALL(nvsm_wait_inputs(model_));        // the previous step has copied this host batch to the device
+            // (window references are slices of the epoch plan, which nothing rewrites before the epoch is over: nothing to wait for)
+            if (!ref_source_) NVSM_CALL(nvsm_wait_inputs(model_));        // the previous step has copied this host batch to the device
             batch->clear();
-            { Range fetch_range("FetchData"); data_source->next(batch); if (pair_source_) next_pairs(); }      // :388-390
+            const uint32_t* refs = nullptr;
+            size_t num_refs = 0;
+            {
+                Range fetch_range("FetchData");                                                  // :388-390
+                if (ref_source_) ref_source_->next_refs(tc_.batch_size, &refs, &num_refs);
+                else { data_source->next(batch); if (pair_source_) next_pairs(); }
+            }
             // a step's instance count is the smaller of the two batches' (BatchHandler<tuple>::num_instances, cpp/main.cu:102-105)
-            const size_t n_global = pair_source_ ? std::min(batch->num_instances(), pair_batch_->num_instances()) : batch->num_instances();
+            const size_t n_global = ref_source_ ? num_refs : pair_source_ ? std::min(batch->num_instances(), pair_batch_->num_instances()) : batch->num_instances();
             const size_t G = static_cast<size_t>(world_size_);
             if (n_global % 1024 != 0 && !FLAGS_allow_ragged_batches) {                        // maxThreadsPerBlock, :392-398
                 NVSM_LOG(ERROR) << "Skipping Batch #" << epoch_num_batches << " as it is not a multiple of " << 1024 << " (" << n_global << " instances).";
@@ -242,7 +260,24 @@ class Trainer {
                 b.labels = batch->labels() + lo; b.weights = batch->weights() + lo;
                 b.num_instances = static_cast<int64_t>(n); b.on_device = 0;
                 float cost = 0.f;
-                if (pair_source_) {
+                if (ref_source_) {
+                    nvsm_window_batch wb{};
+                    wb.refs = refs; wb.num_instances = static_cast<int64_t>(n_global); wb.on_device = 0;
+                    if (backpropagate) {
+                        int64_t ticket = 0;
+                        NVSM_CALL(nvsm_step_windows_deferred(model_, &wb, nullptr, tc_.learning_rate, &ticket));
+                        finish(pending);
+                        pending.valid = true; pending.ticket = ticket; pending.index = epoch_num_batches; pending.start = batch_start;
+                        windows_ += n_global;
+                        if (may_dump && FLAGS_dump_every > 0 && epoch_num_batches > 0 && epoch_num_batches % static_cast<size_t>(FLAGS_dump_every) == 0)
+                            dump_model(dump_epoch, std::to_string(epoch_num_batches));
+                        ++epoch_num_batches;
+                        continue;
+                    }
+                    NVSM_CALL(nvsm_compute_cost_windows(model_, &wb, nullptr));
+                    NVSM_CALL(nvsm_compute_gradients(model_));
+                    NVSM_CALL(nvsm_get_cost(model_, &cost));
+                } else if (pair_source_) {
                     // both batches as they are (the count above only decides whether the step is skipped, as in the reference)
                     b.features = batch->features(); b.feature_weights = batch->feature_weights(); b.labels = batch->labels();
                     b.weights = batch->weights(); b.num_instances = static_cast<int64_t>(batch->num_instances());
@@ -397,6 +432,7 @@ class Trainer {
     int dw_, de_;
     int world_size_, rank_;
     uint64_t windows_ = 0;
+    IndexSource* ref_source_ = nullptr;
     RepeatingPairSource* pair_source_ = nullptr;
     RNG* pair_rng_ = nullptr;
     std::unique_ptr<PairBatch> pair_batch_;
@@ -430,6 +466,15 @@ int run(int argc, char** argv) {
     NVSM_CHECK(FEATURE_WEIGHTING_STRATEGIES.count(FLAGS_feature_weighting)) << "Please specify a valid --feature_weighting.";
     NVSM_CHECK(NONLINEARITIES.count(FLAGS_nonlinearity)) << "Please specify a valid --nonlinearity.";
     NVSM_CHECK(FLAGS_sampler == "host" || FLAGS_sampler == "device") << "--sampler must be host or device.";
+
+    if (FLAGS_device_corpus) {      // (before anything is spawned or indexed)
+        const char* ws = std::getenv("WORLD_SIZE");
+        if (FLAGS_gpus > 1 || FLAGS_world_size > 1 || (FLAGS_world_size == 0 && ws && std::atoll(ws) > 1))
+            NVSM_LOG(FATAL) << "--device_corpus is not implemented under data parallelism (--gpus / --world_size > 1): window references are single-GPU.";
+        if (FLAGS_check_gradients) NVSM_LOG(FATAL) << "--device_corpus cannot be combined with --check_gradients: the gradient checker re-evaluates host batches.";
+        if (args.size() >= 3)
+            NVSM_LOG(FATAL) << "--device_corpus cannot be combined with a similarity file: window references cover the text-entity objective only.";
+    }
 
     // ---- data parallelism: --gpus N spawns the ranks; otherwise world size / rank come from the flags or the launcher's environment
     auto env_int = [](const char* name, int64_t dflt) { const char* v = std::getenv(name); return (v && *v) ? static_cast<int64_t>(std::atoll(v)) : dflt; };
@@ -588,7 +633,10 @@ int run(int argc, char** argv) {
     // initialisation) inside RepeatingSource(-1)
     std::unique_ptr<IdentifiersMapT> identifiers_map;
     if (train_pairs) identifiers_map.reset(new IdentifiersMapT(index_source->build_document_identifiers_map()));
-    std::unique_ptr<DataSourceInterface> data_source(new AsyncSource(10, tc.batch_size, tc.window_size, index_source));
+    // (--device_corpus: no prefetch thread — there are no batches to fill; the source itself hands out slices of its plan)
+    std::unique_ptr<DataSourceInterface> data_source;
+    if (FLAGS_device_corpus) data_source.reset(index_source);
+    else data_source.reset(new AsyncSource(10, tc.batch_size, tc.window_size, index_source));
     std::unique_ptr<RepeatingPairSource> pair_source;
     if (train_pairs) {
         NVSM_LOG(INFO) << "Reading document similarities from " << similarity_path << ".";
@@ -668,8 +716,28 @@ int run(int argc, char** argv) {
         NVSM_CHECK(meta_file.good()) << "cannot write " << FLAGS_output << "_meta";
     }
 
+    if (FLAGS_device_corpus) {
+        // the collection as next(Batch*) reads it, into HBM. Both weight arrays always (all 1.0 where the source has none): the
+        // batches of the run without the flag always carry both, and the two runs are the same bit for bit.
+        const IndexSource::CorpusView v = index_source->corpus_view();
+        NVSM_CHECK(v.num_documents == corpus_size);
+        std::vector<int64_t> offsets(v.first_token, v.first_token + v.num_documents + 1);
+        std::vector<float> ones;
+        if (!v.term_weight) ones.assign(vocabulary_size, 1.0f);
+        else NVSM_CHECK(v.num_term_weights == vocabulary_size);
+        nvsm_corpus corpus{};
+        corpus.tokens = v.tokens; corpus.doc_offsets = offsets.data(); corpus.doc_weights = v.instance_weight;
+        corpus.term_weights = v.term_weight ? v.term_weight : ones.data();
+        corpus.num_tokens = static_cast<int64_t>(v.num_tokens); corpus.num_documents = static_cast<int64_t>(v.num_documents);
+        NVSM_CALL(nvsm_corpus_upload(model, &corpus));
+        index_source->hold_plan_in(pinned_alloc, pinned_free);      // slices of the plan are pulled by the GPU where they lie
+        NVSM_LOG(INFO) << "Device corpus: " << v.num_tokens << " tokens of " << v.num_documents << " documents in GPU memory; batches are "
+                       << "window references (8 bytes per window).";
+    }
+
     Trainer trainer(model, tc, static_cast<int64_t>(vocabulary_size), static_cast<int64_t>(corpus_size),
                     static_cast<int>(FLAGS_word_repr_size), static_cast<int>(FLAGS_entity_repr_size), world_size, rank);
+    if (FLAGS_device_corpus) trainer.train_from_refs(index_source);
     if (train_pairs)
         trainer.train_pairs(pair_source.get(), &rng, static_cast<float>(1.0 - FLAGS_entity_similarity_weight), static_cast<float>(FLAGS_entity_similarity_weight));
     Batch batch(tc.batch_size, tc.window_size);
@@ -680,6 +748,8 @@ int run(int argc, char** argv) {
         uint64_t s = 0;
         NVSM_CALL(nvsm_rng_get_state(model, &s));
         rng_set_state(&rng, s);
+        // (--device_corpus: the new epoch's plan overwrites the page-locked one the last steps' references were slices of)
+        if (FLAGS_device_corpus) NVSM_CALL(nvsm_wait_inputs(model));
         data_source->reset();
         if (pair_source) pair_source->reset();                     // MultiSource::reset: every source in order (cpp/data_multi.cpp:48-51)
         NVSM_CALL(nvsm_rng_set_state(model, rng_state(rng)));

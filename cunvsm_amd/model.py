@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -163,6 +163,112 @@ class PairBatch:
 
     def as_struct(self):
         return NvsmPairBatch(self._ptr(self.pairs), self._ptr(self.weights), self.num_pairs, int(self.on_device))
+
+
+class Corpus:
+    """nvsm_corpus — a collection as the GPU trains from it (nvsm_corpus_upload): tokens [num_tokens] int32 model word ids,
+    documents back to back; doc_offsets [num_documents + 1] int64 (first 0, non-decreasing, last num_tokens); optional
+    doc_weights [num_documents] float32 (the instance weight of every window of the document) and term_weights [num_words]
+    float32 (the feature weight of every occurrence of the word). Host arrays. What needs no device is checked here; that
+    the tokens name words of the model, and the lengths that depend on the model, by Model.upload_corpus."""
+
+    def __init__(self, tokens, doc_offsets, doc_weights=None, term_weights=None):
+        def as_array(a, dtype, kind, name):
+            a = np.asarray(a)
+            if a.ndim != 1:
+                raise ValueError("%s must be a flat array" % name)
+            if a.size and not np.issubdtype(a.dtype, kind):
+                raise ValueError("%s must hold %s" % (name, "integers" if kind is np.integer else "floats"))
+            return a, np.ascontiguousarray(a, dtype=dtype)
+
+        raw, self.tokens = as_array(tokens, np.int32, np.integer, "tokens")
+        if raw.size and (raw.min() < 0 or raw.max() >= 2 ** 31):
+            raise ValueError("a token is outside int32")
+        _, self.doc_offsets = as_array(doc_offsets, np.int64, np.integer, "doc_offsets")
+        off = self.doc_offsets
+        if off.size < 1 or off[0] != 0:
+            raise ValueError("doc_offsets must start at 0")
+        if (off[1:] < off[:-1]).any():
+            raise ValueError("doc_offsets must not decrease")
+        if off[-1] != self.tokens.size:
+            raise ValueError("the last of doc_offsets is %d, expected num_tokens = %d" % (off[-1], self.tokens.size))
+        self.num_tokens, self.num_documents = int(self.tokens.size), int(off.size - 1)
+        self.doc_weights = self.term_weights = None
+        if doc_weights is not None:
+            _, self.doc_weights = as_array(doc_weights, np.float32, np.number, "doc_weights")
+            if self.doc_weights.size != self.num_documents:
+                raise ValueError("doc_weights holds %d values, expected num_documents = %d" % (self.doc_weights.size, self.num_documents))
+        if term_weights is not None:
+            _, self.term_weights = as_array(term_weights, np.float32, np.number, "term_weights")
+
+    def as_struct(self):
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        return NvsmCorpus(ptr(self.tokens), self.doc_offsets.ctypes.data, None if self.doc_weights is None else self.doc_weights.ctypes.data,
+                          None if self.term_weights is None else self.term_weights.ctypes.data, self.num_tokens, self.num_documents)
+
+
+class WindowBatch:
+    """nvsm_window_batch — a batch as window references: refs [n, 2] uint32, (document, first token inside the document) per
+    window. A numpy array (pageable, or the .array of a PinnedArray or a slice of it: page-locked), a torch CUDA tensor
+    (uint32, or int32 holding the same bits), or a device pointer given as an int together with num_instances."""
+
+    def __init__(self, refs, num_instances=None):
+        if isinstance(refs, (int, np.integer)) and not isinstance(refs, bool):
+            if num_instances is None or int(num_instances) < 1:
+                raise ValueError("a device pointer needs num_instances >= 1")
+            if int(refs) == 0:
+                raise ValueError("refs is a null device pointer")
+            self.refs, self.on_device, self.num_instances, self._address = None, True, int(num_instances), int(refs)
+            return
+        self.on_device = hasattr(refs, "data_ptr")
+        if self.on_device:
+            if str(refs.dtype) not in ("torch.uint32", "torch.int32"):
+                raise ValueError("refs must be uint32")
+            if not refs.is_contiguous():
+                raise ValueError("device arrays must be contiguous")
+            shape = tuple(refs.shape)
+            self.refs = refs
+        else:
+            a = np.asarray(refs)
+            if a.dtype != np.uint32:
+                raise ValueError("refs must be uint32, not %s" % a.dtype)
+            shape = a.shape
+            self.refs = a if a.flags["C_CONTIGUOUS"] else np.ascontiguousarray(a)      # (a row slice of a pinned plan stays where it is)
+        if len(shape) != 2 or shape[1] != 2:
+            raise ValueError("refs has shape %s, expected [num_instances][2]" % (shape,))
+        if shape[0] < 1:
+            raise ValueError("refs is empty: a batch needs at least one window")
+        if num_instances is not None and int(num_instances) != shape[0]:
+            raise ValueError("num_instances = %d, but refs holds %d windows" % (int(num_instances), shape[0]))
+        self.num_instances = int(shape[0])
+        self._address = int(self.refs.data_ptr()) if self.on_device else int(self.refs.ctypes.data)
+
+    def as_struct(self):
+        return NvsmWindowBatch(self._address, self.num_instances, int(self.on_device))
+
+
+def expand_windows(corpus, refs, window):
+    """The Batch (host, numpy) that window references denote — the definition in include/cunvsm_amd.h, word for word:
+    features[i, j] = tokens[doc_offsets[doc_i] + pos_i + j], feature_weights = term_weights[features] (None without
+    term_weights), labels[i] = doc_i, weights[i] = doc_weights[doc_i] (None without doc_weights). Raises ValueError for a
+    reference the device would flag: a document >= num_documents, or a window that reaches beyond its document."""
+    refs = np.asarray(refs)
+    if refs.ndim != 2 or refs.shape[1] != 2:
+        raise ValueError("refs has shape %s, expected [num_instances][2]" % (refs.shape,))
+    window = int(window)
+    if window < 1:
+        raise ValueError("window must be at least 1")
+    doc, pos = refs[:, 0].astype(np.int64), refs[:, 1].astype(np.int64)
+    if doc.size and (doc.min() < 0 or doc.max() >= corpus.num_documents):
+        raise ValueError("a reference names a document outside [0, num_documents = %d)" % corpus.num_documents)
+    off = corpus.doc_offsets
+    if ((pos < 0) | (pos + window > off[doc + 1] - off[doc])).any():
+        raise ValueError("a window reaches beyond its document's end")
+    at = (off[doc] + pos)[:, None] + np.arange(window, dtype=np.int64)[None, :]
+    features = corpus.tokens[at].astype(np.int64)
+    fw = None if corpus.term_weights is None else corpus.term_weights[features].astype(np.float32)
+    iw = None if corpus.doc_weights is None else corpus.doc_weights[doc].astype(np.float32)
+    return Batch(features.ravel(), doc, None if fw is None else fw.ravel(), iw)
 
 
 def mixture(text_weight, pair_weight):
@@ -448,6 +554,48 @@ class Model:
         check(lib().nvsm_step(self._h, C.byref(st), None if ids is None else ids.ctypes.data, learning_rate,
                               C.byref(c) if want_cost else None))
         return c.value if want_cost else None
+
+    # -- training from an HBM-resident corpus: window references instead of batches -------------------------------
+    def upload_corpus(self, corpus):
+        """nvsm_corpus_upload: the corpus into HBM (synchronous; replaces an earlier one; None frees it)."""
+        if corpus is None:
+            check(lib().nvsm_corpus_upload(self._h, None))
+            return
+        if corpus.term_weights is not None and corpus.term_weights.size != self.cfg.num_words:
+            raise ValueError("term_weights holds %d values, expected num_words = %d" % (corpus.term_weights.size, self.cfg.num_words))
+        st = corpus.as_struct()
+        check(lib().nvsm_corpus_upload(self._h, C.byref(st)))
+
+    def _checked_windows(self, windows, entity_ids):
+        if not isinstance(windows, WindowBatch):
+            windows = WindowBatch(windows)
+        ids = None
+        if entity_ids is not None:
+            ids = np.ascontiguousarray(entity_ids, dtype=np.int64)
+            if ids.size != windows.num_instances * (self.cfg.num_random_entities + 1):
+                raise ValueError("entity_ids holds %d ids, expected num_instances * (num_random_entities + 1) = %d"
+                                 % (ids.size, windows.num_instances * (self.cfg.num_random_entities + 1)))
+        self._keep = (windows, ids)
+        return windows.as_struct(), ids
+
+    def compute_cost_windows(self, windows, entity_ids=None):
+        """nvsm_compute_cost_windows: compute_cost on the batch the references denote in the uploaded corpus."""
+        st, ids = self._checked_windows(windows, entity_ids)
+        check(lib().nvsm_compute_cost_windows(self._h, C.byref(st), None if ids is None else ids.ctypes.data))
+
+    def step_windows(self, windows, learning_rate, entity_ids=None, want_cost=False):
+        st, ids = self._checked_windows(windows, entity_ids)
+        c = C.c_float()
+        check(lib().nvsm_step_windows(self._h, C.byref(st), None if ids is None else ids.ctypes.data, float(learning_rate),
+                                      C.byref(c) if want_cost else None))
+        return c.value if want_cost else None
+
+    def step_windows_deferred(self, windows, learning_rate, entity_ids=None):
+        """nvsm_step_windows_deferred; returns the ticket for deferred_cost()."""
+        st, ids = self._checked_windows(windows, entity_ids)
+        t = C.c_int64()
+        check(lib().nvsm_step_windows_deferred(self._h, C.byref(st), None if ids is None else ids.ctypes.data, float(learning_rate), C.byref(t)))
+        return t.value
 
     # -- the entity-entity similarity objective, alone (batch None) or mixed into the text objective ----------------
     def _checked_mixed(self, batch, pairs, entity_ids, weights):

@@ -244,6 +244,58 @@ int nvsm_compute_cost_mixed(nvsm_model* m, const nvsm_batch* text /* NULL: pairs
 int nvsm_step_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch* pairs,
                     const nvsm_mixture* mix, float learning_rate, float* cost);
 
+/*
+ * Training from an HBM-resident corpus: window references instead of batches. A host nvsm_batch carries 12·w + 12 bytes per window
+ * (132 at w = 10); the windows of a collection are all slices of one token arena, so a window is fully named by 8 bytes — its
+ * document and the position of its first token inside the document. nvsm_corpus_upload puts the arena, the document offsets and
+ * the two weight tables into HBM once; the *_windows calls then take [num_instances] references and a kernel on the copy stream
+ * writes the batch they denote into the staging set a host batch would have been copied into. No reference counterpart.
+ * SEMANTICS — the contract. With w = window_size, window i of a batch of references (doc_i, pos_i) is the nvsm_batch instance
+ *   features[i·w + j]        = tokens[doc_offsets[doc_i] + pos_i + j]          j = 0 .. w − 1
+ *   feature_weights[i·w + j] = term_weights[that token]                        (term_weights NULL: feature_weights NULL)
+ *   labels[i]                = doc_i
+ *   weights[i]               = doc_weights[doc_i]                               (doc_weights NULL: weights NULL)
+ * and every *_windows call equals its nvsm_batch twin on that batch BIT FOR BIT: the cost, every tensor of nvsm_get_tensor, every
+ * parameter, the optimiser state, the RNG state and the lazy-decay bookkeeping (everything behind the expansion is the twin's code
+ * on an ordinary device batch). Document i of the corpus is document id i of the model, hence num_documents <= num_entities.
+ * LIFETIME of refs is that of nvsm_batch.features: nvsm_wait_inputs covers host refs; device refs must stay untouched until
+ * nvsm_synchronize or be ordered behind the step on the caller's stream (nvsm_set_stream). With NVSM_SAMPLER_HOST_MINSTD the host
+ * needs the labels: it takes them from refs[2i], or reads device refs back on the copy stream as device labels are read back.
+ * nvsm_corpus_upload is synchronous (it waits for everything the handle has queued first), copies the four host arrays — the
+ * caller may free them when it returns —, replaces an earlier corpus, and frees it when corpus is NULL. The new corpus is built and
+ * checked next to the earlier one and takes its place only when every check has passed: a refused upload leaves the handle with the
+ * corpus it had. NVSM_ERR_INVALID_ARGUMENT,
+ * each with a sentence naming the field, before the call ends: doc_offsets that do not start at 0 or that decrease; a last offset
+ * that is not num_tokens; num_documents > num_entities; a token outside [0, num_words) (checked on the device in one pass).
+ * AT STEP TIME the index contract above holds: a reference whose document is >= num_documents, or whose pos + w reaches beyond its
+ * document, becomes a window of word id 0 and label 0 (with their weights) — nothing is read out of bounds — and the next call of
+ * the handle that waits returns NVSM_ERR_INVALID_ARGUMENT once. A *_windows call on a handle without a corpus is
+ * NVSM_ERR_INVALID_ARGUMENT before anything runs; num_instances outside (0, max_batch_size] likewise. world_size > 1 is
+ * NVSM_ERR_UNSUPPORTED (the handle stays usable): the materialised batch would pass through the data-parallel path unchanged, but
+ * that is untested. The mixed / pair step takes no references.
+ * MEMORY: the corpus (4 B per token, 8 per document + 4 with doc_weights, 4 per word with term_weights) and two staging buffers of
+ * 8 B x max_batch_size for host refs are allocated by the upload, not by nvsm_create: a handle that never uploads a corpus allocates
+ * and launches exactly what it did before these calls existed. nvsm_describe reports " corpus=<bytes>B" only when there is one.
+ */
+typedef struct {
+    const int32_t* tokens;        /* [num_tokens] model word ids, documents back to back (host) */
+    const int64_t* doc_offsets;   /* [num_documents + 1], offsets[0] = 0, non-decreasing, last = num_tokens (host) */
+    const float*   doc_weights;   /* [num_documents] instance weight of every window of the document, or NULL (= nvsm_batch.weights NULL) */
+    const float*   term_weights;  /* [num_words] feature weight of every occurrence of the word, or NULL (= feature_weights NULL) */
+    int64_t num_tokens, num_documents;
+    int32_t reserved[4];
+} nvsm_corpus;
+typedef struct {
+    const uint32_t* refs;         /* [2 * num_instances]: document, first token inside the document; interleaved */
+    int64_t num_instances;
+    int32_t on_device;            /* as nvsm_batch: 0 host (page-locked: pulled by the copy-stream kernel; pageable: hipMemcpyAsync), 1 device */
+    int32_t reserved[3];
+} nvsm_window_batch;
+int nvsm_corpus_upload(nvsm_model* m, const nvsm_corpus* corpus);   /* synchronous; replaces an earlier corpus; NULL corpus frees it */
+int nvsm_compute_cost_windows(nvsm_model* m, const nvsm_window_batch* windows, const int64_t* entity_ids);
+int nvsm_step_windows(nvsm_model* m, const nvsm_window_batch* windows, const int64_t* entity_ids, float learning_rate, float* cost);
+int nvsm_step_windows_deferred(nvsm_model* m, const nvsm_window_batch* windows, const int64_t* entity_ids, float learning_rate, int64_t* ticket);
+
 /* The same step for training loops that want the loss of EVERY batch, as cpp/main.cu:427-444 does, without putting the
  * GPU behind the host: nvsm_step_deferred queues the step plus a device→host copy of its loss word and hands back a
  * ticket; nvsm_deferred_cost(ticket) waits for that copy only (not for the step's updates). At most

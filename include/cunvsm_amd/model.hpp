@@ -111,6 +111,29 @@ class Model {
         return c;
     }
 
+    // training from an HBM-resident corpus (cunvsm_amd.h): the corpus goes to the device once, a batch is then [n] window
+    // references — (document, first token inside the document) as interleaved uint32, 8 bytes per window — and every call below
+    // equals its Batch twin on the batch the references denote bit for bit. upload_corpus(nullptr) frees the corpus.
+    void upload_corpus(const nvsm_corpus* corpus) { check(nvsm_corpus_upload(h_, corpus)); }
+    static nvsm_window_batch windows_of(const uint32_t* refs, int64_t num_instances, bool on_device = false) {
+        nvsm_window_batch wb{};
+        wb.refs = refs; wb.num_instances = num_instances; wb.on_device = on_device ? 1 : 0;
+        return wb;
+    }
+    void compute_cost_windows(const nvsm_window_batch& windows, const int64_t* entity_ids = nullptr) {
+        check(nvsm_compute_cost_windows(h_, &windows, entity_ids));
+    }
+    float step_windows(const nvsm_window_batch& windows, float learning_rate, bool want_cost = true) {
+        float c = 0.f;
+        check(nvsm_step_windows(h_, &windows, nullptr, learning_rate, want_cost ? &c : nullptr));
+        return c;
+    }
+    int64_t step_windows_deferred(const nvsm_window_batch& windows, float learning_rate) {
+        int64_t t = 0;
+        check(nvsm_step_windows_deferred(h_, &windows, nullptr, learning_rate, &t));
+        return t;
+    }
+
     // the same loop body with the loss read back one step late (cpp/main.cu:427-444 without the per-step stall):
     //   wait_inputs(); refill the host batch; t = step_deferred(batch, lr); cost of the PREVIOUS step = deferred_cost(t_prev)
     int64_t step_deferred(const Batch& batch, float learning_rate) {
