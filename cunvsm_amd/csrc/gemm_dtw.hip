@@ -9,7 +9,7 @@
 // several pass waves retire together; gemm_dt.hip's whole-CU workgroups fare worse (NOTES_r05.md §1). So this kernel asks for the
 // least a dispatch can ask for — one wave, no LDS, no barrier, under a hundred registers — and goes wherever ONE pass wave has left:
 //   * a wave owns a 32 x 64 tile of the output (phrase columns x dx columns) over one slab of the batch (split-K; the slabs are
-//     added by the projection update, model.cpp fuse_slab_sum_, or by launch_splitk_reduce);
+//     added by the projection update, model.cpp backward_T slab_sum_in_update, or by launch_splitk_reduce);
 //   * both operands enter with the batch as the reduction dimension, i.e. transposed against the way they lie in memory. There is
 //     nothing to transpose when every lane fetches its OWN fragment elements: lane (x, kq) of v_mfma_f32_32x32x16_bf16 holds eight
 //     consecutive k of column x, which are eight dword loads a row pitch apart — 32 lanes wide each (128 B rows: whole sectors), the

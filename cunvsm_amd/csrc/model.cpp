@@ -944,28 +944,36 @@ void Model::draw_reference_negatives(const int64_t* labels, int64_t B, int64_t* 
     rng_.seed(static_cast<std::minstd_rand0::result_type>(x));          // 1 ≤ x < 2^31 − 1: seed() stores it unchanged
 }
 
+// What LossArgs and PairArgs share (kernels.h): the sigmoid clamps of the forward and the backward half — float and double mixed as
+// the reference mixes them — and 1 / d_e for the rows' mean of squares (updates_adam.cu:238-240)
+template <typename Args>
+static void fill_clamps(Args& a, bool clip_sigmoid, int de) {
+    a.sig_eps = clip_sigmoid ? 1e-7f : 0.f;
+    a.sig_hi = static_cast<float>(1.0 - static_cast<double>(a.sig_eps));
+    a.d_eps = clip_sigmoid ? 1e-6f : 0.f;
+    a.d_hi = 1.0 - static_cast<double>(a.d_eps);
+    a.inv_de = static_cast<float>(std::exp(-std::log(static_cast<double>(de))));
+}
+
 // ---------------------------------------------------------------------------------------------
 // compute_cost — cpp/objective.cu:30-313
 // ---------------------------------------------------------------------------------------------
 void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
-    const int64_t B = batch.num_instances;
-    if (B <= 0 || B > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_instances must be in (0, max_batch_size]");
-    if (!win_req_ && (!batch.features || !batch.labels)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "features and labels are required");
-    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
-    const int dw = cfg_.word_repr_size, de = cfg_.entity_repr_size, w = cfg_.window_size, k = cfg_.num_random_entities;
-    const int64_t N = B * R_;
+    forward(ForwardRequest{&batch, nullptr, entity_ids});
+}
+
+// The preamble of every forward pass: the previous result is gone, what this one is, the main stream behind whatever still reads the
+// id buffers this pass is about to rewrite, and the id buffer flipped.
+void Model::begin_forward(int mode, int64_t B, int64_t M, const nvsm_mixture* mix) {
     B_ = B;
     have_forward_ = have_grads_ = false;
     cost_valid_ = false;
     loss_reduced_ = false;
     loss_folded_ = false;
-    // a mixed forward pass (compute_cost_mixed): the pair objective rides along — its ids behind the document ids, its kernel on
-    // side stream 1 under the forward pass, its entries in the documents CSR. Nothing below differs for a text-only pass.
-    const bool mixed = pair_req_ != nullptr;
-    mode_ = mixed ? MODE_MIXED : MODE_TEXT;
-    M_ = mixed ? pair_req_->num_pairs : 0;
-    const int64_t M2 = 2 * M_;
-    RangeScope range_cc("ComputeCost");                 // cpp/main.cu:409
+    mode_ = mode;
+    M_ = M;
+    text_scale_ = mix ? mix->text_weight / (mix->text_weight + mix->pair_weight) : 1.f;      // weight / summed_weight, intermediate_results.cu:19-36
+    pair_scale_ = mix ? mix->pair_weight / (mix->text_weight + mix->pair_weight) : 1.f;
     if (cfg_.l2_normalize_entity_reprs) join_E();      // that documents update still reads ids_, which the prologue rewrites
     // The previous step's CSR builds (radix sorts on the side streams) read ids_ / widx_, which this step's prologue is
     // about to rewrite: the main stream must be behind them. In steady state both are long finished (update() / step()
@@ -980,23 +988,95 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
     }
 
     ids_p_ = (ids_p_ == ids_buf_[0].p) ? ids_buf_[1].p : ids_buf_[0].p;
-    if (mixed) stage_pairs(*pair_req_, ids_p_ + N);      // (in front of the prologue, whose completion event says "ids final")
+}
+
+// The forward pass of one request: its stages in their order. What sits between two stages here is what joins them — the events the
+// side streams follow, and the places the CSR builds may be queued at.
+void Model::forward(const ForwardRequest& req) {
+    if (!req.text()) { forward_pairs_only(req); return; }
+    const int64_t B = req.num_instances();
+    if (B <= 0 || B > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_instances must be in (0, max_batch_size]");
+    if (!req.windows && (!req.batch->features || !req.batch->labels)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "features and labels are required");
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    const int de = cfg_.entity_repr_size;
+    ForwardCall c{req};
+    c.B = B; c.N = B * R_;
+    c.Bu = exact_ ? B * cfg_.world_size : B;          // windows of the table updates
+    // a mixed forward pass (compute_cost_mixed): the pair objective rides along — its ids behind the document ids, its kernel on
+    // side stream 1 under the forward pass, its entries in the documents CSR. Nothing below differs for a text-only pass.
+    c.mixed = req.pairs != nullptr;
+    c.M2 = c.mixed ? 2 * req.pairs->num_pairs : 0;
+    RangeScope range_cc("ComputeCost");                 // cpp/main.cu:409
+    begin_forward(c.mixed ? MODE_MIXED : MODE_TEXT, B, c.mixed ? req.pairs->num_pairs : 0, req.mix);
+    if (c.mixed) stage_pairs(*req.pairs, ids_p_ + c.N);      // (in front of the prologue, whose completion event says "ids final")
     // device-sampler mode: zeroing the statistics, narrowing the word ids and drawing the document ids are one launch
-    const bool fused_prologue = !entity_ids && cfg_.sampler != NVSM_SAMPLER_HOST_MINSTD;
-    if (!fused_prologue) {
+    c.fused_prologue = !req.entity_ids && cfg_.sampler != NVSM_SAMPLER_HOST_MINSTD;
+    if (!c.fused_prologue) {
         settle_words_stamp();      // (the fused prologue sets the previous words update's stamps itself)
         NVSM_HIP_CHECK(hipMemsetAsync(stats_.p, 0, stats_.n * sizeof(double), stream_));   // Σx Σx² | loss Σdy Σdy·x̂
     }
 
-    // F1: batch → HBM (objective.cu:36-61)
+    stage_inputs(c);
+    stage_ids(c);
+
+    // Row-order (CSR) of both tables for the update, on the side streams: needs only the indices.
+    const int csr_after = tune_.csr_after;
+    if (!c.fused_prologue || exact_) NVSM_HIP_CHECK(hipEventRecord(ev_inputs_, stream_));
+    inputs_recorded_ = true;
+    // The pair kernel needs E and the pair ids only: side stream 1, behind the previous step's documents update (which ran there,
+    // or on the main stream in front of this event) and under this step's forward pass. Not where the generic loss kernel has the
+    // batch's rows of a lazily decayed table refreshed in place first (forward_loss): behind the loss kernel then.
+    c.pair_on_main = c.mixed && (debug_ || (ents_.lazy && !loss_reads_lazily(de, static_cast<int>(R_), cfg_.l2_normalize_entity_reprs != 0)));
+    if (c.mixed && !c.pair_on_main) launch_pairs(aux_stream_, ev_inputs_);
+    c.sort_layout = csr_stream_layout();
+    last_csr_layout_ = c.sort_layout;
+    c.any_lazy = words_.lazy || ents_.lazy;
+    // (a lazily decayed documents table read by the generic loss kernel is refreshed by list first: that needs the CSR now)
+    c.csr_first = csr_after == 0 || (ents_.lazy && !loss_reads_lazily(de, static_cast<int>(R_), cfg_.l2_normalize_entity_reprs != 0));
+    // NVSM_WORDS_CSR_LATE=1 (experiment): the words table's build behind the loss kernel instead of at the step's start — it is
+    // needed only behind the dx and dT products, whose MFMA-bound 0.18 ms it then runs next to, instead of next to the
+    // HBM-bound loss kernel
+    const bool words_csr_late_env = tune_.words_csr_late;
+    c.words_csr_late = words_csr_late_env && csr_after == 0 && !c.any_lazy;
+    // (the previous step's hoisted decay of the words rows without entries — see `wrds` in launch_csr_builds — wrote rows this step's word gather
+    //  may read: the main stream follows its event; issued here, in front of the builds that record the event anew)
+    if (words_untouched_pending_) { NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_untouched_, 0)); words_untouched_pending_ = false; }
+    if (c.csr_first) launch_csr_builds(c, ev_inputs_, c.words_csr_late ? 1 : 3);
+    // (lazy dense decay: the gathers below bring the rows they read up to date on the fly — LazyView — and the row passes of
+    //  the update do it for real; nothing waits for the sorts here)
+
+    forward_product(c);
+    forward_loss(c);
+
+    if (c.pair_on_main) launch_pairs(stream_, nullptr);
+    if (csr_after == 3 && !c.csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(c, ev_gathered_); }
+    if (c.words_csr_late) { NVSM_HIP_CHECK(hipEventRecord(ev_words_late_, stream_)); launch_csr_builds(c, ev_words_late_, 2); }
+    NVSM_HIP_CHECK(hipGetLastError());      // a failed launch of any kernel above surfaces here, not at the next sync
+    have_forward_ = true;
+    if (debug_) {
+        if (c.any_lazy) { NVSM_HIP_CHECK(hipStreamSynchronize(stream_)); lazy_flush_all(); }
+        debug_check(proj_.p, B * de, 2); debug_check(probs_.p, c.N, 3); debug_check(dy_.p, B * de, 4);
+        debug_check(words_.P.p, static_cast<int64_t>(words_.P.n), 7); debug_check(ents_.P.p, static_cast<int64_t>(ents_.P.n), 8);
+        debug_check(T_.p, static_cast<int64_t>(T_.n), 9);
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        raise_device_error();                // ids out of range / non-finite values are reported by the call that saw them
+    }
+}
+
+// F1: batch → HBM (objective.cu:36-61)
+void Model::stage_inputs(ForwardCall& c) {
+    const ForwardRequest& req = c.req;
+    const nvsm_window_batch* win = req.windows;
+    const int64_t B = c.B;
+    const int w = cfg_.window_size;
     const int64_t* words_dev;
     {
         PROF("h2d_batch");
-        if (batch.on_device && !win_req_) {
-            words_dev = batch.features;
-            labels_dev_ = batch.labels;
-            wwts_ = batch.feature_weights;
-            instw_ = batch.weights;
+        if (!win && req.batch->on_device) {
+            words_dev = req.batch->features;
+            labels_dev_ = req.batch->labels;
+            wwts_ = req.batch->feature_weights;
+            instw_ = req.batch->weights;
         } else {
             // Host batch: the four arrays go to the device on a copy stream of their own, into the staging set the step
             // before last used — so the copies of step k run while step k-1 is still computing (the caller, running
@@ -1006,10 +1086,10 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
             // (host sampler, device references: the host needs the labels. Read back NOW, in front of everything this step queues on
             //  the copy stream — the wait for the staging set's last reader and the expansion — so that the host waits for these
             //  2·B words only, exactly as device labels are read back in F2)
-            const bool refs_back = win_req_ && win_req_->on_device && !entity_ids && cfg_.sampler == NVSM_SAMPLER_HOST_MINSTD;
+            const bool refs_back = win && win->on_device && !req.entity_ids && cfg_.sampler == NVSM_SAMPLER_HOST_MINSTD;
             if (refs_back) {
                 host_refs_.resize(2 * B);
-                NVSM_HIP_CHECK(hipMemcpyAsync(host_refs_.data(), win_req_->refs, 2 * B * sizeof(uint32_t), hipMemcpyDeviceToHost, copy_stream_));
+                NVSM_HIP_CHECK(hipMemcpyAsync(host_refs_.data(), win->refs, 2 * B * sizeof(uint32_t), hipMemcpyDeviceToHost, copy_stream_));
                 NVSM_HIP_CHECK(hipStreamSynchronize(copy_stream_));
             }
             const int p = in_parity_ ^= 1;
@@ -1046,27 +1126,27 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
             words_dev = in_words_[p].p;
             labels_dev_ = in_labels_[p].p;
             wwts_ = nullptr; instw_ = nullptr;
-            if (win_req_) {
+            if (win) {
                 // Window references (nvsm_step_windows): the batch is not brought over, it is WRITTEN here — by a kernel that reads
                 // the references and the corpus in HBM — into the same staging set, on the same stream, behind the same wait: what
                 // is said above about the set's last reader holds word for word, and so does everything behind ev_copied_. Host
                 // references (8 B per window) come over first, by the pull or the copy engine like any array of a host batch
                 // (a slice of a page-locked plan at an odd instance offset is only 8-byte aligned: the copy engine's); device
                 // references are read in place.
-                const Corpus& c = *corpus_;
-                const uint32_t* refs_dev = win_req_->refs;
-                if (!win_req_->on_device) {
-                    bring(in_refs_[p].p, win_req_->refs, B * 2 * sizeof(uint32_t));
+                const Corpus& corp = *corpus_;
+                const uint32_t* refs_dev = win->refs;
+                if (!win->on_device) {
+                    bring(in_refs_[p].p, win->refs, B * 2 * sizeof(uint32_t));
                     launch_host_pull(pull, copy_stream_);
                     refs_dev = in_refs_[p].p;
                 }
-                if (c.with_term_weights) wwts_ = in_wwts_[p].p;
-                if (c.with_doc_weights) instw_ = in_instw_[p].p;
+                if (corp.with_term_weights) wwts_ = in_wwts_[p].p;
+                if (corp.with_doc_weights) instw_ = in_instw_[p].p;
                 WindowExpandArgs a{};
-                a.refs = refs_dev; a.tokens = c.tokens.p; a.doc_offsets = c.offsets.p;
-                a.doc_weights = c.with_doc_weights ? c.doc_weights.p : nullptr;
-                a.term_weights = c.with_term_weights ? c.term_weights.p : nullptr;
-                a.num_documents = c.num_documents; a.B = B; a.w = w;
+                a.refs = refs_dev; a.tokens = corp.tokens.p; a.doc_offsets = corp.offsets.p;
+                a.doc_weights = corp.with_doc_weights ? corp.doc_weights.p : nullptr;
+                a.term_weights = corp.with_term_weights ? corp.term_weights.p : nullptr;
+                a.num_documents = corp.num_documents; a.B = B; a.w = w;
                 a.words = in_words_[p].p; a.labels = in_labels_[p].p; a.wwts = in_wwts_[p].p; a.instw = in_instw_[p].p;
                 a.err_flag = err_host_;
                 // (timed, when the profiler is on, by an event pair that rides on the launch: the kernel's own time)
@@ -1074,45 +1154,53 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
                 if (prof.bind("window_expand", &t0, &t1)) set_launch_events(t0, t1);
                 launch_window_expand(a, copy_stream_);
             } else {
-                bring(in_words_[p].p, batch.features, B * w * sizeof(int64_t));
-                bring(in_labels_[p].p, batch.labels, B * sizeof(int64_t));
-                if (batch.feature_weights) { bring(in_wwts_[p].p, batch.feature_weights, B * w * sizeof(float)); wwts_ = in_wwts_[p].p; }
-                if (batch.weights) { bring(in_instw_[p].p, batch.weights, B * sizeof(float)); instw_ = in_instw_[p].p; }
+                bring(in_words_[p].p, req.batch->features, B * w * sizeof(int64_t));
+                bring(in_labels_[p].p, req.batch->labels, B * sizeof(int64_t));
+                if (req.batch->feature_weights) { bring(in_wwts_[p].p, req.batch->feature_weights, B * w * sizeof(float)); wwts_ = in_wwts_[p].p; }
+                if (req.batch->weights) { bring(in_instw_[p].p, req.batch->weights, B * sizeof(float)); instw_ = in_instw_[p].p; }
                 launch_host_pull(pull, copy_stream_);
             }
             NVSM_HIP_CHECK(hipEventRecord(ev_copied_, copy_stream_));
             NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_copied_, 0));
             copied_recorded_ = true;
         }
-        last_batch_on_host_ = !batch.on_device;
-        if (!fused_prologue) launch_narrow_i64(words_dev, widx_.p, B * w, cfg_.num_words, err_host_, NVSM_BAD_WORD_ID, stream_);
+        last_batch_on_host_ = !req.on_device();
+        if (!c.fused_prologue) launch_narrow_i64(words_dev, widx_.p, B * w, cfg_.num_words, err_host_, NVSM_BAD_WORD_ID, stream_);
     }
+    c.words_dev = words_dev;
+}
 
-    // F2: target + negative document ids (objective.cu:63-89 → labels.cu:4-22)
+// F2: target + negative document ids (objective.cu:63-89 → labels.cu:4-22)
+void Model::stage_ids(ForwardCall& c) {
+    const ForwardRequest& req = c.req;
+    const nvsm_window_batch* win = req.windows;
+    const int64_t B = c.B, N = c.N;
+    const int w = cfg_.window_size;
+    const int64_t* words_dev = c.words_dev;
     {
         PROF("sample_entities");
-        if (entity_ids) {
-            NVSM_HIP_CHECK(hipMemcpyAsync(in_ids64_.p, entity_ids, N * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+        if (req.entity_ids) {
+            NVSM_HIP_CHECK(hipMemcpyAsync(in_ids64_.p, req.entity_ids, N * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
             launch_narrow_i64(in_ids64_.p, ids_p_, N, cfg_.num_entities, err_host_, NVSM_BAD_ENTITY_ID, stream_);
         } else if (cfg_.sampler == NVSM_SAMPLER_HOST_MINSTD) {
             host_labels_.resize(B);
-            if (win_req_) {
+            if (win) {
                 // the labels are the references' documents (0 for a bad reference, as on the device); device references were read
                 // back in F1, in front of the expansion
-                const uint32_t* refs = win_req_->on_device ? host_refs_.data() : win_req_->refs;
+                const uint32_t* refs = win->on_device ? host_refs_.data() : win->refs;
                 const std::vector<int64_t>& off = corpus_->host_offsets;
                 for (int64_t i = 0; i < B; ++i) {
                     const int64_t d = refs[2 * i], pos = refs[2 * i + 1];
                     const bool ok = d < corpus_->num_documents && pos + w <= off[d + 1] - off[d];
                     host_labels_[i] = ok ? d : 0;
                 }
-            } else if (batch.on_device) {
+            } else if (req.batch->on_device) {
                 // device-resident labels: read back on the copy stream — the host waits for these B words only, not for
                 // whatever the main stream still has queued
-                NVSM_HIP_CHECK(hipMemcpyAsync(host_labels_.data(), batch.labels, B * sizeof(int64_t), hipMemcpyDeviceToHost, copy_stream_));
+                NVSM_HIP_CHECK(hipMemcpyAsync(host_labels_.data(), req.batch->labels, B * sizeof(int64_t), hipMemcpyDeviceToHost, copy_stream_));
                 NVSM_HIP_CHECK(hipStreamSynchronize(copy_stream_));
             } else {
-                std::memcpy(host_labels_.data(), batch.labels, B * sizeof(int64_t));
+                std::memcpy(host_labels_.data(), req.batch->labels, B * sizeof(int64_t));
             }
             // page-locked, two of them: this one was last read by the copy of the step before last (its event has long
             // fired), so the host never waits for the stream here and a deferred-loss loop stays one step ahead of the GPU
@@ -1148,98 +1236,83 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         allgather(widx_.p, xg_widx_.p, B * w * sizeof(int), stream_);
         if (wwts_) allgather(wwts_, xg_wwts_.p, B * w * sizeof(float), stream_);
     }
-    const int64_t Bu = exact_ ? B * cfg_.world_size : B;          // windows of the table updates
-    const int* csr_ids = exact_ ? xg_ids_p_ : ids_p_;
-    const int* csr_widx = exact_ ? xg_widx_.p : widx_.p;
+    c.csr_ids = exact_ ? xg_ids_p_ : ids_p_;
+    c.csr_widx = exact_ ? xg_widx_.p : widx_.p;
+}
 
-    // Row-order (CSR) of both tables for the update, on the side streams: needs only the indices.
-    const int csr_after = tune_.csr_after;
-    if (!fused_prologue || exact_) NVSM_HIP_CHECK(hipEventRecord(ev_inputs_, stream_));
-    inputs_recorded_ = true;
-    // The pair kernel needs E and the pair ids only: side stream 1, behind the previous step's documents update (which ran there,
-    // or on the main stream in front of this event) and under this step's forward pass. Not where the generic loss kernel has the
-    // batch's rows of a lazily decayed table refreshed in place first (below): behind the loss kernel then.
-    const bool pair_on_main = mixed && (debug_ || (ents_.lazy && !loss_reads_lazily(de, static_cast<int>(R_), cfg_.l2_normalize_entity_reprs != 0)));
-    if (mixed && !pair_on_main) launch_pairs(aux_stream_, ev_inputs_);
-    // two side streams: the sorts are latency-bound chains of small launches, so the two tables' builds run next to
-    // each other (at batch 4096 one behind the other they were the longest chain of the whole step)
-    // Which side stream builds which table's CSR. Side stream 1 still carries the PREVIOUS step's documents update when this
-    // step begins (it runs ~150 us into it), so a sort queued there starts late and lands on the loss kernel; side stream 2
-    // (dT GEMM + projection update of the previous step) is free by then. NVSM_SORT_LAYOUT: 0 = documents on side stream 1,
-    // words on 2 (default); 1 = both on 2, words first; 2 = both on 2, documents first; 3 = documents on 2, words on 1.
-    // The documents CSR arrays are still being read by the previous step's documents update, so a build on another stream
-    // would have to wait for it (ev_E_done_) all the same; hence the second set of CSR arrays (TableState::CsrIndex).
-    // 4 = documents on side stream 3, words on 2: neither queues behind the previous step's tails (default).
-    // Where the dT product runs on the main stream (dt_on_main(): large batches of eager tables) side stream 2 is idle for the
-    // whole step, and both builds go there one behind the other, documents first (2): the loss kernel then runs next to
-    // one sort at a time instead of two, and the words CSR is still early (NVSM shape 0.933 -> 0.911 ms, loss kernel
-    // 185 -> 176 us in-step; everywhere else 2 is 4-25 % slower than 4: interleaved A/B).
-    const int sort_layout = csr_stream_layout();
-    last_csr_layout_ = sort_layout;
-    // which: 1 = the documents table, 2 = the words table, 3 = both
-    auto launch_csr_builds = [&](hipEvent_t after, int which = 3) {
-        const int layout = aux3_stream_ ? sort_layout : (sort_layout == 4 ? 0 : sort_layout);
-        hipStream_t se = (layout == 0) ? aux_stream_ : (layout == 4 ? aux3_stream_ : aux2_stream_);
-        hipStream_t sw = (layout == 3) ? aux_stream_ : aux2_stream_;
-        if (which & 1) NVSM_HIP_CHECK(hipStreamWaitEvent(se, after, 0));
-        if (which & 2) NVSM_HIP_CHECK(hipStreamWaitEvent(sw, after, 0));
-        // (the documents table has two sets of CSR arrays: its build does not wait for the previous documents update)
-        if ((which & 1) && se != aux_stream_ && E_pending_ && ents_.idx_sets < 2) NVSM_HIP_CHECK(hipStreamWaitEvent(se, ev_E_done_, 0));
-        if (which & 1) csr_joined_ents_ = false;
-        if (which & 2) { csr_joined_words_ = false; words_csr_stream_ = sw; }
-        auto ents = [&] { { PROF_ON("csr_entities", se); build_csr(ents_, csr_ids, Bu * R_ + M2, se, M2); } NVSM_HIP_CHECK(hipEventRecord(ev_csr_ents_, se)); };
-        // (lazily decayed words table with a per-row scalar: the scalars of the rows this batch touches are brought up to date
-        //  into the snapshot the moments pass reads right here, behind the build that lists those rows — it needs nothing the
-        //  step computes, and in front of the words update it was a launch of 7 us on the critical stream)
-        auto wrds = [&] {
-            { PROF_ON("csr_words", sw); build_csr(words_, csr_widx, Bu * w, sw); }
-            if (words_.lazy && words_.lazy_scalar && tune_.early_snapshot) { lazy_scalar_snapshot(words_, csr_of(words_, Bu * w), sw); words_snapshot_early_ = true; }
-            // The fused step knows lr and λ already: the decay of the words rows WITHOUT entries (SGD / Adagrad, λ > 0, a table
-            // much larger than the batch: launch_untouched_rows) goes here, under the forward pass, instead of into the update's
-            // tail where the next step's word gather waited for it (LSE batch 4096: 16-22 us per step). Nothing of this step
-            // reads those rows; the NEXT word gather may. NVSM_HOIST_UNTOUCHED=2 (the default, tuning.h): behind the event the words
-            // update waits for, with an event of its own that the next word gather follows (the build is not lengthened by the
-            // pass's 11 us); 1: in front of that event — the main stream is then behind the pass without a wait of its own (a wait is
-            // a packet the stream stops at for 6-10 us even when the event has long fired). Mode 2 leans on `sw` being the SAME
-            // stream in consecutive steps (the next build's sort on it clears the row bounds this pass reads): the layout is a
-            // function of the batch size and the handle's switches only — checked below.
-            words_untouched_hoisted_ = false;
-            const bool hoist = hoist_untouched_ && !words_.lazy && (cfg_.update_method == NVSM_SGD || cfg_.update_method == NVSM_ADAGRAD);
-            auto hoisted_pass = [&] {
-                RowPassArgs ua = final_words_pass_args(hoist_lr_, hoist_sl_);
-                if (!launch_untouched_rows(csr_of(words_, Bu * w), ua, sw)) return false;
-                words_untouched_hoisted_ = true;
-                prof.note("untouched_words_hoisted");
-                return true;
-            };
-            if (hoist && tune_.hoist_untouched == 1) (void)hoisted_pass();
-            NVSM_HIP_CHECK(hipEventRecord(ev_csr_, sw));
-            if (hoist && tune_.hoist_untouched == 2 && words_untouched_stream_prev_ && words_untouched_stream_prev_ != sw)
-                throw Error(NVSM_ERR_STATE, "the words CSR stream changed between steps while a hoisted decay leans on it");
-            if (hoist && tune_.hoist_untouched == 2) words_untouched_stream_prev_ = sw;
-            if (hoist && tune_.hoist_untouched == 2 && hoisted_pass()) {
-                NVSM_HIP_CHECK(hipEventRecord(ev_untouched_, sw));
-                words_untouched_pending_ = true;
-            }
+// two side streams: the sorts are latency-bound chains of small launches, so the two tables' builds run next to
+// each other (at batch 4096 one behind the other they were the longest chain of the whole step)
+// Which side stream builds which table's CSR. Side stream 1 still carries the PREVIOUS step's documents update when this
+// step begins (it runs ~150 us into it), so a sort queued there starts late and lands on the loss kernel; side stream 2
+// (dT GEMM + projection update of the previous step) is free by then. NVSM_SORT_LAYOUT: 0 = documents on side stream 1,
+// words on 2 (default); 1 = both on 2, words first; 2 = both on 2, documents first; 3 = documents on 2, words on 1.
+// The documents CSR arrays are still being read by the previous step's documents update, so a build on another stream
+// would have to wait for it (ev_E_done_) all the same; hence the second set of CSR arrays (TableState::CsrIndex).
+// 4 = documents on side stream 3, words on 2: neither queues behind the previous step's tails (default).
+// Where the dT product runs on the main stream (dt_on_main(): large batches of eager tables) side stream 2 is idle for the
+// whole step, and both builds go there one behind the other, documents first (2): the loss kernel then runs next to
+// one sort at a time instead of two, and the words CSR is still early (NVSM shape 0.933 -> 0.911 ms, loss kernel
+// 185 -> 176 us in-step; everywhere else 2 is 4-25 % slower than 4: interleaved A/B).
+// which: 1 = the documents table, 2 = the words table, 3 = both
+void Model::launch_csr_builds(const ForwardCall& c, hipEvent_t after, int which) {
+    const int sort_layout = c.sort_layout, w = cfg_.window_size;
+    const int64_t Bu = c.Bu, M2 = c.M2;
+    const int* csr_ids = c.csr_ids;
+    const int* csr_widx = c.csr_widx;
+    const int layout = aux3_stream_ ? sort_layout : (sort_layout == 4 ? 0 : sort_layout);
+    hipStream_t se = (layout == 0) ? aux_stream_ : (layout == 4 ? aux3_stream_ : aux2_stream_);
+    hipStream_t sw = (layout == 3) ? aux_stream_ : aux2_stream_;
+    if (which & 1) NVSM_HIP_CHECK(hipStreamWaitEvent(se, after, 0));
+    if (which & 2) NVSM_HIP_CHECK(hipStreamWaitEvent(sw, after, 0));
+    // (the documents table has two sets of CSR arrays: its build does not wait for the previous documents update)
+    if ((which & 1) && se != aux_stream_ && E_pending_ && ents_.idx_sets < 2) NVSM_HIP_CHECK(hipStreamWaitEvent(se, ev_E_done_, 0));
+    if (which & 1) csr_joined_ents_ = false;
+    if (which & 2) { csr_joined_words_ = false; words_csr_stream_ = sw; }
+    auto ents = [&] { { PROF_ON("csr_entities", se); build_csr(ents_, csr_ids, Bu * R_ + M2, se, M2); } NVSM_HIP_CHECK(hipEventRecord(ev_csr_ents_, se)); };
+    // (lazily decayed words table with a per-row scalar: the scalars of the rows this batch touches are brought up to date
+    //  into the snapshot the moments pass reads right here, behind the build that lists those rows — it needs nothing the
+    //  step computes, and in front of the words update it was a launch of 7 us on the critical stream)
+    auto wrds = [&] {
+        { PROF_ON("csr_words", sw); build_csr(words_, csr_widx, Bu * w, sw); }
+        if (words_.lazy && words_.lazy_scalar && tune_.early_snapshot) { lazy_scalar_snapshot(words_, csr_of(words_, Bu * w), sw); words_snapshot_early_ = true; }
+        // The fused step knows lr and λ already: the decay of the words rows WITHOUT entries (SGD / Adagrad, λ > 0, a table
+        // much larger than the batch: launch_untouched_rows) goes here, under the forward pass, instead of into the update's
+        // tail where the next step's word gather waited for it (LSE batch 4096: 16-22 us per step). Nothing of this step
+        // reads those rows; the NEXT word gather may. NVSM_HOIST_UNTOUCHED=2 (the default, tuning.h): behind the event the words
+        // update waits for, with an event of its own that the next word gather follows (the build is not lengthened by the
+        // pass's 11 us); 1: in front of that event — the main stream is then behind the pass without a wait of its own (a wait is
+        // a packet the stream stops at for 6-10 us even when the event has long fired). Mode 2 leans on `sw` being the SAME
+        // stream in consecutive steps (the next build's sort on it clears the row bounds this pass reads): the layout is a
+        // function of the batch size and the handle's switches only — checked below.
+        words_untouched_hoisted_ = false;
+        const bool hoist = c.req.hoist && !words_.lazy && (cfg_.update_method == NVSM_SGD || cfg_.update_method == NVSM_ADAGRAD);
+        auto hoisted_pass = [&] {
+            RowPassArgs ua = final_words_pass_args(c.req.lr, c.req.sl);
+            if (!launch_untouched_rows(csr_of(words_, Bu * w), ua, sw)) return false;
+            words_untouched_hoisted_ = true;
+            hoisted_lr_ = c.req.lr; hoisted_sl_ = c.req.sl;
+            prof.note("untouched_words_hoisted");
+            return true;
         };
-        if (layout == 1) { if (which & 2) wrds(); if (which & 1) ents(); } else { if (which & 1) ents(); if (which & 2) wrds(); }
-        if ((which & 1) && se != aux_stream_) NVSM_HIP_CHECK(hipStreamWaitEvent(aux_stream_, ev_csr_ents_, 0));     // the documents update follows its CSR
+        if (hoist && tune_.hoist_untouched == 1) (void)hoisted_pass();
+        NVSM_HIP_CHECK(hipEventRecord(ev_csr_, sw));
+        if (hoist && tune_.hoist_untouched == 2 && words_untouched_stream_prev_ && words_untouched_stream_prev_ != sw)
+            throw Error(NVSM_ERR_STATE, "the words CSR stream changed between steps while a hoisted decay leans on it");
+        if (hoist && tune_.hoist_untouched == 2) words_untouched_stream_prev_ = sw;
+        if (hoist && tune_.hoist_untouched == 2 && hoisted_pass()) {
+            NVSM_HIP_CHECK(hipEventRecord(ev_untouched_, sw));
+            words_untouched_pending_ = true;
+        }
     };
-    const bool any_lazy = words_.lazy || ents_.lazy;
-    // (a lazily decayed documents table read by the generic loss kernel is refreshed by list first: that needs the CSR now)
-    const bool csr_first = csr_after == 0 || (ents_.lazy && !loss_reads_lazily(de, static_cast<int>(R_), cfg_.l2_normalize_entity_reprs != 0));
-    // NVSM_WORDS_CSR_LATE=1 (experiment): the words table's build behind the loss kernel instead of at the step's start — it is
-    // needed only behind the dx and dT products, whose MFMA-bound 0.18 ms it then runs next to, instead of next to the
-    // HBM-bound loss kernel
-    const bool words_csr_late_env = tune_.words_csr_late;
-    const bool words_csr_late = words_csr_late_env && csr_after == 0 && !any_lazy;
-    // (the previous step's hoisted decay of the words rows without entries — see `wrds` above — wrote rows this step's word gather
-    //  may read: the main stream follows its event; issued here, in front of the builds that record the event anew)
-    if (words_untouched_pending_) { NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_untouched_, 0)); words_untouched_pending_ = false; }
-    if (csr_first) launch_csr_builds(ev_inputs_, words_csr_late ? 1 : 3);
-    // (lazy dense decay: the gathers below bring the rows they read up to date on the fly — LazyView — and the row passes of
-    //  the update do it for real; nothing waits for the sorts here)
+    if (layout == 1) { if (which & 2) wrds(); if (which & 1) ents(); } else { if (which & 1) ents(); if (which & 2) wrds(); }
+    if ((which & 1) && se != aux_stream_) NVSM_HIP_CHECK(hipStreamWaitEvent(aux_stream_, ev_csr_ents_, 0));     // the documents update follows its CSR
+}
 
+// F3 + F5: the phrase representations and their projection
+void Model::forward_product(const ForwardCall& c) {
+    const int dw = cfg_.word_repr_size, de = cfg_.entity_repr_size, w = cfg_.window_size;
+    const int64_t B = c.B;
+    const int csr_after = tune_.csr_after;
     // F3: phrase representations (objective.cu:126-130). The previous step's dT GEMM may still be reading its phrase
     // matrix on the side stream: write the other one.
     if (T_pending_) phrase_p_ = (phrase_p_ == phrase_.p) ? phrase_alt_.p : phrase_.p;
@@ -1265,7 +1338,7 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
             if (l2p) launch_l2_rows_forward(phrase_raw_.p, B, dw, phrase_p_, phrase_norms_.p, stream_);
         });
     }
-    if (csr_after == 1 && !csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(ev_gathered_); }
+    if (csr_after == 1 && !c.csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(c, ev_gathered_); }
     if (!gather_in_product) debug_check(phrase_p_, B * dw, 0);                  // CHECK_MATRIX(*result->phrase_reprs_), objective.cu:134,141
 
     // F5: projection GEMM  pre[B][de] = phrase[B][dw] · Tt[dw][de] (+ b when no BN)   (params.cu:417-421)
@@ -1293,10 +1366,16 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
                     /*busy_chip=*/words_.lazy || ents_.lazy,       // long sorts and a long documents-update tail next to it
                     &sums_fwd_.ws, &split_fwd_);
     }
+}
 
+// F6 + F7–F16 + B1–B4: the batch statistics and the fused loss
+void Model::forward_loss(const ForwardCall& c) {
+    const int de = cfg_.entity_repr_size, k = cfg_.num_random_entities;
+    const int64_t B = c.B, Bu = c.Bu, M2 = c.M2;
+    const int csr_after = tune_.csr_after;
     const double B_global = static_cast<double>(B) * ((cfg_.world_size > 1) ? cfg_.world_size : 1);
     const double bn_n = (cfg_.world_size > 1 && cfg_.sync_batch_norm) ? B_global : static_cast<double>(B);
-    if (csr_after == 2 && !csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(ev_gathered_); }
+    if (csr_after == 2 && !c.csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(c, ev_gathered_); }
     debug_check(pre_.p, B * de, 1);                     // CHECK_MATRIX(*result->word_projections_), objective.cu:152
     // F6: batch statistics (cudnn_utils.cu:107-124), ε = 1e-4 (objective.cu:114)
     if (cfg_.batch_normalization && cfg_.world_size > 1 && cfg_.sync_batch_norm) {
@@ -1312,14 +1391,14 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         // start / stop events — the kernel's own execution time, and no record packets around it on the critical stream
         // (two plain records cost the step ~15 us). Not when the kernel already carries ev_loss_ (small batches).
         hipEvent_t prof_start = nullptr, prof_stop = nullptr;
-        const bool prof_bound = !loss_stop_event_ && stop_events_enabled() && prof.bind("loss_fused", &prof_start, &prof_stop);
+        const bool prof_bound = !c.req.loss_event && stop_events_enabled() && prof.bind("loss_fused", &prof_start, &prof_stop);
         RangeScope loss_range("loss_fused");
         if (!prof_bound) prof.begin("loss_fused", stream_);
         LossArgs a{};
         a.pre = pre_.p; a.bn_mean = bn_mean_.p; a.bn_inv_std = bn_inv_std_.p; a.bias = b_.p;
         a.bn_sums = stats_fwd_; a.bn_n = bn_n; a.bn_eps = 1e-4f;
         a.E = ents_.P.p; a.E_rows = ents_.rows; a.ids = ids_p_; a.inst_w = instw_;
-        if (mixed) {
+        if (c.mixed) {
             // the text objective's share w_te / (w_te + w_ee) (MergeGradientsFn): dy and the multipliers are linear in the instance
             // weights, so a scaled copy of them carries it; get_cost divides the loss word back
             launch_pair_scale_weights(instw_, text_scale_, instw_scaled_.p, B, stream_);
@@ -1331,16 +1410,12 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         a.bn = cfg_.batch_normalization; a.nonlinearity = cfg_.nonlinearity;
         a.l2_entity = cfg_.l2_normalize_entity_reprs;
         a.rebalance = (!cfg_.bias_negative_samples && k > 1);                                 // objective.cu:268
-        a.sig_eps = cfg_.clip_sigmoid ? 1e-7f : 0.f;                                            // :245-246
-        a.sig_hi = static_cast<float>(1.0 - static_cast<double>(a.sig_eps));
-        a.d_eps = cfg_.clip_sigmoid ? 1e-6f : 0.f;                                              // :367-368
-        a.d_hi = 1.0 - static_cast<double>(a.d_eps);
+        fill_clamps(a, cfg_.clip_sigmoid != 0, de);                                             // :245-246, :367-368
         a.inv_batch = static_cast<float>(std::exp(-std::log(B_global)));                        // :354
         a.neg_scale = static_cast<float>((static_cast<double>(static_cast<float>(k)) + 1.0) /
                                          (2.0 * static_cast<double>(static_cast<float>(k))));   // :270-273
         a.clip_min = std::nextafter(-1.0f, -1.0f - 1e-5f);                                      // cuda_utils.h:91-96
         a.clip_max = std::nextafter(1.0f, 1.0f + 1e-5f);
-        a.inv_de = static_cast<float>(std::exp(-std::log(static_cast<double>(de))));
         if (ents_.lazy) {
             if (loss_reads_lazily(a.de, a.R, a.l2_entity != 0)) a.lazyE = lazy_view(ents_);
             else {
@@ -1353,7 +1428,7 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         }
         if (loss_reads_lazily(a.de, a.R, a.l2_entity != 0) && a.R <= 17 && loss_two_row_sets(a.E_rows, a.de)) prof.note("loss_two_row_sets");
         // (the fused step at small batches starts the documents update behind the loss kernel: ev_loss_ rides on the kernel)
-        if (loss_stop_event_) { launch_and_record(loss_stop_event_, stream_, [&] { launch_loss(a, stream_); }); loss_stop_event_ = nullptr; }
+        if (c.req.loss_event) { launch_and_record(c.req.loss_event, stream_, [&] { launch_loss(a, stream_); }); }
         else if (prof_bound) {
             set_launch_events(prof_start, prof_stop);
             launch_loss(a, stream_);
@@ -1365,19 +1440,6 @@ void Model::compute_cost(const nvsm_batch& batch, const int64_t* entity_ids) {
         } else launch_loss(a, stream_);
         if (!prof_bound) prof.end(stream_);
     }
-    if (pair_on_main) launch_pairs(stream_, nullptr);
-    if (csr_after == 3 && !csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(ev_gathered_); }
-    if (words_csr_late) { NVSM_HIP_CHECK(hipEventRecord(ev_words_late_, stream_)); launch_csr_builds(ev_words_late_, 2); }
-    NVSM_HIP_CHECK(hipGetLastError());      // a failed launch of any kernel above surfaces here, not at the next sync
-    have_forward_ = true;
-    if (debug_) {
-        if (any_lazy) { NVSM_HIP_CHECK(hipStreamSynchronize(stream_)); lazy_flush_all(); }
-        debug_check(proj_.p, B * de, 2); debug_check(probs_.p, N, 3); debug_check(dy_.p, B * de, 4);
-        debug_check(words_.P.p, static_cast<int64_t>(words_.P.n), 7); debug_check(ents_.P.p, static_cast<int64_t>(ents_.P.n), 8);
-        debug_check(T_.p, static_cast<int64_t>(T_.n), 9);
-        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
-        raise_device_error();                // ids out of range / non-finite values are reported by the call that saw them
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1388,8 +1450,8 @@ void Model::compute_gradients() {
     NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
     RangeScope range_cg("ComputeGradients");            // cpp/main.cu:414
     if (mode_ == MODE_PAIRS) { have_grads_ = true; return; }      // (the pair kernel left rows, coefficients and means of squares: nothing else has a gradient)
-    backward_dx();
-    backward_T(stream_);
+    backward_dx(nullptr);
+    backward_T(stream_, false);
     NVSM_HIP_CHECK(hipGetLastError());
     have_grads_ = true;
     if (debug_) {
@@ -1400,7 +1462,7 @@ void Model::compute_gradients() {
     }
 }
 
-void Model::backward_dx() {
+void Model::backward_dx(hipStream_t dx_follower) {
     const int dw = cfg_.word_repr_size, de = cfg_.entity_repr_size, w = cfg_.window_size;
     const int64_t B = B_;
     const bool dp = cfg_.world_size > 1;
@@ -1453,7 +1515,7 @@ void Model::backward_dx() {
         if (launched) {
             // dx is final when this kernel is through: the dT GEMM of the fused step follows it (a wait on a kernel-borne event
             // must be issued right behind the launch, see below)
-            if (dx_follower_) NVSM_HIP_CHECK(hipStreamWaitEvent(dx_follower_, ev_bwdx_, 0));
+            if (dx_follower) NVSM_HIP_CHECK(hipStreamWaitEvent(dx_follower, ev_bwdx_, 0));
             if (dp) loss_reduced_ = true;
             return;
         }
@@ -1475,7 +1537,7 @@ void Model::backward_dx() {
             launch_and_record(ev_bwdx_, stream_, [&] { launched = dx_product(&bias_only); });
         }
         if (!launched) throw Error(NVSM_ERR_UNSUPPORTED, "fused backward GEMM refused a shape its caller had checked");
-        if (dx_follower_) NVSM_HIP_CHECK(hipStreamWaitEvent(dx_follower_, ev_bwdx_, 0));
+        if (dx_follower) NVSM_HIP_CHECK(hipStreamWaitEvent(dx_follower, ev_bwdx_, 0));
         if (dp && !dp_fold()) loss_reduced_ = true;
         return;
     }
@@ -1490,7 +1552,7 @@ void Model::backward_dx() {
         //  statistics instead of next to the dx GEMM. The stream that is to follow dx waits right here.)
         auto dx_final = [&](auto&& launch) {
             launch_and_record(ev_dx_, stream_, launch);
-            if (dx_follower_) NVSM_HIP_CHECK(hipStreamWaitEvent(dx_follower_, ev_dx_, 0));
+            if (dx_follower) NVSM_HIP_CHECK(hipStreamWaitEvent(dx_follower, ev_dx_, 0));
         };
         auto bn_dx = [&](double n) {
             launch_bn_dx(dy_.p, pre_.p, bn_mean_.p, bn_inv_std_.p, stats_bwd_ + 1, dbeta_.p, dgamma_.p, gb_.p, n, B, de, stream_);
@@ -1547,7 +1609,7 @@ bool Model::dp_fold() const {
 }
 
 // B6: ∂T (stored [dw][de]) = phraseᵀ[dw x B] · dx[B x de], split-K over the batch   (params.cu:526-531)
-void Model::backward_T(hipStream_t strm) {
+void Model::backward_T(hipStream_t strm, bool slab_sum_in_update) {
     const int dw = cfg_.word_repr_size, de = cfg_.entity_repr_size;
     const int64_t B = B_;
     const bool dp = cfg_.world_size > 1;
@@ -1558,7 +1620,7 @@ void Model::backward_T(hipStream_t strm) {
         const size_t stride = static_cast<size_t>(de) * dw;
         auto reduce = [&](int n) {
             // (the fused step without collectives: the projection update that follows on this stream adds the slabs up itself)
-            if (fuse_slab_sum_) { pending_slabs_ = n; prof.note("slab_sum_in_update"); return; }
+            if (slab_sum_in_update) { pending_slabs_ = n; prof.note("slab_sum_in_update"); return; }
             timed_launch(prof, "gemm_bwd_T_reduce", strm, true, [&] { launch_splitk_reduce(gT_partial_.p, n, stride, gT_.p, static_cast<int64_t>(stride), strm); });
         };
         pending_slabs_ = 0;
@@ -1906,7 +1968,7 @@ RowPassArgs Model::final_words_pass_args(float lr, float sl) {
     return a;
 }
 
-void Model::update_words(float lr, float sl) {
+void Model::update_words(float lr, float sl, hipStream_t untouched_stream) {
     const int dw = cfg_.word_repr_size, w = cfg_.window_size;
     const UpdateInputs u = update_inputs();
     const int64_t n = u.B * w;
@@ -1920,14 +1982,14 @@ void Model::update_words(float lr, float sl) {
     a.decay = sl > 0.f ? static_cast<float>(1.0 - static_cast<double>(sl) * static_cast<double>(lr)) : 1.f;
     const int method = cfg_.update_method, mode = cfg_.adam_mode;
     // (the fused step queued the decay of the rows without entries behind the CSR build already — with these very lr and λ)
-    const bool hoisted = words_untouched_hoisted_ && lr == hoist_lr_ && sl == hoist_sl_;
+    const bool hoisted = words_untouched_hoisted_ && lr == hoisted_lr_ && sl == hoisted_sl_;
     if (words_untouched_hoisted_ && !hoisted) throw Error(NVSM_ERR_STATE, "the hoisted words decay was queued with another learning rate / lambda");
     words_untouched_hoisted_ = false;
 
     if (method == NVSM_SGD) {
         a.kind = ROW_SGD; a.dense = sl > 0.f; a.untouched_done = hoisted;
         lazy_begin_update(t, a, false);
-        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, words_untouched_stream_); }
+        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, untouched_stream); }
         lazy_end_update(t, c, stream_);
         return;
     }
@@ -1937,11 +1999,11 @@ void Model::update_words(float lr, float sl) {
         // it is updated in place: rows without entries keep their value without being visited at all
         s.kind = ROW_SCALAR_ACC; s.sq_src = u.msq_w; s.dense = 0;
         s.sc_in = t.sc[t.sc_cur].p; s.sc_out = t.sc[t.sc_cur].p;
-        { PROF("adagrad_acc_words"); launch_table_pass(c, s, stream_, words_untouched_stream_); }
+        { PROF("adagrad_acc_words"); launch_table_pass(c, s, stream_, untouched_stream); }
         { PROF("adagrad_scale_words"); launch_adagrad_scale(t.sc[t.sc_cur].p, u.widx, w, u.B, 1e-6f, scale_w_.p, stream_); }
         a.kind = ROW_SGD; a.src_scale = scale_w_.p; a.dense = sl > 0.f; a.untouched_done = hoisted;
         lazy_begin_update(t, a, false);
-        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, words_untouched_stream_); }
+        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, untouched_stream); }
         lazy_end_update(t, c, stream_);
         return;
     }
@@ -1950,14 +2012,14 @@ void Model::update_words(float lr, float sl) {
     t.t += 1;
     if (mode == NVSM_ADAM_DENSE_UPDATE_DENSE_VARIANCE) {
         a.kind = ROW_ADAM_FULL; a.dense = 1; a.decay = 1.f;
-        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, words_untouched_stream_); }
+        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, untouched_stream); }
         return;
     }
     a.sq_src = u.msq_w; a.dense = 1;     // from the dx GEMM's epilogue
     a.sc_in = t.sc[t.sc_cur].p; a.sc_out = t.sc[t.sc_cur ^ 1].p;
     if (mode == NVSM_ADAM_DENSE_UPDATE) {
         a.kind = ROW_ADAM_DENSE;
-        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, words_untouched_stream_); }
+        { PROF("row_pass_words"); launch_table_pass(c, a, stream_, untouched_stream); }
         t.sc_cur ^= 1;
         return;
     }
@@ -1968,14 +2030,14 @@ void Model::update_words(float lr, float sl) {
     if (!words_snapshot_early_) lazy_scalar_snapshot(t, c, stream_);      // (else: done behind the CSR build, compute_cost)
     words_snapshot_early_ = false;
     int path;
-    { PROF("row_pass_words_mv"); path = launch_table_pass(c, a, stream_, words_untouched_stream_); }
+    { PROF("row_pass_words_mv"); path = launch_table_pass(c, a, stream_, untouched_stream); }
     if (path == TABLE_PASS_ENTRY_WALK) prof.note("entry_walk_words");
     if (!t.lazy) t.sc_cur ^= 1;
     { PROF("adam_u_words"); launch_adam_u(t.m.p, t.sc[t.sc_cur].p, dw, u.widx, w, u.B, a.bc, a.eps, U_.p, stream_); }
     RowPassArgs r = a;
     r.kind = ROW_SGD; r.X = U_.p; r.sq_src = nullptr; r.dense = sl > 0.f; r.wide = 1;
     r.nt_m = 0; r.nt_p = (nt_mask() >> 3) & 1;
-    { PROF("row_pass_words_u"); launch_table_pass(c, r, stream_, words_untouched_stream_); }
+    { PROF("row_pass_words_u"); launch_table_pass(c, r, stream_, untouched_stream); }
     lazy_end_update(t, c, stream_);
 }
 
@@ -2162,10 +2224,53 @@ void Model::update(float lr, float scaled_lambda) {
     }
     gather_update_inputs();
     update_entities(lr, scaled_lambda, stream_);
-    update_words(lr, scaled_lambda);
+    update_words(lr, scaled_lambda, nullptr);
     update_transform(lr, scaled_lambda, stream_);
     NVSM_HIP_CHECK(hipGetLastError());
     have_grads_ = false;      // gradients are consumed (the reference's optimisers overwrite them too)
+}
+
+void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, float* cost) {
+    step(ForwardRequest{&batch, nullptr, entity_ids}, lr, cost);
+}
+
+// the three calls in a row, behind the forward pass: what a step is where nothing can run next to anything
+void Model::finish_unfused(float lr, float* cost) {
+    const float sl = scaled_regularization_lambda();
+    if (lr < 0.f || sl < 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "learning_rate and lambda must be >= 0");
+    compute_gradients();
+    update(lr, sl);
+    if (cost) *cost = get_cost();
+}
+
+// The projection matrix's half of a fused step without collectives on the main stream: the dT product, then the projection update
+// on side stream 2
+void Model::step_transform_tail(float lr, float sl) {
+    // side stream 2 (behind the words CSR build): the MFMA-bound dT GEMM next to the HBM-bound words update, then the
+    // projection update; the next projection GEMM joins it
+    // (started as soon as dx is final rather than after the dx GEMM: 1.084 vs 1.100 ms per step, interleaved A/B)
+    // (the wait for ev_dx_ was issued by backward_dx, right behind the kernel that carries the event)
+    // Large batches of the eager tables: the dT product (split-bf16, gemm_dt.hip: workgroups of a whole CU's LDS and most
+    // of its registers) on the MAIN stream in front of the words update. On side stream 2 such workgroups trickle in
+    // behind the thousands of small workgroups of the two table passes (0.55 ms next to them, 0.05 ms alone) and the
+    // projection update behind them came too late for the next step; the 128 x 128-tiled fp32 kernel fits into the gaps
+    // but costs the passes 70 us of the step (a timing run without the product). In front of the passes it has the chip
+    // for 45-70 us while the documents pass starts up, and the projection update still runs on side stream 2.
+    // Interleaved A/B: NVSM shape 0.931 -> 0.921 ms, full_adam 0.850 -> 0.787; batch 25 600 0.588 -> 0.597 and
+    // |D| = 2 M 1.71 -> 1.72 the other way (the main stream is their longer chain): hence the rule. NVSM_DT_ON_MAIN=0 / 1.
+    if (dt_on_main()) {
+        // (the slab sum leaves the main stream too: the projection update on side stream 2 adds the slabs up)
+        backward_T(stream_, slab_sum_fusable());
+        NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_));
+        NVSM_HIP_CHECK(hipStreamWaitEvent(aux2_stream_, ev_gathered_, 0));
+    } else {
+        // (the slabs of the split-K product are added up by the projection update behind it on the same stream)
+        backward_T(aux2_stream_, slab_sum_fusable());      // (data parallel: the summed gradient is all-reduced first)
+    }
+    NVSM_HIP_CHECK(hipStreamWaitEvent(aux2_stream_, ev_bwdx_, 0));      // the dx GEMM is the last reader of T
+    update_transform(lr, sl, aux2_stream_);
+    NVSM_HIP_CHECK(hipEventRecord(ev_T_done_, aux2_stream_));
+    T_pending_ = true;
 }
 
 // One loop body of iterate_data (cpp/main.cu:400-444). With everything known up front the independent chains of the
@@ -2176,33 +2281,29 @@ void Model::update(float lr, float scaled_lambda) {
 //                   GEMM has read T)
 // and the two side-stream tails are joined by the NEXT compute_cost where it needs T and E (join_T / join_E), not here.
 // Results are identical to compute_cost; compute_gradients; update — only the interleaving differs.
-void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, float* cost) {
+void Model::step(const ForwardRequest& given, float lr, float* cost) {
     if (exact_) {
         // exact data-parallel tables: the table passes need every rank's loss-kernel and backward results, gathered on the main
         // stream — nothing to run next to anything: the three calls in a row
-        compute_cost(batch, entity_ids);
-        const float sl_exact = scaled_regularization_lambda();
-        if (lr < 0.f || sl_exact < 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "learning_rate and lambda must be >= 0");
-        compute_gradients();
-        update(lr, sl_exact);
-        if (cost) *cost = get_cost();
+        forward(given);
+        finish_unfused(lr, cost);
         return;
     }
+    const int64_t instances = given.num_instances();
     const bool fewer_events = tune_.fewer_events;
     const int docs_after_dx_env = tune_.docs_after_dx;
-    const bool docs_after_dx = docs_after_dx_env >= 0 ? docs_after_dx_env != 0 : batch.num_instances >= 16384;
+    const bool docs_after_dx = docs_after_dx_env >= 0 ? docs_after_dx_env != 0 : instances >= 16384;
     const bool loss_event = !(docs_after_dx && fewer_events);      // (see below)
-    loss_stop_event_ = loss_event ? ev_loss_ : nullptr;
+    ForwardRequest req = given;
+    req.loss_event = loss_event ? ev_loss_ : nullptr;
     {
         // lr and λ are known before the forward pass: parts of the update that depend on nothing else can be queued early (compute_cost)
-        const double Bg = static_cast<double>(batch.num_instances > 0 ? batch.num_instances : 1) * (cfg_.world_size > 1 ? cfg_.world_size : 1);
-        hoist_lr_ = lr; hoist_sl_ = cfg_.regularization_lambda / static_cast<float>(Bg);      // = scaled_regularization_lambda() behind compute_cost
-        if (pair_req_) hoist_sl_ = scaled_lambda_for(MODE_MIXED, batch.num_instances > 0 ? batch.num_instances : 1, pair_req_->num_pairs);
-        hoist_untouched_ = tune_.hoist_untouched != 0 && lr >= 0.f && hoist_sl_ > 0.f;
+        const double Bg = static_cast<double>(instances > 0 ? instances : 1) * (cfg_.world_size > 1 ? cfg_.world_size : 1);
+        req.lr = lr; req.sl = cfg_.regularization_lambda / static_cast<float>(Bg);      // = scaled_regularization_lambda() behind compute_cost
+        if (req.pairs) req.sl = scaled_lambda_for(MODE_MIXED, instances > 0 ? instances : 1, req.pairs->num_pairs);
+        req.hoist = tune_.hoist_untouched != 0 && lr >= 0.f && req.sl > 0.f;
     }
-    try { compute_cost(batch, entity_ids); } catch (...) { loss_stop_event_ = nullptr; hoist_untouched_ = false; words_untouched_hoisted_ = false; throw; }
-    loss_stop_event_ = nullptr;
-    hoist_untouched_ = false;
+    forward(req);
     // The caller wants this step's loss: the loss word is final behind the loss kernel, 0.3 ms into a 0.9 ms step. A copy on side
     // stream 3 behind an event recorded here lets the host read it while the backward pass and the updates still run, and
     // queue the next step in the meantime (waiting for the whole step instead — get_cost() — left the GPU idle while the host
@@ -2235,8 +2336,8 @@ void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, f
     // NVSM_DOCS_ON_MAIN (experiments): 1 = the documents update on the main stream in front of the words update, 2 = behind
     // it (two HBM-bound passes one after the other instead of next to each other)
     const int docs_on_main = tune_.docs_on_main;
-    dx_follower_ = dp ? nullptr : aux2_stream_;      // side stream 2 runs the dT GEMM as soon as dx is final
-    if (docs_after_dx || docs_on_main) backward_dx();
+    hipStream_t dx_follower = dp ? nullptr : aux2_stream_;      // side stream 2 runs the dT GEMM as soon as dx is final
+    if (docs_after_dx || docs_on_main) backward_dx(dx_follower);
     if (docs_on_main == 1) {
         NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_ents_, 0));
         update_entities(lr, sl, stream_, nullptr);
@@ -2247,41 +2348,9 @@ void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, f
         NVSM_HIP_CHECK(hipEventRecord(ev_E_done_, aux_stream_));
         E_pending_ = true;
     }
-    if (!docs_after_dx && !docs_on_main) backward_dx();
-    dx_follower_ = nullptr;
-    if (dp) {
-        backward_T(stream_);
-    } else {
-        // side stream 2 (behind the words CSR build): the MFMA-bound dT GEMM next to the HBM-bound words update, then the
-        // projection update; the next projection GEMM joins it
-        // (started as soon as dx is final rather than after the dx GEMM: 1.084 vs 1.100 ms per step, interleaved A/B)
-        // (the wait for ev_dx_ was issued by backward_dx, right behind the kernel that carries the event)
-        // Large batches of the eager tables: the dT product (split-bf16, gemm_dt.hip: workgroups of a whole CU's LDS and most
-        // of its registers) on the MAIN stream in front of the words update. On side stream 2 such workgroups trickle in
-        // behind the thousands of small workgroups of the two table passes (0.55 ms next to them, 0.05 ms alone) and the
-        // projection update behind them came too late for the next step; the 128 x 128-tiled fp32 kernel fits into the gaps
-        // but costs the passes 70 us of the step (a timing run without the product). In front of the passes it has the chip
-        // for 45-70 us while the documents pass starts up, and the projection update still runs on side stream 2.
-        // Interleaved A/B: NVSM shape 0.931 -> 0.921 ms, full_adam 0.850 -> 0.787; batch 25 600 0.588 -> 0.597 and
-        // |D| = 2 M 1.71 -> 1.72 the other way (the main stream is their longer chain): hence the rule. NVSM_DT_ON_MAIN=0 / 1.
-        if (dt_on_main()) {
-            // (the slab sum leaves the main stream too: the projection update on side stream 2 adds the slabs up)
-            fuse_slab_sum_ = slab_sum_fusable();
-            try { backward_T(stream_); } catch (...) { fuse_slab_sum_ = false; throw; }
-            fuse_slab_sum_ = false;
-            NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_));
-            NVSM_HIP_CHECK(hipStreamWaitEvent(aux2_stream_, ev_gathered_, 0));
-        } else {
-            // (the slabs of the split-K product are added up by the projection update behind it on the same stream)
-            fuse_slab_sum_ = slab_sum_fusable();      // (data parallel: the summed gradient is all-reduced first)
-            try { backward_T(aux2_stream_); } catch (...) { fuse_slab_sum_ = false; throw; }
-            fuse_slab_sum_ = false;
-        }
-        NVSM_HIP_CHECK(hipStreamWaitEvent(aux2_stream_, ev_bwdx_, 0));      // the dx GEMM is the last reader of T
-        update_transform(lr, sl, aux2_stream_);
-        NVSM_HIP_CHECK(hipEventRecord(ev_T_done_, aux2_stream_));
-        T_pending_ = true;
-    }
+    if (!docs_after_dx && !docs_on_main) backward_dx(dx_follower);
+    if (dp) backward_T(stream_, false);
+    else step_transform_tail(lr, sl);
     // The words update follows the words CSR build only. The documents build is not waited for on this stream at all: its
     // ids live in the buffer this step's prologue wrote, the next prologue writes the other one, and the step after that is
     // behind the next loss kernel, which joins this step's documents update, which followed its CSR build. (One event for
@@ -2299,9 +2368,7 @@ void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, f
     //  step's sort on that stream clears them — a pass queued on any other stream would have neither order)
     const bool words_aside = untouched_aside && !dp && !words_.lazy && words_csr_stream_ == aux2_stream_ && !words_untouched_hoisted_ &&
                              row_pass_split(csr_of(words_, B_ * cfg_.window_size));
-    words_untouched_stream_ = words_aside ? aux2_stream_ : nullptr;
-    update_words(lr, sl);
-    words_untouched_stream_ = nullptr;
+    update_words(lr, sl, words_aside ? aux2_stream_ : nullptr);
     if (words_aside) {
         NVSM_HIP_CHECK(hipEventRecord(ev_T_done_, aux2_stream_));      // (again: now it stands for the streaming decay too)
         T_pending_ = true;
@@ -2326,7 +2393,11 @@ void Model::step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, f
 }
 
 int64_t Model::step_deferred(const nvsm_batch& batch, const int64_t* entity_ids, float lr) {
-    step(batch, entity_ids, lr, nullptr);
+    return step_deferred(ForwardRequest{&batch, nullptr, entity_ids}, lr);
+}
+
+int64_t Model::step_deferred(const ForwardRequest& req, float lr) {
+    step(req, lr, nullptr);
     DeferredCost& d = deferred_[next_ticket_ % NVSM_MAX_DEFERRED];
     if (!d.host) {
         NVSM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&d.host), sizeof(double), hipHostMallocDefault));
@@ -2429,38 +2500,26 @@ void Model::corpus_upload(const nvsm_corpus* corpus) {
     corpus_ = fresh;
 }
 
-nvsm_batch Model::check_window_request(const nvsm_window_batch& wb) const {
+void Model::check_window_request(const nvsm_window_batch& wb) const {
     if (!wb.refs) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: refs");
     if (cfg_.world_size > 1) throw Error(NVSM_ERR_UNSUPPORTED, "window references are not implemented under data parallelism (world_size > 1)");
     if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "window references need a corpus: call nvsm_corpus_upload first");
     if (wb.num_instances <= 0 || wb.num_instances > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_instances must be in (0, max_batch_size]");
-    nvsm_batch b{};      // (what compute_cost and step look at: the size, and where the references live)
-    b.num_instances = wb.num_instances;
-    b.on_device = wb.on_device;
-    return b;
 }
 
 void Model::compute_cost_windows(const nvsm_window_batch& wb, const int64_t* entity_ids) {
-    const nvsm_batch b = check_window_request(wb);
-    win_req_ = &wb;
-    try { compute_cost(b, entity_ids); } catch (...) { win_req_ = nullptr; throw; }
-    win_req_ = nullptr;
+    check_window_request(wb);
+    forward(ForwardRequest{nullptr, &wb, entity_ids});
 }
 
 void Model::step_windows(const nvsm_window_batch& wb, const int64_t* entity_ids, float lr, float* cost) {
-    const nvsm_batch b = check_window_request(wb);
-    win_req_ = &wb;
-    try { step(b, entity_ids, lr, cost); } catch (...) { win_req_ = nullptr; throw; }
-    win_req_ = nullptr;
+    check_window_request(wb);
+    step(ForwardRequest{nullptr, &wb, entity_ids}, lr, cost);
 }
 
 int64_t Model::step_windows_deferred(const nvsm_window_batch& wb, const int64_t* entity_ids, float lr) {
-    const nvsm_batch b = check_window_request(wb);
-    win_req_ = &wb;
-    int64_t ticket;
-    try { ticket = step_deferred(b, entity_ids, lr); } catch (...) { win_req_ = nullptr; throw; }
-    win_req_ = nullptr;
-    return ticket;
+    check_window_request(wb);
+    return step_deferred(ForwardRequest{nullptr, &wb, entity_ids}, lr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2543,13 +2602,9 @@ void Model::launch_pairs(hipStream_t strm, hipEvent_t after) {
     a.probs = pair_probs_.p; a.mults = pair_mults_.p;
     a.loss_acc = pair_loss_.p; a.sums = sums_pair_.ws;
     a.M = M_; a.de = de;
-    a.sig_eps = cfg_.clip_sigmoid ? 1e-7f : 0.f;                                            // objective.cu:546-550
-    a.sig_hi = static_cast<float>(1.0 - static_cast<double>(a.sig_eps));
-    a.d_eps = cfg_.clip_sigmoid ? 1e-6f : 0.f;                                              // :622-623
-    a.d_hi = 1.0 - static_cast<double>(a.d_eps);
+    fill_clamps(a, cfg_.clip_sigmoid != 0, de);                                             // objective.cu:546-550, :622-623
     a.inv_batch = static_cast<float>(std::exp(-std::log(static_cast<double>(M_))));         // :609
     a.scale = pair_scale_;
-    a.inv_de = static_cast<float>(std::exp(-std::log(static_cast<double>(de))));             // updates_adam.cu:238-240
     timed_launch(prof, "pair_loss", strm, /*single=*/true, [&] { launch_pair_loss(a, strm); });
     NVSM_HIP_CHECK(hipEventRecord(ev_pair_, strm));
     pair_stream_ = strm;
@@ -2560,29 +2615,15 @@ void Model::compute_cost_mixed(const nvsm_batch* text, const int64_t* entity_ids
     check_pair_request(text, pairs, mix);
     NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
     ensure_pair_workspace();
-    if (text) {
-        text_scale_ = mix->text_weight / (mix->text_weight + mix->pair_weight);      // weight / summed_weight, intermediate_results.cu:19-36
-        pair_scale_ = mix->pair_weight / (mix->text_weight + mix->pair_weight);
-        pair_req_ = &pairs;
-        try { compute_cost(*text, entity_ids); } catch (...) { pair_req_ = nullptr; throw; }
-        pair_req_ = nullptr;
-        return;
-    }
-    // the pair objective alone: ids -> CSR -> kernel on the main stream; no other parameter is read or written
+    forward(ForwardRequest{text, nullptr, text ? entity_ids : nullptr, &pairs, text ? mix : nullptr});
+}
+
+// the pair objective alone: ids -> CSR -> kernel on the main stream; no other parameter is read or written
+void Model::forward_pairs_only(const ForwardRequest& req) {
     RangeScope range_cc("ComputeCost");
-    have_forward_ = have_grads_ = false;
-    cost_valid_ = false;
-    loss_reduced_ = false; loss_folded_ = false;
-    mode_ = MODE_PAIRS; M_ = pairs.num_pairs; B_ = 0;
-    text_scale_ = 1.f; pair_scale_ = 1.f;
-    if (inputs_recorded_) {      // the previous CSR builds read the id buffers (compute_cost)
-        if (!csr_joined_ents_) NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_ents_, 0));
-        if (!csr_joined_words_) NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_, 0));
-        csr_joined_ents_ = csr_joined_words_ = true;
-    }
+    begin_forward(MODE_PAIRS, 0, req.pairs->num_pairs, nullptr);
     join_E();      // the previous documents update: reads the rows / coefficients this pass rewrites, writes E
-    ids_p_ = (ids_p_ == ids_buf_[0].p) ? ids_buf_[1].p : ids_buf_[0].p;
-    stage_pairs(pairs, ids_p_);
+    stage_pairs(*req.pairs, ids_p_);
     NVSM_HIP_CHECK(hipEventRecord(ev_inputs_, stream_));
     inputs_recorded_ = true;
     last_batch_on_host_ = false;
@@ -2604,18 +2645,10 @@ void Model::step_mixed(const nvsm_batch* text, const int64_t* entity_ids, const 
     ensure_pair_workspace();
     if (!text) {
         compute_cost_mixed(nullptr, nullptr, pairs, nullptr);
-        const float sl = scaled_regularization_lambda();
-        if (lr < 0.f || sl < 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "learning_rate and lambda must be >= 0");
-        compute_gradients();
-        update(lr, sl);
-        if (cost) *cost = get_cost();
+        finish_unfused(lr, cost);
         return;
     }
-    text_scale_ = mix->text_weight / (mix->text_weight + mix->pair_weight);
-    pair_scale_ = mix->pair_weight / (mix->text_weight + mix->pair_weight);
-    pair_req_ = &pairs;
-    try { step(*text, entity_ids, lr, cost); } catch (...) { pair_req_ = nullptr; throw; }
-    pair_req_ = nullptr;
+    step(ForwardRequest{text, nullptr, entity_ids, &pairs, mix}, lr, cost);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -192,10 +192,10 @@ class Model {
     void build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s, int64_t n_pair_entries = 0);
     void alloc_table_csr(TableState& t, int64_t max_entries, bool chunk_order);
     Csr csr_of(TableState& t, int64_t n);
-    void backward_dx();                                  // B5, B7, B9 on the main stream
-    void backward_T(hipStream_t s);                      // B6 (+ its all-reduce)
+    void backward_dx(hipStream_t dx_follower);           // B5, B7, B9 on the main stream; dx_follower (or null): the stream that waits for dx
+    void backward_T(hipStream_t s, bool slab_sum_in_update);      // B6 (+ its all-reduce); true: the slab sum is left to the projection update behind it
     void update_entities(float lr, float sl, hipStream_t s, hipEvent_t row_pass_after = nullptr);
-    void update_words(float lr, float sl);
+    void update_words(float lr, float sl, hipStream_t untouched_stream);      // (kernels.h launch_table_pass untouched_s; null: the main stream)
     void update_transform(float lr, float sl, hipStream_t s);
     void allreduce_f64(double* dev, int64_t n);
     void allreduce_f32(float* dev, int64_t n, hipStream_t s);
@@ -206,19 +206,79 @@ class Model {
     void lazy_begin_update(TableState& t, RowPassArgs& a, bool scalar_pingpong);
     void lazy_end_update(TableState& t, const Csr& c, hipStream_t s);
     RowPassArgs final_words_pass_args(float lr, float sl);
-    bool hoist_untouched_ = false;        // step() -> compute_cost: queue the words rows-without-entries decay behind the CSR build
-    float hoist_lr_ = 0.f, hoist_sl_ = 0.f;
-    bool words_untouched_hoisted_ = false;      // ... done for this step's update
-    bool words_untouched_pending_ = false;      // ... and not yet followed by the main stream (the next word gather does)
     hipEvent_t ev_untouched_ = nullptr;
     void settle_words_stamp();            // the words table's pending stamps, now (see lazy_end_update)
     bool words_stamp_pending_ = false;    // the last words update's stamps have not been set yet
     int64_t words_stamp_n_ = 0;           //   ... entries of that update's CSR
-    bool words_snapshot_early_ = false;   // this step's words scalar snapshot was taken behind the CSR build
     void raise_device_error();             // throws when a kernel has flagged bad ids / non-finite values since the last check
     void debug_check(const float* x, int64_t n, int which);
     void alloc_table(TableState& t, int64_t rows, int dim, int64_t max_entries);
     float adam_bc(uint64_t t) const;
+
+    // ---- one call's request. Built on the public method's stack and passed down by const reference: nothing a call is asked to do
+    // lives in a member, so nothing has to be cleared again when the call returns or throws.
+    struct ForwardRequest {
+        const nvsm_batch* batch = nullptr;              // the text batch, or
+        const nvsm_window_batch* windows = nullptr;     // ... the window references F1 expands into one (neither: the pair objective alone)
+        const int64_t* entity_ids = nullptr;
+        const nvsm_pair_batch* pairs = nullptr;         // the pair objective rides along (or stands alone)
+        const nvsm_mixture* mix = nullptr;              // ... with these shares
+        // what only a fused step knows up front
+        hipEvent_t loss_event = nullptr;                // the loss kernel carries it as its completion event
+        bool hoist = false;                             // queue the decay of the words rows without entries behind the CSR build,
+        float lr = 0.f, sl = 0.f;                       // ... with this learning rate and scaled lambda
+        bool text() const { return batch || windows; }
+        int64_t num_instances() const { return windows ? windows->num_instances : batch->num_instances; }
+        bool on_device() const { return (windows ? windows->on_device : batch->on_device) != 0; }
+    };
+    // what the stages of one forward pass share: filled by forward() and by the stage that produces the value, never a member
+    struct ForwardCall {
+        const ForwardRequest& req;
+        int64_t B = 0, N = 0, M2 = 0;                   // windows, document ids (B * R), pair ids (2 M) of this rank
+        int64_t Bu = 0;                                 // windows of the table updates (exact tables: of all ranks)
+        bool mixed = false, fused_prologue = false;
+        int sort_layout = 0;
+        bool any_lazy = false, csr_first = false, words_csr_late = false, pair_on_main = false;
+        const int64_t* words_dev = nullptr;             // F1: the word ids in HBM
+        const int* csr_ids = nullptr;                   // F2: the ids the CSR builds sort (exact tables: the gathered ones)
+        const int* csr_widx = nullptr;
+    };
+    void forward(const ForwardRequest& req);
+    void step(const ForwardRequest& req, float lr, float* cost);
+    int64_t step_deferred(const ForwardRequest& req, float lr);
+    void finish_unfused(float lr, float* cost);         // compute_gradients; update(scaled lambda); get_cost — behind a forward pass
+    void step_transform_tail(float lr, float sl);       // a fused step's dT product and projection update (side stream 2)
+    // the stages of forward(), in its order
+    void begin_forward(int mode, int64_t B, int64_t M, const nvsm_mixture* mix);      // the preamble (shared with the pairs-only pass)
+    void forward_pairs_only(const ForwardRequest& req);
+    void stage_inputs(ForwardCall& c);                  // F1
+    void stage_ids(ForwardCall& c);                     // F2
+    void launch_csr_builds(const ForwardCall& c, hipEvent_t after, int which = 3);
+    void forward_product(const ForwardCall& c);         // F3 + F5
+    void forward_loss(const ForwardCall& c);            // F6 + the loss launch
+
+    // ---- state carried from one call to the next (everything else a call needs is in its ForwardRequest / ForwardCall)
+    //   item                              written by                                      consumed by
+    //   words_untouched_hoisted_          launch_csr_builds (a fused step's hoisted pass)  update_words of the same step (skips that pass)
+    //   hoisted_lr_, hoisted_sl_          ... with the values the pass was queued with     update_words: other values are NVSM_ERR_STATE
+    //   words_untouched_pending_          launch_csr_builds (hoist_untouched == 2)         the next forward(): the main stream follows ev_untouched_
+    //   words_untouched_stream_prev_      launch_csr_builds (hoist_untouched == 2)         the next launch_csr_builds: the words CSR stream must not change
+    //   words_snapshot_early_             launch_csr_builds (lazy words, scalar state)     update_words: the snapshot is taken already
+    //   words_tail_pending_               step (streaming decay on side stream 2)          the next forward_product: join_T in front of the word gather
+    //   E_pending_, T_pending_            step (side-stream tails not yet joined)          join_E / join_T; forward_product (which phrase matrix to write)
+    //   last_csr_layout_                  forward                                          the next stage_inputs (host-batch copies lean on it)
+    // A call that throws half way leaves these as they are, which is what they mean: the *_pending_ flags name work that IS queued, and
+    // so does words_untouched_hoisted_ — the next words CSR build resets it. Where a forward pass throws behind its launches and leaves
+    // have_forward_ set (NVSM_DEBUG: raise_device_error), compute_gradients; update on that pass skip the decay that is queued already,
+    // and another lr / lambda is NVSM_ERR_STATE. (step() used to clear the flag on that path; the decay would then have run twice.)
+    bool words_untouched_hoisted_ = false;      // the decay of the words rows without entries is queued behind the CSR build already
+    float hoisted_lr_ = 0.f, hoisted_sl_ = 0.f;
+    bool words_untouched_pending_ = false;      // ... and not yet followed by the main stream (the next word gather does)
+    hipStream_t words_untouched_stream_prev_ = nullptr;      // the stream the hoisted words decay of the last step ran on (hoist_untouched == 2)
+    bool words_snapshot_early_ = false;   // this step's words scalar snapshot was taken behind the CSR build
+    bool words_tail_pending_ = false;                   // side stream 2 still decays words rows: the next word gather joins it
+    bool E_pending_ = false, T_pending_ = false;      // side-stream tails of the last nvsm_step not yet joined
+    int last_csr_layout_ = -1;          // the layout of the previous step's builds (host-batch copies lean on it)
 
     Tuning tune_;                     // the switches of this handle: read from the environment once, by the constructor (tuning.h)
     nvsm_config cfg_;
@@ -239,10 +299,6 @@ class Model {
     hipEvent_t ev_cost_ready_ = nullptr, ev_cost_copied_ = nullptr;      // step(cost): the loss word copied out behind the loss kernel
     double* cost_host_ = nullptr;                                         // ... into this page-locked word
     hipStream_t words_csr_stream_ = nullptr;            // the side stream that built this step's words CSR (NVSM_SORT_LAYOUT)
-    hipStream_t words_untouched_stream_ = nullptr;      // set by step() around update_words (kernels.h launch_table_pass untouched_s)
-    bool words_tail_pending_ = false;                   // side stream 2 still decays words rows: the next word gather joins it
-    hipStream_t dx_follower_ = nullptr;                 // set by step(): the stream that waits for ev_dx_ (issued inside backward_dx)
-    hipEvent_t loss_stop_event_ = nullptr;      // set by step(): the loss kernel of this compute_cost carries it as its completion event
     std::minstd_rand0 rng_;           // include/cuNVSM/base.h:36
     uint64_t device_seed_ = 1, step_count_ = 0;
 
@@ -278,7 +334,6 @@ class Model {
     DevBuf<float> phrase_raw_, phrase_norms_, ge_msq_;      // optional L2 normalisers: cached raw phrase means + norms; per-entry mean of squares
     DevBuf<float> phrase_alt_;            // second phrase matrix (see compute_cost)
     float* phrase_p_ = nullptr;           // the one the current forward result lives in
-    bool E_pending_ = false, T_pending_ = false;      // side-stream tails of the last nvsm_step not yet joined
     DevBuf<float> phrase_, pre_, proj_, dy_, gphrase_, coef_, probs_, pp_, msq_w_, msq_parts_, U_, scale_w_, grad_entity_;
     DevBuf<double> stats_;                   // [2 de | 1 + 2 de] = Σx Σx² | loss Σdy Σdy·x̂ — written by the ordered grid sums
     // workspaces of those sums (kernels.h GridSumWs): projection GEMM epilogue / loss kernel
@@ -287,8 +342,7 @@ class Model {
     // the projection matrix cut into bf16 planes for the split-bf16 GEMM (gemm_split.hip), in the forward and the backward
     // product's layout; `ready` is cleared by everything that writes T
     DevBuf<char> planes_fwd_, planes_bwd_, rplanes_fwd_, rplanes_bwd_;
-    bool fuse_slab_sum_ = false;         // step(): backward_T leaves the slab sum to the projection update behind it
-    int pending_slabs_ = 0;              //   ... that many slabs in gT_partial_
+    int pending_slabs_ = 0;              // backward_T left the slab sum to the projection update behind it: that many slabs in gT_partial_
     void planes_stale();                 // T changed: every set of planes is out of date
     GemmSplitWs split_fwd_{}, split_bwd_{};
     void cut_transform_planes(hipStream_t strm);
@@ -298,10 +352,8 @@ class Model {
     bool use_dtw_at(int64_t B) const;    // ... on the wave-sized kernel (gemm_dtw.hip: per-rank batches)
     int csr_stream_layout() const;
     bool slab_sum_fusable() const;     // the projection update's own slab sum is launch_splitk_reduce's (vector order, alignment)
-    hipStream_t words_untouched_stream_prev_ = nullptr;      // the stream the hoisted words decay of the last step ran on (hoist_untouched == 2)
     bool dp_fold() const;              // data parallel: [db | loss] ride on the dT all-reduce (one collective per step)
     bool gather_fused_at(int64_t B) const;      // the forward product at this batch size forms the phrase rows itself
-    int last_csr_layout_ = -1;          // the layout of the previous step's builds (host-batch copies lean on it)
     void alloc_sums(SumsBufs& b, int colgroups, int contrib_cap, int width_cap);
     bool csr_joined_words_ = true, csr_joined_ents_ = true;      // the main stream is behind the current CSR builds
     double* stats_fwd_ = nullptr;
@@ -324,8 +376,7 @@ class Model {
     enum { MODE_TEXT = 0, MODE_PAIRS = 1, MODE_MIXED = 2 };
     int mode_ = MODE_TEXT;                      // what the current forward result is
     int64_t M_ = 0;                             // its pairs
-    float text_scale_ = 1.f, pair_scale_ = 1.f; // w / (w_te + w_ee) (MergeGradientsFn, cpp/intermediate_results.cu:19-38)
-    const nvsm_pair_batch* pair_req_ = nullptr; // set around compute_cost by compute_cost_mixed: this forward pass is a mixed one
+    float text_scale_ = 1.f, pair_scale_ = 1.f; // w / (w_te + w_ee) (MergeGradientsFn, cpp/intermediate_results.cu:19-38): set by begin_forward
     bool pairs_ready_ = false;
     DevBuf<int64_t> pair_ids64_;
     DevBuf<float> pair_w_, pair_probs_, pair_mults_, instw_scaled_;
@@ -360,8 +411,7 @@ class Model {
     Corpus* corpus_ = nullptr;
     DevBuf<uint32_t> in_refs_[2];               // host references, one per staging set
     std::vector<uint32_t> host_refs_;           // host sampler: device references read back
-    const nvsm_window_batch* win_req_ = nullptr;      // set around compute_cost by the *_windows calls: F1 expands these references
-    nvsm_batch check_window_request(const nvsm_window_batch& wb) const;      // the checks; the nvsm_batch that stands for it in compute_cost
+    void check_window_request(const nvsm_window_batch& wb) const;
 
     // ranking scratch: allocated by the first infer / rank call (training-only handles never pay for it), grown on demand
     struct RankScratch {
