@@ -18,6 +18,10 @@ SAMPLER_HOST_MINSTD, SAMPLER_DEVICE = 0, 1
 SIM_COSINE, SIM_DOT = 0, 1
 SPACE_WORDS, SPACE_PROJECTED_WORDS, SPACE_ENTITIES = 0, 1, 2
 ACT_MODEL, ACT_IDENTITY = -1, -2
+LEX_JM, LEX_DIRICHLET = 0, 1
+NORM_STANDARDIZE, NORM_MINMAX, NORM_NONE = 0, 1, 2
+LEXICAL_MAX_QUERY_TERMS = 1024
+ENSEMBLE_MAX_TOP_K = 1024
 
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "DEVICE", 4: "STATE", 5: "NO_DEVICE"}
 
@@ -92,6 +96,14 @@ class NvsmJudgments(C.Structure):
         ("doc_ids", C.c_void_p), ("grades", C.c_void_p), ("offsets", C.c_void_p), ("cutoffs", C.c_void_p),
         ("num_cutoffs", C.c_int32), ("reserved", C.c_int32 * 3),
     ]
+
+
+class NvsmLexicalOptions(C.Structure):
+    _fields_ = [("method", C.c_int32), ("param", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class NvsmEnsembleOptions(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("normalizer", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
 class NvsmNeighborQueries(C.Structure):
@@ -254,6 +266,11 @@ def lib():
         "nvsm_infer": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp]),
         "nvsm_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), vp, vp, vp]),
         "nvsm_evaluate": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmJudgments), vp, vp, vp, vp]),
+        "nvsm_lexical_options_default": (None, [P(NvsmLexicalOptions)]),
+        "nvsm_ensemble_options_default": (None, [P(NvsmEnsembleOptions)]),
+        "nvsm_lexical_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), vp, vp, vp]),
+        "nvsm_rank_ensemble": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmEnsembleOptions),
+                                         P(NvsmJudgments), vp, vp, vp, vp]),
         "nvsm_neighbor_options_default": (None, [P(NvsmNeighborOptions)]),
         "nvsm_neighbors": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNeighborOptions), vp, vp, vp]),
         "nvsm_similarity": (C.c_int, [vp, C.c_int32, vp, vp, i64, C.c_int32, vp]),

@@ -321,6 +321,31 @@ int nvsm_evaluate(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_op
     return guarded_on(m, [&] { m->impl.evaluate(*queries, *opt, *judgments, metrics, doc_ids, scores, counts); });
 }
 
+void nvsm_lexical_options_default(nvsm_lexical_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->method = NVSM_LEX_JM; o->param = 0.f; o->top_k = 1000;
+}
+void nvsm_ensemble_options_default(nvsm_ensemble_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->alpha = 0.5f; o->normalizer = NVSM_NORM_STANDARDIZE;
+}
+int nvsm_lexical_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, int64_t* doc_ids, float* scores,
+                      int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(lex); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.lexical_rank(*queries, *lex, doc_ids, scores, counts); });
+}
+int nvsm_rank_ensemble(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                       const nvsm_ensemble_options* ens, const nvsm_judgments* judgments, double* metrics, int64_t* doc_ids,
+                       float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(rank_opt); NVSM_REQUIRE(lex); NVSM_REQUIRE(ens);
+    NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    if (judgments) NVSM_REQUIRE(metrics);
+    if (metrics) NVSM_REQUIRE(judgments);
+    return guarded_on(m, [&] { m->impl.rank_ensemble(*queries, *rank_opt, *lex, *ens, judgments, metrics, doc_ids, scores, counts); });
+}
+
 void nvsm_neighbor_options_default(nvsm_neighbor_options* o) {
     if (!o) return;
     std::memset(o, 0, sizeof(*o));

@@ -529,5 +529,35 @@ struct EvalArgs {
 };
 void launch_eval_metrics(const EvalArgs& a, int Q, hipStream_t s);
 
+// ---- query-likelihood ranking over the resident corpus, and run fusion (lexical.hip; include/cunvsm_amd.h nvsm_lexical_rank /
+// nvsm_rank_ensemble) ----
+constexpr int kLexSlots = 1024;            // distinct query terms of a round: 4 KiB of LDS counters per workgroup
+constexpr int kFuseMaxTopK = 1024;         // fuse_lists_kernel: 2 k entries x 20 B of LDS (NVSM_ENSEMBLE_MAX_TOP_K)
+void launch_lex_cf(const int* tokens, int64_t n, unsigned long long* cf, hipStream_t s);      // cf[t] += occurrences; cf zeroed by the caller
+void launch_lex_fill_int(int* p, int64_t n, int v, hipStream_t s);
+// slot_of[terms[i]] = i (set) or -1 (clear), i < n; the terms are distinct
+void launch_lex_set_slots(int* slot_of, const int* terms, int n, bool set, hipStream_t s);
+// scores[q][d - d0] for q < Q, d in [d0, d0 + S): Σ over the query's terms j in [qoff[q], qoff[q + 1]) — in that order, fp64, narrowed
+// once — of log((1 − param)·tf/len + c0[j]) (NVSM_LEX_JM) or log((tf + c0[j]) / (len + param)) (NVSM_LEX_DIRICHLET); -inf when no
+// term of q occurs in d. tslot[j]: the term's slot < num_slots <= kLexSlots; base[j] = log(c0[j]).
+struct LexScoreArgs {
+    const int* tokens; const int64_t* doc_offsets; const int* slot_of;
+    int64_t d0; int S; int Q; int num_slots; int method; double param;
+    const int* qoff; const int* tslot; const double* c0; const double* base;
+    float* scores; int64_t ld;
+};
+void launch_lex_score(const LexScoreArgs& a, hipStream_t s);
+// launch_rank_write for keys that may carry -inf scores: ids / scores [Q][k] up to the first -inf or padding key, counts [Q] likewise
+void launch_lex_write(const unsigned long long* keys, int64_t npad, int Q, int k, int64_t n_all, int64_t* ids, float* scores,
+                      int64_t* counts, hipStream_t s);
+// two ranked lists [Q][k] (+ counts) -> their fused list [Q][2 k] (+ counts); npad: a power of two >= 2 k; k <= kFuseMaxTopK
+struct FuseArgs {
+    const int64_t* ids_a; const float* scores_a; const int64_t* counts_a;
+    const int64_t* ids_b; const float* scores_b; const int64_t* counts_b;
+    int k; int npad; float alpha; int normalizer;
+    int64_t* out_ids; float* out_scores; int64_t* out_counts;
+};
+void launch_fuse_lists(const FuseArgs& a, int Q, hipStream_t s);
+
 
 }  // namespace cunvsm

@@ -1,0 +1,273 @@
+// gfx950 kernels of query-likelihood ranking over the HBM-resident corpus and of run fusion (include/cunvsm_amd.h
+// nvsm_lexical_rank / nvsm_rank_ensemble; kernels.h "lexical").
+//
+//   lex_cf_kernel         cf(t): one histogram pass over the token arena. Integer atomics: their sum does not depend on their order.
+//   lex_set_slots_kernel  term -> slot table of num_words ints: set for a round's distinct remaining query terms, cleared behind it
+//   lex_score_kernel      scores[q][d - d0] of one slab of documents, the slab layout of launch_rank_scan. One workgroup per
+//                         document at a time, grid-strided: the document's tokens are read coalesced, every token's slot is looked
+//                         up (the table is L2-resident), hits are counted into an LDS tf[slot] array with LDS integer adds; behind
+//                         a barrier a fixed lane visits the terms of one query IN QUERY ORDER, adds their logs in fp64 in that order
+//                         and stores the sum narrowed to fp32, -inf when no term of the query occurs in the document. Then the
+//                         counters are zeroed. A document longer than the workgroup is looped over.
+//   lex_write_kernel      launch_rank_write for slabs that hold -inf entries: what is retrieved ends at the first -inf
+//   fuse_lists_kernel     one workgroup per query: normalises two ranked lists over their returned entries, matches the documents
+//                         both hold by a bitonic sort of (id, list, position) keys, computes the fused fp64 scores and sorts
+//                         (fused score, id)
+// No float atomics anywhere: a repeated call returns the same bits. All arena offsets are 64-bit.
+//
+// Arithmetic of a term: fp64 throughout (allowed by the contract, and the accurate log the contract asks for). With tf = 0 — nearly
+// every (document, term) pair — the term is base[j] − log(den), base[j] = log(c0[j]) evaluated once per term by the host and
+// log(den) once per document: no log per pair.
+#include <cmath>
+#include <cstdint>
+#include "../../include/cunvsm_amd.h"
+#include "kernels.h"
+#include "device_utils.h"
+
+namespace cunvsm {
+
+namespace {
+
+__global__ __launch_bounds__(256) void lex_cf_kernel(const int* __restrict__ tokens, int64_t n, unsigned long long* __restrict__ cf) {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) atomicAdd(&cf[tokens[i]], 1ull);
+}
+
+__global__ __launch_bounds__(256) void lex_fill_int_kernel(int* __restrict__ p, int64_t n, int v) {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) p[i] = v;
+}
+
+// slot_of[terms[i]] = i (set) or -1 (clear); the terms are distinct
+__global__ __launch_bounds__(256) void lex_set_slots_kernel(int* __restrict__ slot_of, const int* __restrict__ terms, int n, int set) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) slot_of[terms[i]] = set ? i : -1;
+}
+
+__global__ __launch_bounds__(256) void lex_score_kernel(LexScoreArgs a) {
+    __shared__ int tf[kLexSlots];
+    for (int i = threadIdx.x; i < kLexSlots; i += 256) tf[i] = 0;
+    __syncthreads();
+    for (int64_t d = a.d0 + blockIdx.x; d < a.d0 + a.S; d += gridDim.x) {
+        const int64_t lo = a.doc_offsets[d], hi = a.doc_offsets[d + 1];
+        for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+            const int slot = a.slot_of[a.tokens[i]];
+            if (slot >= 0) atomicAdd(&tf[slot], 1);
+        }
+        __syncthreads();
+        const double len = static_cast<double>(hi - lo);
+        // JM: log((1 − λ)·tf/len + λ·p);  Dirichlet: log((tf + μ·p) / (len + μ)).  c0 = λ·p or μ·p, base = log(c0)
+        const double log_den = a.method == NVSM_LEX_DIRICHLET ? log(len + a.param) : 0.0;
+        const double jm_scale = hi > lo ? (1.0 - a.param) / len : 0.0;
+        for (int q = threadIdx.x; q < a.Q; q += 256) {
+            double sum = 0.0;
+            bool any = false;
+            for (int j = a.qoff[q]; j < a.qoff[q + 1]; ++j) {
+                const int t = tf[a.tslot[j]];
+                if (t > 0) {
+                    any = true;
+                    sum += a.method == NVSM_LEX_DIRICHLET ? log((static_cast<double>(t) + a.c0[j]) / (len + a.param))
+                                                          : log(jm_scale * static_cast<double>(t) + a.c0[j]);
+                } else {
+                    sum += a.base[j] - log_den;
+                }
+            }
+            a.scores[static_cast<size_t>(q) * a.ld + (d - a.d0)] = any ? static_cast<float>(sum) : -__builtin_inff();
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < a.num_slots; i += 256) tf[i] = 0;
+        __syncthreads();
+    }
+}
+
+// the sorted keys of a query as (id, score) up to the first -inf score; (-1, -inf) behind it. A key 0 is a padding key.
+__global__ __launch_bounds__(256) void lex_write_kernel(const unsigned long long* __restrict__ keys, int64_t npad, int k, int64_t n_all,
+                                                        int64_t* __restrict__ ids, float* __restrict__ scores, int64_t* __restrict__ counts) {
+    const int q = blockIdx.y;
+    const unsigned long long* g = keys + static_cast<size_t>(q) * npad;
+    const int most = static_cast<int>(n_all < k ? n_all : k);
+    constexpr unsigned kNegInf = 0x007fffffu;      // rank_key(-inf): below the key of every finite score
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (most == 0 || static_cast<unsigned>(g[0] >> 32) <= kNegInf)) counts[q] = 0;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < k; i += gridDim.x * 256) {
+        const size_t o = static_cast<size_t>(q) * k + i;
+        const unsigned long long key = i < most ? g[i] : 0ull;
+        const unsigned u = static_cast<unsigned>(key >> 32);
+        if (u > kNegInf) {
+            ids[o] = static_cast<int64_t>(0xffffffffu - static_cast<unsigned>(key & 0xffffffffull));
+            scores[o] = __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+            // the last retrieved entry names the count (the keys are sorted: what is retrieved is a prefix)
+            if (i + 1 == most || static_cast<unsigned>(g[i + 1] >> 32) <= kNegInf) counts[q] = i + 1;
+        } else {
+            ids[o] = -1;
+            scores[o] = -__builtin_inff();
+        }
+    }
+}
+
+// ---- fusion --------------------------------------------------------------------------------------------------------------------
+// double -> uint64 whose order is the doubles' order; never 0 for a number
+__device__ __forceinline__ unsigned long long fuse_key(double v) {
+    v = v + 0.0;      // -0 folded into +0
+    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double fuse_unkey(unsigned long long u) {
+    return __longlong_as_double(static_cast<long long>((u >> 63) ? (u & 0x7fffffffffffffffull) : ~u));
+}
+
+struct FuseStats { double mean, std, lo, hi; };
+
+// mean, population standard deviation, min and max of x[0 .. n) in index order (one lane)
+// (no contraction into fused multiply-adds in the fusion arithmetic: the contract's fixed order is that of plain fp64 operations)
+__device__ FuseStats fuse_stats(const float* __restrict__ x, int n) {
+#pragma clang fp contract(off)
+    FuseStats s{0.0, 0.0, 0.0, 0.0};
+    if (n <= 0) return s;
+    double sum = 0.0, lo = x[0], hi = x[0];
+    for (int i = 0; i < n; ++i) { const double v = x[i]; sum += v; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
+    const double mean = sum / n;
+    double sq = 0.0;
+    for (int i = 0; i < n; ++i) { const double e = static_cast<double>(x[i]) - mean; sq += e * e; }
+    s.mean = mean; s.std = sqrt(sq / n); s.lo = lo; s.hi = hi;
+    return s;
+}
+__device__ __forceinline__ double fuse_normalise(double v, const FuseStats& s, int normalizer) {
+#pragma clang fp contract(off)
+    if (normalizer == NVSM_NORM_STANDARDIZE) return s.std > 0.0 ? (v - s.mean) / s.std : 0.0;
+    if (normalizer == NVSM_NORM_MINMAX) return s.hi > s.lo ? (v - s.lo) / (s.hi - s.lo) : 0.0;
+    return v;
+}
+
+// bitonic sort of n (a power of two) LDS keys, ascending or descending; with `second`, (key, second) pairs compared lexicographically
+template <bool DESC, bool PAIRS>
+__device__ void fuse_sort(unsigned long long* key, unsigned* second, int n) {
+    for (int k = 2; k <= n; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int p = threadIdx.x; p < n / 2; p += 256) {
+                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+                const int l = i | j;
+                const bool fwd = (i & k) == 0;      // this run sorts in the wanted direction
+                const unsigned long long x = key[i], y = key[l];
+                bool x_first;      // x belongs before y in the wanted direction
+                if (PAIRS) {
+                    const unsigned sx = second[i], sy = second[l];
+                    x_first = DESC ? (x > y || (x == y && sx >= sy)) : (x < y || (x == y && sx <= sy));
+                    if (x_first != fwd) { key[i] = y; key[l] = x; second[i] = sy; second[l] = sx; }
+                } else {
+                    x_first = DESC ? x >= y : x <= y;
+                    if (x_first != fwd) { key[i] = y; key[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void fuse_lists_kernel(FuseArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ unsigned long long fuse_lds[];
+    const int n2 = a.npad;                               // a power of two >= 2 k
+    unsigned long long* sk = fuse_lds;                   // [n2] (id, list, position), ascending
+    unsigned long long* fk = fuse_lds + n2;              // [n2] fused score keys, descending
+    unsigned* fid = reinterpret_cast<unsigned*>(fuse_lds + 2 * n2);      // [n2] ~id next to them
+    __shared__ FuseStats stats[2];
+    __shared__ int fused_count;
+    const int q = blockIdx.x, k = a.k;
+    const int64_t* idA = a.ids_a + static_cast<size_t>(q) * k;
+    const int64_t* idB = a.ids_b + static_cast<size_t>(q) * k;
+    const float* scA = a.scores_a + static_cast<size_t>(q) * k;
+    const float* scB = a.scores_b + static_cast<size_t>(q) * k;
+    int nA = static_cast<int>(a.counts_a[q]), nB = static_cast<int>(a.counts_b[q]);
+    nA = nA < 0 ? 0 : (nA > k ? k : nA);
+    nB = nB < 0 ? 0 : (nB > k ? k : nB);
+    if (threadIdx.x == 0) { stats[0] = fuse_stats(scA, nA); fused_count = 0; }
+    if (threadIdx.x == 64) stats[1] = fuse_stats(scB, nB);
+    for (int i = threadIdx.x; i < n2; i += 256) {
+        unsigned long long key = ~0ull;
+        if (i < nA) key = (static_cast<unsigned long long>(idA[i]) << 32) | static_cast<unsigned long long>(i);
+        else if (i >= k && i - k < nB) key = (static_cast<unsigned long long>(idB[i - k]) << 32) | 0x80000000ull | static_cast<unsigned long long>(i - k);
+        sk[i] = key;
+    }
+    __syncthreads();
+    fuse_sort<false, false>(sk, nullptr, n2);
+    const double wA = static_cast<double>(a.alpha), wB = 1.0 - wA;
+    for (int i = threadIdx.x; i < n2; i += 256) {
+        const unsigned long long key = sk[i];
+        unsigned long long out = 0ull;
+        unsigned id = 0u;
+        if (key != ~0ull) {
+            id = static_cast<unsigned>(key >> 32);
+            const bool dup = i > 0 && static_cast<unsigned>(sk[i - 1] >> 32) == id && sk[i - 1] != ~0ull;      // list B's entry of a document list A holds
+            if (!dup) {
+                const bool in_b = (key & 0x80000000ull) != 0;
+                const int pos = static_cast<int>(key & 0x7fffffffull);
+                double f;
+                if (in_b) {
+                    f = wB * fuse_normalise(scB[pos], stats[1], a.normalizer);
+                } else {
+                    f = wA * fuse_normalise(scA[pos], stats[0], a.normalizer);
+                    if (i + 1 < n2 && sk[i + 1] != ~0ull && static_cast<unsigned>(sk[i + 1] >> 32) == id) {
+                        const int pb = static_cast<int>(sk[i + 1] & 0x7fffffffull);
+                        f = (f + wB * fuse_normalise(scB[pb], stats[1], a.normalizer)) / 2.0;
+                    }
+                }
+                out = fuse_key(f);
+            }
+        }
+        fk[i] = out;
+        fid[i] = 0xffffffffu - id;
+    }
+    __syncthreads();
+    fuse_sort<true, true>(fk, fid, n2);
+    int64_t* oid = a.out_ids + static_cast<size_t>(q) * 2 * k;
+    float* osc = a.out_scores + static_cast<size_t>(q) * 2 * k;
+    for (int i = threadIdx.x; i < 2 * k; i += 256) {
+        const unsigned long long key = fk[i];
+        if (key != 0ull) {
+            oid[i] = static_cast<int64_t>(0xffffffffu - fid[i]);
+            osc[i] = static_cast<float>(fuse_unkey(key));
+            if (i + 1 == 2 * k || fk[i + 1] == 0ull) fused_count = i + 1;
+        } else {
+            oid[i] = -1;
+            osc[i] = -__builtin_inff();
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.out_counts[q] = fused_count;
+}
+
+int grid_for(int64_t n) { return stream_grid(n, 256); }
+
+}  // namespace
+
+void launch_lex_cf(const int* tokens, int64_t n, unsigned long long* cf, hipStream_t s) {
+    if (n > 0) NVSM_LAUNCH(lex_cf_kernel, dim3(grid_for(n)), dim3(256), 0, s, tokens, n, cf);
+}
+
+void launch_lex_fill_int(int* p, int64_t n, int v, hipStream_t s) {
+    if (n > 0) NVSM_LAUNCH(lex_fill_int_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, n, v);
+}
+
+void launch_lex_set_slots(int* slot_of, const int* terms, int n, bool set, hipStream_t s) {
+    if (n > 0) NVSM_LAUNCH(lex_set_slots_kernel, dim3((n + 255) / 256), dim3(256), 0, s, slot_of, terms, n, set ? 1 : 0);
+}
+
+void launch_lex_score(const LexScoreArgs& a, hipStream_t s) {
+    if (a.S <= 0 || a.Q <= 0) return;
+    // (grid-strided: enough workgroups to fill the device several times over, not one per document of a large slab)
+    const int grid = static_cast<int>(a.S < 8192 ? a.S : 8192);
+    NVSM_LAUNCH(lex_score_kernel, dim3(grid), dim3(256), 0, s, a);
+}
+
+void launch_lex_write(const unsigned long long* keys, int64_t npad, int Q, int k, int64_t n_all, int64_t* ids, float* scores,
+                      int64_t* counts, hipStream_t s) {
+    if (Q <= 0) return;
+    const int gx = (k + 255) / 256 < 64 ? (k + 255) / 256 : 64;
+    NVSM_LAUNCH(lex_write_kernel, dim3(gx, Q), dim3(256), 0, s, keys, npad, k, n_all, ids, scores, counts);
+}
+
+void launch_fuse_lists(const FuseArgs& a, int Q, hipStream_t s) {
+    if (Q <= 0) return;
+    const size_t lds = static_cast<size_t>(a.npad) * (2 * sizeof(unsigned long long) + sizeof(unsigned));
+    NVSM_LAUNCH(fuse_lists_kernel, dim3(Q), dim3(256), lds, s, a);
+}
+
+}  // namespace cunvsm

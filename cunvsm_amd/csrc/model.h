@@ -158,6 +158,10 @@ class Model {
     void infer(const nvsm_queries& q, const nvsm_rank_options& opt, float* out);
     void rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts);
     // the same ranking plus per-query retrieval metrics computed on the device (eval.hip); doc_ids / scores / counts may be null
+    // query-likelihood ranking over the resident corpus and its fusion with rank's list (include/cunvsm_amd.h; lexical.hip)
+    void lexical_rank(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts);
+    void rank_ensemble(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_ensemble_options& ens,
+                       const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
     void evaluate(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_judgments& j, double* metrics, int64_t* doc_ids,
                   float* scores, int64_t* counts);
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
@@ -407,6 +411,7 @@ class Model {
         int64_t num_tokens = 0, num_documents = 0;
         bool with_doc_weights = false, with_term_weights = false;
         size_t bytes = 0;
+        std::vector<int64_t> cf;            // lexical ranking: occurrences of every word, made by the first lexical call (empty: not yet)
     };
     Corpus* corpus_ = nullptr;
     DevBuf<uint32_t> in_refs_[2];               // host references, one per staging set
@@ -425,6 +430,10 @@ class Model {
         DevBuf<int> jids, jgrades;                 // evaluate: the call's judged ids (ascending per query) and grades,
         DevBuf<int64_t> joff;                      //           ... their offsets,
         DevBuf<double> jconst, metrics;            //           ... R / idcg / idcg@c per query, and the metric rows
+        DevBuf<int> lex_slot_of, lex_terms, lex_qoff, lex_tslot;      // lexical: term -> slot [num_words] (-1 between rounds), a round's terms
+        DevBuf<double> lex_c0, lex_base;                              //          ... and their constants
+        DevBuf<int64_t> fuse_ids, fuse_counts, fuse_out_ids, fuse_out_counts;      // ensemble: both lists of a round [2][round][k], the fused list
+        DevBuf<float> fuse_scores, fuse_out_scores;
     };
     RankScratch rank_;
     void rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt);      // argument checks; the handle's streams joined
@@ -433,6 +442,8 @@ class Model {
     void eval_plan(EvalPlan& p, int64_t Q) const;                                 // checks, sorts, R / idcg / idcg@c
     // the rounds of rank and evaluate (ev null: rank); null result pointers are not copied to
     void rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts, EvalPlan* ev);
+    void lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex) const;      // the refusals of nvsm_lexical_rank, before anything runs
+    void lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts);
     void rank_join();                       // the handle's four streams waited for on the host; the words table's pending stamps settled
     struct RowSpace { const float* rows; int64_t count; int dim; const TableState* table; };      // rows null: the projected vocabulary
     RowSpace row_space(int space) const;

@@ -340,6 +340,260 @@ void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int
     raise_device_error();
 }
 
+// ---- query-likelihood ranking over the resident corpus (include/cunvsm_amd.h nvsm_lexical_rank; kernels: lexical.hip) ----
+// Rounds, slabs, selection and sort are nvsm_rank's; what differs is who fills the score slab (launch_lex_score from the token arena)
+// and that a slab entry may be -inf — a document without any of the query's terms — which launch_lex_write leaves out and counts.
+// A round takes queries while their distinct remaining terms fit kLexSlots counters.
+void Model::lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex) const {
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical ranking needs a corpus: call nvsm_corpus_upload first");
+    if (lex.method != NVSM_LEX_JM && lex.method != NVSM_LEX_DIRICHLET) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown lexical method");
+    if (!std::isfinite(lex.param)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical param is not finite");
+    if (lex.method == NVSM_LEX_JM && lex.param != 0.f && !(lex.param > 0.f && lex.param < 1.f))
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "lambda (lexical param, Jelinek-Mercer) must be in (0, 1), or 0 for auto");
+    if (lex.method == NVSM_LEX_DIRICHLET && lex.param < 0.f)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "mu (lexical param, Dirichlet) must not be negative (0 is auto)");
+    if (lex.top_k < 1 || lex.top_k > corpus_->num_documents) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical top_k must be in [1, num_documents of the corpus]");
+    if (corpus_->num_documents >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "ranking supports fewer than 2^31 documents");
+    if (q.num_queries < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_queries is negative");
+    if (!q.offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->offsets");
+    if (q.offsets[0] != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->offsets[0] must be 0");
+    for (int64_t i = 0; i < q.num_queries; ++i)
+        if (q.offsets[i + 1] < q.offsets[i]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->offsets decrease");
+    if (q.offsets[q.num_queries] > 0 && !q.word_ids) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->word_ids");
+    std::vector<int64_t> one;
+    for (int64_t i = 0; i < q.num_queries; ++i) {
+        if (q.offsets[i + 1] - q.offsets[i] <= kLexSlots) continue;
+        one.assign(q.word_ids + q.offsets[i], q.word_ids + q.offsets[i + 1]);
+        std::sort(one.begin(), one.end());
+        if (std::unique(one.begin(), one.end()) - one.begin() > kLexSlots)
+            throw Error(NVSM_ERR_UNSUPPORTED, "a query has more than NVSM_LEXICAL_MAX_QUERY_TERMS distinct terms");
+    }
+}
+
+void Model::lexical_rank(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts) {
+    lexical_check(q, lex);
+    rank_join();
+    lexical_rounds(q, lex, doc_ids, scores, counts);
+}
+
+void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts) {
+    Corpus& c = *corpus_;
+    const int64_t Dc = c.num_documents, N = c.num_tokens, Q = q.num_queries, V = cfg_.num_words;
+    const int k = lex.top_k;
+    RankScratch& r = rank_;
+    if (c.cf.empty()) {      // one histogram pass over the arena, kept with the corpus (a new upload is a new Corpus)
+        DevBuf<unsigned long long> cf;
+        cf.alloc(static_cast<size_t>(V), true);
+        { RankProf scope(prof, "lex_cf", stream_); launch_lex_cf(c.tokens.p, N, cf.p, stream_); }
+        std::vector<int64_t> host(static_cast<size_t>(V));
+        NVSM_HIP_CHECK(hipMemcpyAsync(host.data(), cf.p, static_cast<size_t>(V) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        c.cf.swap(host);
+    }
+    if (r.lex_slot_of.n < static_cast<size_t>(V)) {
+        r.lex_slot_of.alloc(static_cast<size_t>(V));
+        launch_lex_fill_int(r.lex_slot_of.p, V, -1, stream_);
+    }
+    const double param = lex.method == NVSM_LEX_JM ? (lex.param == 0.f ? 0.5 : static_cast<double>(lex.param))
+                                                   : (lex.param == 0.f ? static_cast<double>(N) / static_cast<double>(Dc) : static_cast<double>(lex.param));
+    const int64_t kScoreFloats = static_cast<int64_t>(tune_.rank_slab_mb) * (int64_t(1) << 18);
+    bool bad_word = false;
+    std::vector<int> terms, qoff, tslot;
+    std::vector<double> c0, base;
+    std::vector<std::pair<int64_t, int>> slot_of;      // (term, slot) of the round, kept sorted by term
+
+    for (int64_t q0 = 0; q0 < Q;) {
+        int64_t qn = std::min(kRankChunk, Q - q0);
+        int64_t S = 0, npad = 1, n_keys = 0;
+        for (;;) {
+            S = std::min<int64_t>(Dc, std::max<int64_t>(kSlabAlign, kScoreFloats / qn / kSlabAlign * kSlabAlign));
+            n_keys = 0;
+            for (int64_t d0 = 0; d0 < Dc; d0 += S) n_keys += std::min<int64_t>(k, std::min(S, Dc - d0));
+            npad = pow2_at_least(n_keys);
+            if (qn * npad <= kKeyCount || qn == 1) break;
+            qn = (qn + 1) / 2;
+        }
+        // ---- the round's queries: as many of the qn as their distinct remaining terms leave room for (at least one: lexical_check)
+        terms.clear(); tslot.clear(); c0.clear(); base.clear(); slot_of.clear();
+        qoff.assign(1, 0);
+        int64_t taken = 0;
+        for (; taken < qn; ++taken) {
+            const size_t terms_before = terms.size(), entries_before = tslot.size();
+            bool fits = true;
+            for (int64_t j = q.offsets[q0 + taken]; j < q.offsets[q0 + taken + 1]; ++j) {
+                const int64_t t = q.word_ids[j];
+                if (t < 0 || t >= V) { bad_word = true; continue; }      // the index contract: matches nothing, reported at the end
+                if (c.cf[static_cast<size_t>(t)] == 0) continue;
+                auto it = std::lower_bound(slot_of.begin(), slot_of.end(), std::make_pair(t, -1));
+                int slot;
+                if (it != slot_of.end() && it->first == t) {
+                    slot = it->second;
+                } else {
+                    if (terms.size() == static_cast<size_t>(kLexSlots)) { fits = false; break; }
+                    slot = static_cast<int>(terms.size());
+                    slot_of.insert(it, std::make_pair(t, slot));
+                    terms.push_back(static_cast<int>(t));
+                }
+                const double p = static_cast<double>(c.cf[static_cast<size_t>(t)]) / static_cast<double>(N);
+                tslot.push_back(slot);
+                c0.push_back(param * p);
+                base.push_back(std::log(param * p));
+            }
+            if (!fits) {      // this query opens the next round: take back what it added
+                for (size_t s = terms_before; s < terms.size(); ++s) {
+                    auto it = std::lower_bound(slot_of.begin(), slot_of.end(), std::make_pair(static_cast<int64_t>(terms[s]), -1));
+                    slot_of.erase(it);
+                }
+                terms.resize(terms_before); tslot.resize(entries_before); c0.resize(entries_before); base.resize(entries_before);
+                break;
+            }
+            qoff.push_back(static_cast<int>(tslot.size()));
+        }
+        qn = taken;
+        const int nslots = static_cast<int>(terms.size());
+        const size_t nent = tslot.size();
+        grow(r.lex_terms, static_cast<size_t>(kLexSlots));
+        grow(r.lex_qoff, static_cast<size_t>(kRankChunk) + 1);
+        grow(r.lex_tslot, std::max<size_t>(nent, 1));
+        grow(r.lex_c0, std::max<size_t>(nent, 1));
+        grow(r.lex_base, std::max<size_t>(nent, 1));
+        // (the main stream is idle here: every round ends with a wait)
+        if (nslots > 0) NVSM_HIP_CHECK(hipMemcpy(r.lex_terms.p, terms.data(), static_cast<size_t>(nslots) * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.lex_qoff.p, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (nent > 0) {
+            NVSM_HIP_CHECK(hipMemcpy(r.lex_tslot.p, tslot.data(), nent * sizeof(int), hipMemcpyHostToDevice));
+            NVSM_HIP_CHECK(hipMemcpy(r.lex_c0.p, c0.data(), nent * sizeof(double), hipMemcpyHostToDevice));
+            NVSM_HIP_CHECK(hipMemcpy(r.lex_base.p, base.data(), nent * sizeof(double), hipMemcpyHostToDevice));
+        }
+        grow(r.keys, static_cast<size_t>(qn * npad));
+        grow(r.out_ids, static_cast<size_t>(qn) * k);
+        grow(r.out_scores, static_cast<size_t>(qn) * k);
+        grow(r.out_counts, static_cast<size_t>(kInferChunk));
+        const int64_t ld = (S + 3) / 4 * 4;
+        grow(r.scores, static_cast<size_t>(qn * ld));
+        grow(r.sel_ws, rank_select_ws_bytes(static_cast<int>(qn), static_cast<int>(S)));
+        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);
+        LexScoreArgs a{};
+        a.tokens = c.tokens.p; a.doc_offsets = c.offsets.p; a.slot_of = r.lex_slot_of.p;
+        a.Q = static_cast<int>(qn); a.num_slots = nslots; a.method = lex.method; a.param = param;
+        a.qoff = r.lex_qoff.p; a.tslot = r.lex_tslot.p; a.c0 = r.lex_c0.p; a.base = r.lex_base.p;
+        a.scores = r.scores.p; a.ld = ld;
+        int64_t key_off = 0;
+        for (int64_t d0 = 0; d0 < Dc; d0 += S) {
+            const int Ss = static_cast<int>(std::min(S, Dc - d0));
+            a.d0 = d0; a.S = Ss;
+            { RankProf scope(prof, "lex_score", stream_); launch_lex_score(a, stream_); }
+            {
+                RankProf scope(prof, "rank_select", stream_);
+                const bool radix = launch_rank_select(r.scores.p, ld, Ss, d0, static_cast<int>(qn), k, r.sel_ws.p, r.keys.p, npad, key_off, stream_);
+                prof.note(radix ? "rank_select_radix" : "rank_select_all");
+            }
+            key_off += std::min<int64_t>(k, Ss);
+        }
+        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
+        launch_rank_fill_keys(r.keys.p, npad, n_keys, npad, static_cast<int>(qn), stream_);
+        {
+            RankProf scope(prof, "rank_sort", stream_);
+            const bool global_steps = launch_rank_sort(r.keys.p, npad, static_cast<int>(qn), stream_);
+            prof.note(global_steps ? "rank_sort_global" : "rank_sort_lds");
+            launch_lex_write(r.keys.p, npad, static_cast<int>(qn), k, n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
+        }
+        NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        q0 += qn;
+    }
+    raise_device_error();
+    if (bad_word) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a query word id is outside [0, num_words)");
+}
+
+// ---- fusion of nvsm_rank's list with the lexical one (include/cunvsm_amd.h nvsm_rank_ensemble; fuse_lists_kernel) ----------------
+// Both rankings are made by their own calls' rounds (whose sizes differ) into host lists; a round of fusion takes kRankChunk queries'
+// lists back up, fuses them on the device and, with judgments, runs nvsm_evaluate's kernel on the fused ids where they lie.
+void Model::rank_ensemble(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_ensemble_options& ens,
+                          const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores, int64_t* counts) {
+    const int64_t Q = q.num_queries;
+    lexical_check(q, lex);
+    if (ens.normalizer != NVSM_NORM_STANDARDIZE && ens.normalizer != NVSM_NORM_MINMAX && ens.normalizer != NVSM_NORM_NONE)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown score normalizer");
+    if (!(ens.alpha >= 0.f && ens.alpha <= 1.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "alpha must be in [0, 1]");
+    if (opt.top_k != lex.top_k) throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_opt->top_k and lex->top_k must be equal");
+    if (opt.candidates || opt.candidate_offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_opt->candidates must be NULL: the ensemble ranks every document");
+    if (opt.similarity != NVSM_SIM_COSINE && opt.similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
+    if (opt.top_k < 1 || opt.top_k > cfg_.num_entities) throw Error(NVSM_ERR_INVALID_ARGUMENT, "top_k must be in [1, num_entities]");
+    rank_check(q, opt);
+    if (opt.top_k > kFuseMaxTopK) throw Error(NVSM_ERR_UNSUPPORTED, "the ensemble supports top_k up to NVSM_ENSEMBLE_MAX_TOP_K");
+    EvalPlan plan;
+    if (j) { plan.request = j; plan.metrics = metrics; eval_plan(plan, Q); }
+    const int k = opt.top_k;
+    const size_t cells = static_cast<size_t>(std::max<int64_t>(Q, 1)) * k;
+    std::vector<int64_t> ids_a(cells), ids_b(cells), cnt_a(static_cast<size_t>(Q) + 1), cnt_b(static_cast<size_t>(Q) + 1);
+    std::vector<float> sc_a(cells), sc_b(cells);
+    rank_rounds(q, opt, ids_a.data(), sc_a.data(), cnt_a.data(), nullptr);
+    lexical_rounds(q, lex, ids_b.data(), sc_b.data(), cnt_b.data());
+
+    RankScratch& r = rank_;
+    const size_t chunk_cells = static_cast<size_t>(kRankChunk) * k;
+    grow(r.fuse_ids, 2 * chunk_cells);
+    grow(r.fuse_scores, 2 * chunk_cells);
+    grow(r.fuse_counts, static_cast<size_t>(2 * kRankChunk));
+    grow(r.fuse_out_ids, 2 * chunk_cells);
+    grow(r.fuse_out_scores, 2 * chunk_cells);
+    grow(r.fuse_out_counts, static_cast<size_t>(kRankChunk));
+    EvalArgs ea{};
+    if (j) {
+        grow(r.jids, std::max<size_t>(plan.ids.size(), 1));
+        grow(r.jgrades, std::max<size_t>(plan.ids.size(), 1));
+        grow(r.joff, static_cast<size_t>(Q) + 1);
+        grow(r.jconst, std::max<size_t>(plan.consts.size(), 1));
+        grow(r.metrics, std::max<size_t>(static_cast<size_t>(Q) * plan.width, 1));
+        if (!plan.ids.empty()) {
+            NVSM_HIP_CHECK(hipMemcpy(r.jids.p, plan.ids.data(), plan.ids.size() * sizeof(int), hipMemcpyHostToDevice));
+            NVSM_HIP_CHECK(hipMemcpy(r.jgrades.p, plan.grades.data(), plan.grades.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
+        NVSM_HIP_CHECK(hipMemcpy(r.joff.p, plan.off.data(), plan.off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (!plan.consts.empty()) NVSM_HIP_CHECK(hipMemcpy(r.jconst.p, plan.consts.data(), plan.consts.size() * sizeof(double), hipMemcpyHostToDevice));
+        ea.k = 2 * k;
+        ea.jids = r.jids.p; ea.jgrades = r.jgrades.p; ea.joff = r.joff.p; ea.consts = r.jconst.p;
+        for (int c = 0; c < kEvalMaxCutoffs; ++c) ea.cutoffs[c] = plan.cutoffs[c];
+        ea.num_cutoffs = plan.num_cutoffs;
+        ea.metrics = r.metrics.p;
+    }
+    for (int64_t q0 = 0; q0 < Q; q0 += kRankChunk) {
+        const int64_t qn = std::min(kRankChunk, Q - q0);
+        const size_t n = static_cast<size_t>(qn) * k;
+        // (the main stream is idle here: both rankings, and every round, end with a wait)
+        NVSM_HIP_CHECK(hipMemcpy(r.fuse_ids.p, ids_a.data() + q0 * k, n * sizeof(int64_t), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.fuse_ids.p + chunk_cells, ids_b.data() + q0 * k, n * sizeof(int64_t), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.fuse_scores.p, sc_a.data() + q0 * k, n * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.fuse_scores.p + chunk_cells, sc_b.data() + q0 * k, n * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.fuse_counts.p, cnt_a.data() + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.fuse_counts.p + kRankChunk, cnt_b.data() + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
+        FuseArgs f{};
+        f.ids_a = r.fuse_ids.p; f.scores_a = r.fuse_scores.p; f.counts_a = r.fuse_counts.p;
+        f.ids_b = r.fuse_ids.p + chunk_cells; f.scores_b = r.fuse_scores.p + chunk_cells; f.counts_b = r.fuse_counts.p + kRankChunk;
+        f.k = k; f.npad = static_cast<int>(pow2_at_least(2 * k)); f.alpha = ens.alpha; f.normalizer = ens.normalizer;
+        f.out_ids = r.fuse_out_ids.p; f.out_scores = r.fuse_out_scores.p; f.out_counts = r.fuse_out_counts.p;
+        { RankProf scope(prof, "fuse_lists", stream_); launch_fuse_lists(f, static_cast<int>(qn), stream_); }
+        if (j) {
+            RankProf scope(prof, "rank_eval", stream_);
+            ea.ids = r.fuse_out_ids.p; ea.counts = r.fuse_out_counts.p; ea.q0 = q0;
+            launch_eval_metrics(ea, static_cast<int>(qn), stream_);
+        }
+        NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * 2 * k, r.fuse_out_ids.p, 2 * n * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * 2 * k, r.fuse_out_scores.p, 2 * n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.fuse_out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    if (j && Q > 0) {
+        NVSM_HIP_CHECK(hipMemcpy(metrics, r.metrics.p, static_cast<size_t>(Q) * plan.width * sizeof(double), hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < Q; ++i)      // a query without words gets all zeros, as in nvsm_evaluate
+            if (q.offsets[i + 1] == q.offsets[i]) std::fill(metrics + i * plan.width, metrics + (i + 1) * plan.width, 0.0);
+    }
+    raise_device_error();
+}
+
 // ---- nearest neighbours (include/cunvsm_amd.h nvsm_neighbors / nvsm_similarity) ---------------------------------
 // The searched matrix is a pointer, a row count and a dimension: W or E directly (through their LazyView), or, for the projected
 // vocabulary, a scratch slab that is produced with the query side's own kernels right before it is scanned. Rounds, slabs,

@@ -1,4 +1,5 @@
 #include "index_source.hpp"
+#include "token_arena.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -153,41 +154,29 @@ class IndexSource::WindowFeeder {
     // every chosen document's term list → model term ids (cpp/data_indri.cpp:112-136: unknown terms become the OoV token 0
     // or are dropped). The shuffled orders leave out documents with fewer in-vocabulary tokens than a window (:258-276).
     void load_documents() {
-        TERMID_T max_index_term = 0;
-        for (const auto& m : owner_->model_term_of_) max_index_term = std::max(max_index_term, m.first);
-        std::vector<int32_t> model_term(static_cast<size_t>(max_index_term) + 1, -1);
-        for (const auto& m : owner_->model_term_of_) model_term[static_cast<size_t>(m.first)] = static_cast<int32_t>(m.second);
-
+        const std::vector<int32_t> model_term = model_term_table(owner_->model_term_of_);
         const size_t docs = owner_->index_doc_of_.empty() ? 0 : owner_->index_doc_of_.rbegin()->first + 1;
-        first_token_.assign(docs + 1, 0);
         usable_.assign(docs, 0);
         if (order_ != DOCUMENT_ORDER) NVSM_LOG(INFO) << "Loading documents into memory.";
         size_t too_short = 0, usable_tokens = 0, usable_docs = 0;
-        size_t next_doc = 0;
-        for (const auto& d : owner_->index_doc_of_) {              // ascending model document id
-            for (; next_doc < d.first; ++next_doc) first_token_[next_doc + 1] = arena_.size();
-            const size_t before = arena_.size();
-            for (const TERMID_T t : owner_->index_->termList(d.second)) {
-                const int32_t m = (t >= 0 && static_cast<size_t>(t) < model_term.size()) ? model_term[static_cast<size_t>(t)] : -1;
-                if (m >= 0) arena_.push_back(m);
-                else if (owner_->oov_token_) arena_.push_back(0);
-            }
-            size_t n = arena_.size() - before;
-            if (order_ != DOCUMENT_ORDER && n < window_) {
-                NVSM_LOG(WARNING) << "Document " << d.second << " only has " << n << " in-vocabulary tokens.";
-                arena_.resize(before);
-                n = 0;
-                ++too_short;
-            } else {
-                // the index's document length counts stopped / out-of-vocabulary positions too (:337-339)
-                NVSM_CHECK(owner_->index_document_length_.at(d.first) >= static_cast<int64_t>(n));
-                usable_[d.first] = 1;
-                usable_tokens += n;
-                ++usable_docs;
-            }
-            first_token_[d.first + 1] = arena_.size();
-            next_doc = d.first + 1;
-        }
+        TokenArena arena;
+        build_token_arena(owner_->index_.get(), model_term, owner_->oov_token_, owner_->index_doc_of_, docs,      // ascending model document id
+                          [&](size_t model_doc, DOCID_T index_doc, size_t n) {
+                              if (order_ != DOCUMENT_ORDER && n < window_) {
+                                  NVSM_LOG(WARNING) << "Document " << index_doc << " only has " << n << " in-vocabulary tokens.";
+                                  ++too_short;
+                                  return false;
+                              }
+                              // the index's document length counts stopped / out-of-vocabulary positions too (:337-339)
+                              NVSM_CHECK(owner_->index_document_length_.at(model_doc) >= static_cast<int64_t>(n));
+                              usable_[model_doc] = 1;
+                              usable_tokens += n;
+                              ++usable_docs;
+                              return true;
+                          },
+                          &arena);
+        arena_.swap(arena.tokens);
+        first_token_.swap(arena.first_token);
         if (order_ != DOCUMENT_ORDER) {
             NVSM_LOG(INFO) << "Unable to generate n-grams for " << too_short << " documents as they were too short.";
             mean_tokens_ = static_cast<double>(usable_tokens) / static_cast<double>(usable_docs);

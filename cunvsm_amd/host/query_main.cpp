@@ -11,6 +11,10 @@
 //     the same ranking.
 //   * ties in a ranking are broken by ascending model document id, not by docno.
 //   * not offered: --rerank_exact_matching_documents, --num_workers, --l2norm_phrase (see --help).
+// The last stage of rank-cranfield-collection.sh — a query-likelihood run and its fusion with the NVSM run (py/combine_runs.py
+// --alpha) — is --qlm / --ensemble_alpha: the collection goes to HBM as the token arena the trainer would upload (token_arena.hpp:
+// IndexSource's term mapping and out-of-vocabulary rule, documents in model id order) and nvsm_lexical_rank / nvsm_rank_ensemble do
+// the rest. The lexical model is over the MODEL's vocabulary, not Indri's.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -27,13 +31,15 @@
 #include "hdf5_writer.hpp"
 #include "indri_index.hpp"
 #include "query_lib.hpp"
+#include "token_arena.hpp"
 #include "trectext_index.hpp"
 
 using namespace nvsm_host;
 
 namespace {
 
-std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs;
+std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs, FLAGS_qlm, FLAGS_qlm_param, FLAGS_qlm_run_out,
+    FLAGS_ensemble_alpha, FLAGS_score_normalizer;
 bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
     FLAGS_l2norm_phrase, FLAGS_help;
 double FLAGS_bias_coefficient;
@@ -63,6 +69,15 @@ void define_flags(Flags* f) {
     f->define_int64("num_workers", &FLAGS_num_workers, 0, "NOT OFFERED (accepted and ignored): every topic file is one GPU pass.");
     f->define_bool("l2norm_phrase", &FLAGS_l2norm_phrase, false, "NOT OFFERED: py/nvsm/base.py has no such argument (the reference's "
                    "py/query.py fails when it is given).");
+    f->define_string("qlm", &FLAGS_qlm, "", "jm | dirichlet: also rank every topic with the query-likelihood model (Jelinek-Mercer or Dirichlet "
+                     "smoothing) over the collection in the model's vocabulary, uploaded to the device. Needs --qlm_run_out or --ensemble_alpha.");
+    f->define_string("qlm_param", &FLAGS_qlm_param, "auto", "auto | <number>: lambda in (0, 1) for jm (auto: 0.5), mu > 0 for dirichlet (auto: the "
+                     "average document length).");
+    f->define_string("qlm_run_out", &FLAGS_qlm_run_out, "", "With --qlm: prefix of the query-likelihood runs, written as <prefix>-<topic file> in TREC format.");
+    f->define_string("ensemble_alpha", &FLAGS_ensemble_alpha, "", "With --qlm: <run_out> holds the fusion of the NVSM ranking (weight alpha in [0, 1]) and "
+                     "the query-likelihood ranking (weight 1 - alpha), up to 2 x top_k documents per topic, and the printed means are the fused list's.");
+    f->define_string("score_normalizer", &FLAGS_score_normalizer, "standardize", "standardize | minmax | none: how --ensemble_alpha normalises each "
+                     "list's scores per topic before mixing them.");
     f->define_bool("help", &FLAGS_help, false, "Print the options and exit.");
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
     f->define_int64("v", &FLAGS_v, 0, "Verbosity of VLOG messages.");
@@ -148,6 +163,39 @@ int run(int argc, char** argv) {
     NVSM_CHECK(is_file(model_path)) << "cannot read the model " << model_path;
     const std::vector<int32_t> cutoffs = parse_cutoffs(FLAGS_cutoffs);
 
+    // ---- --qlm / --ensemble_alpha (rank-cranfield-collection.sh's last stage)
+    const bool with_qlm = !FLAGS_qlm.empty(), with_ensemble = !FLAGS_ensemble_alpha.empty();
+    nvsm_lexical_options lex;
+    nvsm_lexical_options_default(&lex);
+    nvsm_ensemble_options ens;
+    nvsm_ensemble_options_default(&ens);
+    if (with_qlm) {
+        if (FLAGS_qlm == "jm") lex.method = NVSM_LEX_JM;
+        else if (FLAGS_qlm == "dirichlet") lex.method = NVSM_LEX_DIRICHLET;
+        else NVSM_LOG(FATAL) << "--qlm: '" << FLAGS_qlm << "' is neither jm nor dirichlet.";
+        if (FLAGS_qlm_param != "auto") {
+            char* end = nullptr;
+            const double v = std::strtod(FLAGS_qlm_param.c_str(), &end);
+            if (FLAGS_qlm_param.empty() || *end != '\0' || !(v > 0.0) || (lex.method == NVSM_LEX_JM && !(v < 1.0)))
+                NVSM_LOG(FATAL) << "--qlm_param: '" << FLAGS_qlm_param << "' is neither auto, nor a lambda in (0, 1) (jm), nor a mu > 0 (dirichlet).";
+            lex.param = static_cast<float>(v);
+        }
+        NVSM_CHECK(with_ensemble || !FLAGS_qlm_run_out.empty()) << "--qlm needs --qlm_run_out or --ensemble_alpha: nothing would be written.";
+    } else {
+        NVSM_CHECK(!with_ensemble && FLAGS_qlm_run_out.empty() && FLAGS_qlm_param == "auto" && FLAGS_score_normalizer == "standardize")
+            << "--qlm_param, --qlm_run_out, --ensemble_alpha and --score_normalizer need --qlm.";
+    }
+    if (with_ensemble) {
+        char* end = nullptr;
+        const double a = std::strtod(FLAGS_ensemble_alpha.c_str(), &end);
+        if (*end != '\0' || !(a >= 0.0 && a <= 1.0)) NVSM_LOG(FATAL) << "--ensemble_alpha: '" << FLAGS_ensemble_alpha << "' is no weight in [0, 1].";
+        ens.alpha = static_cast<float>(a);
+    }
+    if (FLAGS_score_normalizer == "standardize") ens.normalizer = NVSM_NORM_STANDARDIZE;
+    else if (FLAGS_score_normalizer == "minmax") ens.normalizer = NVSM_NORM_MINMAX;
+    else if (FLAGS_score_normalizer == "none") ens.normalizer = NVSM_NORM_NONE;
+    else NVSM_LOG(FATAL) << "--score_normalizer: '" << FLAGS_score_normalizer << "' is none of standardize, minmax, none.";
+
     // ---- --top_k (py/query.py:118-139)
     int64_t top_k = 1000;
     bool top_k_all = false;
@@ -163,6 +211,7 @@ int run(int argc, char** argv) {
             if (!exists(p)) NVSM_LOG(FATAL) << "--top_k: '" << FLAGS_top_k << "' is neither a number, nor 'all', nor existing qrel files (" << p << ").";
         candidate_qrels.reset(new Qrels(read_qrels(paths)));
     }
+    NVSM_CHECK(!(with_qlm && candidate_qrels)) << "--qlm ranks every document: with it --top_k is a number or 'all', not qrel files.";
     std::unique_ptr<Qrels> qrels;
     if (!FLAGS_qrels.empty()) qrels.reset(new Qrels(read_qrels(split_blanks(FLAGS_qrels))));
 
@@ -218,6 +267,24 @@ int run(int argc, char** argv) {
     NVSM_CALL(nvsm_create(&cfg, &model));
     for (int i = 0; i < 4; ++i)
         NVSM_CALL(nvsm_set_param(model, kNames[i], arrays[static_cast<size_t>(i)].data.data(), static_cast<int64_t>(arrays[static_cast<size_t>(i)].data.size())));
+
+    if (with_qlm) {      // the collection as the trainer would upload it: model term ids, documents in model id order
+        NVSM_LOG(INFO) << "Uploading the collection for the query-likelihood model.";
+        std::vector<std::pair<size_t, DOCID_T>> documents;
+        for (int64_t d = 0; d < num_entities; ++d)
+            if (maps.index_object_of[static_cast<size_t>(d)] >= 0)
+                documents.emplace_back(static_cast<size_t>(d), static_cast<DOCID_T>(maps.index_object_of[static_cast<size_t>(d)]));
+        TokenArena arena;
+        // (the model holds the out-of-vocabulary token exactly when the meta file maps index term 0)
+        build_token_arena(index.get(), model_term_table(maps.model_term_of), maps.model_term_of.count(0) != 0, documents,
+                          static_cast<size_t>(num_entities), [](size_t, DOCID_T, size_t) { return true; }, &arena);
+        const std::vector<int64_t> offsets(arena.first_token.begin(), arena.first_token.end());
+        nvsm_corpus corpus{};
+        corpus.tokens = arena.tokens.data(); corpus.doc_offsets = offsets.data();
+        corpus.num_tokens = static_cast<int64_t>(arena.tokens.size()); corpus.num_documents = num_entities;
+        NVSM_CALL(nvsm_corpus_upload(model, &corpus));
+        NVSM_LOG(INFO) << "<collection of " << corpus.num_documents << " documents and " << corpus.num_tokens << " in-vocabulary tokens>";
+    }
 
     nvsm_rank_options opt;
     nvsm_rank_options_default(&opt);
@@ -297,10 +364,46 @@ int run(int argc, char** argv) {
         nvsm_queries queries;
         queries.word_ids = word_ids.data(); queries.word_weights = FLAGS_self_information ? word_weights.data() : nullptr;
         queries.offsets = word_off.data(); queries.num_queries = Q;
-        std::vector<int64_t> doc_ids(static_cast<size_t>(Q * k) + 1), counts(static_cast<size_t>(Q) + 1);
-        std::vector<float> scores(static_cast<size_t>(Q * k) + 1);
+        const int64_t run_width = with_ensemble ? 2 * k : k;               // entries per topic of <run_out>: the fused list is a union
+        std::vector<int64_t> doc_ids(static_cast<size_t>(Q * run_width) + 1), counts(static_cast<size_t>(Q) + 1);
+        std::vector<float> scores(static_cast<size_t>(Q * run_width) + 1);
         std::vector<double> metrics(static_cast<size_t>(Q) * width + 1);
-        if (qrels) {      // ranking and metrics in ONE call: the metrics are computed from each round's ranked ids where they lie
+        // "<topic> Q0 <docno> <rank from 1> <score> cuNVSM"; %.9g round-trips a float32
+        auto write_run = [&](const std::string& path, const std::vector<int64_t>& ids, const std::vector<float>& sc, const std::vector<int64_t>& n,
+                             int64_t per_topic) {
+            std::ofstream run(path);
+            NVSM_CHECK(run.good()) << "cannot write " << path;
+            char score[32];
+            for (int64_t q = 0; q < Q; ++q)
+                for (int64_t r = 0; r < n[static_cast<size_t>(q)]; ++r) {
+                    const size_t at = static_cast<size_t>(q * per_topic + r);
+                    std::snprintf(score, sizeof(score), "%.9g", static_cast<double>(sc[at]));
+                    run << ranked[static_cast<size_t>(q)] << " Q0 " << index->docno(maps.index_object_of[static_cast<size_t>(ids[at])]) << " " << r + 1
+                        << " " << score << " cuNVSM\n";
+                }
+            run.close();
+            NVSM_CHECK(run.good()) << "cannot write " << path;
+            NVSM_LOG(INFO) << "Run outputted to " << path << ".";
+        };
+        lex.top_k = static_cast<int32_t>(k);
+        if (with_qlm && !FLAGS_qlm_run_out.empty()) {
+            const std::string qlm_path = FLAGS_qlm_run_out + "-" + basename_of(topic_path);
+            if (exists(qlm_path)) {
+                NVSM_LOG(WARNING) << "Run for topics " << topic_path << " already exists (" << qlm_path << "); skipping.";
+            } else {
+                std::vector<int64_t> lex_ids(static_cast<size_t>(Q * k) + 1), lex_counts(static_cast<size_t>(Q) + 1);
+                std::vector<float> lex_scores(static_cast<size_t>(Q * k) + 1);
+                NVSM_CALL(nvsm_lexical_rank(model, &queries, &lex, lex_ids.data(), lex_scores.data(), lex_counts.data()));
+                write_run(qlm_path, lex_ids, lex_scores, lex_counts, k);
+            }
+        }
+        if (with_ensemble) {      // both rankings, their fusion and, with --qrels, the fused list's metrics in ONE call
+            nvsm_judgments judgments{};
+            judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
+            judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());
+            NVSM_CALL(nvsm_rank_ensemble(model, &queries, &opt, &lex, &ens, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr, doc_ids.data(),
+                                         scores.data(), counts.data()));
+        } else if (qrels) {      // ranking and metrics in ONE call: the metrics are computed from each round's ranked ids where they lie
             nvsm_judgments judgments{};
             judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
             judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());
@@ -309,22 +412,7 @@ int run(int argc, char** argv) {
             NVSM_CALL(nvsm_rank(model, &queries, &opt, doc_ids.data(), scores.data(), counts.data()));
         }
 
-        // ---- the run: "<topic> Q0 <docno> <rank from 1> <score> cuNVSM"; %.9g round-trips a float32
-        {
-            std::ofstream run(run_out_path);
-            NVSM_CHECK(run.good()) << "cannot write " << run_out_path;
-            char score[32];
-            for (int64_t q = 0; q < Q; ++q)
-                for (int64_t r = 0; r < counts[static_cast<size_t>(q)]; ++r) {
-                    const size_t at = static_cast<size_t>(q * k + r);
-                    std::snprintf(score, sizeof(score), "%.9g", static_cast<double>(scores[at]));
-                    run << ranked[static_cast<size_t>(q)] << " Q0 " << index->docno(maps.index_object_of[static_cast<size_t>(doc_ids[at])]) << " " << r + 1
-                        << " " << score << " cuNVSM\n";
-                }
-            run.close();
-            NVSM_CHECK(run.good()) << "cannot write " << run_out_path;
-        }
-        NVSM_LOG(INFO) << "Run outputted to " << run_out_path << ".";
+        write_run(run_out_path, doc_ids, scores, counts, run_width);
 
         if (qrels) {      // means over the topics that are in the run and have relevant judged documents, in trec_eval's layout
             std::vector<double> sums(width, 0.0);

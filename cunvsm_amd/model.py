@@ -422,6 +422,42 @@ def eval_metric_names(cutoffs):
     return names
 
 
+LEXICAL_METHODS = {"jm": _lib.LEX_JM, "dirichlet": _lib.LEX_DIRICHLET}
+NORMALIZERS = {"standardize": _lib.NORM_STANDARDIZE, "minmax": _lib.NORM_MINMAX, "none": _lib.NORM_NONE}
+
+
+def lexical_options(method="jm", param=None, top_k=1000):
+    """nvsm_lexical_options from keywords (param None or "auto": 0 = auto); raises ValueError for what the ABI would refuse
+    without a device. top_k against the corpus is checked by the library, which holds it."""
+    opt = _lib.NvsmLexicalOptions()
+    if isinstance(method, str):
+        if method not in LEXICAL_METHODS:
+            raise ValueError("unknown lexical method %r (one of %s)" % (method, sorted(LEXICAL_METHODS)))
+        method = LEXICAL_METHODS[method]
+    value = 0.0 if param is None or param == "auto" else float(param)
+    if method == _lib.LEX_JM and value != 0.0 and not 0.0 < value < 1.0:
+        raise ValueError("lambda = %r outside (0, 1)" % (param,))
+    if method == _lib.LEX_DIRICHLET and value < 0.0:
+        raise ValueError("mu = %r is negative" % (param,))
+    if int(top_k) < 1:
+        raise ValueError("top_k = %d is smaller than 1" % int(top_k))
+    opt.method, opt.param, opt.top_k = int(method), value, int(top_k)
+    return opt
+
+
+def ensemble_options(alpha=0.5, normalizer="standardize"):
+    """nvsm_ensemble_options from keywords; raises ValueError for what the ABI would refuse."""
+    opt = _lib.NvsmEnsembleOptions()
+    if isinstance(normalizer, str):
+        if normalizer not in NORMALIZERS:
+            raise ValueError("unknown normalizer %r (one of %s)" % (normalizer, sorted(NORMALIZERS)))
+        normalizer = NORMALIZERS[normalizer]
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha = %r outside [0, 1]" % (alpha,))
+    opt.alpha, opt.normalizer = float(alpha), int(normalizer)
+    return opt
+
+
 SPACES = {"words": _lib.SPACE_WORDS, "projected_words": _lib.SPACE_PROJECTED_WORDS, "entities": _lib.SPACE_ENTITIES}
 
 
@@ -700,6 +736,57 @@ class Model:
         del keep
         result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}
         return (result, ids, scores, counts) if return_ranking else result
+
+    # -- query-likelihood ranking over the uploaded corpus, and its fusion with rank()'s list --------
+    def lexical_rank(self, queries, method="jm", param=None, top_k=1000):
+        """nvsm_lexical_rank: the top_k documents of the uploaded corpus per query under the query-likelihood model with
+        Jelinek-Mercer ("jm", param = lambda) or Dirichlet ("dirichlet", param = mu) smoothing; param None = auto (lambda 0.5,
+        mu the average document length). Returns (ids [Q, k], scores [Q, k], counts [Q]) as rank() does; a document is
+        retrieved only if it holds a query term, so counts[q] may be smaller than top_k."""
+        q = queries if isinstance(queries, Queries) else Queries(queries)
+        opt = lexical_options(method, param, top_k)
+        k = opt.top_k
+        ids = np.empty((q.num_queries, k), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        check(lib().nvsm_lexical_rank(self._h, C.byref(st), C.byref(opt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids, scores, counts
+
+    def rank_ensemble(self, queries, alpha=0.5, normalizer="standardize", judgments=None, top_k=1000, method="jm", param=None,
+                      cutoffs=(5, 10, 20, 100, 1000), weights=None, **opts):
+        """nvsm_rank_ensemble: rank()'s list and lexical_rank()'s list of every query, each normalised over its returned
+        entries ("standardize" | "minmax" | "none") and fused with weights alpha and 1 - alpha (include/cunvsm_amd.h has the
+        formula). Returns (ids [Q, 2k], scores [Q, 2k], counts [Q]); with judgments, (metrics, ids, scores, counts) where
+        metrics is evaluate()'s dict computed on the fused list. opts: as rank()."""
+        q = queries if isinstance(queries, Queries) else Queries(queries, weights)
+        ropt = rank_options(self.cfg.num_entities, top_k, **opts)
+        lopt = lexical_options(method, param, top_k)
+        eopt = ensemble_options(alpha, normalizer)
+        k = ropt.top_k
+        ids = np.empty((q.num_queries, 2 * k), dtype=np.int64)
+        scores = np.empty((q.num_queries, 2 * k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        js = metrics = names = cut = None
+        if judgments is not None:
+            j = judgments if isinstance(judgments, Judgments) else Judgments(judgments)
+            if j.num_queries != q.num_queries:
+                raise ValueError("judgments holds %d lists, expected one per query = %d" % (j.num_queries, q.num_queries))
+            if j.doc_ids.size and (j.doc_ids.min() < -1 or j.doc_ids.max() >= self.cfg.num_entities):
+                raise ValueError("a judged document id is outside [-1, num_entities = %d)" % self.cfg.num_entities)
+            cut = eval_cutoffs(cutoffs)
+            names = eval_metric_names(cut.tolist())
+            metrics = np.empty((q.num_queries, len(names)), dtype=np.float64)
+            js = j.as_struct(cut)
+        check(lib().nvsm_rank_ensemble(
+            self._h, C.byref(st), C.byref(ropt), C.byref(lopt), C.byref(eopt), None if js is None else C.byref(js),
+            None if js is None else (metrics.ctypes.data if metrics.size else _EMPTY_F64.ctypes.data),
+            ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        if js is None:
+            return ids, scores, counts
+        result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}
+        return result, ids, scores, counts
 
     # -- nearest neighbours in word, projected-word and document space (py/nvsm/base.py:106-162, 325-353, 362-430) ----
     def neighbors(self, space, ids=None, vectors=None, source=None, top_k=30, exclude_self=False, similarity="cosine",

@@ -417,6 +417,80 @@ int nvsm_evaluate(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_op
                   double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
 
 /*
+ * Query-likelihood ranking over the HBM-resident corpus, and the fusion of that run with nvsm_rank's — the last stage of the
+ * reference's rank-cranfield-collection.sh, which takes its lexical run from Indri and fuses with py/combine_runs.py --alpha.
+ * SEMANTICS — the contract. The lexical model is defined on the corpus AS UPLOADED (nvsm_corpus_upload): model word ids, with
+ * out-of-vocabulary positions already dropped or mapped by whoever built the arena. It is a model over the uploaded vocabulary, not
+ * over Indri's. With D_c = num_documents, N = num_tokens, len(d) = doc_offsets[d + 1] − doc_offsets[d], tf(t, d) = occurrences of
+ * word t in document d, cf(t) = occurrences of t in the arena and p(t) = cf(t) / N, a query is the nvsm_queries list of word ids
+ * t_1 .. t_L:
+ *   duplicates      a word repeated in a query contributes once per occurrence. word_weights are not looked at.
+ *   absent terms    a query term with cf(t) = 0 is dropped. A query with no remaining terms, or without words, retrieves nothing:
+ *                   counts[q] = 0, ids -1, scores -inf, as in nvsm_rank.
+ *   NVSM_LEX_JM         s(q, d) = Σ_j log((1 − λ)·tf(t_j, d) / len(d) + λ·p(t_j)), λ in (0, 1) the weight of the collection model
+ *   NVSM_LEX_DIRICHLET  s(q, d) = Σ_j log((tf(t_j, d) + μ·p(t_j)) / (len(d) + μ)), μ > 0
+ *   param = 0       "auto": λ = 0.5, μ = N / D_c (the average document length).
+ *   retrieved set   a document is retrieved if it contains at least one remaining query term; a document with len(d) = 0 never is.
+ *                   counts[q] = min(top_k, matching documents), 1 <= top_k <= num_documents.
+ *   order           score descending, ties by ASCENDING document id; a pure function of corpus and query (a repeated call returns
+ *                   the same bits). Document i of the corpus is model document i.
+ *   accuracy        scores are float32. With a_j the fp64 value of term j, |score − the fp64 sum| <= 2^-23 · Σ_j (8 + (L + 2)·|a_j|):
+ *                   the argument of a log takes at most seven fp32 roundings from exact integers, an accurate logf adds about one
+ *                   ulp of |a_j|, an fp32 sum of L terms about (L − 1) ulps of Σ|a_j|. (The kernel evaluates in fp64 and narrows the
+ *                   sum once, which is well inside that bound; no fast-math log.)
+ * A query of more than NVSM_LEXICAL_MAX_QUERY_TERMS DISTINCT word ids is NVSM_ERR_UNSUPPORTED (the per-document counters of
+ * a round's terms live in LDS).
+ * FUSION (nvsm_rank_ensemble). Inputs per query: list A, the nvsm_rank result, and list B, the lexical result, with weights
+ * w_A = alpha and w_B = 1 − alpha. Each list's scores are normalised over THAT LIST'S RETURNED ENTRIES (its first counts[q]):
+ *   NVSM_NORM_STANDARDIZE  (x − mean) / population standard deviation        NVSM_NORM_MINMAX  (x − min) / (max − min)
+ *   NVSM_NORM_NONE         x
+ * The fused score of a document is the MEAN OVER THE LISTS THAT CONTAIN IT of w·normalised score: (w_A·n_A + w_B·n_B) / 2 for a
+ * document in both, w·n UNDIVIDED for a document in one list only — the reference's behaviour, reproduced as it is. Two deviations
+ * from the reference, which raises an exception in the first case and produces NaN in the second: a list whose scores are all equal
+ * (standard deviation 0, or max = min) normalises to 0 everywhere; a query with one empty list is fused from the other list alone.
+ * The result is the union of both lists, at most 2·top_k entries, by fused score descending, ties by ascending id; slots beyond
+ * counts[q] hold (-1, -inf). Arithmetic is fp64 in a fixed order (sums in index order; mean, then Σ(x − mean)² / n), the order is
+ * decided on the fp64 values, and the fused scores are returned narrowed to float32.
+ * With judgments and metrics the call also returns nvsm_evaluate's metrics of the fused list (the same kernel on the fused ids,
+ * width 2·top_k). rank_opt->top_k and lex->top_k must be equal, rank_opt->candidates must be NULL, and top_k may not exceed
+ * NVSM_ENSEMBLE_MAX_TOP_K (NVSM_ERR_UNSUPPORTED: a query's 2·top_k entries are matched and sorted in LDS).
+ * Both calls are synchronous, run behind everything queued, and touch no parameter, optimiser state, RNG state or lazy bookkeeping.
+ * Scratch, and the cf table (one histogram pass over the arena at the first lexical call after an upload, kept with the corpus:
+ * uploading or freeing a corpus drops it), are allocated on first use: a handle that never makes these calls allocates and launches
+ * what it did before they existed, and its nvsm_describe text is unchanged. NVSM_ERR_INVALID_ARGUMENT before anything runs, each
+ * with a sentence: no corpus uploaded; unknown method or normaliser; λ outside (0, 1); μ < 0; alpha outside [0, 1]; top_k out of
+ * range; unequal top_ks; candidates given; null arguments, by name. A word id outside [0, num_words) follows the index contract:
+ * it matches nothing and the call returns NVSM_ERR_INVALID_ARGUMENT. Pseudo-relevance feedback is out of scope.
+ */
+enum { NVSM_LEX_JM = 0, NVSM_LEX_DIRICHLET = 1 };
+enum { NVSM_NORM_STANDARDIZE = 0, NVSM_NORM_MINMAX = 1, NVSM_NORM_NONE = 2 };
+#define NVSM_LEXICAL_MAX_QUERY_TERMS 1024
+#define NVSM_ENSEMBLE_MAX_TOP_K 1024
+typedef struct {
+    int32_t method;               /* NVSM_LEX_* */
+    float   param;                /* λ (JM) or μ (Dirichlet); 0 = auto */
+    int32_t top_k;
+    int32_t reserved[5];
+} nvsm_lexical_options;
+typedef struct {
+    float   alpha;                /* weight of nvsm_rank's list; the lexical list weighs 1 − alpha */
+    int32_t normalizer;           /* NVSM_NORM_* */
+    int32_t reserved[6];
+} nvsm_ensemble_options;
+/* NVSM_LEX_JM, auto, top_k 1000 */
+void nvsm_lexical_options_default(nvsm_lexical_options* opt);
+/* alpha 0.5, NVSM_NORM_STANDARDIZE: what rank-cranfield-collection.sh passes */
+void nvsm_ensemble_options_default(nvsm_ensemble_options* opt);
+/* doc_ids, scores [num_queries][top_k], counts [num_queries], all host */
+int nvsm_lexical_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex,
+                      int64_t* doc_ids, float* scores, int64_t* counts);
+/* doc_ids, scores [num_queries][2 * top_k], counts [num_queries], all host; judgments and metrics both given or both NULL:
+ * metrics [num_queries][NVSM_EVAL_FIXED + 3 * num_cutoffs] */
+int nvsm_rank_ensemble(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                       const nvsm_ensemble_options* ens, const nvsm_judgments* judgments, double* metrics,
+                       int64_t* doc_ids, float* scores, int64_t* counts);
+
+/*
  * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query
  * library does with the same parameters (py/nvsm/base.py). Semantics, pinned by the reference:
  *   space        NVSM_SPACE_WORDS: the rows of W, dimension word_repr_size — NVSM.related_terms (base.py:325-342) and

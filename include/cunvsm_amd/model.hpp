@@ -208,6 +208,37 @@ class Model {
         return e;
     }
 
+    // nvsm_lexical_rank: query-likelihood ranking over the uploaded corpus (cunvsm_amd.h has the model); a Ranking as rank() returns
+    Ranking lexical_rank(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_lexical_options& lex) {
+        const nvsm_queries q = queries_of(word_ids, offsets, nullptr);
+        Ranking r;
+        r.top_k = lex.top_k;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(lex.top_k > 0 ? lex.top_k : 0);
+        r.doc_ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_lexical_rank(h_, &q, &lex, r.doc_ids.data(), r.scores.data(), r.counts.data()));
+        r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+    // nvsm_rank_ensemble: rank()'s and lexical_rank()'s lists fused; the ranking is [num_queries][2 * top_k] (its top_k field says
+    // 2 * top_k). judgments null: no metrics (width 0).
+    Evaluation rank_ensemble(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                             const nvsm_lexical_options& lex, const nvsm_ensemble_options& ens, const nvsm_judgments* judgments = nullptr,
+                             const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        Evaluation e;
+        e.width = judgments ? NVSM_EVAL_FIXED + 3 * (judgments->num_cutoffs > 0 ? judgments->num_cutoffs : 0) : 0;
+        e.ranking.top_k = 2 * opt.top_k;
+        const size_t Q = static_cast<size_t>(q.num_queries);
+        const size_t n = Q * 2 * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        e.metrics.resize(Q * static_cast<size_t>(e.width) + 1);
+        e.ranking.doc_ids.resize(n ? n : 1); e.ranking.scores.resize(n ? n : 1); e.ranking.counts.resize(Q + 1);
+        check(nvsm_rank_ensemble(h_, &q, &opt, &lex, &ens, judgments, judgments ? e.metrics.data() : nullptr, e.ranking.doc_ids.data(),
+                                 e.ranking.scores.data(), e.ranking.counts.data()));
+        e.metrics.resize(Q * static_cast<size_t>(e.width));
+        e.ranking.doc_ids.resize(n); e.ranking.scores.resize(n); e.ranking.counts.resize(Q);
+        return e;
+    }
+
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
     // 362-430): queries are row ids of `source_space`, or vectors [n][dim] of the searched space (neighbors_of_vectors)
     struct Neighbors { std::vector<int64_t> ids; std::vector<float> scores; std::vector<int64_t> counts; int32_t top_k; };
