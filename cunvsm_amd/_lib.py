@@ -205,6 +205,7 @@ class _Library:
                 "nvsm_debug_gemm_epilogue": (C.c_int, [P(GemmEpilogueArgs)]),
                 "nvsm_debug_table_pass": (C.c_int, [P(TablePassArgs)]),
                 "nvsm_debug_gemm_plan": (C.c_int, [C.c_int] * 7 + [P(C.c_int), P(C.c_uint)]),
+                "nvsm_debug_rank_layout": (C.c_int, [i64] * 5 + [P(i64), P(i64)]),
                 "nvsm_debug_gemm_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float)]),
                 "nvsm_debug_dt_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]),
                 "nvsm_debug_sort": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, P(C.c_float)]),

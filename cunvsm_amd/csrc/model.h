@@ -119,6 +119,13 @@ struct TableState {           // one embedding table + its optimiser state + its
     float decay_hist[kLazyHistory];
 };
 
+// The layout of one round of a retrieval call (ranking.cpp, DESIGN.md §9 "Dispatch by Q and k"), host arithmetic only: qn queries,
+// slabs of S rows at leading dimension ld, n_keys selected keys per query padded to npad. Candidate lists (offsets of the queries on
+// offer) have no slabs: S, ld and n_keys stay 0.
+struct RankLayout { int64_t qn, S, ld, n_keys, npad; };
+RankLayout rank_layout(int64_t rows, int64_t k, int64_t queries, int64_t score_floats, int64_t slab_cap = 0);      // slab_cap 0: none
+RankLayout rank_layout_candidates(const int64_t* offsets, int64_t queries);
+
 class Model {
  public:
     explicit Model(const nvsm_config& cfg);
@@ -436,10 +443,16 @@ class Model {
         DevBuf<float> fuse_scores, fuse_out_scores;
     };
     RankScratch rank_;
-    void rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt);      // argument checks; the handle's streams joined
-    void rank_check(const nvsm_queries& q, const nvsm_rank_options& opt);      // ... the checks alone
+    int64_t score_floats() const { return static_cast<int64_t>(tune_.rank_slab_mb) << 18; }      // the score slab: 256 MB unless NVSM_RANK_SLAB_MB says otherwise
+    // one round behind its layout (ranking.cpp): scratch, the slabs through the caller's fill step, sort + the caller's write, results
+    void round_grow(const RankLayout& l, int k);
+    template <typename Fill> void round_slabs(const RankLayout& l, int64_t rows, int k, Fill fill);
+    template <typename Write> void round_sort(const RankLayout& l, Write write);
+    void round_results(int64_t q0, int64_t qn, int k, int64_t* ids, float* scores, int64_t* counts);      // null pointers are not copied to
+    void rank_check(const nvsm_queries& q, const nvsm_rank_options& opt);      // the refusals of nvsm_infer, before anything runs
     struct EvalPlan;                        // evaluate: the judgments as the kernel reads them (ranking.cpp)
     void eval_plan(EvalPlan& p, int64_t Q) const;                                 // checks, sorts, R / idcg / idcg@c
+    EvalArgs eval_upload(const EvalPlan& p, int64_t Q, int width);                // ... on the device; width: the length of the ranked lists
     // the rounds of rank and evaluate (ev null: rank); null result pointers are not copied to
     void rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts, EvalPlan* ev);
     void lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex) const;      // the refusals of nvsm_lexical_rank, before anything runs

@@ -30,20 +30,53 @@ constexpr int64_t kSlabAlign = 4096;                        // rank.hip kSelPart
 
 int64_t pow2_at_least(int64_t n) { int64_t p = 1; while (p < n) p <<= 1; return p; }
 
-}  // namespace
-
-void Model::rank_begin(const nvsm_queries& q, const nvsm_rank_options& opt) {
-    rank_check(q, opt);
-    rank_join();
-}
-
-void Model::rank_check(const nvsm_queries& q, const nvsm_rank_options& opt) {
+// ---- refusals several entry points share; every entry point runs its checks in an order of its own, which decides the message
+// of a call that is wrong in two ways
+void check_queries(const nvsm_queries& q) {
     if (q.num_queries < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_queries is negative");
     if (!q.offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->offsets");
     if (q.offsets[0] != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->offsets[0] must be 0");
     for (int64_t i = 0; i < q.num_queries; ++i)
         if (q.offsets[i + 1] < q.offsets[i]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->offsets decrease");
     if (q.offsets[q.num_queries] > 0 && !q.word_ids) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->word_ids");
+}
+void check_similarity(int s) { if (s != NVSM_SIM_COSINE && s != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity"); }
+void check_activation(int a) {
+    if (a != NVSM_ACT_MODEL && a != NVSM_ACT_IDENTITY && a != NVSM_TANH && a != NVSM_HARD_TANH) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown activation");
+}
+void check_top_k(int64_t k, int64_t rows, const char* refusal) { if (k < 1 || k > rows) throw Error(NVSM_ERR_INVALID_ARGUMENT, refusal); }
+void check_row_count(int64_t rows, const char* refusal) { if (rows >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, refusal); }
+
+}  // namespace
+
+// ---- the layout of a round (DESIGN.md §9 "Dispatch by Q and k"): host arithmetic only -------------------------------------------
+RankLayout rank_layout(int64_t rows, int64_t k, int64_t queries, int64_t score_floats, int64_t slab_cap) {
+    RankLayout l{};
+    for (l.qn = std::min(kRankChunk, queries);; l.qn = (l.qn + 1) / 2) {
+        l.S = std::min(rows, std::max(kSlabAlign, score_floats / l.qn / kSlabAlign * kSlabAlign));
+        if (slab_cap > 0) l.S = std::min(l.S, slab_cap);
+        const int64_t last = rows % l.S;                    // every slab gives its min(k, slab size) best
+        l.n_keys = rows / l.S * std::min(k, l.S) + std::min(k, last);
+        l.npad = pow2_at_least(l.n_keys);
+        if (l.qn * l.npad <= kKeyCount || l.qn == 1) break;
+    }
+    l.ld = (l.S + 3) / 4 * 4;                               // rows of the slab start 16-byte aligned (rank.hip rank_keys4)
+    return l;
+}
+
+RankLayout rank_layout_candidates(const int64_t* offsets, int64_t queries) {
+    RankLayout l{};
+    for (l.qn = std::min(kInferChunk, queries);; l.qn = (l.qn + 1) / 2) {
+        int64_t most = 1;                                   // the longest list of the queries that remain
+        for (int64_t i = 0; i < l.qn; ++i) most = std::max(most, offsets[i + 1] - offsets[i]);
+        l.npad = pow2_at_least(most);
+        if (l.qn * l.npad <= kKeyCount || l.qn == 1) break;
+    }
+    return l;
+}
+
+void Model::rank_check(const nvsm_queries& q, const nvsm_rank_options& opt) {
+    check_queries(q);
     if (q.word_weights) {
         for (int64_t i = 0; i < q.num_queries; ++i) {
             double sum = 0.0;
@@ -52,9 +85,7 @@ void Model::rank_check(const nvsm_queries& q, const nvsm_rank_options& opt) {
                 throw Error(NVSM_ERR_INVALID_ARGUMENT, "the word weights of a query sum to zero (np.average: weights sum to zero)");
         }
     }
-    const int act = opt.activation;
-    if (act != NVSM_ACT_MODEL && act != NVSM_ACT_IDENTITY && act != NVSM_TANH && act != NVSM_HARD_TANH)
-        throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown activation");
+    check_activation(opt.activation);
     if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
 }
 
@@ -74,7 +105,7 @@ void Model::rank_project(const nvsm_queries& q, const nvsm_rank_options& opt, in
     grow(r.ids, static_cast<size_t>(std::max<int64_t>(nw, 1)));
     grow(r.phrase, static_cast<size_t>(kInferChunk) * dw);
     grow(r.proj, static_cast<size_t>(kInferChunk) * de);
-    // (the main stream is idle here: rank_begin, and every chunk, end with a wait)
+    // (the main stream is idle here: rank_join, and every chunk, end with a wait)
     NVSM_HIP_CHECK(hipMemcpy(r.offsets.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     if (nw > 0) NVSM_HIP_CHECK(hipMemcpy(r.ids.p, q.word_ids + w0, static_cast<size_t>(nw) * sizeof(int64_t), hipMemcpyHostToDevice));
     const float* wts = nullptr;
@@ -92,7 +123,8 @@ void Model::rank_project(const nvsm_queries& q, const nvsm_rank_options& opt, in
 }
 
 void Model::infer(const nvsm_queries& q, const nvsm_rank_options& opt, float* out) {
-    rank_begin(q, opt);
+    rank_check(q, opt);
+    rank_join();
     const int de = cfg_.entity_repr_size;
     for (int64_t q0 = 0; q0 < q.num_queries; q0 += kInferChunk) {
         const int64_t qn = std::min(kInferChunk, q.num_queries - q0);
@@ -102,6 +134,57 @@ void Model::infer(const nvsm_queries& q, const nvsm_rank_options& opt, float* ou
     }
     prof.note("rank_infer");
     raise_device_error();
+}
+
+// ---- one round of rank / evaluate, lexical_rank and neighbors behind its layout: round_grow; round_slabs with the caller's "fill this
+// slab of r.scores" step; round_sort with the caller's write kernel; round_results ---------------------------------------------------
+void Model::round_grow(const RankLayout& l, int k) {
+    RankScratch& r = rank_;
+    grow(r.keys, static_cast<size_t>(l.qn * l.npad));
+    grow(r.out_ids, static_cast<size_t>(l.qn) * k);
+    grow(r.out_scores, static_cast<size_t>(l.qn) * k);
+    grow(r.out_counts, static_cast<size_t>(kInferChunk));
+}
+
+// every slab of `rows`: fill(d0, rows of the slab) writes its scores [qn][ld], the selection adds each query's min(k, slab) best keys
+template <typename Fill>
+void Model::round_slabs(const RankLayout& l, int64_t rows, int k, Fill fill) {
+    RankScratch& r = rank_;
+    const int qn = static_cast<int>(l.qn);
+    grow(r.scores, static_cast<size_t>(l.qn * l.ld));
+    grow(r.sel_ws, rank_select_ws_bytes(qn, static_cast<int>(l.S)));
+    int64_t key_off = 0;
+    for (int64_t d0 = 0; d0 < rows; d0 += l.S) {
+        const int Ss = static_cast<int>(std::min(l.S, rows - d0));
+        fill(d0, Ss);
+        {
+            RankProf scope(prof, "rank_select", stream_);
+            const bool radix = launch_rank_select(r.scores.p, l.ld, Ss, d0, qn, k, r.sel_ws.p, r.keys.p, l.npad, key_off, stream_);
+            prof.note(radix ? "rank_select_radix" : "rank_select_all");
+        }
+        key_off += std::min<int64_t>(k, Ss);
+    }
+}
+
+// the keys behind the slabs' (n_keys 0, candidate lists: the scan wrote and padded them) filled up to npad, the sort, and the caller's
+// write kernel inside the sort's profiler group
+template <typename Write>
+void Model::round_sort(const RankLayout& l, Write write) {
+    RankScratch& r = rank_;
+    if (l.n_keys > 0) launch_rank_fill_keys(r.keys.p, l.npad, l.n_keys, l.npad, static_cast<int>(l.qn), stream_);
+    RankProf scope(prof, "rank_sort", stream_);
+    const bool global_steps = launch_rank_sort(r.keys.p, l.npad, static_cast<int>(l.qn), stream_);
+    prof.note(global_steps ? "rank_sort_global" : "rank_sort_lds");
+    write();
+}
+
+// a round's results to the host where the caller wants them, and the wait that ends the round
+void Model::round_results(int64_t q0, int64_t qn, int k, int64_t* ids, float* scores, int64_t* counts) {
+    RankScratch& r = rank_;
+    if (ids) NVSM_HIP_CHECK(hipMemcpyAsync(ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+    if (scores) NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    if (counts) NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
 void Model::rank(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts) {
@@ -184,12 +267,35 @@ void Model::eval_plan(EvalPlan& p, int64_t Q) const {
     }
 }
 
+// the judgments and their constants go up once per call, not per round; `width` is the length of the lists the kernel will read
+EvalArgs Model::eval_upload(const EvalPlan& p, int64_t Q, int width) {
+    RankScratch& r = rank_;
+    grow(r.jids, std::max<size_t>(p.ids.size(), 1));
+    grow(r.jgrades, std::max<size_t>(p.ids.size(), 1));
+    grow(r.joff, static_cast<size_t>(Q) + 1);
+    grow(r.jconst, std::max<size_t>(p.consts.size(), 1));
+    grow(r.metrics, std::max<size_t>(static_cast<size_t>(Q) * p.width, 1));
+    if (!p.ids.empty()) {
+        NVSM_HIP_CHECK(hipMemcpy(r.jids.p, p.ids.data(), p.ids.size() * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.jgrades.p, p.grades.data(), p.grades.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    NVSM_HIP_CHECK(hipMemcpy(r.joff.p, p.off.data(), p.off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!p.consts.empty()) NVSM_HIP_CHECK(hipMemcpy(r.jconst.p, p.consts.data(), p.consts.size() * sizeof(double), hipMemcpyHostToDevice));
+    EvalArgs ea{};
+    ea.k = width;
+    ea.jids = r.jids.p; ea.jgrades = r.jgrades.p; ea.joff = r.joff.p; ea.consts = r.jconst.p;
+    for (int c = 0; c < kEvalMaxCutoffs; ++c) ea.cutoffs[c] = p.cutoffs[c];
+    ea.num_cutoffs = p.num_cutoffs;
+    ea.metrics = r.metrics.p;
+    return ea;
+}
+
 void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts, EvalPlan* ev) {
     const int64_t D = cfg_.num_entities, Q = q.num_queries;
     const int de = cfg_.entity_repr_size;
-    if (opt.similarity != NVSM_SIM_COSINE && opt.similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
-    if (opt.top_k < 1 || opt.top_k > D) throw Error(NVSM_ERR_INVALID_ARGUMENT, "top_k must be in [1, num_entities]");
-    if (D >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "ranking supports fewer than 2^31 documents");
+    check_similarity(opt.similarity);
+    check_top_k(opt.top_k, D, "top_k must be in [1, num_entities]");
+    check_row_count(D, "ranking supports fewer than 2^31 documents");
     const int k = opt.top_k;
     const int cosine = opt.similarity == NVSM_SIM_COSINE;
     // candidate lists: distinct, ascending (base.py ranks a document_set: a set)
@@ -218,63 +324,23 @@ void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int
         }
     }
     const bool by_candidates = !cand_off.empty();
-    const int64_t kScoreFloats = static_cast<int64_t>(tune_.rank_slab_mb) * (int64_t(1) << 18);      // score slab: 256 MB unless NVSM_RANK_SLAB_MB says otherwise
     rank_check(q, opt);
     if (ev) eval_plan(*ev, Q);      // (host work only: refusals come before anything runs)
     rank_join();
     RankScratch& r = rank_;
     const LazyView view = lazy_view(ents_);
     EvalArgs ea{};
-    if (ev) {      // the judgments and their constants go up once, not per round
-        grow(r.jids, std::max<size_t>(ev->ids.size(), 1));
-        grow(r.jgrades, std::max<size_t>(ev->ids.size(), 1));
-        grow(r.joff, static_cast<size_t>(Q) + 1);
-        grow(r.jconst, std::max<size_t>(ev->consts.size(), 1));
-        grow(r.metrics, std::max<size_t>(static_cast<size_t>(Q) * ev->width, 1));
-        if (!ev->ids.empty()) {
-            NVSM_HIP_CHECK(hipMemcpy(r.jids.p, ev->ids.data(), ev->ids.size() * sizeof(int), hipMemcpyHostToDevice));
-            NVSM_HIP_CHECK(hipMemcpy(r.jgrades.p, ev->grades.data(), ev->grades.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-        NVSM_HIP_CHECK(hipMemcpy(r.joff.p, ev->off.data(), ev->off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        if (!ev->consts.empty()) NVSM_HIP_CHECK(hipMemcpy(r.jconst.p, ev->consts.data(), ev->consts.size() * sizeof(double), hipMemcpyHostToDevice));
-        ea.k = k;
-        ea.jids = r.jids.p; ea.jgrades = r.jgrades.p; ea.joff = r.joff.p; ea.consts = r.jconst.p;
-        for (int c = 0; c < kEvalMaxCutoffs; ++c) ea.cutoffs[c] = ev->cutoffs[c];
-        ea.num_cutoffs = ev->num_cutoffs;
-        ea.metrics = r.metrics.p;
-    }
+    if (ev) ea = eval_upload(*ev, Q, k);
 
     for (int64_t q0 = 0; q0 < Q;) {
-        // ---- how many queries this round, and the layout of their scratch
-        int64_t qn = std::min(by_candidates ? kInferChunk : kRankChunk, Q - q0);
-        int64_t S = 0, npad = 1, n_keys = 0;
-        if (by_candidates) {
-            for (;;) {
-                int64_t most = 1;
-                for (int64_t i = 0; i < qn; ++i) most = std::max(most, cand_off[q0 + i + 1] - cand_off[q0 + i]);
-                npad = pow2_at_least(most);
-                if (qn * npad <= kKeyCount || qn == 1) break;
-                qn = (qn + 1) / 2;
-            }
-        } else {
-            for (;;) {
-                S = std::min<int64_t>(D, std::max<int64_t>(kSlabAlign, kScoreFloats / qn / kSlabAlign * kSlabAlign));
-                n_keys = 0;
-                for (int64_t d0 = 0; d0 < D; d0 += S) n_keys += std::min<int64_t>(k, std::min(S, D - d0));
-                npad = pow2_at_least(n_keys);
-                if (qn * npad <= kKeyCount || qn == 1) break;
-                qn = (qn + 1) / 2;
-            }
-        }
+        const RankLayout l = by_candidates ? rank_layout_candidates(cand_off.data() + q0, Q - q0) : rank_layout(D, k, Q - q0, score_floats());
+        const int64_t qn = l.qn;
         rank_project(q, opt, q0, qn);
         grow(r.qinv, static_cast<size_t>(kInferChunk));
-        grow(r.keys, static_cast<size_t>(qn * npad));
-        grow(r.out_ids, static_cast<size_t>(qn) * k);
-        grow(r.out_scores, static_cast<size_t>(qn) * k);
-        grow(r.out_counts, static_cast<size_t>(kInferChunk));
+        round_grow(l, k);
         const int64_t* cand_off_dev = nullptr;
         { RankProf scope(prof, "rank_query", stream_); launch_rank_query_norm(r.proj.p, qn, de, r.qinv.p, cosine, stream_); }
-        if (by_candidates) {
+        if (by_candidates) {      // no slabs: the scan writes every list's keys, padded to npad
             const int64_t c0 = cand_off[q0], nc = cand_off[q0 + qn] - c0;
             std::vector<int64_t> off(static_cast<size_t>(qn) + 1);
             for (int64_t i = 0; i <= qn; ++i) off[static_cast<size_t>(i)] = cand_off[q0 + i] - c0;
@@ -286,43 +352,23 @@ void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int
             cand_off_dev = r.cand_off.p;
             RankProf scope(prof, "rank_scan", stream_);
             prof.note("rank_scan_candidates");
-            launch_rank_scan_candidates(ents_.P.p, de, r.proj.p, r.qinv.p, r.cand.p, r.cand_off.p, static_cast<int>(qn), npad, r.keys.p, cosine, view, stream_);
+            launch_rank_scan_candidates(ents_.P.p, de, r.proj.p, r.qinv.p, r.cand.p, r.cand_off.p, static_cast<int>(qn), l.npad, r.keys.p, cosine, view, stream_);
         } else {
-            const int64_t ld = (S + 3) / 4 * 4;                 // rows of the slab start 16-byte aligned (rank.hip rank_keys4)
-            grow(r.scores, static_cast<size_t>(qn * ld));
-            grow(r.sel_ws, rank_select_ws_bytes(static_cast<int>(qn), static_cast<int>(S)));
-            int64_t key_off = 0;
-            for (int64_t d0 = 0; d0 < D; d0 += S) {
-                const int Ss = static_cast<int>(std::min(S, D - d0));
-                {
-                    RankProf scope(prof, "rank_scan", stream_);
-                    prof.note(rank_scan_uses_mfma(de) ? "rank_scan_mfma" : "rank_scan_plain");
-                    launch_rank_scan(ents_.P.p, de, d0, Ss, r.proj.p, static_cast<int>(qn), r.qinv.p, r.scores.p, ld, cosine, view, stream_);
-                }
-                {
-                    RankProf scope(prof, "rank_select", stream_);
-                    const bool radix = launch_rank_select(r.scores.p, ld, Ss, d0, static_cast<int>(qn), k, r.sel_ws.p, r.keys.p, npad, key_off, stream_);
-                    prof.note(radix ? "rank_select_radix" : "rank_select_all");
-                }
-                key_off += std::min<int64_t>(k, Ss);
-            }
-            launch_rank_fill_keys(r.keys.p, npad, n_keys, npad, static_cast<int>(qn), stream_);
+            round_slabs(l, D, k, [&](int64_t d0, int Ss) {
+                RankProf scope(prof, "rank_scan", stream_);
+                prof.note(rank_scan_uses_mfma(de) ? "rank_scan_mfma" : "rank_scan_plain");
+                launch_rank_scan(ents_.P.p, de, d0, Ss, r.proj.p, static_cast<int>(qn), r.qinv.p, r.scores.p, l.ld, cosine, view, stream_);
+            });
         }
-        {
-            RankProf scope(prof, "rank_sort", stream_);
-            const bool global_steps = launch_rank_sort(r.keys.p, npad, static_cast<int>(qn), stream_);
-            prof.note(global_steps ? "rank_sort_global" : "rank_sort_lds");
-            launch_rank_write(r.keys.p, npad, static_cast<int>(qn), k, cand_off_dev, n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
-        }
+        round_sort(l, [&] {
+            launch_rank_write(r.keys.p, l.npad, static_cast<int>(qn), k, cand_off_dev, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
+        });
         if (ev) {      // the round's metrics from the ranked ids where they lie: one wave per query
             RankProf scope(prof, "rank_eval", stream_);
             ea.ids = r.out_ids.p; ea.counts = r.out_counts.p; ea.q0 = q0;
             launch_eval_metrics(ea, static_cast<int>(qn), stream_);
         }
-        if (doc_ids) NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        if (scores) NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
-        if (counts) NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        round_results(q0, qn, k, doc_ids, scores, counts);
         q0 += qn;
     }
     if (ev && Q > 0)
@@ -352,14 +398,9 @@ void Model::lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "lambda (lexical param, Jelinek-Mercer) must be in (0, 1), or 0 for auto");
     if (lex.method == NVSM_LEX_DIRICHLET && lex.param < 0.f)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "mu (lexical param, Dirichlet) must not be negative (0 is auto)");
-    if (lex.top_k < 1 || lex.top_k > corpus_->num_documents) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical top_k must be in [1, num_documents of the corpus]");
-    if (corpus_->num_documents >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "ranking supports fewer than 2^31 documents");
-    if (q.num_queries < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_queries is negative");
-    if (!q.offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->offsets");
-    if (q.offsets[0] != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->offsets[0] must be 0");
-    for (int64_t i = 0; i < q.num_queries; ++i)
-        if (q.offsets[i + 1] < q.offsets[i]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->offsets decrease");
-    if (q.offsets[q.num_queries] > 0 && !q.word_ids) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->word_ids");
+    check_top_k(lex.top_k, corpus_->num_documents, "lexical top_k must be in [1, num_documents of the corpus]");
+    check_row_count(corpus_->num_documents, "ranking supports fewer than 2^31 documents");
+    check_queries(q);
     std::vector<int64_t> one;
     for (int64_t i = 0; i < q.num_queries; ++i) {
         if (q.offsets[i + 1] - q.offsets[i] <= kLexSlots) continue;
@@ -396,28 +437,19 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
     }
     const double param = lex.method == NVSM_LEX_JM ? (lex.param == 0.f ? 0.5 : static_cast<double>(lex.param))
                                                    : (lex.param == 0.f ? static_cast<double>(N) / static_cast<double>(Dc) : static_cast<double>(lex.param));
-    const int64_t kScoreFloats = static_cast<int64_t>(tune_.rank_slab_mb) * (int64_t(1) << 18);
     bool bad_word = false;
     std::vector<int> terms, qoff, tslot;
     std::vector<double> c0, base;
     std::vector<std::pair<int64_t, int>> slot_of;      // (term, slot) of the round, kept sorted by term
 
     for (int64_t q0 = 0; q0 < Q;) {
-        int64_t qn = std::min(kRankChunk, Q - q0);
-        int64_t S = 0, npad = 1, n_keys = 0;
-        for (;;) {
-            S = std::min<int64_t>(Dc, std::max<int64_t>(kSlabAlign, kScoreFloats / qn / kSlabAlign * kSlabAlign));
-            n_keys = 0;
-            for (int64_t d0 = 0; d0 < Dc; d0 += S) n_keys += std::min<int64_t>(k, std::min(S, Dc - d0));
-            npad = pow2_at_least(n_keys);
-            if (qn * npad <= kKeyCount || qn == 1) break;
-            qn = (qn + 1) / 2;
-        }
-        // ---- the round's queries: as many of the qn as their distinct remaining terms leave room for (at least one: lexical_check)
+        RankLayout l = rank_layout(Dc, k, Q - q0, score_floats());
+        // ---- the round's queries: as many of the l.qn as their distinct remaining terms leave room for (at least one: lexical_check);
+        // the slabs stay those of the layout, the scratch is sized by the queries taken
         terms.clear(); tslot.clear(); c0.clear(); base.clear(); slot_of.clear();
         qoff.assign(1, 0);
         int64_t taken = 0;
-        for (; taken < qn; ++taken) {
+        for (; taken < l.qn; ++taken) {
             const size_t terms_before = terms.size(), entries_before = tslot.size();
             bool fits = true;
             for (int64_t j = q.offsets[q0 + taken]; j < q.offsets[q0 + taken + 1]; ++j) {
@@ -449,7 +481,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
             }
             qoff.push_back(static_cast<int>(tslot.size()));
         }
-        qn = taken;
+        const int64_t qn = l.qn = taken;
         const int nslots = static_cast<int>(terms.size());
         const size_t nent = tslot.size();
         grow(r.lex_terms, static_cast<size_t>(kLexSlots));
@@ -465,43 +497,21 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
             NVSM_HIP_CHECK(hipMemcpy(r.lex_c0.p, c0.data(), nent * sizeof(double), hipMemcpyHostToDevice));
             NVSM_HIP_CHECK(hipMemcpy(r.lex_base.p, base.data(), nent * sizeof(double), hipMemcpyHostToDevice));
         }
-        grow(r.keys, static_cast<size_t>(qn * npad));
-        grow(r.out_ids, static_cast<size_t>(qn) * k);
-        grow(r.out_scores, static_cast<size_t>(qn) * k);
-        grow(r.out_counts, static_cast<size_t>(kInferChunk));
-        const int64_t ld = (S + 3) / 4 * 4;
-        grow(r.scores, static_cast<size_t>(qn * ld));
-        grow(r.sel_ws, rank_select_ws_bytes(static_cast<int>(qn), static_cast<int>(S)));
-        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);
+        round_grow(l, k);
         LexScoreArgs a{};
         a.tokens = c.tokens.p; a.doc_offsets = c.offsets.p; a.slot_of = r.lex_slot_of.p;
         a.Q = static_cast<int>(qn); a.num_slots = nslots; a.method = lex.method; a.param = param;
         a.qoff = r.lex_qoff.p; a.tslot = r.lex_tslot.p; a.c0 = r.lex_c0.p; a.base = r.lex_base.p;
-        a.scores = r.scores.p; a.ld = ld;
-        int64_t key_off = 0;
-        for (int64_t d0 = 0; d0 < Dc; d0 += S) {
-            const int Ss = static_cast<int>(std::min(S, Dc - d0));
-            a.d0 = d0; a.S = Ss;
-            { RankProf scope(prof, "lex_score", stream_); launch_lex_score(a, stream_); }
-            {
-                RankProf scope(prof, "rank_select", stream_);
-                const bool radix = launch_rank_select(r.scores.p, ld, Ss, d0, static_cast<int>(qn), k, r.sel_ws.p, r.keys.p, npad, key_off, stream_);
-                prof.note(radix ? "rank_select_radix" : "rank_select_all");
-            }
-            key_off += std::min<int64_t>(k, Ss);
-        }
+        a.ld = l.ld;
+        round_slabs(l, Dc, k, [&](int64_t d0, int Ss) {
+            if (d0 == 0) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);      // (behind round_slabs' grows)
+            a.scores = r.scores.p; a.d0 = d0; a.S = Ss;
+            RankProf scope(prof, "lex_score", stream_);
+            launch_lex_score(a, stream_);
+        });
         launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
-        launch_rank_fill_keys(r.keys.p, npad, n_keys, npad, static_cast<int>(qn), stream_);
-        {
-            RankProf scope(prof, "rank_sort", stream_);
-            const bool global_steps = launch_rank_sort(r.keys.p, npad, static_cast<int>(qn), stream_);
-            prof.note(global_steps ? "rank_sort_global" : "rank_sort_lds");
-            launch_lex_write(r.keys.p, npad, static_cast<int>(qn), k, n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
-        }
-        NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        round_sort(l, [&] { launch_lex_write(r.keys.p, l.npad, static_cast<int>(qn), k, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_); });
+        round_results(q0, qn, k, doc_ids, scores, counts);
         q0 += qn;
     }
     raise_device_error();
@@ -520,8 +530,8 @@ void Model::rank_ensemble(const nvsm_queries& q, const nvsm_rank_options& opt, c
     if (!(ens.alpha >= 0.f && ens.alpha <= 1.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "alpha must be in [0, 1]");
     if (opt.top_k != lex.top_k) throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_opt->top_k and lex->top_k must be equal");
     if (opt.candidates || opt.candidate_offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_opt->candidates must be NULL: the ensemble ranks every document");
-    if (opt.similarity != NVSM_SIM_COSINE && opt.similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
-    if (opt.top_k < 1 || opt.top_k > cfg_.num_entities) throw Error(NVSM_ERR_INVALID_ARGUMENT, "top_k must be in [1, num_entities]");
+    check_similarity(opt.similarity);
+    check_top_k(opt.top_k, cfg_.num_entities, "top_k must be in [1, num_entities]");
     rank_check(q, opt);
     if (opt.top_k > kFuseMaxTopK) throw Error(NVSM_ERR_UNSUPPORTED, "the ensemble supports top_k up to NVSM_ENSEMBLE_MAX_TOP_K");
     EvalPlan plan;
@@ -542,24 +552,7 @@ void Model::rank_ensemble(const nvsm_queries& q, const nvsm_rank_options& opt, c
     grow(r.fuse_out_scores, 2 * chunk_cells);
     grow(r.fuse_out_counts, static_cast<size_t>(kRankChunk));
     EvalArgs ea{};
-    if (j) {
-        grow(r.jids, std::max<size_t>(plan.ids.size(), 1));
-        grow(r.jgrades, std::max<size_t>(plan.ids.size(), 1));
-        grow(r.joff, static_cast<size_t>(Q) + 1);
-        grow(r.jconst, std::max<size_t>(plan.consts.size(), 1));
-        grow(r.metrics, std::max<size_t>(static_cast<size_t>(Q) * plan.width, 1));
-        if (!plan.ids.empty()) {
-            NVSM_HIP_CHECK(hipMemcpy(r.jids.p, plan.ids.data(), plan.ids.size() * sizeof(int), hipMemcpyHostToDevice));
-            NVSM_HIP_CHECK(hipMemcpy(r.jgrades.p, plan.grades.data(), plan.grades.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-        NVSM_HIP_CHECK(hipMemcpy(r.joff.p, plan.off.data(), plan.off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        if (!plan.consts.empty()) NVSM_HIP_CHECK(hipMemcpy(r.jconst.p, plan.consts.data(), plan.consts.size() * sizeof(double), hipMemcpyHostToDevice));
-        ea.k = 2 * k;
-        ea.jids = r.jids.p; ea.jgrades = r.jgrades.p; ea.joff = r.joff.p; ea.consts = r.jconst.p;
-        for (int c = 0; c < kEvalMaxCutoffs; ++c) ea.cutoffs[c] = plan.cutoffs[c];
-        ea.num_cutoffs = plan.num_cutoffs;
-        ea.metrics = r.metrics.p;
-    }
+    if (j) ea = eval_upload(plan, Q, 2 * k);
     for (int64_t q0 = 0; q0 < Q; q0 += kRankChunk) {
         const int64_t qn = std::min(kRankChunk, Q - q0);
         const size_t n = static_cast<size_t>(qn) * k;
@@ -640,10 +633,8 @@ void Model::project_words(const int64_t* ids_dev, int64_t first, int64_t n, floa
 
 void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts) {
     if (!known_space(opt.space)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space");
-    if (opt.similarity != NVSM_SIM_COSINE && opt.similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
-    const int act_opt = opt.activation;
-    if (act_opt != NVSM_ACT_MODEL && act_opt != NVSM_ACT_IDENTITY && act_opt != NVSM_TANH && act_opt != NVSM_HARD_TANH)
-        throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown activation");
+    check_similarity(opt.similarity);
+    check_activation(opt.activation);
     if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
     const RowSpace sp = row_space(opt.space);
     const int64_t R = sp.count, Q = q.num_queries;
@@ -661,14 +652,13 @@ void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_option
     }
     if (opt.exclude_self && !(q.ids && q.source_space == opt.space))
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "exclude_self needs queries given as row ids of the searched space");
-    if (opt.top_k < 1 || opt.top_k > R) throw Error(NVSM_ERR_INVALID_ARGUMENT, "top_k must be in [1, rows of the searched space]");
-    if (R >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "neighbour search supports fewer than 2^31 rows");
+    check_top_k(opt.top_k, R, "top_k must be in [1, rows of the searched space]");
+    check_row_count(R, "neighbour search supports fewer than 2^31 rows");
     const int k = opt.top_k;
     const int cosine = opt.similarity == NVSM_SIM_COSINE;
-    const int act = act_opt == NVSM_ACT_MODEL ? cfg_.nonlinearity : act_opt;
+    const int act = opt.activation == NVSM_ACT_MODEL ? cfg_.nonlinearity : opt.activation;
     const bool exclude = opt.exclude_self != 0;
     const int64_t n_out = exclude ? R - 1 : R;               // rows a query can retrieve
-    const int64_t kScoreFloats = static_cast<int64_t>(tune_.rank_slab_mb) * (int64_t(1) << 18);
     const int64_t proj_rows = std::max<int64_t>(kSlabAlign, kProjSlabBytes / (static_cast<int64_t>(dim) * 4) / kSlabAlign * kSlabAlign);
     rank_join();
     RankScratch& r = rank_;
@@ -677,17 +667,8 @@ void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_option
     const LazyView view = sp.table ? lazy_view(*sp.table) : none;
 
     for (int64_t q0 = 0; q0 < Q;) {
-        int64_t qn = std::min(kRankChunk, Q - q0);
-        int64_t S = 0, npad = 1, n_keys = 0;
-        for (;;) {
-            S = std::min<int64_t>(R, std::max<int64_t>(kSlabAlign, kScoreFloats / qn / kSlabAlign * kSlabAlign));
-            if (!sp.rows) S = std::min(S, proj_rows);
-            n_keys = 0;
-            for (int64_t d0 = 0; d0 < R; d0 += S) n_keys += std::min<int64_t>(k, std::min(S, R - d0));
-            npad = pow2_at_least(n_keys);
-            if (qn * npad <= kKeyCount || qn == 1) break;
-            qn = (qn + 1) / 2;
-        }
+        const RankLayout l = rank_layout(R, k, Q - q0, score_floats(), sp.rows ? 0 : proj_rows);      // (a projected slab is scratch of its own)
+        const int64_t qn = l.qn;
         // ---- the round's query panel [qn][dim]
         grow(r.panel, static_cast<size_t>(kRankChunk) * dim);
         grow(r.ids, static_cast<size_t>(kInferChunk));
@@ -709,49 +690,26 @@ void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_option
             launch_rank_gather_rows(src.rows, dim, r.ids.p, 0, qn, r.panel.p, lazy_view(*src.table), stream_);
         }
         { RankProf scope(prof, "nbr_gather", stream_); launch_rank_query_norm(r.panel.p, qn, dim, r.qinv.p, cosine, stream_); }
-        grow(r.keys, static_cast<size_t>(qn * npad));
-        grow(r.out_ids, static_cast<size_t>(qn) * k);
-        grow(r.out_scores, static_cast<size_t>(qn) * k);
-        grow(r.out_counts, static_cast<size_t>(kInferChunk));
-        const int64_t ld = (S + 3) / 4 * 4;
-        grow(r.scores, static_cast<size_t>(qn * ld));
-        grow(r.sel_ws, rank_select_ws_bytes(static_cast<int>(qn), static_cast<int>(S)));
-        if (!sp.rows) grow(r.pslab, static_cast<size_t>(S) * dim);
-        int64_t key_off = 0;
-        for (int64_t d0 = 0; d0 < R; d0 += S) {
-            const int Ss = static_cast<int>(std::min(S, R - d0));
+        round_grow(l, k);
+        round_slabs(l, R, k, [&](int64_t d0, int Ss) {
             const float* rows = sp.rows;
             int64_t begin = d0;
             if (!sp.rows) {      // this slab of the projected vocabulary, then scanned as rows 0 .. Ss of the scratch
+                grow(r.pslab, static_cast<size_t>(l.S) * dim);
                 project_words(nullptr, d0, Ss, opt.bias_coefficient, act, r.pslab.p);
                 rows = r.pslab.p;
                 begin = 0;
             }
-            {
-                RankProf scope(prof, "nbr_scan", stream_);
-                prof.note(nbr_scan_uses_mfma(dim) ? "nbr_scan_mfma" : "nbr_scan_plain");
-                launch_nbr_scan(rows, dim, begin, Ss, r.panel.p, static_cast<int>(qn), r.qinv.p, r.scores.p, ld, cosine, view, stream_);
-                if (self) launch_rank_exclude_self(r.scores.p, ld, d0, Ss, self, static_cast<int>(qn), stream_);
-            }
-            {
-                RankProf scope(prof, "rank_select", stream_);
-                const bool radix = launch_rank_select(r.scores.p, ld, Ss, d0, static_cast<int>(qn), k, r.sel_ws.p, r.keys.p, npad, key_off, stream_);
-                prof.note(radix ? "rank_select_radix" : "rank_select_all");
-            }
-            key_off += std::min<int64_t>(k, Ss);
-        }
-        launch_rank_fill_keys(r.keys.p, npad, n_keys, npad, static_cast<int>(qn), stream_);
-        {
-            RankProf scope(prof, "rank_sort", stream_);
-            const bool global_steps = launch_rank_sort(r.keys.p, npad, static_cast<int>(qn), stream_);
-            prof.note(global_steps ? "rank_sort_global" : "rank_sort_lds");
-            launch_rank_write(r.keys.p, npad, static_cast<int>(qn), k, nullptr, std::min<int64_t>(n_keys, n_out), r.out_ids.p, r.out_scores.p,
+            RankProf scope(prof, "nbr_scan", stream_);
+            prof.note(nbr_scan_uses_mfma(dim) ? "nbr_scan_mfma" : "nbr_scan_plain");
+            launch_nbr_scan(rows, dim, begin, Ss, r.panel.p, static_cast<int>(qn), r.qinv.p, r.scores.p, l.ld, cosine, view, stream_);
+            if (self) launch_rank_exclude_self(r.scores.p, l.ld, d0, Ss, self, static_cast<int>(qn), stream_);
+        });
+        round_sort(l, [&] {
+            launch_rank_write(r.keys.p, l.npad, static_cast<int>(qn), k, nullptr, std::min<int64_t>(l.n_keys, n_out), r.out_ids.p, r.out_scores.p,
                               r.out_counts.p, stream_);
-        }
-        NVSM_HIP_CHECK(hipMemcpyAsync(ids + q0 * k, r.out_ids.p, static_cast<size_t>(qn) * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * k, r.out_scores.p, static_cast<size_t>(qn) * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        });
+        round_results(q0, qn, k, ids, scores, counts);
         q0 += qn;
     }
     raise_device_error();
@@ -759,7 +717,7 @@ void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_option
 
 void Model::similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out) {
     if (!known_space(space)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space");
-    if (similarity != NVSM_SIM_COSINE && similarity != NVSM_SIM_DOT) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown similarity");
+    check_similarity(similarity);
     if (n < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "n is negative");
     const RowSpace sp = row_space(space);
     for (int64_t i = 0; i < n; ++i)

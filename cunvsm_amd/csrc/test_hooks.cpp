@@ -232,6 +232,19 @@ int nvsm_debug_gemm_plan(int kernel, int b_layout, int M, int N, int K, int flag
     });
 }
 
+// The round layout of the retrieval calls (cunvsm_amd_test_hooks.h) — host arithmetic only, no HIP call: the answer of the function
+// the rounds of ranking.cpp themselves call.
+int nvsm_debug_rank_layout(int64_t rows, int64_t k, int64_t queries, int64_t slab_mb, int64_t slab_cap, const int64_t* lengths, int64_t* out) {
+    NVSM_REQUIRE(out);
+    return guarded_hook([&] {
+        if (queries < 1 || (!lengths && (rows < 1 || k < 1 || k > rows || slab_mb < 1 || slab_cap < 0))) throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_layout: bad sizes");
+        std::vector<int64_t> off(lengths ? static_cast<size_t>(queries) + 1 : 0, 0);
+        for (size_t i = 1; i < off.size(); ++i) off[i] = off[i - 1] + lengths[i - 1];
+        const cunvsm::RankLayout l = lengths ? cunvsm::rank_layout_candidates(off.data(), queries) : cunvsm::rank_layout(rows, k, queries, slab_mb << 18, slab_cap);
+        out[0] = l.qn; out[1] = l.S; out[2] = l.ld; out[3] = l.n_keys; out[4] = l.npad;
+    });
+}
+
 // average milliseconds of one launch_gemm of the batch-sized products on device-resident operands (A [M][K], B per b_layout):
 // extras bit 0 = ordered column statistics (the forward product), bit 1 = row sums of squares (the backward one)
 int nvsm_debug_gemm_time(int b_layout, int M, int N, int K, int extras, int repeats, float* avg_ms) {

@@ -46,6 +46,12 @@ int nvsm_debug_gemm_epilogue(const nvsm_debug_gemm_epilogue_args* args);
 enum { NVSM_DEBUG_EPI_COLSTATS = 1, NVSM_DEBUG_EPI_ROWSQ = 2, NVSM_DEBUG_EPI_BN = 4, NVSM_DEBUG_EPI_BIAS = 8, NVSM_DEBUG_EPI_GATHER = 16,
        NVSM_DEBUG_EPI_BIAS_GRAD = 32 };
 int nvsm_debug_gemm_plan(int kernel, int b_layout, int M, int N, int K, int flags, int window, int* covers, unsigned* plan);
+/* Host-only (never touches the GPU): the layout of the first round of a retrieval call that searches `rows` rows for the top k of
+ * `queries` queries with a score slab of slab_mb MB (NVSM_RANK_SLAB_MB) and at most slab_cap rows per slab (0: no cap) - the
+ * function the rounds of nvsm_rank, nvsm_lexical_rank and nvsm_neighbors call. out[5] = queries of the round, rows per slab, leading
+ * dimension of the slab, keys selected per query, keys per query padded to a power of two. With lengths[queries] (the candidate
+ * lists' lengths) the candidate form: rows, k, slab_mb and slab_cap are not read, out = round, 0, 0, 0, padded longest list. */
+int nvsm_debug_rank_layout(int64_t rows, int64_t k, int64_t queries, int64_t slab_mb, int64_t slab_cap, const int64_t* lengths, int64_t* out);
 /* Queues a kernel on the handle's stream that spins for `microseconds` of GPU wall clock: profiling runs put it in
  * front of a step so that the host has queued the whole step before the GPU starts it (tools/rocprof_summary.py timeline). */
 int nvsm_debug_delay(nvsm_model* m, int microseconds);

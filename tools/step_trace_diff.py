@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Compares two rocprofv3 csv traces of tools/step_trace.py (--hip-runtime-trace --kernel-trace -f csv):
+"""Compares two rocprofv3 csv traces of tools/step_trace.py or of tools/rank_trace.py (--hip-runtime-trace --kernel-trace -f csv):
 
   * the sequence of HIP API call names on the thread that made the most calls (the one that drives the engine), and
   * the sequence of kernel names per queue (and per stream, where the trace names streams), in dispatch order, with the queue /
