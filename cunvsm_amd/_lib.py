@@ -147,6 +147,21 @@ class TablePassArgs(C.Structure):
     ]
 
 
+class LossArgs(C.Structure):
+    """nvsm_debug_loss_args (include/cunvsm_amd_test_hooks.h)."""
+    _fields_ = [
+        ("B", C.c_int64), ("de", C.c_int), ("R", C.c_int), ("k", C.c_int),
+        ("pre", C.c_void_p), ("bn", C.c_int), ("bn_sums", C.c_void_p), ("bn_n", C.c_double), ("bias", C.c_void_p),
+        ("E", C.c_void_p), ("rows", C.c_int64), ("ids", C.c_void_p), ("inst_w", C.c_void_p),
+        ("nonlinearity", C.c_int), ("clip_sigmoid", C.c_int), ("bias_negative_samples", C.c_int), ("l2_entity", C.c_int),
+        ("b_global", C.c_double),
+        ("stamp", C.c_void_p), ("decay", C.c_void_p), ("now", C.c_int), ("rows_for_dispatch", C.c_int64), ("repeats", C.c_int),
+        ("proj", C.c_void_p), ("dy", C.c_void_p), ("coef", C.c_void_p), ("probs", C.c_void_p), ("pp", C.c_void_p),
+        ("bn_mean", C.c_void_p), ("bn_inv_std", C.c_void_p), ("loss", C.c_void_p), ("colstats", C.c_void_p),
+        ("plan", C.POINTER(C.c_int)), ("arrive_left", C.POINTER(C.c_int)),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_void_p)
 
 
@@ -204,6 +219,7 @@ class _Library:
                 "nvsm_debug_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
                 "nvsm_debug_gemm_epilogue": (C.c_int, [P(GemmEpilogueArgs)]),
                 "nvsm_debug_table_pass": (C.c_int, [P(TablePassArgs)]),
+                "nvsm_debug_loss": (C.c_int, [P(LossArgs)]),
                 "nvsm_debug_gemm_plan": (C.c_int, [C.c_int] * 7 + [P(C.c_int), P(C.c_uint)]),
                 "nvsm_debug_rank_layout": (C.c_int, [i64] * 5 + [P(i64), P(i64)]),
                 "nvsm_debug_gemm_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float)]),

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include <stdexcept>
 #include <string>
@@ -248,6 +249,40 @@ struct LossArgs {
     float clip_min, clip_max; // nextafter-widened hard_tanh bounds
     float inv_de;             // exp(−log(de))
 };
+// What LossArgs and PairArgs share: the sigmoid clamps of the forward and the backward half — float and double mixed as the
+// reference mixes them — and 1 / d_e for the rows' mean of squares (updates_adam.cu:238-240)
+template <typename Args>
+inline void fill_clamps(Args& a, bool clip_sigmoid, int de) {
+    a.sig_eps = clip_sigmoid ? 1e-7f : 0.f;
+    a.sig_hi = static_cast<float>(1.0 - static_cast<double>(a.sig_eps));
+    a.d_eps = clip_sigmoid ? 1e-6f : 0.f;
+    a.d_hi = 1.0 - static_cast<double>(a.d_eps);
+    a.inv_de = static_cast<float>(std::exp(-std::log(static_cast<double>(de))));
+}
+// Every constant of LossArgs that follows from the configuration, the number k of negatives and the global batch size (a.de is
+// set): what Model::forward hands the loss kernel and what nvsm_debug_loss hands it — one statement of it, so the same bits.
+inline void fill_loss_consts(LossArgs& a, bool clip_sigmoid, bool bias_negative_samples, int k, double B_global) {
+    a.k = k;
+    a.rebalance = (!bias_negative_samples && k > 1);                                      // objective.cu:268
+    fill_clamps(a, clip_sigmoid, a.de);                                                     // :245-246, :367-368
+    a.inv_batch = static_cast<float>(std::exp(-std::log(B_global)));                        // :354
+    a.neg_scale = static_cast<float>((static_cast<double>(static_cast<float>(k)) + 1.0) /
+                                     (2.0 * static_cast<double>(static_cast<float>(k))));   // :270-273
+    a.clip_min = std::nextafter(-1.0f, -1.0f - 1e-5f);                                      // cuda_utils.h:91-96
+    a.clip_max = std::nextafter(1.0f, 1.0f + 1e-5f);
+}
+// What launch_loss does with a LossArgs — every decision of the dispatch, host arithmetic only: the kernel family and its template
+// numbers, the examples a wave walks, the grid and the dynamic LDS. launch_loss launches from this plan and from nothing else.
+enum { LOSS_NONE = 0, LOSS_ROWS = 1, LOSS_GENERIC = 2 };
+struct LossPlan {
+    int family;              // LOSS_NONE (B <= 0: nothing is launched), LOSS_ROWS loss_rows_kernel<rb, lazy, pipe>, LOSS_GENERIC loss_kernel<v, niter, l2e>
+    int rb, lazy, pipe;      // rows
+    int v, niter, l2e;       // generic
+    int epw;                 // examples per wave
+    int grid;                // workgroups of four waves
+    int shmem;               // bytes of dynamic LDS
+};
+void loss_plan(const LossArgs& a, LossPlan* plan);
 void launch_loss(const LossArgs& a, hipStream_t s);
 // true: the kernel launch_loss picks for these shapes applies LossArgs::lazyE itself; false: the rows must be current
 bool loss_reads_lazily(int de, int R, bool l2_entity);

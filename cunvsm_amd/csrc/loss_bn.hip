@@ -542,33 +542,31 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(LossArgs a, int ex_per_w
 //  where twelve register-landing waves hold up to 204, and the kernel took 222 instead of 180 us in-step at |D| = 100 k, 383
 //  instead of 279 us at |D| = 2 M. The register file (512 KB per CU) is the larger landing buffer; removed.)
 
-template <int V, int NITER>
-static void launch_loss_t(const LossArgs& a_in, hipStream_t s) {
-    const int grid = ceil_div(a_in.B, 4 * kExamplesPerWave);
-    LossArgs a = a_in;
-    a.sums.fan = grid_sum_fan(grid);
-    const size_t shmem = (8 * static_cast<size_t>(a.de) + 8) * sizeof(float);
-    if (a.l2_entity) NVSM_LAUNCH((loss_kernel<V, NITER, true>), dim3(grid), dim3(256), shmem, s, a);
-    else NVSM_LAUNCH((loss_kernel<V, NITER, false>), dim3(grid), dim3(256), shmem, s, a);
+bool loss_two_row_sets(int64_t table_rows, int de) {
+    const int pipe_env = tuning().loss_pipe;
+    return pipe_env >= 0 ? pipe_env != 0 : table_rows * static_cast<int64_t>(de) * 4 > (static_cast<int64_t>(256) << 20);
 }
 
-template <int RB>
-static void launch_loss_rows(const LossArgs& a_in, hipStream_t s) {
-    LossArgs a = a_in;
+bool loss_reads_lazily(int de, int R, bool l2_entity) { return de % 4 == 0 && de <= 256 && R <= 64 && !l2_entity; }
+
+// examples per wave of loss_rows_kernel<rb> and whether it keeps two row sets in flight
+static void loss_rows_shape(const LossArgs& a, int rb, int* epw_out, bool* pipe_out) {
+    const int64_t B = a.B;
+    const int R = a.R;
     // ~5 blocks per CU; at most 16 examples per wave ...
-    int epw = static_cast<int>((a.B + 4 * 1280 - 1) / (4 * 1280));
+    int epw = static_cast<int>((B + 4 * 1280 - 1) / (4 * 1280));
     epw = epw < 1 ? 1 : (epw > 16 ? 16 : epw);
     // ... and twenty from 40 k examples: 640 workgroups, fewer than the 768 the chip holds at once (three per CU at 161
     // registers). A workgroup ends by handing its column sums over (device_utils.h grid_sum_ordered: stores, a wait for them,
     // a counter) — 3-4 us of idle waves that a second round of workgroups queues behind; in a single round only the last
     // hand-over shows. 51 200 examples: 180 -> 176 us in-step (1 280 / 800 / 753 workgroups: 180 / 196 / 183 us).
-    if (a.B >= 40960) epw = 20;
+    if (B >= 40960) epw = 20;
     // (batch 4096: two examples per wave, 512 workgroups — half as many fp64 atomics per column: 44 -> 33 us)
-    if (epw < 2 && a.B >= 2048) epw = 2;
+    if (epw < 2 && B >= 2048) epw = 2;
     // per-rank batches (round 5): about 400-500 workgroups — ONE round of workgroups with room to spare (768 fit) instead of a
     // round and a bit (batch 6 400: 800 workgroups of two examples per wave; the stragglers of the second round cost a whole
     // workgroup's latency): alone 47.9 -> 42.8 us, step 0.2637 -> 0.2569 ms with four examples per wave (3: 0.2604; 5, 6: slower)
-    if (a.B > 4096 && a.B <= 8192) epw = static_cast<int>((a.B + 4 * 512 - 1) / (4 * 512));
+    if (B > 4096 && B <= 8192) epw = static_cast<int>((B + 4 * 512 - 1) / (4 * 512));
     // Two row sets per wave (PIPE; two workgroups fit a CU) where the documents table does not fit the 256 MB Infinity Cache and
     // every row comes out of HBM at 1 800 cycles: |D| = 2 M, batch 51 200: 295 -> 244 us in the step (0.44 -> 0.54 of peak) with
     // one round of 512 workgroups. But two such workgroups leave a CU no registers for anything else, and what runs next to this
@@ -577,46 +575,84 @@ static void launch_loss_rows(const LossArgs& a_in, hipStream_t s) {
     // ms (30 examples per wave: 1.567, 32: 1.572, 36: 1.557, 38: 1.567, 40: 1.60, 50: 1.63). Where the table is cache-resident
     // (|D| = 100 k) the two-set kernel gains 6 us (179 -> 173) and the STEP loses 8 (0.894 -> 0.902) for the same reason: single
     // set. Interleaved A/B, tools/ab_roof.sh; NVSM_LOSS_PIPE=0/1, NVSM_LOSS_EPW (experiments build) override.
-    const bool pipe = a.R <= RB && loss_two_row_sets(a.E_rows, a.de);
-    if (pipe && a.B >= 40960) epw = static_cast<int>((a.B + 4 * 380 - 1) / (4 * 380));
+    const bool pipe = R <= rb && loss_two_row_sets(a.E_rows, a.de);
+    if (pipe && B >= 40960) epw = static_cast<int>((B + 4 * 380 - 1) / (4 * 380));
     const int epw_env = tuning().loss_epw;      // experiments
     if (epw_env > 0) epw = epw_env;
-    const int grid = ceil_div(a.B, 4 * epw);
-    a.sums.fan = grid_sum_fan(grid);
-    const size_t shmem = (10 * static_cast<size_t>(a.de) + 8) * sizeof(float);      // column-sum scratch [2][4][de] | loss [4] | flag | μ [de] | 1/σ [de]
-    if (pipe) {
-        if (a.lazyE.stamp) NVSM_LAUNCH((loss_rows_kernel<RB, true, true>), dim3(grid), dim3(256), shmem, s, a, epw);
-        else NVSM_LAUNCH((loss_rows_kernel<RB, false, true>), dim3(grid), dim3(256), shmem, s, a, epw);
-        return;
-    }
-    if (a.lazyE.stamp) NVSM_LAUNCH((loss_rows_kernel<RB, true>), dim3(grid), dim3(256), shmem, s, a, epw);
-    else NVSM_LAUNCH((loss_rows_kernel<RB, false>), dim3(grid), dim3(256), shmem, s, a, epw);
+    *epw_out = epw; *pipe_out = pipe;
 }
 
-bool loss_two_row_sets(int64_t table_rows, int de) {
-    const int pipe_env = tuning().loss_pipe;
-    return pipe_env >= 0 ? pipe_env != 0 : table_rows * static_cast<int64_t>(de) * 4 > (static_cast<int64_t>(256) << 20);
-}
-
-bool loss_reads_lazily(int de, int R, bool l2_entity) { return de % 4 == 0 && de <= 256 && R <= 64 && !l2_entity; }
-
-void launch_loss(const LossArgs& a, hipStream_t s) {
+void loss_plan(const LossArgs& a, LossPlan* plan) {
+    LossPlan p{};
+    *plan = p;
     if (a.B <= 0) return;
     const int de = a.de;
-    if (de % 4 == 0 && de <= 256 && a.R <= 64 && !a.l2_entity) {      // (the optional entity normaliser: generic kernel)
-        if (a.R <= 6) launch_loss_rows<6>(a, s);
-        else if (a.R <= 11) launch_loss_rows<11>(a, s);
-        else launch_loss_rows<17>(a, s);
+    if (loss_reads_lazily(de, a.R, a.l2_entity != 0)) {      // (the optional entity normaliser: generic kernel)
+        p.family = LOSS_ROWS;
+        p.rb = a.R <= 6 ? 6 : (a.R <= 11 ? 11 : 17);
+        bool pipe = false;
+        loss_rows_shape(a, p.rb, &p.epw, &pipe);
+        p.pipe = pipe;
+        p.lazy = a.lazyE.stamp != nullptr;
+        p.shmem = static_cast<int>((10 * static_cast<size_t>(de) + 8) * sizeof(float));      // column-sum scratch [2][4][de] | loss [4] | flag | μ [de] | 1/σ [de]
+    } else {
+        p.family = LOSS_GENERIC;
+        if (de % 4 == 0) {
+            p.v = 4;
+            p.niter = de <= 256 ? 1 : (de <= 512 ? 2 : 4);      // de ≤ 1024, the reference's own limit (block = dim)
+        } else {
+            p.v = 1;
+            p.niter = de <= 64 ? 1 : (de <= 128 ? 2 : 4);       // odd dims up to 256
+        }
+        p.l2e = a.l2_entity != 0;
+        p.epw = kExamplesPerWave;
+        p.shmem = static_cast<int>((8 * static_cast<size_t>(de) + 8) * sizeof(float));
+    }
+    p.grid = ceil_div(a.B, 4 * p.epw);
+    *plan = p;
+}
+
+template <int RB>
+static void launch_loss_rows(const LossArgs& a, const LossPlan& p, hipStream_t s) {
+    const dim3 grid(p.grid), block(256);
+    const size_t shmem = p.shmem;
+    const int epw = p.epw;
+    if (p.pipe) {
+        if (p.lazy) NVSM_LAUNCH((loss_rows_kernel<RB, true, true>), grid, block, shmem, s, a, epw);
+        else NVSM_LAUNCH((loss_rows_kernel<RB, false, true>), grid, block, shmem, s, a, epw);
         return;
     }
-    if (de % 4 == 0) {
-        if (de <= 256) launch_loss_t<4, 1>(a, s);
-        else if (de <= 512) launch_loss_t<4, 2>(a, s);
-        else launch_loss_t<4, 4>(a, s);                 // de ≤ 1024, the reference's own limit (block = dim)
-    } else {
-        if (de <= 64) launch_loss_t<1, 1>(a, s);
-        else if (de <= 128) launch_loss_t<1, 2>(a, s);
-        else launch_loss_t<1, 4>(a, s);                 // odd dims up to 256
+    if (p.lazy) NVSM_LAUNCH((loss_rows_kernel<RB, true>), grid, block, shmem, s, a, epw);
+    else NVSM_LAUNCH((loss_rows_kernel<RB, false>), grid, block, shmem, s, a, epw);
+}
+
+template <int V, int NITER>
+static void launch_loss_t(const LossArgs& a, const LossPlan& p, hipStream_t s) {
+    const size_t shmem = p.shmem;
+    if (p.l2e) NVSM_LAUNCH((loss_kernel<V, NITER, true>), dim3(p.grid), dim3(256), shmem, s, a);
+    else NVSM_LAUNCH((loss_kernel<V, NITER, false>), dim3(p.grid), dim3(256), shmem, s, a);
+}
+
+void launch_loss(const LossArgs& a_in, hipStream_t s) {
+    LossPlan p;
+    loss_plan(a_in, &p);
+    if (p.family == LOSS_NONE) return;
+    LossArgs a = a_in;
+    a.sums.fan = grid_sum_fan(p.grid);
+    if (p.family == LOSS_ROWS) {
+        if (p.rb == 6) launch_loss_rows<6>(a, p, s);
+        else if (p.rb == 11) launch_loss_rows<11>(a, p, s);
+        else launch_loss_rows<17>(a, p, s);
+        return;
+    }
+    const int vn = p.v * 10 + p.niter;
+    switch (vn) {
+    case 41: launch_loss_t<4, 1>(a, p, s); break;
+    case 42: launch_loss_t<4, 2>(a, p, s); break;
+    case 44: launch_loss_t<4, 4>(a, p, s); break;
+    case 11: launch_loss_t<1, 1>(a, p, s); break;
+    case 12: launch_loss_t<1, 2>(a, p, s); break;
+    default: launch_loss_t<1, 4>(a, p, s); break;
     }
 }
 

@@ -944,17 +944,6 @@ void Model::draw_reference_negatives(const int64_t* labels, int64_t B, int64_t* 
     rng_.seed(static_cast<std::minstd_rand0::result_type>(x));          // 1 ≤ x < 2^31 − 1: seed() stores it unchanged
 }
 
-// What LossArgs and PairArgs share (kernels.h): the sigmoid clamps of the forward and the backward half — float and double mixed as
-// the reference mixes them — and 1 / d_e for the rows' mean of squares (updates_adam.cu:238-240)
-template <typename Args>
-static void fill_clamps(Args& a, bool clip_sigmoid, int de) {
-    a.sig_eps = clip_sigmoid ? 1e-7f : 0.f;
-    a.sig_hi = static_cast<float>(1.0 - static_cast<double>(a.sig_eps));
-    a.d_eps = clip_sigmoid ? 1e-6f : 0.f;
-    a.d_hi = 1.0 - static_cast<double>(a.d_eps);
-    a.inv_de = static_cast<float>(std::exp(-std::log(static_cast<double>(de))));
-}
-
 // ---------------------------------------------------------------------------------------------
 // compute_cost — cpp/objective.cu:30-313
 // ---------------------------------------------------------------------------------------------
@@ -1406,16 +1395,10 @@ void Model::forward_loss(const ForwardCall& c) {
         }
         a.proj = proj_.p; a.dy = dy_.p; a.coef = coef_.p; a.probs = probs_.p; a.pp = pp_.p;
         a.loss_acc = stats_bwd_; a.colstats = stats_bwd_ + 1; a.sums = sums_bwd_.ws;
-        a.B = B; a.de = de; a.R = R_; a.k = k;
+        a.B = B; a.de = de; a.R = R_;
         a.bn = cfg_.batch_normalization; a.nonlinearity = cfg_.nonlinearity;
         a.l2_entity = cfg_.l2_normalize_entity_reprs;
-        a.rebalance = (!cfg_.bias_negative_samples && k > 1);                                 // objective.cu:268
-        fill_clamps(a, cfg_.clip_sigmoid != 0, de);                                             // :245-246, :367-368
-        a.inv_batch = static_cast<float>(std::exp(-std::log(B_global)));                        // :354
-        a.neg_scale = static_cast<float>((static_cast<double>(static_cast<float>(k)) + 1.0) /
-                                         (2.0 * static_cast<double>(static_cast<float>(k))));   // :270-273
-        a.clip_min = std::nextafter(-1.0f, -1.0f - 1e-5f);                                      // cuda_utils.h:91-96
-        a.clip_max = std::nextafter(1.0f, 1.0f + 1e-5f);
+        fill_loss_consts(a, cfg_.clip_sigmoid != 0, cfg_.bias_negative_samples != 0, k, B_global);
         if (ents_.lazy) {
             if (loss_reads_lazily(a.de, a.R, a.l2_entity != 0)) a.lazyE = lazy_view(ents_);
             else {

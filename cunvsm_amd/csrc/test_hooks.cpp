@@ -538,6 +538,114 @@ int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* a) {
     });
 }
 
+// One launch_loss on caller-supplied inputs (cunvsm_amd_test_hooks.h): the arguments of Model::forward's loss block — the constants
+// by the same fill_loss_consts —, the grid-sum workspace as Model::alloc_sums sizes it for a batch of B, every output behind a guard.
+int nvsm_debug_loss(const nvsm_debug_loss_args* a) {
+    NVSM_REQUIRE(a); NVSM_REQUIRE(a->pre); NVSM_REQUIRE(a->E); NVSM_REQUIRE(a->ids);
+    return cunvsm::guarded([&] {
+        using namespace cunvsm;
+        const int64_t B = a->B, rows = a->rows;
+        const int de = a->de, R = a->R, k = a->k;
+        const bool bn = a->bn != 0, lazy = a->stamp != nullptr;
+        auto bad = [](const char* what) { throw Error(NVSM_ERR_INVALID_ARGUMENT, std::string("loss: ") + what); };
+        if (B < 1 || B >= (int64_t(1) << 24) || R < 1 || R > 4096 || k < 0 || rows < 1 || rows >= (int64_t(1) << 31)) bad("bad sizes");
+        if (de < 1 || de > 1024 || (de % 4 != 0 && de > 256)) bad("entity_dim is at most 1024, and at most 256 where it is no multiple of 4");      // (Model's own limits)
+        if (bn && (!a->bn_sums || !a->bias || !(a->bn_n > 0))) bad("batch-norm needs bn_sums, bn_n and bias");
+        if (!(a->b_global > 0) || a->repeats < 1 || a->rows_for_dispatch < 0) bad("b_global > 0, repeats >= 1, rows_for_dispatch >= 0");
+        if (a->nonlinearity != 0 && a->nonlinearity != 1) bad("nonlinearity 0 tanh / 1 hard_tanh");
+        for (int64_t i = 0; i < B * R; ++i) if (a->ids[i] < 0 || a->ids[i] >= rows) bad("id out of range");
+        if (lazy) {
+            if (!a->decay) bad("a lazy view needs the factor ring");
+            if (!loss_reads_lazily(de, R, a->l2_entity != 0)) throw Error(NVSM_ERR_UNSUPPORTED, "loss: the kernel for this shape reads the rows as they are (the model refreshes them first)");
+            for (int64_t r = 0; r < rows; ++r)      // kernels.h "lazy dense decay": nobody falls further behind than the factor ring is long
+                if (a->stamp[r] < 0 || a->stamp[r] > a->now || a->now - a->stamp[r] > kLazyHistory) bad("a row lags further behind than the lazy decay contract allows");
+        }
+
+        // the dispatch by its rules, whatever the environment says
+        Tuning t;
+        TuningScope scope(&t);
+
+        auto fill = [](void* p, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemset(p, 0xFF, bytes)); };
+        auto up = [](void* d, const void* h, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice)); };
+        auto down = [](void* h, const void* d, size_t bytes) { if (h && bytes) NVSM_HIP_CHECK(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost)); };
+        const size_t Bde = static_cast<size_t>(B) * de, BR = static_cast<size_t>(B) * R, sde = static_cast<size_t>(de);
+
+        DevBuf<float> pre, bias, E, inst_w, proj, dy, coef, probs, pp, bn_mean, bn_inv_std;
+        DevBuf<double> bn_sums, acc, part, part2;
+        DevBuf<int> ids, stamp, arrive;
+        pre.alloc(Bde); up(pre.p, a->pre, Bde * sizeof(float));
+        E.alloc(static_cast<size_t>(rows) * de); up(E.p, a->E, E.n * sizeof(float));
+        ids.alloc(BR); up(ids.p, a->ids, BR * sizeof(int));
+        if (bn) { bn_sums.alloc(2 * sde); up(bn_sums.p, a->bn_sums, 2 * sde * sizeof(double)); }
+        if (a->bias) { bias.alloc(sde); up(bias.p, a->bias, sde * sizeof(float)); }
+        if (a->inst_w) { inst_w.alloc(B); up(inst_w.p, a->inst_w, B * sizeof(float)); }
+        if (lazy) { stamp.alloc(rows); up(stamp.p, a->stamp, rows * sizeof(int)); }
+        // outputs: one more row (R more elements) than the kernel owns, everything 0xFF
+        proj.alloc(Bde + sde); dy.alloc(Bde + sde); coef.alloc(BR + R); probs.alloc(BR + R); pp.alloc(B + 1);
+        bn_mean.alloc(2 * sde); bn_inv_std.alloc(2 * sde); acc.alloc(1 + 3 * sde);
+        auto fill_outputs = [&] {
+            fill(proj.p, proj.n * sizeof(float)); fill(dy.p, dy.n * sizeof(float)); fill(coef.p, coef.n * sizeof(float));
+            fill(probs.p, probs.n * sizeof(float)); fill(pp.p, pp.n * sizeof(float)); fill(bn_mean.p, bn_mean.n * sizeof(float));
+            fill(bn_inv_std.p, bn_inv_std.n * sizeof(float)); fill(acc.p, acc.n * sizeof(double));
+        };
+        // the workspace of the ordered sum, as Model::alloc_sums sizes it for a largest batch of B; the counters zeroed ONCE
+        GridSumWs ws{};
+        ws.colgroups = 1; ws.contrib_cap = static_cast<int>((B + 3) / 4); ws.width_cap = 2 * de + 1;
+        ws.groups_cap = ws.contrib_cap / 16 + 1; ws.fan = 16;
+        part.alloc(static_cast<size_t>(ws.contrib_cap) * ws.width_cap); part2.alloc(static_cast<size_t>(ws.groups_cap) * ws.width_cap);
+        arrive.alloc(static_cast<size_t>(ws.groups_cap) + 1, true);
+        fill(part.p, part.n * sizeof(double)); fill(part2.p, part2.n * sizeof(double));
+        ws.part = part.p; ws.part2 = part2.p; ws.arrive = arrive.p;
+
+        LossArgs l{};
+        l.pre = pre.p; l.bn_mean = bn_mean.p; l.bn_inv_std = bn_inv_std.p; l.bias = bias.p;
+        l.bn_sums = bn_sums.p; l.bn_n = a->bn_n; l.bn_eps = 1e-4f;
+        l.E = E.p; l.E_rows = a->rows_for_dispatch ? a->rows_for_dispatch : rows; l.ids = ids.p; l.inst_w = inst_w.p;
+        l.proj = proj.p; l.dy = dy.p; l.coef = coef.p; l.probs = probs.p; l.pp = pp.p;
+        l.loss_acc = acc.p; l.colstats = acc.p + 1; l.sums = ws;
+        l.B = B; l.de = de; l.R = R;
+        l.bn = bn; l.nonlinearity = a->nonlinearity; l.l2_entity = a->l2_entity != 0;
+        fill_loss_consts(l, a->clip_sigmoid != 0, a->bias_negative_samples != 0, k, a->b_global);
+        if (lazy) { l.lazyE.stamp = stamp.p; l.lazyE.now = a->now; std::memcpy(l.lazyE.decay, a->decay, sizeof(l.lazyE.decay)); }
+
+        LossPlan plan;
+        loss_plan(l, &plan);
+        if (plan.grid > ws.contrib_cap) throw Error(NVSM_ERR_STATE, "loss: the plan has more workgroups than the workspace has contributions");
+        hipStream_t s;
+        NVSM_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        try {
+            for (int rep = 0; rep < a->repeats; ++rep) {
+                fill_outputs();
+                NVSM_HIP_CHECK(hipDeviceSynchronize());
+                launch_loss(l, s);
+                NVSM_HIP_CHECK(hipGetLastError());
+                NVSM_HIP_CHECK(hipStreamSynchronize(s));
+            }
+        } catch (...) {
+            (void)hipStreamDestroy(s);
+            throw;
+        }
+        (void)hipStreamDestroy(s);
+
+        down(a->proj, proj.p, proj.n * sizeof(float)); down(a->dy, dy.p, dy.n * sizeof(float));
+        down(a->coef, coef.p, coef.n * sizeof(float)); down(a->probs, probs.p, probs.n * sizeof(float));
+        down(a->pp, pp.p, pp.n * sizeof(float));
+        down(a->bn_mean, bn_mean.p, bn_mean.n * sizeof(float)); down(a->bn_inv_std, bn_inv_std.p, bn_inv_std.n * sizeof(float));
+        down(a->loss, acc.p, sizeof(double)); down(a->colstats, acc.p + 1, 3 * sde * sizeof(double));
+        if (a->plan) {
+            const int out[10] = {plan.family, plan.rb, plan.lazy, plan.pipe, plan.v, plan.niter, plan.l2e, plan.epw, plan.grid, plan.shmem};
+            std::memcpy(a->plan, out, sizeof(out));
+        }
+        if (a->arrive_left) {
+            std::vector<int> h(arrive.n);
+            down(h.data(), arrive.p, arrive.n * sizeof(int));
+            int left = 0;
+            for (int v : h) left += v != 0;
+            *a->arrive_left = left;
+        }
+    });
+}
+
 int nvsm_debug_gather_mean(int64_t num_rows, int dim, const float* table, const int64_t* idx, const float* wts,
                            int window, int64_t num_out, float* out) {
     NVSM_REQUIRE(table); NVSM_REQUIRE(idx); NVSM_REQUIRE(out);

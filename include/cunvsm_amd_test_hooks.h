@@ -93,6 +93,41 @@ typedef struct nvsm_debug_table_pass_args {
     int* arrive_left;                /* arrival counters of the one-launch pass that are not back at zero after it */
 } nvsm_debug_table_pass_args;
 int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* args);
+/* ONE launch_loss (csrc/loss_bn.hip) on caller-supplied inputs (tests/test_gpu_loss_shapes.py): the host arrays are uploaded, the
+ * constants of the kernel's arguments come from the function Model::forward fills them with (kernels.h fill_loss_consts, batch-norm
+ * epsilon 1e-4), the product's own launch_loss runs `repeats` times on ONE grid-sum workspace - sized as the model sizes it for a
+ * batch of B, ceil(B / 4) contributions, its arrival counters zeroed once in front of the first launch - and everything is copied
+ * back. The dispatch follows its rules alone - a Tuning of the hook's own at its defaults -, never the environment.
+ * Every output buffer starts as 0xFF bytes in front of every launch and carries a guard behind what the kernel owns, which comes
+ * back too: one more row for proj, dy ([B + 1][de]), bn_mean, bn_inv_std ([2][de]) and colstats ([3][de]), one more element for
+ * pp ([B + 1]), R more for coef and probs ([(B + 1) * R]). Output pointers may be null.
+ * Refused: NVSM_ERR_UNSUPPORTED for a lazy view (stamp non-null) where the kernel of the shape does not apply one
+ * (loss_reads_lazily false: the model refreshes the rows instead); NVSM_ERR_INVALID_ARGUMENT for a row whose stamp is negative,
+ * ahead of `now` or more than 128 updates (kLazyHistory, the length of the factor ring) behind it, and for ids outside the table. */
+typedef struct nvsm_debug_loss_args {
+    int64_t B; int de, R, k;
+    const float* pre;                /* [B][de] */
+    int bn; const double* bn_sums;   /* [2][de]: column sums of pre and of its squares over bn_n rows */
+    double bn_n; const float* bias;  /* [de] (read with bn only: without it pre holds the bias already) */
+    const float* E; int64_t rows;    /* [rows][de] */
+    const int32_t* ids;              /* [B * R], each in [0, rows) */
+    const float* inst_w;             /* [B] or null */
+    int nonlinearity;                /* 0 tanh, 1 hard_tanh */
+    int clip_sigmoid, bias_negative_samples, l2_entity;
+    double b_global;                 /* the global batch size behind 1 / B in the multipliers */
+    const int32_t* stamp;            /* [rows] or null: updates applied to each row of E (a lazy view) */
+    const float* decay;              /* [128]: factor of update u + 1 at [u % 128] */
+    int now;                         /* updates applied to the table */
+    int64_t rows_for_dispatch;       /* 0: rows. Stands in for LossArgs::E_rows, which only the choice of the two-row-set form reads */
+    int repeats;
+    /* out */
+    float* proj; float* dy; float* coef; float* probs; float* pp; float* bn_mean; float* bn_inv_std;
+    double* loss;                    /* [1] */
+    double* colstats;                /* [3][de]: sums of dy, sums of dy * xhat (written with bn only), guard */
+    int* plan;                       /* [10], LossPlan (kernels.h): family (1 rows, 2 generic), rb, lazy, pipe, v, niter, l2e, examples per wave, grid, LDS bytes */
+    int* arrive_left;                /* arrival counters that are not back at zero after the last launch */
+} nvsm_debug_loss_args;
+int nvsm_debug_loss(const nvsm_debug_loss_args* args);
 /* nvsm_neighbors' scan through the plain kernel whatever the dimension (1) or by its own dispatch (0, the default): how
  * tools/bench_neighbors.py holds the MFMA scan with the tail chunk against the plain scan on the same table; process-wide */
 int nvsm_debug_neighbors_force_plain(int on);
