@@ -272,6 +272,8 @@ def lib():
         "nvsm_step": (C.c_int, [vp, P(NvsmBatch), vp, C.c_float, P(C.c_float)]),
         "nvsm_compute_cost_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture)]),
         "nvsm_step_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture), C.c_float, P(C.c_float)]),
+        "nvsm_compute_cost_term_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture)]),
+        "nvsm_step_term_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture), C.c_float, P(C.c_float)]),
         "nvsm_corpus_upload": (C.c_int, [vp, P(NvsmCorpus)]),
         "nvsm_compute_cost_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp]),
         "nvsm_step_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp, C.c_float, P(C.c_float)]),

@@ -266,6 +266,18 @@ int nvsm_step_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity
     return guarded_on(m, [&] { m->impl.step_mixed(text, entity_ids, *pairs, mix, learning_rate, cost); });
 }
 
+int nvsm_compute_cost_term_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch* pairs, const nvsm_mixture* mix) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(pairs);
+    if (text) NVSM_REQUIRE(mix);
+    return guarded_on(m, [&] { m->impl.compute_cost_term_mixed(text, entity_ids, *pairs, mix); });
+}
+int nvsm_step_term_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch* pairs, const nvsm_mixture* mix,
+                         float learning_rate, float* cost) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(pairs);
+    if (text) NVSM_REQUIRE(mix);
+    return guarded_on(m, [&] { m->impl.step_term_mixed(text, entity_ids, *pairs, mix, learning_rate, cost); });
+}
+
 int nvsm_step_deferred(nvsm_model* m, const nvsm_batch* batch, const int64_t* entity_ids, float lr, int64_t* ticket) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(batch); NVSM_REQUIRE(ticket);
     return guarded_on(m, [&] { *ticket = m->impl.step_deferred(*batch, entity_ids, lr); });

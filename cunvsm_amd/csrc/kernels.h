@@ -311,6 +311,8 @@ struct PairArgs {
     float inv_batch;          // exp(−log(M))
     float scale;              // mixture scale w_ee / (w_te + w_ee); 1 for the pair objective alone
     float inv_de;
+    int mul_rows;             // the words-table form (pairs.hip): E is the words table, X gets the MULTIPLIED rows mults[p]·E[·], sq the
+                              //   means of squares of those stored rows, coef is not written (the entries weigh 1)
 };
 int pair_loss_blocks(int64_t M, int de);      // workgroups launch_pair_loss uses (sizes GridSumWs::contrib_cap)
 void launch_pair_loss(const PairArgs& a, hipStream_t s);
@@ -318,6 +320,8 @@ void launch_pair_loss(const PairArgs& a, hipStream_t s);
 // the id whose quotient by R is the entry's source row behind the text objective's (model.cpp compute_cost)
 void launch_pair_entry_ids(int* vals, int64_t n_text, int64_t first_src, int R, int64_t n_pair, hipStream_t s);
 void launch_pair_scale_weights(const float* w, float scale, float* out, int64_t n, hipStream_t s);      // out[i] = (w ? w[i] : 1) · scale
+// the per-entry weights of the merged words update: out[i] = w[i] for the n_text text entries, out[(first_src + j) * R] = 1 for pair entry j
+void launch_pair_entry_weights(const float* w, float* out, int64_t n_text, int64_t first_src, int R, int64_t n_pair, hipStream_t s);
 void launch_pair_materialize(const float* coef, int coef_stride, const float* X, int64_t n, int de, float* out, hipStream_t s);   // tests
 
 // per-row mean of squares: out[b] = Σ_t G[b][t]² · inv_dim  (cpp/updates_adam.cu:232-240)

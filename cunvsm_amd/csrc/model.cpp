@@ -961,6 +961,7 @@ void Model::begin_forward(int mode, int64_t B, int64_t M, const nvsm_mixture* mi
     loss_folded_ = false;
     mode_ = mode;
     M_ = M;
+    pair_table_ = 0;      // (the term-pair passes say otherwise right behind this call)
     text_scale_ = mix ? mix->text_weight / (mix->text_weight + mix->pair_weight) : 1.f;      // weight / summed_weight, intermediate_results.cu:19-36
     pair_scale_ = mix ? mix->pair_weight / (mix->text_weight + mix->pair_weight) : 1.f;
     if (cfg_.l2_normalize_entity_reprs) join_E();      // that documents update still reads ids_, which the prologue rewrites
@@ -982,7 +983,7 @@ void Model::begin_forward(int mode, int64_t B, int64_t M, const nvsm_mixture* mi
 // The forward pass of one request: its stages in their order. What sits between two stages here is what joins them — the events the
 // side streams follow, and the places the CSR builds may be queued at.
 void Model::forward(const ForwardRequest& req) {
-    if (!req.text()) { forward_pairs_only(req); return; }
+    if (!req.text()) { if (req.term_pairs) forward_terms_only(req); else forward_pairs_only(req); return; }
     const int64_t B = req.num_instances();
     if (B <= 0 || B > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_instances must be in (0, max_batch_size]");
     if (!req.windows && (!req.batch->features || !req.batch->labels)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "features and labels are required");
@@ -993,11 +994,18 @@ void Model::forward(const ForwardRequest& req) {
     c.Bu = exact_ ? B * cfg_.world_size : B;          // windows of the table updates
     // a mixed forward pass (compute_cost_mixed): the pair objective rides along — its ids behind the document ids, its kernel on
     // side stream 1 under the forward pass, its entries in the documents CSR. Nothing below differs for a text-only pass.
+    // (term pairs, compute_cost_term_mixed: their ids behind the WORD ids, their entries in the words CSR, their kernel on the main
+    //  stream behind the loss kernel — DESIGN.md §15)
     c.mixed = req.pairs != nullptr;
-    c.M2 = c.mixed ? 2 * req.pairs->num_pairs : 0;
+    c.terms = c.mixed && req.term_pairs;
+    c.M2 = c.mixed && !c.terms ? 2 * req.pairs->num_pairs : 0;
+    c.T2 = c.terms ? 2 * req.pairs->num_pairs : 0;
     RangeScope range_cc("ComputeCost");                 // cpp/main.cu:409
     begin_forward(c.mixed ? MODE_MIXED : MODE_TEXT, B, c.mixed ? req.pairs->num_pairs : 0, req.mix);
-    if (c.mixed) stage_pairs(*req.pairs, ids_p_ + c.N);      // (in front of the prologue, whose completion event says "ids final")
+    if (c.terms) {
+        pair_table_ = 1;
+        stage_pairs(*req.pairs, widx_.p + B * cfg_.window_size, cfg_.num_words, NVSM_BAD_WORD_ID);
+    } else if (c.mixed) stage_pairs(*req.pairs, ids_p_ + c.N, cfg_.num_entities, NVSM_BAD_ENTITY_ID);      // (in front of the prologue, whose completion event says "ids final")
     // device-sampler mode: zeroing the statistics, narrowing the word ids and drawing the document ids are one launch
     c.fused_prologue = !req.entity_ids && cfg_.sampler != NVSM_SAMPLER_HOST_MINSTD;
     if (!c.fused_prologue) {
@@ -1007,6 +1015,8 @@ void Model::forward(const ForwardRequest& req) {
 
     stage_inputs(c);
     stage_ids(c);
+    // term pairs with feature weights: the words update reads a copy of the weights in which every pair entry weighs 1
+    if (c.terms && wwts_) launch_pair_entry_weights(wwts_, wts_ext_.p, B * cfg_.window_size, B, cfg_.window_size, c.T2, stream_);
 
     // Row-order (CSR) of both tables for the update, on the side streams: needs only the indices.
     const int csr_after = tune_.csr_after;
@@ -1015,7 +1025,7 @@ void Model::forward(const ForwardRequest& req) {
     // The pair kernel needs E and the pair ids only: side stream 1, behind the previous step's documents update (which ran there,
     // or on the main stream in front of this event) and under this step's forward pass. Not where the generic loss kernel has the
     // batch's rows of a lazily decayed table refreshed in place first (forward_loss): behind the loss kernel then.
-    c.pair_on_main = c.mixed && (debug_ || (ents_.lazy && !loss_reads_lazily(de, static_cast<int>(R_), cfg_.l2_normalize_entity_reprs != 0)));
+    c.pair_on_main = c.mixed && (c.terms || debug_ || (ents_.lazy && !loss_reads_lazily(de, static_cast<int>(R_), cfg_.l2_normalize_entity_reprs != 0)));
     if (c.mixed && !c.pair_on_main) launch_pairs(aux_stream_, ev_inputs_);
     c.sort_layout = csr_stream_layout();
     last_csr_layout_ = c.sort_layout;
@@ -1037,7 +1047,10 @@ void Model::forward(const ForwardRequest& req) {
     forward_product(c);
     forward_loss(c);
 
-    if (c.pair_on_main) launch_pairs(stream_, nullptr);
+    // (term pairs: the main stream is behind every writer of W here — the previous words update, its hoisted and streamed decays,
+    //  which the word gather joined, and the stamps the prologue set — and in front of this step's words update)
+    if (c.terms) launch_term_pairs();
+    else if (c.pair_on_main) launch_pairs(stream_, nullptr);
     if (csr_after == 3 && !c.csr_first) { NVSM_HIP_CHECK(hipEventRecord(ev_gathered_, stream_)); launch_csr_builds(c, ev_gathered_); }
     if (c.words_csr_late) { NVSM_HIP_CHECK(hipEventRecord(ev_words_late_, stream_)); launch_csr_builds(c, ev_words_late_, 2); }
     NVSM_HIP_CHECK(hipGetLastError());      // a failed launch of any kernel above surfaces here, not at the next sync
@@ -1245,7 +1258,7 @@ void Model::stage_ids(ForwardCall& c) {
 // which: 1 = the documents table, 2 = the words table, 3 = both
 void Model::launch_csr_builds(const ForwardCall& c, hipEvent_t after, int which) {
     const int sort_layout = c.sort_layout, w = cfg_.window_size;
-    const int64_t Bu = c.Bu, M2 = c.M2;
+    const int64_t Bu = c.Bu, M2 = c.M2, T2 = c.T2;
     const int* csr_ids = c.csr_ids;
     const int* csr_widx = c.csr_widx;
     const int layout = aux3_stream_ ? sort_layout : (sort_layout == 4 ? 0 : sort_layout);
@@ -1262,8 +1275,8 @@ void Model::launch_csr_builds(const ForwardCall& c, hipEvent_t after, int which)
     //  into the snapshot the moments pass reads right here, behind the build that lists those rows — it needs nothing the
     //  step computes, and in front of the words update it was a launch of 7 us on the critical stream)
     auto wrds = [&] {
-        { PROF_ON("csr_words", sw); build_csr(words_, csr_widx, Bu * w, sw); }
-        if (words_.lazy && words_.lazy_scalar && tune_.early_snapshot) { lazy_scalar_snapshot(words_, csr_of(words_, Bu * w), sw); words_snapshot_early_ = true; }
+        { PROF_ON("csr_words", sw); build_csr(words_, csr_widx, Bu * w + T2, sw, T2); }
+        if (words_.lazy && words_.lazy_scalar && tune_.early_snapshot) { lazy_scalar_snapshot(words_, csr_of(words_, Bu * w + T2), sw); words_snapshot_early_ = true; }
         // The fused step knows lr and λ already: the decay of the words rows WITHOUT entries (SGD / Adagrad, λ > 0, a table
         // much larger than the batch: launch_untouched_rows) goes here, under the forward pass, instead of into the update's
         // tail where the next step's word gather waited for it (LSE batch 4096: 16-22 us per step). Nothing of this step
@@ -1277,7 +1290,7 @@ void Model::launch_csr_builds(const ForwardCall& c, hipEvent_t after, int which)
         const bool hoist = c.req.hoist && !words_.lazy && (cfg_.update_method == NVSM_SGD || cfg_.update_method == NVSM_ADAGRAD);
         auto hoisted_pass = [&] {
             RowPassArgs ua = final_words_pass_args(c.req.lr, c.req.sl);
-            if (!launch_untouched_rows(csr_of(words_, Bu * w), ua, sw)) return false;
+            if (!launch_untouched_rows(csr_of(words_, Bu * w + T2), ua, sw)) return false;
             words_untouched_hoisted_ = true;
             hoisted_lr_ = c.req.lr; hoisted_sl_ = c.req.sl;
             prof.note("untouched_words_hoisted");
@@ -1768,7 +1781,13 @@ void Model::build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s, 
     TableState::CsrIndex& x = t.idx[t.idx_cur];
     // the merged documents update: the last n_pair_entries keys are pair ids, whose entries are numbered (B + i) * R (model.h)
     const int* vals = nullptr;
-    if (n_pair_entries > 0) {
+    if (n_pair_entries > 0 && &t == &words_) {
+        // ... and of the merged words update: the last keys are term-pair ids, entries (B + i) * w
+        const int64_t n_text = n - n_pair_entries;
+        const int w = cfg_.window_size;
+        launch_pair_entry_ids(term_vals_.p, n_text, n_text / w, w, n_pair_entries, s);
+        vals = term_vals_.p;
+    } else if (n_pair_entries > 0) {
         const int64_t n_text = n - n_pair_entries;
         launch_pair_entry_ids(pair_vals_[t.idx_cur].p, n_text, n_text / R_, R_, n_pair_entries, s);
         vals = pair_vals_[t.idx_cur].p;
@@ -1889,7 +1908,7 @@ void Model::update_entities(float lr, float sl, hipStream_t strm, hipEvent_t row
     const int64_t N = ents_entries(u.B);      // (with pairs: the text entries and the 2M pair entries in one CSR — one decay, one step counter)
     const int de = cfg_.entity_repr_size;
     TableState& t = ents_;
-    if (mode_ != MODE_TEXT && pair_stream_ != strm) {      // the pair kernel wrote the pair entries' rows and coefficients
+    if (mode_ != MODE_TEXT && pair_table_ == 0 && pair_stream_ != strm) {      // the pair kernel wrote the pair entries' rows and coefficients
         NVSM_HIP_CHECK(hipStreamWaitEvent(strm, ev_pair_, 0));
         if (strm == stream_) pair_pending_ = false;
     }
@@ -1933,7 +1952,7 @@ void Model::update_entities(float lr, float sl, hipStream_t strm, hipEvent_t row
     int path;
     // (timed by an event pair that rides on the pass's own launch: the kernel's execution time in the step — bench.py
     //  roofline_update —, not the side stream's wait for it)
-    timed_launch(prof, mode_ != MODE_TEXT ? "row_pass_entities_mixed" : "row_pass_entities", strm, /*single=*/true, [&] { path = launch_table_pass(c, a, strm); });
+    timed_launch(prof, mode_ != MODE_TEXT && pair_table_ == 0 ? "row_pass_entities_mixed" : "row_pass_entities", strm, /*single=*/true, [&] { path = launch_table_pass(c, a, strm); });
     if (path == TABLE_PASS_ENTRY_WALK) prof.note("entry_walk_entities");
     if (swap_sc) t.sc_cur ^= 1;
     lazy_end_update(t, c, strm);
@@ -1954,11 +1973,15 @@ RowPassArgs Model::final_words_pass_args(float lr, float sl) {
 void Model::update_words(float lr, float sl, hipStream_t untouched_stream) {
     const int dw = cfg_.word_repr_size, w = cfg_.window_size;
     const UpdateInputs u = update_inputs();
-    const int64_t n = u.B * w;
+    // (term pairs, model.h: 2M more entries behind the text objective's, their own weight 1; alone: 2M source rows of one entry each)
+    const bool terms = term_result(), terms_alone = terms && mode_ == MODE_PAIRS;
+    const int64_t n = words_entries(u.B);
+    const int win = terms_alone ? 1 : w;                           // entries per source row
+    const int64_t srcs = terms_alone ? 2 * M_ : u.B;               // source rows of the per-source passes (sparse Adam / Adagrad: not mixed)
     TableState& t = words_;
     Csr c = csr_of(t, n);
     RowPassArgs a{};
-    a.table = 0; a.X = u.gphrase; a.wts = u.wwts; a.div = static_cast<uint32_t>(w);
+    a.table = 0; a.X = u.gphrase; a.wts = terms ? (terms_alone || !u.wwts ? nullptr : wts_ext_.p) : u.wwts; a.div = static_cast<uint32_t>(win);
     a.div_magic = (uint64_t(1) << 37) / a.div + 1;
     a.P = t.P.p; a.m = t.m.p; a.v = t.vfull.p; a.dim = dw;
     a.lr = lr; a.lambda = sl; a.eps = 1e-6f;
@@ -1983,7 +2006,7 @@ void Model::update_words(float lr, float sl, hipStream_t untouched_stream) {
         s.kind = ROW_SCALAR_ACC; s.sq_src = u.msq_w; s.dense = 0;
         s.sc_in = t.sc[t.sc_cur].p; s.sc_out = t.sc[t.sc_cur].p;
         { PROF("adagrad_acc_words"); launch_table_pass(c, s, stream_, untouched_stream); }
-        { PROF("adagrad_scale_words"); launch_adagrad_scale(t.sc[t.sc_cur].p, u.widx, w, u.B, 1e-6f, scale_w_.p, stream_); }
+        { PROF("adagrad_scale_words"); launch_adagrad_scale(t.sc[t.sc_cur].p, u.widx, win, srcs, 1e-6f, scale_w_.p, stream_); }
         a.kind = ROW_SGD; a.src_scale = scale_w_.p; a.dense = sl > 0.f; a.untouched_done = hoisted;
         lazy_begin_update(t, a, false);
         { PROF("row_pass_words"); launch_table_pass(c, a, stream_, untouched_stream); }
@@ -2016,7 +2039,7 @@ void Model::update_words(float lr, float sl, hipStream_t untouched_stream) {
     { PROF("row_pass_words_mv"); path = launch_table_pass(c, a, stream_, untouched_stream); }
     if (path == TABLE_PASS_ENTRY_WALK) prof.note("entry_walk_words");
     if (!t.lazy) t.sc_cur ^= 1;
-    { PROF("adam_u_words"); launch_adam_u(t.m.p, t.sc[t.sc_cur].p, dw, u.widx, w, u.B, a.bc, a.eps, U_.p, stream_); }
+    { PROF("adam_u_words"); launch_adam_u(t.m.p, t.sc[t.sc_cur].p, dw, u.widx, win, srcs, a.bc, a.eps, U_.p, stream_); }
     RowPassArgs r = a;
     r.kind = ROW_SGD; r.X = U_.p; r.sq_src = nullptr; r.dense = sl > 0.f; r.wide = 1;
     r.nt_m = 0; r.nt_p = (nt_mask() >> 3) & 1;
@@ -2102,6 +2125,10 @@ std::string Model::describe(int64_t batch) const {
                : std::string("pair_loss on side stream 1 under the forward pass, entries merged into the documents pass") +
                  (multi_ok ? "" : "; the pair objective alone only (the mixed one is refused for this update method)") +
                  (pairs_ready_ ? "" : "; workspaces not allocated yet"));
+        out += std::string(" | term pairs: ") + (cfg_.world_size > 1 ? "refused (data parallel)"
+               : std::string("term_pair_loss (multiplied rows) behind the loss kernel on its stream, entries merged into the words passes") +
+                 (multi_ok ? "" : "; the pair objective alone only (the mixed one is refused for this update method)") +
+                 (terms_ready_ ? "" : "; workspaces not allocated yet"));
     }
     if (corpus_) out += " | corpus=" + std::to_string(corpus_->bytes) + "B in HBM (" + std::to_string(corpus_->num_tokens) + " tokens, " +
                         std::to_string(corpus_->num_documents) + " documents)";
@@ -2199,8 +2226,9 @@ void Model::update(float lr, float scaled_lambda) {
     NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_, 0));
     csr_joined_ents_ = csr_joined_words_ = true;
     if (mode_ == MODE_PAIRS) {
-        // only the documents table has a gradient: the other parameters are left alone (cpp/params.cu:304-307), their step counters too
-        update_entities(lr, scaled_lambda, stream_);
+        // only the pairs' table has a gradient: the other parameters are left alone (cpp/params.cu:304-307), their step counters too
+        if (pair_table_ == 1) update_words(lr, scaled_lambda, nullptr);
+        else update_entities(lr, scaled_lambda, stream_);
         NVSM_HIP_CHECK(hipGetLastError());
         have_grads_ = false;
         return;
@@ -2350,7 +2378,7 @@ void Model::step(const ForwardRequest& given, float lr, float* cost) {
     // (only when side stream 2 is the stream that built the words CSR: the untouched pass reads its row bounds, and the next
     //  step's sort on that stream clears them — a pass queued on any other stream would have neither order)
     const bool words_aside = untouched_aside && !dp && !words_.lazy && words_csr_stream_ == aux2_stream_ && !words_untouched_hoisted_ &&
-                             row_pass_split(csr_of(words_, B_ * cfg_.window_size));
+                             row_pass_split(csr_of(words_, words_entries(B_)));
     update_words(lr, sl, words_aside ? aux2_stream_ : nullptr);
     if (words_aside) {
         NVSM_HIP_CHECK(hipEventRecord(ev_T_done_, aux2_stream_));      // (again: now it stands for the streaming decay too)
@@ -2549,12 +2577,14 @@ void Model::ensure_pair_workspace() {
     pair_ids64_.alloc(2 * Mx); pair_w_.alloc(Mx); pair_probs_.alloc(Mx); pair_mults_.alloc(Mx); instw_scaled_.alloc(B);
     pair_loss_.alloc(1, true);
     alloc_sums(sums_pair_, 1, pair_loss_blocks(Mx, de), 1);
-    NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_, hipEventDisableTiming));
-    NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_copied_, hipEventDisableTiming));
+    if (!ev_pair_) {      // (a term-pair call made them already)
+        NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_, hipEventDisableTiming));
+        NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_copied_, hipEventDisableTiming));
+    }
     pairs_ready_ = true;
 }
 
-void Model::stage_pairs(const nvsm_pair_batch& pairs, int* ids_dst) {
+void Model::stage_pairs(const nvsm_pair_batch& pairs, int* ids_dst, int64_t limit, int code) {
     const int64_t M = pairs.num_pairs;
     // the previous pair kernel may still be reading the staged weights
     if (pair_pending_) { NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_pair_, 0)); pair_pending_ = false; }
@@ -2570,7 +2600,7 @@ void Model::stage_pairs(const nvsm_pair_batch& pairs, int* ids_dst) {
         NVSM_HIP_CHECK(hipEventRecord(ev_pair_copied_, stream_));
         pair_copy_pending_ = true;
     }
-    launch_narrow_i64(ids64, ids_dst, 2 * M, cfg_.num_entities, err_host_, NVSM_BAD_ENTITY_ID, stream_);
+    launch_narrow_i64(ids64, ids_dst, 2 * M, limit, err_host_, code, stream_);
 }
 
 void Model::launch_pairs(hipStream_t strm, hipEvent_t after) {
@@ -2606,7 +2636,7 @@ void Model::forward_pairs_only(const ForwardRequest& req) {
     RangeScope range_cc("ComputeCost");
     begin_forward(MODE_PAIRS, 0, req.pairs->num_pairs, nullptr);
     join_E();      // the previous documents update: reads the rows / coefficients this pass rewrites, writes E
-    stage_pairs(*req.pairs, ids_p_);
+    stage_pairs(*req.pairs, ids_p_, cfg_.num_entities, NVSM_BAD_ENTITY_ID);
     NVSM_HIP_CHECK(hipEventRecord(ev_inputs_, stream_));
     inputs_recorded_ = true;
     last_batch_on_host_ = false;
@@ -2632,6 +2662,131 @@ void Model::step_mixed(const nvsm_batch* text, const int64_t* entity_ids, const 
         return;
     }
     step(ForwardRequest{text, nullptr, entity_ids, &pairs, mix}, lr, cost);
+}
+
+// ---------------------------------------------------------------------------------------------
+// term-term pairs — RepresentationSimilarity::Objective on WORD_REPRS (cpp/objective.cu:485-696) and its mixture with the text
+// objective, TextEntityTermTerm (:747-794). The arithmetic is pairs.hip's words-table form; the layout is model.h's; DESIGN.md §15.
+// ---------------------------------------------------------------------------------------------
+void Model::check_term_request(const nvsm_batch* text, const nvsm_pair_batch& pairs, const nvsm_mixture* mix) const {
+    if (pairs.num_pairs < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_pairs must be at least 1");
+    if (pairs.num_pairs > cfg_.max_batch_size) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_pairs must not exceed max_batch_size");
+    if (!pairs.pairs) throw Error(NVSM_ERR_INVALID_ARGUMENT, "pairs are required");
+    if (text) {
+        if (!mix) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: mix");
+        // CHECK_NE(text_entity_weight_, 0.0) / CHECK_NE(term_term_weight_, 0.0), cpp/objective.cu:757-758 (negative shares have no meaning)
+        if (!(mix->text_weight > 0.f) || !(mix->pair_weight > 0.f))
+            throw Error(NVSM_ERR_INVALID_ARGUMENT, "text_weight and pair_weight of a mixture must both be > 0");
+    }
+    if (cfg_.world_size > 1) throw Error(NVSM_ERR_UNSUPPORTED, "the term-term objective is not implemented under data parallelism (world_size > 1)");
+    if (text && cfg_.update_method == NVSM_ADAGRAD)
+        throw Error(NVSM_ERR_UNSUPPORTED, "Adagrad currently does not implement multiple gradients.");            // cpp/updates_adagrad.cu:108
+    if (text && cfg_.update_method == NVSM_ADAM && cfg_.adam_mode <= NVSM_ADAM_SPARSE)
+        throw Error(NVSM_ERR_UNSUPPORTED, "Sparse Adam currently does not implement multiple gradients.");        // cpp/updates_adam.cu:348
+    const int dw = cfg_.word_repr_size;
+    if (dw > 1024 || (dw > 256 && dw % 4 != 0))
+        throw Error(NVSM_ERR_UNSUPPORTED, "the term-term objective covers word_repr_size up to 1024 where it is a multiple of 4, and up to 256 otherwise");
+    const int64_t rows = static_cast<int64_t>(cfg_.max_batch_size) * 3;      // B + 2M gradient source rows at most
+    if (rows * cfg_.window_size >= (int64_t(1) << 26))
+        throw Error(NVSM_ERR_UNSUPPORTED, "term pairs: 3 x max_batch_size x window_size must stay below 2^26 (entry ids of the merged update)");
+}
+
+// First term-pair call of a handle: what model.h lists. Every stream is quiet and no forward result survives.
+void Model::ensure_term_workspace() {
+    if (terms_ready_) return;
+    synchronize();
+    settle_words_stamp();
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    have_forward_ = have_grads_ = false;      // (the forward result lived in the buffers replaced below)
+    const int64_t B = cfg_.max_batch_size, Mx = cfg_.max_batch_size;
+    const int dw = cfg_.word_repr_size, w = cfg_.window_size;
+    gphrase_.alloc((B + 2 * Mx) * dw); msq_w_.alloc(B + 2 * Mx); widx_.alloc(B * w + 2 * Mx);
+    csr_joined_ents_ = csr_joined_words_ = true;
+    words_untouched_hoisted_ = words_untouched_pending_ = words_snapshot_early_ = false;
+    alloc_table_csr(words_, B * w + 2 * Mx, words_.idx[0].chunk_order.p != nullptr);
+    term_vals_.alloc(B * w + 2 * Mx); wts_ext_.alloc((B + 2 * Mx) * w);
+    // the per-source buffers of sparse Adam / Adagrad: the pair objective alone has 2M source rows
+    if (U_.p) U_.alloc(std::max<size_t>(U_.n, static_cast<size_t>(2 * Mx) * dw));
+    if (scale_w_.p) scale_w_.alloc(std::max<size_t>(scale_w_.n, static_cast<size_t>(2 * Mx)));
+    if (!pair_ids64_.p) {
+        pair_ids64_.alloc(2 * Mx); pair_w_.alloc(Mx); pair_probs_.alloc(Mx); pair_mults_.alloc(Mx); instw_scaled_.alloc(B);
+        pair_loss_.alloc(1, true);
+    }
+    alloc_sums(sums_term_, 1, pair_loss_blocks(Mx, dw), 1);
+    if (!ev_pair_) {
+        NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_, hipEventDisableTiming));
+        NVSM_HIP_CHECK(hipEventCreateWithFlags(&ev_pair_copied_, hipEventDisableTiming));
+    }
+    terms_ready_ = true;
+}
+
+void Model::launch_term_pairs() {
+    const int dw = cfg_.word_repr_size;
+    const int64_t B = mode_ == MODE_MIXED ? B_ : 0;      // the pair entries' rows / means of squares / ids sit behind the text objective's
+    PairArgs a{};
+    a.E = words_.P.p; a.E_rows = words_.rows;
+    if (words_.lazy) a.lazyE = lazy_view(words_);
+    a.ids = widx_.p + B * cfg_.window_size; a.w = pair_wdev_;
+    a.X = gphrase_.p + B * dw; a.coef = nullptr; a.coef_stride = 0; a.sq = msq_w_.p + B;
+    a.probs = pair_probs_.p; a.mults = pair_mults_.p;
+    a.loss_acc = pair_loss_.p; a.sums = sums_term_.ws;
+    a.M = M_; a.de = dw; a.mul_rows = 1;
+    fill_clamps(a, cfg_.clip_sigmoid != 0, dw);                                             // objective.cu:546-550, :622-623
+    a.inv_batch = static_cast<float>(std::exp(-std::log(static_cast<double>(M_))));         // :609
+    a.scale = pair_scale_;
+    timed_launch(prof, "term_pair_loss", stream_, /*single=*/true, [&] { launch_pair_loss(a, stream_); });
+    NVSM_HIP_CHECK(hipEventRecord(ev_pair_, stream_));
+    pair_stream_ = stream_;
+    pair_pending_ = false;
+}
+
+void Model::compute_cost_term_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix) {
+    check_term_request(text, pairs, mix);
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    ensure_term_workspace();
+    ForwardRequest req{text, nullptr, text ? entity_ids : nullptr, &pairs, text ? mix : nullptr};
+    req.term_pairs = true;
+    forward(req);
+}
+
+// the term-pair objective alone: ids -> words CSR -> kernel, all on the main stream; no other parameter is read or written
+void Model::forward_terms_only(const ForwardRequest& req) {
+    RangeScope range_cc("ComputeCost");
+    begin_forward(MODE_PAIRS, 0, req.pairs->num_pairs, nullptr);
+    pair_table_ = 1;
+    // every writer of W in front of the kernel: the previous words update ran on this stream; its hoisted / streamed decays did not
+    if (words_untouched_pending_) { NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_untouched_, 0)); words_untouched_pending_ = false; }
+    if (words_tail_pending_) { join_T(); words_tail_pending_ = false; }
+    settle_words_stamp();
+    stage_pairs(*req.pairs, widx_.p, cfg_.num_words, NVSM_BAD_WORD_ID);
+    NVSM_HIP_CHECK(hipEventRecord(ev_inputs_, stream_));
+    inputs_recorded_ = true;
+    last_batch_on_host_ = false;
+    words_untouched_hoisted_ = false;      // (as every words CSR build says: launch_csr_builds)
+    words_snapshot_early_ = false;
+    { PROF("csr_words"); build_csr(words_, widx_.p, 2 * M_, stream_); }      // entry i is source row i
+    NVSM_HIP_CHECK(hipEventRecord(ev_csr_, stream_));
+    words_csr_stream_ = stream_;
+    launch_term_pairs();
+    NVSM_HIP_CHECK(hipGetLastError());
+    have_forward_ = true;
+    if (debug_) { NVSM_HIP_CHECK(hipStreamSynchronize(stream_)); raise_device_error(); }
+}
+
+// compute_cost_term_mixed; compute_gradients; update(scaled lambda) through nvsm_step's streams. The pair kernel sits on the main
+// stream in both forms, so per buffer the order is that of the three calls: the same bits.
+void Model::step_term_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix, float lr, float* cost) {
+    check_term_request(text, pairs, mix);
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    ensure_term_workspace();
+    if (!text) {
+        compute_cost_term_mixed(nullptr, nullptr, pairs, nullptr);
+        finish_unfused(lr, cost);
+        return;
+    }
+    ForwardRequest req{text, nullptr, entity_ids, &pairs, mix};
+    req.term_pairs = true;
+    step(req, lr, cost);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2707,8 +2862,10 @@ int64_t Model::tensor_size(const std::string& name) {
     if (name == "grad_transform") return static_cast<int64_t>(de) * dw;
     if (name == "grad_entity") return N * de;
     if (name == "arrival_counters") return 6;
-    if (name == "pair_probs" || name == "pair_multipliers") return M_;
+    if (name == "pair_probs" || name == "pair_multipliers" || name == "term_pair_probs" || name == "term_pair_multipliers") return M_;
     if (name == "grad_pair_entity") return 2 * M_ * de;
+    if (name == "grad_pair_word") return 2 * M_ * dw;
+    if (name == "term_pair_msq") return 2 * M_;
     if (name == "pair_cost" || name == "text_cost") return 1;
     throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown tensor: " + name);
 }
@@ -2717,8 +2874,12 @@ void Model::get_tensor(const std::string& name, float* dst, int64_t count) {
     if (!have_forward_) throw Error(NVSM_ERR_STATE, "no forward result");
     if (count != tensor_size(name)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "size mismatch for " + name);
     const bool needs_grads = name.rfind("grad_", 0) == 0;
-    const bool pair_tensor = name.rfind("pair_", 0) == 0 || name == "grad_pair_entity";
-    if (pair_tensor && mode_ == MODE_TEXT) throw Error(NVSM_ERR_STATE, name + " requires a forward result with pairs (compute_cost_mixed)");
+    const bool term_tensor = name.rfind("term_pair_", 0) == 0 || name == "grad_pair_word";
+    const bool pair_tensor = name.rfind("pair_", 0) == 0 || name == "grad_pair_entity" || term_tensor;
+    if (pair_tensor && mode_ == MODE_TEXT) throw Error(NVSM_ERR_STATE, name + " requires a forward result with pairs (compute_cost_mixed / compute_cost_term_mixed)");
+    if (term_tensor && pair_table_ != 1) throw Error(NVSM_ERR_STATE, name + " requires a forward result with term pairs (compute_cost_term_mixed)");
+    if ((name == "pair_probs" || name == "pair_multipliers" || name == "grad_pair_entity") && pair_table_ != 0)
+        throw Error(NVSM_ERR_STATE, name + " requires a forward result with document pairs (compute_cost_mixed)");
     if (mode_ == MODE_PAIRS && !pair_tensor && name != "arrival_counters")
         throw Error(NVSM_ERR_STATE, name + " does not exist in a forward result of the pair objective alone");
     if (mode_ != MODE_MIXED && name == "text_cost") throw Error(NVSM_ERR_STATE, "text_cost requires a mixed forward result");
@@ -2743,8 +2904,10 @@ void Model::get_tensor(const std::string& name, float* dst, int64_t count) {
         else
             launch_materialize_grad_entity(coef_.p, proj_.p, B_ * R_, R_, cfg_.entity_repr_size, grad_entity_.p, stream_);
         src = grad_entity_.p;
-    } else if (name == "pair_probs") src = pair_probs_.p;
-    else if (name == "pair_multipliers") src = pair_mults_.p;
+    } else if (name == "pair_probs" || name == "term_pair_probs") src = pair_probs_.p;
+    else if (name == "pair_multipliers" || name == "term_pair_multipliers") src = pair_mults_.p;
+    else if (name == "term_pair_msq") src = msq_w_.p + (mode_ == MODE_MIXED ? B_ : 0);      // ... and their means of squares
+    else if (name == "grad_pair_word") src = gphrase_.p + (mode_ == MODE_MIXED ? B_ : 0) * cfg_.word_repr_size;      // the multiplied rows, as the kernel left them
     else if (name == "pair_cost" || name == "text_cost") {
         (void)get_cost();
         dst[0] = static_cast<float>(name == "pair_cost" ? pair_cost_ : text_cost_);

@@ -147,6 +147,10 @@ class Model {
     // cpp/objective.cu:698-745): see "entity-entity pairs" below
     void compute_cost_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix);
     void step_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix, float lr, float* cost);
+    // the term-term similarity objective on the words table, alone or mixed into the text objective (TextEntityTermTerm,
+    // cpp/objective.cu:747-794): see "term-term pairs" below
+    void compute_cost_term_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix);
+    void step_term_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix, float lr, float* cost);
 
     // training from an HBM-resident corpus (include/cunvsm_amd.h; corpus.hip): see "window references" below
     void corpus_upload(const nvsm_corpus* corpus);      // null: free it
@@ -234,6 +238,7 @@ class Model {
         const int64_t* entity_ids = nullptr;
         const nvsm_pair_batch* pairs = nullptr;         // the pair objective rides along (or stands alone)
         const nvsm_mixture* mix = nullptr;              // ... with these shares
+        bool term_pairs = false;                        // ... on the words table (pairs of word ids) instead of the documents table
         // what only a fused step knows up front
         hipEvent_t loss_event = nullptr;                // the loss kernel carries it as its completion event
         bool hoist = false;                             // queue the decay of the words rows without entries behind the CSR build,
@@ -246,6 +251,8 @@ class Model {
     struct ForwardCall {
         const ForwardRequest& req;
         int64_t B = 0, N = 0, M2 = 0;                   // windows, document ids (B * R), pair ids (2 M) of this rank
+        int64_t T2 = 0;                                 // term-pair ids (2 M) behind the word ids (M2 is 0 then)
+        bool terms = false;
         int64_t Bu = 0;                                 // windows of the table updates (exact tables: of all ranks)
         bool mixed = false, fused_prologue = false;
         int sort_layout = 0;
@@ -402,10 +409,34 @@ class Model {
     double pair_cost_ = 0.0, text_cost_ = 0.0;
     void check_pair_request(const nvsm_batch* text, const nvsm_pair_batch& pairs, const nvsm_mixture* mix) const;
     void ensure_pair_workspace();
-    void stage_pairs(const nvsm_pair_batch& pairs, int* ids_dst);      // ids narrowed into ids_dst, weights on the device (main stream)
+    // ids narrowed into ids_dst, weights on the device (main stream); ids outside [0, limit) become row 0 and flag `code`
+    void stage_pairs(const nvsm_pair_batch& pairs, int* ids_dst, int64_t limit, int code);
     void launch_pairs(hipStream_t s, hipEvent_t after);                // the pair kernel of the current forward result
-    int64_t ents_entries(int64_t text_windows) const { return text_windows * R_ + (mode_ != MODE_TEXT ? 2 * M_ : 0); }
+    int64_t ents_entries(int64_t text_windows) const { return text_windows * R_ + (mode_ != MODE_TEXT && pair_table_ == 0 ? 2 * M_ : 0); }
     float scaled_lambda_for(int mode, int64_t B, int64_t M) const;
+
+    // ---- term-term pairs (pairs.hip, the words-table form). The pair entries ride in the words table's sorted passes:
+    // the 2M MULTIPLIED gradient rows sit behind the text objective's in gphrase_ (rows B .. B + 2M - 1), their means of squares at
+    // msq_w_[B + i], pair entry i carries the entry id (B + i) * w and weighs 1, and the words CSR is built from the step's B * w word
+    // ids followed by the 2M pair ids (widx_). The pair objective alone: entries = 2M, div = 1, widx_ = the pair ids. With feature
+    // weights the B * w weights are copied into wts_ext_ ((B + 2M) * w floats) and slot (B + i) * w is 1. Allocated by the first
+    // term-pair call (ensure_term_workspace), beyond what a handle without one holds:
+    //   gphrase_ +2Mx·d_w floats, msq_w_ +2Mx, widx_ +2Mx ints, term_vals_ B·w + 2Mx ints, wts_ext_ (B + 2Mx)·w floats, the words CSR
+    //   workspace again for B·w + 2Mx entries, U_ / scale_w_ (sparse Adam / Adagrad) for max(B, 2Mx) source rows, sums_term_, and — unless
+    //   an entity-pair call made them — pair_ids64_ 2Mx int64, pair_w_ / pair_probs_ / pair_mults_ Mx floats, instw_scaled_ B floats
+    // with B = Mx = max_batch_size.
+    int pair_table_ = 0;                        // the current forward result's pairs are 0: document pairs, 1: term pairs
+    bool terms_ready_ = false;
+    DevBuf<int> term_vals_;                     // entry ids of the merged words CSR
+    DevBuf<float> wts_ext_;
+    SumsBufs sums_term_;
+    void check_term_request(const nvsm_batch* text, const nvsm_pair_batch& pairs, const nvsm_mixture* mix) const;
+    void ensure_term_workspace();
+    void launch_term_pairs();                   // the words-table pair kernel of the current forward result, on the main stream
+    void forward_terms_only(const ForwardRequest& req);
+    bool term_result() const { return mode_ != MODE_TEXT && pair_table_ == 1; }
+    // entries of the words update of the current forward result for `text_windows` windows
+    int64_t words_entries(int64_t text_windows) const { return text_windows * cfg_.window_size + (term_result() ? 2 * M_ : 0); }
 
     // ---- window references (corpus.hip). The corpus lives in HBM from nvsm_corpus_upload on; a *_windows call is compute_cost / step
     // on a batch that window_expand_kernel writes into a host batch's staging set (compute_cost F1). Everything here is allocated by

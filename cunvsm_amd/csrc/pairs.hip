@@ -22,11 +22,32 @@
 // lane; a row shorter than a wave's 1 KB shares the wave with other pairs (groups of G = 2 .. 64 lanes, one pair per group and turn),
 // a longer one (d_e up to 1024) takes up to four turns of the whole wave. 44-54 registers at d_e = 256: eight waves per SIMD, each with two rows
 // (2 x 16 B per lane) requested per turn, is 64 KB of loads in flight per CU — twice what the memory system needs to stream.
+//
+// The WORDS-table form (template switch MUL; PairArgs::mul_rows): RepresentationSimilarity::Objective with param_id_ == WORD_REPRS
+// (cpp/objective.cu:485-696), the term-term half of TextEntityTermTerm (:747-794). For a batch of M pairs (a_p, b_p, ω_p) of model
+// word ids, interleaved:
+//   s_p       = W[a_p]·W[b_p];   prob_p = clip(σ(s_p), 1e-7, 1 − 1e-7) in float32 with the two-branch sigmoid
+//   cost      = −(1/M)·Σ ω_p·log prob_p;   mult_p = ω_p·d(prob_p)·exp(−log M), the derivative clamp at 1e-6
+//   gradient  entry 2p = mult_p·W[b_p], entry 2p + 1 = mult_p·W[a_p], both from the rows as they were at compute_cost
+// Window 1, no per-entry weights (include/cuNVSM/intermediate_results.h:328-334), gradient ascent, scaled λ = λ/M; only the words table
+// has a gradient (cpp/params.cu:304-307). Mixed with the text objective: cost = (cost_text + cost_pairs)/2, scaled λ = (λ/B + λ/M)/2, the
+// pair gradient scaled by w_tt/(w_te + w_tt) (MergeGradientsFn, cpp/intermediate_results.cu:3-60), ONE update of the words table from
+// both gradient lists (CompositeGradients, cpp/storage.cu:65-99).
+// The words table pass weighs an entry's mean of squares LINEARLY by its coefficient (update.hip: sq = c·s, because the reference
+// scatters v with the same repr_weights as the gradient, updates_adam.cu:242-252), where the documents pass has c²·s. A pair entry can
+// therefore not ride as "raw row + coefficient": its v share would come out as c_p·msq instead of c_p²·msq. So this form writes the
+// MULTIPLIED rows X[2p] = c_p·W[b_p], X[2p + 1] = c_p·W[a_p] (c_p = mult_p x the mixture scale, one v_mul per element), the entries
+// weigh 1, and sq[·] is the mean of squares of the stored rows. c_p is known in the group's last lane only, behind the reduction of the
+// dot product: that lane hands it to its group (one ds_bpermute), and the squares are summed behind the multiplication.
+// A bandwidth kernel like the documents-table form: 2·M·d_w·4 bytes in, the same out. Registers from the compiler's output (hipcc -O3,
+// gfx950; profiles/NOTES_term_pairs.md lists every instantiation): d_w = 300 is <V = 4, NITER = 2, G = 64>, 63 VGPRs (56 with a lazily
+// decayed table), d_w = 128 <4, 1, 32> 52 (44): eight waves per SIMD; four column turns (d_w 516 .. 1024) 90 (76): five (six).
 #include "../../include/cunvsm_amd.h"
 #include "kernels.h"
 #include "device_utils.h"
 
 #include <algorithm>
+#include <string>
 
 namespace cunvsm {
 
@@ -52,8 +73,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-// V floats per lane and turn; NITER column turns of the group (NITER > 1 only with G = 64); LAZY: E decays lazily (LazyView)
-template <int V, int NITER, int G, bool LAZY>
+// V floats per lane and turn; NITER column turns of the group (NITER > 1 only with G = 64); LAZY: E decays lazily (LazyView);
+// MUL: the words-table form (see the head of this file) — every statement it adds or leaves out sits behind `if constexpr (MUL)`
+template <int V, int NITER, int G, bool LAZY, bool MUL>
 __global__ __launch_bounds__(256) void pair_loss_kernel(PairArgs a) {
 #pragma clang fp contract(on)
     __shared__ float hist[kLazyHistory];
@@ -129,29 +151,70 @@ __global__ __launch_bounds__(256) void pair_loss_kernel(PairArgs a) {
                 dot += x * y; qa += x * x; qb += y * y;
             }
         }
-        dot = group_sum<G>(dot); qa = group_sum<G>(qa); qb = group_sum<G>(qb);
-        // the rows, swapped: entry 2p's gradient source is E[b_p], entry 2p + 1's is E[a_p]
-        if (pv) {
-            float* xa = a.X + static_cast<size_t>(2 * p) * de;
+        dot = group_sum<G>(dot);
+        if constexpr (MUL) {
+            // probability, log and coefficient once per pair, in the group's last lane, which hands the coefficient to its group
+            float c = 0.f;
+            if (leader && pv) {
+                const float sx = dot;
+                float pr = (sx >= 0.f) ? 1.f / (1.f + expf(-sx)) : expf(sx) / (1.f + expf(sx));
+                pr = fminf(fmaxf(pr, a.sig_eps), a.sig_hi);
+                lane_loss += static_cast<double>(logf(pr) * w);
+                const float d = (static_cast<double>(pr) >= a.d_hi || pr <= a.d_eps) ? 0.f : 1.f - pr;
+                c = (w * (d * a.inv_batch)) * a.scale;
+                a.probs[p] = pr;
+                a.mults[p] = c;
+            }
+            c = __shfl(c, lane | (G - 1), 64);
+            // the multiplied rows (one multiplication per element) and the sums of their squares
+            float ga = 0.f, gb = 0.f;
 #pragma unroll
             for (int it = 0; it < NITER; ++it) {
-                if (cv[it]) { stv<V>(xa + col[it], eb[it]); stv<V>(xa + de + col[it], ea[it]); }
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    ea[it][i] = c * ea[it][i]; eb[it][i] = c * eb[it][i];
+                    const float x = cv[it] ? ea[it][i] : 0.f, y = cv[it] ? eb[it][i] : 0.f;
+                    ga += x * x; gb += y * y;
+                }
             }
-        }
-        // probability, log and multiplier once per pair, in the group's last lane
-        if (leader && pv) {
-            const float sx = dot;
-            float pr = (sx >= 0.f) ? 1.f / (1.f + expf(-sx)) : expf(sx) / (1.f + expf(sx));
-            pr = fminf(fmaxf(pr, a.sig_eps), a.sig_hi);
-            lane_loss += static_cast<double>(logf(pr) * w);
-            const float d = (static_cast<double>(pr) >= a.d_hi || pr <= a.d_eps) ? 0.f : 1.f - pr;
-            const float m = (w * (d * a.inv_batch)) * a.scale;
-            a.probs[p] = pr;
-            a.mults[p] = m;
-            a.coef[static_cast<size_t>(2 * p) * a.coef_stride] = m;
-            a.coef[static_cast<size_t>(2 * p + 1) * a.coef_stride] = m;
-            a.sq[2 * p] = qb * a.inv_de;
-            a.sq[2 * p + 1] = qa * a.inv_de;
+            ga = group_sum<G>(ga); gb = group_sum<G>(gb);
+            // swapped: entry 2p's gradient row is c·W[b_p], entry 2p + 1's is c·W[a_p]
+            if (pv) {
+                float* xa = a.X + static_cast<size_t>(2 * p) * de;
+#pragma unroll
+                for (int it = 0; it < NITER; ++it) {
+                    if (cv[it]) { stv<V>(xa + col[it], eb[it]); stv<V>(xa + de + col[it], ea[it]); }
+                }
+            }
+            if (leader && pv) {
+                a.sq[2 * p] = gb * a.inv_de;
+                a.sq[2 * p + 1] = ga * a.inv_de;
+            }
+        } else {
+            qa = group_sum<G>(qa); qb = group_sum<G>(qb);
+            // the rows, swapped: entry 2p's gradient source is E[b_p], entry 2p + 1's is E[a_p]
+            if (pv) {
+                float* xa = a.X + static_cast<size_t>(2 * p) * de;
+#pragma unroll
+                for (int it = 0; it < NITER; ++it) {
+                    if (cv[it]) { stv<V>(xa + col[it], eb[it]); stv<V>(xa + de + col[it], ea[it]); }
+                }
+            }
+            // probability, log and multiplier once per pair, in the group's last lane
+            if (leader && pv) {
+                const float sx = dot;
+                float pr = (sx >= 0.f) ? 1.f / (1.f + expf(-sx)) : expf(sx) / (1.f + expf(sx));
+                pr = fminf(fmaxf(pr, a.sig_eps), a.sig_hi);
+                lane_loss += static_cast<double>(logf(pr) * w);
+                const float d = (static_cast<double>(pr) >= a.d_hi || pr <= a.d_eps) ? 0.f : 1.f - pr;
+                const float m = (w * (d * a.inv_batch)) * a.scale;
+                a.probs[p] = pr;
+                a.mults[p] = m;
+                a.coef[static_cast<size_t>(2 * p) * a.coef_stride] = m;
+                a.coef[static_cast<size_t>(2 * p + 1) * a.coef_stride] = m;
+                a.sq[2 * p] = qb * a.inv_de;
+                a.sq[2 * p + 1] = qa * a.inv_de;
+            }
         }
     }
     const double wl = wave_sum_f64(lane_loss);
@@ -165,8 +228,13 @@ __global__ __launch_bounds__(256) void pair_loss_kernel(PairArgs a) {
 
 template <int V, int NITER, int G>
 void launch_pair_t(const PairArgs& a, int grid, hipStream_t s) {
-    if (a.lazyE.stamp) NVSM_LAUNCH((pair_loss_kernel<V, NITER, G, true>), dim3(grid), dim3(256), 0, s, a);
-    else NVSM_LAUNCH((pair_loss_kernel<V, NITER, G, false>), dim3(grid), dim3(256), 0, s, a);
+    if (a.mul_rows) {
+        if (a.lazyE.stamp) NVSM_LAUNCH((pair_loss_kernel<V, NITER, G, true, true>), dim3(grid), dim3(256), 0, s, a);
+        else NVSM_LAUNCH((pair_loss_kernel<V, NITER, G, false, true>), dim3(grid), dim3(256), 0, s, a);
+        return;
+    }
+    if (a.lazyE.stamp) NVSM_LAUNCH((pair_loss_kernel<V, NITER, G, true, false>), dim3(grid), dim3(256), 0, s, a);
+    else NVSM_LAUNCH((pair_loss_kernel<V, NITER, G, false, false>), dim3(grid), dim3(256), 0, s, a);
 }
 
 template <int V>
@@ -203,6 +271,13 @@ __global__ void pair_scale_weights_kernel(const float* __restrict__ w, float sca
         out[i] = (w ? w[i] : 1.f) * scale;
 }
 
+__global__ void pair_entry_weights_kernel(const float* __restrict__ w, float* __restrict__ out, int64_t n_text, int64_t first_src, int R, int64_t n_pair) {
+    for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n_text + n_pair; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        if (i < n_text) out[i] = w[i];
+        else out[(first_src + (i - n_text)) * R] = 1.f;
+    }
+}
+
 __global__ void pair_materialize_kernel(const float* __restrict__ coef, int coef_stride, const float* __restrict__ X, int64_t n, int de,
                                         float* __restrict__ out) {
     for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n * de; i += static_cast<int64_t>(gridDim.x) * blockDim.x)
@@ -220,10 +295,11 @@ int pair_loss_blocks(int64_t M, int de) {
 
 void launch_pair_loss(const PairArgs& a_in, hipStream_t s) {
     if (a_in.M <= 0) return;
-    if (a_in.de > 1024 || a_in.de < 1) throw Error(NVSM_ERR_UNSUPPORTED, "pair objective: entity_repr_size must be in [1, 1024]");
+    const std::string dim_name = a_in.mul_rows ? "word_repr_size" : "entity_repr_size";
+    if (a_in.de > 1024 || a_in.de < 1) throw Error(NVSM_ERR_UNSUPPORTED, "pair objective: " + dim_name + " must be in [1, 1024]");
     int V, G, niter;
     pair_plan(a_in.de, &V, &G, &niter);
-    if (niter > 4) throw Error(NVSM_ERR_UNSUPPORTED, "pair objective: entity_repr_size beyond 256 must be a multiple of 4");
+    if (niter > 4) throw Error(NVSM_ERR_UNSUPPORTED, "pair objective: " + dim_name + " beyond 256 must be a multiple of 4");
     PairArgs a = a_in;
     const int grid = pair_loss_blocks(a.M, a.de);
     if (grid > a.sums.contrib_cap) throw Error(NVSM_ERR_INVALID_ARGUMENT, "pair objective: more pairs than the workspace was sized for");
@@ -239,6 +315,11 @@ void launch_pair_entry_ids(int* vals, int64_t n_text, int64_t first_src, int R, 
 void launch_pair_scale_weights(const float* w, float scale, float* out, int64_t n, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(pair_scale_weights_kernel, dim3(stream_grid(n, 256)), dim3(256), 0, s, w, scale, out, n);
+}
+
+void launch_pair_entry_weights(const float* w, float* out, int64_t n_text, int64_t first_src, int R, int64_t n_pair, hipStream_t s) {
+    if (n_text + n_pair <= 0) return;
+    hipLaunchKernelGGL(pair_entry_weights_kernel, dim3(stream_grid(n_text + n_pair, 256)), dim3(256), 0, s, w, out, n_text, first_src, R, n_pair);
 }
 
 void launch_pair_materialize(const float* coef, int coef_stride, const float* X, int64_t n, int de, float* out, hipStream_t s) {

@@ -12,7 +12,18 @@
 //     built after the index source and before the model is initialised, so its shuffles sit where the reference's do in the one
 //     generator's stream. Refused: w = 1 (CHECK_NE(text_entity_weight_, 0.0), cpp/objective.cu:708), w != 0 without a similarity
 //     file, Adagrad and sparse Adam together with pairs (the reference's own refusal), pairs under data parallelism, with
-//     --l2_entity_normalization or with --check_gradients, and the term-term objective (--term_similarity_weight != 0).
+//     --l2_entity_normalization or with --check_gradients.
+//   * the term-term objective (TextEntityTermTerm, cpp/main.cu:742-750): --term_similarities <path> names a file of `term term weight`
+//     lines (terms outside the model's vocabulary are skipped with LoadSimilarities' warning; the map is build_term_identifiers_map())
+//     and --term_similarity_weight w (0 < w < 1) trains with the weights (1 - w, w), through the same PairSource /
+//     RepeatingPairSource(-1), generator hand-over and skip rule as the entity mixture. THIS DEPARTS FROM THE REFERENCE, which reuses
+//     the second positional argument for the term pairs: here a second positional argument always names DOCUMENT similarities, and
+//     --term_similarity_weight != 0 without --term_similarities stays fatal ("--term_similarity_weight must be 0 ..."). The reason is
+//     that command line's history: `--term_similarity_weight 0.3 <collection> <document similarities>` has always been refused here,
+//     docnos are often numbers, numbers can be vocabulary terms, and reading a file of docno pairs as term pairs would train
+//     on them silently. Refused: both similarity weights non-zero (cpp/main.cu:733-745 excludes it), w = 1, Adagrad and sparse Adam
+//     (the reference's own refusal), data parallelism, --device_corpus, --check_gradients, a file none of whose pairs names two terms
+//     of the model.
 //   * --device_corpus: the collection goes into HBM once (nvsm_corpus_upload) and every batch is handed over as window references —
 //     8 bytes per window, slices of the epoch plan in page-locked memory — instead of as a 132-byte-per-window host batch
 //     (nvsm_step_windows_deferred). The epochs, the random stream, the skip rule, the log lines and every number are those of the run
@@ -50,7 +61,7 @@ namespace {
 uint64_t FLAGS_num_epochs, FLAGS_document_cutoff, FLAGS_word_repr_size, FLAGS_entity_repr_size, FLAGS_batch_size, FLAGS_window_size,
     FLAGS_num_random_entities, FLAGS_seed, FLAGS_max_vocabulary_size, FLAGS_min_document_frequency;
 std::string FLAGS_document_list, FLAGS_term_blacklist, FLAGS_update_method, FLAGS_weighting, FLAGS_feature_weighting, FLAGS_nonlinearity,
-    FLAGS_output, FLAGS_stopwords, FLAGS_sampler;
+    FLAGS_output, FLAGS_stopwords, FLAGS_sampler, FLAGS_term_similarities;
 double FLAGS_regularization_lambda, FLAGS_learning_rate, FLAGS_max_document_frequency, FLAGS_entity_similarity_weight,
     FLAGS_term_similarity_weight;
 bool FLAGS_bias_negative_samples, FLAGS_l2_phrase_normalization, FLAGS_l2_entity_normalization, FLAGS_batch_normalization,
@@ -94,6 +105,9 @@ void define_flags(Flags* f) {      // names, defaults and help strings of cpp/ma
     f->define_double("entity_similarity_weight", &FLAGS_entity_similarity_weight, 0.0, "Mixture weight of the entity-entity objective.");
     f->define_double("term_similarity_weight", &FLAGS_term_similarity_weight, 0.0, "Mixture weight of the term-term objective.");
     f->define_string("output", &FLAGS_output, "", "Path to output model.");
+    f->define_string("term_similarities", &FLAGS_term_similarities, "", "Path to term similarities (lines of `term term weight`): the pairs of the "
+                     "term-term objective, mixed in with --term_similarity_weight. (The reference takes them as the second positional argument, which "
+                     "names document similarities here.)");
     // extensions
     f->define_string("stopwords", &FLAGS_stopwords, "", "Stop list applied while indexing the collection (Indri <word> parameter file or plain words).");
     f->define_int64("device", &FLAGS_device, -1, "HIP device ordinal (default: LOCAL_RANK, else the rank, else 0).");
@@ -167,8 +181,9 @@ class Trainer {
 
     // the mixed objective (TextEntityEntityEntity): every step also takes a batch of the repeating pair source; `rng` is the
     // generator the pair source reshuffles with, shared with the model (handed over around every reshuffle)
-    void train_pairs(RepeatingPairSource* pair_source, RNG* rng, float text_weight, float pair_weight) {
-        pair_source_ = pair_source; pair_rng_ = rng;
+    // term_pairs: the pairs are pairs of model word ids (TextEntityTermTerm): the step is nvsm_step_term_mixed
+    void train_pairs(RepeatingPairSource* pair_source, RNG* rng, float text_weight, float pair_weight, bool term_pairs = false) {
+        pair_source_ = pair_source; pair_rng_ = rng; term_pairs_ = term_pairs;
         pair_batch_.reset(new PairBatch(tc_.batch_size));
         mix_.text_weight = text_weight; mix_.pair_weight = pair_weight;
     }
@@ -285,9 +300,11 @@ class Trainer {
                     pb.pairs = pair_batch_->features(); pb.weights = pair_batch_->weights();
                     pb.num_pairs = static_cast<int64_t>(pair_batch_->num_instances()); pb.on_device = 0;
                     if (backpropagate) {
-                        NVSM_CALL(nvsm_step_mixed(model_, &b, nullptr, &pb, &mix_, tc_.learning_rate, &cost));
+                        if (term_pairs_) NVSM_CALL(nvsm_step_term_mixed(model_, &b, nullptr, &pb, &mix_, tc_.learning_rate, &cost));
+                        else NVSM_CALL(nvsm_step_mixed(model_, &b, nullptr, &pb, &mix_, tc_.learning_rate, &cost));
                     } else {
-                        NVSM_CALL(nvsm_compute_cost_mixed(model_, &b, nullptr, &pb, &mix_));
+                        if (term_pairs_) NVSM_CALL(nvsm_compute_cost_term_mixed(model_, &b, nullptr, &pb, &mix_));
+                        else NVSM_CALL(nvsm_compute_cost_mixed(model_, &b, nullptr, &pb, &mix_));
                         NVSM_CALL(nvsm_get_cost(model_, &cost));
                     }
                 } else if (FLAGS_check_gradients) {
@@ -435,6 +452,7 @@ class Trainer {
     IndexSource* ref_source_ = nullptr;
     RepeatingPairSource* pair_source_ = nullptr;
     RNG* pair_rng_ = nullptr;
+    bool term_pairs_ = false;
     std::unique_ptr<PairBatch> pair_batch_;
     nvsm_mixture mix_{};
 };
@@ -474,6 +492,8 @@ int run(int argc, char** argv) {
         if (FLAGS_check_gradients) NVSM_LOG(FATAL) << "--device_corpus cannot be combined with --check_gradients: the gradient checker re-evaluates host batches.";
         if (args.size() >= 3)
             NVSM_LOG(FATAL) << "--device_corpus cannot be combined with a similarity file: window references cover the text-entity objective only.";
+        if (!FLAGS_term_similarities.empty() && FLAGS_term_similarity_weight != 0.0)
+            NVSM_LOG(FATAL) << "--device_corpus cannot be combined with --term_similarities: window references cover the text-entity objective only.";
     }
 
     // ---- data parallelism: --gpus N spawns the ranks; otherwise world size / rank come from the flags or the launcher's environment
@@ -574,9 +594,27 @@ int run(int argc, char** argv) {
     NVSM_CHECK(FLAGS_seed > 0) << "Please specify a --seed value.";
     if (tc.learning_rate == 0.0f) tc.learning_rate = (tc.update_method == NVSM_ADAM) ? 0.001f : 0.01f;   // :710-721
     const std::string similarity_path = args.size() >= 3 ? args[2] : std::string();      // cpp/main.cu:657-660
-    if (FLAGS_term_similarity_weight != 0.0)
-        NVSM_LOG(FATAL) << "only the text-entity objective (LSE / NVSM) and its mixture with the entity-entity objective are implemented on "
-                           "this platform; --term_similarity_weight must be 0.";
+    // (the reference takes the term pairs as the second positional argument, cpp/main.cu:742-750; here they have a flag of their
+    //  own — see the head of this file — and without it the weight stays refused)
+    if (FLAGS_term_similarity_weight != 0.0 && FLAGS_term_similarities.empty())
+        NVSM_LOG(FATAL) << "without --term_similarities <path> only the text-entity objective (LSE / NVSM) and its mixture with the entity-entity "
+                           "objective can be trained; --term_similarity_weight must be 0 unless --term_similarities names the file of "
+                           "`term term weight` lines (a second positional argument always names document similarities).";
+    const bool train_terms = FLAGS_term_similarity_weight != 0.0;                          // :742-750
+    if (train_terms) {
+        if (FLAGS_entity_similarity_weight != 0.0)
+            NVSM_LOG(FATAL) << "--entity_similarity_weight and --term_similarity_weight cannot both be non-zero: one run mixes one pair objective "
+                               "into the text-entity objective.";
+        NVSM_CHECK(FLAGS_term_similarity_weight < 1.0) << "--term_similarity_weight must be below 1: the text-entity objective's weight "
+                                                          "1 - w must not be 0 (CHECK_NE(text_entity_weight_, 0.0)).";
+        if (tc.update_method == NVSM_ADAGRAD) NVSM_LOG(FATAL) << "Adagrad currently does not implement multiple gradients.";
+        if (tc.update_method == NVSM_ADAM && tc.adam_mode <= NVSM_ADAM_SPARSE) NVSM_LOG(FATAL) << "Sparse Adam currently does not implement multiple gradients.";
+        NVSM_CHECK(world_size == 1) << "the term-term objective is not implemented under data parallelism.";
+        NVSM_CHECK(!FLAGS_check_gradients) << "--check_gradients covers the text-entity objective only.";
+        NVSM_CHECK(is_file(FLAGS_term_similarities)) << "cannot read the term similarities " << FLAGS_term_similarities;
+    } else if (!FLAGS_term_similarities.empty()) {
+        NVSM_LOG(WARNING) << "--term_similarity_weight is 0: the term similarities in " << FLAGS_term_similarities << " are not used.";
+    }
     const bool train_pairs = FLAGS_entity_similarity_weight != 0.0;                        // :733-741
     if (train_pairs) {
         if (similarity_path.empty())                                                      // CHECK(!data_config.similarity_path().empty()), :734
@@ -604,7 +642,8 @@ int run(int argc, char** argv) {
     NVSM_LOG(INFO) << "Training configuration: num_epochs: " << tc.num_epochs << " batch_size: " << tc.batch_size << " window_size: "
                    << tc.window_size << " num_random_entities: " << tc.num_random_entities << " regularization_lambda: " << tc.regularization_lambda
                    << " learning_rate: " << tc.learning_rate << " update_method: " << FLAGS_update_method << " no_shuffle: " << (tc.no_shuffle ? "true" : "false")
-                   << " text_entity_weight: " << 1.0 - FLAGS_entity_similarity_weight << " entity_entity_weight: " << FLAGS_entity_similarity_weight;
+                   << " text_entity_weight: " << 1.0 - FLAGS_entity_similarity_weight - FLAGS_term_similarity_weight
+                   << " entity_entity_weight: " << FLAGS_entity_similarity_weight << " term_term_weight: " << FLAGS_term_similarity_weight;
     NVSM_LOG(INFO) << "FLOATING_POINT_TYPE=float32";
 
     RNG rng;
@@ -633,6 +672,8 @@ int run(int argc, char** argv) {
     // initialisation) inside RepeatingSource(-1)
     std::unique_ptr<IdentifiersMapT> identifiers_map;
     if (train_pairs) identifiers_map.reset(new IdentifiersMapT(index_source->build_document_identifiers_map()));
+    // construct_data_source<TextEntityTermTerm::Objective> (:308-333): the same with the term -> model word id map
+    if (train_terms) identifiers_map.reset(new IdentifiersMapT(index_source->build_term_identifiers_map()));
     // (--device_corpus: no prefetch thread — there are no batches to fill; the source itself hands out slices of its plan)
     std::unique_ptr<DataSourceInterface> data_source;
     if (FLAGS_device_corpus) data_source.reset(index_source);
@@ -644,6 +685,14 @@ int run(int argc, char** argv) {
         NVSM_CHECK(pairs->size() > 0) << "no pair of " << similarity_path << " names two documents of the model.";
         NVSM_LOG(INFO) << "Entity-entity objective: " << pairs->size() << " pairs, mixture weights text " << 1.0 - FLAGS_entity_similarity_weight
                        << " / pairs " << FLAGS_entity_similarity_weight << ".";
+        pair_source.reset(new RepeatingPairSource(size_t(-1), pairs));
+    }
+    if (train_terms) {
+        NVSM_LOG(INFO) << "Reading term similarities from " << FLAGS_term_similarities << ".";
+        PairSource* pairs = new PairSource(FLAGS_term_similarities, *identifiers_map, &rng);
+        NVSM_CHECK(pairs->size() > 0) << "no pair of " << FLAGS_term_similarities << " names two terms of the model.";
+        NVSM_LOG(INFO) << "Term-term objective: " << pairs->size() << " pairs, mixture weights text " << 1.0 - FLAGS_term_similarity_weight
+                       << " / pairs " << FLAGS_term_similarity_weight << ".";
         pair_source.reset(new RepeatingPairSource(size_t(-1), pairs));
     }
 
@@ -740,6 +789,8 @@ int run(int argc, char** argv) {
     if (FLAGS_device_corpus) trainer.train_from_refs(index_source);
     if (train_pairs)
         trainer.train_pairs(pair_source.get(), &rng, static_cast<float>(1.0 - FLAGS_entity_similarity_weight), static_cast<float>(FLAGS_entity_similarity_weight));
+    if (train_terms)
+        trainer.train_pairs(pair_source.get(), &rng, static_cast<float>(1.0 - FLAGS_term_similarity_weight), static_cast<float>(FLAGS_term_similarity_weight), true);
     Batch batch(tc.batch_size, tc.window_size);
     std::vector<float> epoch_costs;
 

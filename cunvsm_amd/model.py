@@ -663,6 +663,22 @@ class Model:
                                     C.byref(ps), None if mix is None else C.byref(mix), learning_rate, C.byref(c) if want_cost else None))
         return c.value if want_cost else None
 
+    # -- the term-term similarity objective on the words table: `pairs` holds model word ids, weights = (text, term pairs) --
+    def compute_cost_term_mixed(self, batch, pairs, weights=(0.5, 0.5), entity_ids=None):
+        """nvsm_compute_cost_term_mixed: `pairs` (a PairBatch of model word ids) with the text `batch`, mixed with weights =
+        (text, pairs); batch None: the term-pair objective alone."""
+        st, ids, ps, mix = self._checked_mixed(batch, pairs, entity_ids, weights)
+        check(lib().nvsm_compute_cost_term_mixed(self._h, None if st is None else C.byref(st), None if ids is None else ids.ctypes.data,
+                                                 C.byref(ps), None if mix is None else C.byref(mix)))
+
+    def step_term_mixed(self, batch, pairs, learning_rate, weights=(0.5, 0.5), entity_ids=None, want_cost=False):
+        """nvsm_step_term_mixed: compute_cost_term_mixed + compute_gradients + update with the scaled lambda, as one step."""
+        st, ids, ps, mix = self._checked_mixed(batch, pairs, entity_ids, weights)
+        c = C.c_float()
+        check(lib().nvsm_step_term_mixed(self._h, None if st is None else C.byref(st), None if ids is None else ids.ctypes.data,
+                                         C.byref(ps), None if mix is None else C.byref(mix), learning_rate, C.byref(c) if want_cost else None))
+        return c.value if want_cost else None
+
     def get_cost_f64(self):
         c = C.c_double()
         check(lib().nvsm_get_cost_f64(self._h, C.byref(c)))

@@ -245,6 +245,50 @@ int nvsm_step_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity
                     const nvsm_mixture* mix, float learning_rate, float* cost);
 
 /*
+ * The term-term similarity objective (RepresentationSimilarity::Objective with param_id_ == WORD_REPRS, cpp/objective.cu:485-696) and
+ * its mixture with the text objective (TextEntityTermTerm, cpp/objective.cu:747-794, cpp/main.cu:742-750). Both calls take the
+ * structs of the entity-pair calls unchanged; nvsm_pair_batch::pairs holds MODEL WORD IDS here, nvsm_mixture::pair_weight is w_tt.
+ *   pair objective   a batch is M pairs (a_p, b_p, ω_p) of model word ids, interleaved. s_p = W[a_p]·W[b_p];
+ *                    prob_p = clip(σ(s_p), 1e-7, 1 − 1e-7) in float32 with the two-branch sigmoid; cost = −(1/M)·Σ ω_p·log prob_p;
+ *                    mult_p = ω_p·d(prob_p)·exp(−log M), the derivative clamp at 1e-6. The gradient of entry 2p is mult_p·W[b_p], that
+ *                    of entry 2p + 1 mult_p·W[a_p], both from the rows as they were at compute_cost. Window 1, no per-entry weights
+ *                    (include/cuNVSM/intermediate_results.h:328-334), gradient ascent, scaled lambda = lambda / M. Only the words
+ *                    table has a gradient: T, b, E, the batch-norm parameters and their step counters are left alone
+ *                    (cpp/params.cu:304-307). All five update methods: sparse Adam runs with window 1, Adagrad uses the per-entry
+ *                    accumulator and scale of updates_adagrad.cu:136-158 with window 1.
+ *   mixed objective  cost = (cost_text + cost_pairs) / 2; scaled lambda = (lambda/B + lambda/M) / 2; text gradients are scaled by
+ *                    w_te / (w_te + w_tt), the pair gradient by w_tt / (w_te + w_tt) (MergeGradientsFn, cpp/intermediate_results.cu:3-60).
+ *                    The WORDS table is updated once from both gradient lists (CompositeGradients, cpp/storage.cu:65-99): one decay, the
+ *                    text list's scatter with window w and the feature weights, then the pair list's with window 1 and weight 1. Adam's m
+ *                    comes from both lists (updates_adam.cu:196-200), dense_update's per-row v from both lists' per-source means of
+ *                    squares, scattered with the same window and weights (:216-252), full Adam squares the summed gradient (:253-282).
+ *                    The documents table and the projection see the text objective only, at its share. Refused, as the reference
+ *                    refuses them: Adagrad (updates_adagrad.cu:108) and sparse Adam (updates_adam.cu:348).
+ * The words table pass weighs an entry's mean of squares linearly by its coefficient (the reference scatters v with the gradient's
+ * repr_weights), so a pair entry carries its MULTIPLIED row c_p·W[other] (c_p = mult_p x the mixture scale), weight 1, and the mean of
+ * squares of that row (pairs.hip).
+ * nvsm_compute_gradients / nvsm_update / nvsm_get_cost(_f64) / nvsm_scaled_regularization_lambda act on the current forward result.
+ * nvsm_get_tensor additionally knows "term_pair_probs" [M], "term_pair_multipliers" [M] (mixture scale included), "grad_pair_word"
+ * [2M][word_repr_size] (the rows as stored: multiplied), "term_pair_msq" [2M] (their means of squares, as the words update reads
+ * them), "pair_cost" and "text_cost" [1]. A word id outside [0, num_words) follows the index contract: row 0, and
+ * NVSM_ERR_INVALID_ARGUMENT at the next call that waits.
+ * NVSM_ERR_UNSUPPORTED (the handle stays usable): mixed with Adagrad or sparse Adam; world_size > 1; word_repr_size above 1024, or
+ * above 256 and no multiple of 4; 3 x max_batch_size x window_size >= 2^26. NVSM_ERR_INVALID_ARGUMENT: a mixture weight <= 0,
+ * num_pairs outside [1, max_batch_size], null pairs. A handle may make entity-pair and term-pair calls at different times; one call
+ * takes one kind (the reference excludes both at once, cpp/main.cu:733-745).
+ * Allocated by the first of these calls (B = Mx = max_batch_size, w = window_size): 2Mx more gradient rows (2Mx·word_repr_size floats),
+ * 2Mx means of squares, 2Mx word ids, B·w + 2Mx entry ids, (B + 2Mx)·w entry weights, the words CSR workspace again for B·w + 2Mx
+ * entries, the per-source buffers of sparse Adam / Adagrad for max(B, 2Mx) rows, and the pair kernel's ids, weights, probabilities and
+ * multipliers (2Mx int64 + 3Mx floats + B floats) where no entity-pair call made them. nvsm_describe says whether this has happened.
+ * A handle that never makes one of these calls allocates and launches exactly what it did before they existed.
+ * nvsm_step_term_mixed equals nvsm_compute_cost_term_mixed; nvsm_compute_gradients; nvsm_update(scaled lambda) bit for bit.
+ */
+int nvsm_compute_cost_term_mixed(nvsm_model* m, const nvsm_batch* text /* NULL: pairs only */, const int64_t* entity_ids,
+                                 const nvsm_pair_batch* pairs /* word ids */, const nvsm_mixture* mix /* pair_weight = w_tt */);
+int nvsm_step_term_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch* pairs,
+                         const nvsm_mixture* mix, float learning_rate, float* cost);
+
+/*
  * Training from an HBM-resident corpus: window references instead of batches. A host nvsm_batch carries 12·w + 12 bytes per window
  * (132 at w = 10); the windows of a collection are all slices of one token arena, so a window is fully named by 8 bytes — its
  * document and the position of its first token inside the document. nvsm_corpus_upload puts the arena, the document offsets and

@@ -110,6 +110,22 @@ class Model {
         check(nvsm_step_mixed(h_, text ? &text->raw : nullptr, nullptr, &pairs.raw, &mix, learning_rate, want_cost ? &c : nullptr));
         return c;
     }
+    // the term-term similarity objective on the words table (TextEntityTermTerm, cpp/objective.cu:747-794): `pairs` holds model word
+    // ids, pair_weight is w_tt; alone with text == nullptr
+    void compute_cost_term_mixed(const Batch* text, const PairBatch& pairs, float text_weight = 0.5f, float pair_weight = 0.5f,
+                                 const int64_t* entity_ids = nullptr) {
+        nvsm_mixture mix{};
+        mix.text_weight = text_weight; mix.pair_weight = pair_weight;
+        check(nvsm_compute_cost_term_mixed(h_, text ? &text->raw : nullptr, entity_ids, &pairs.raw, &mix));
+    }
+    float step_term_mixed(const Batch* text, const PairBatch& pairs, float learning_rate, float text_weight = 0.5f, float pair_weight = 0.5f,
+                          bool want_cost = true) {
+        nvsm_mixture mix{};
+        mix.text_weight = text_weight; mix.pair_weight = pair_weight;
+        float c = 0.f;
+        check(nvsm_step_term_mixed(h_, text ? &text->raw : nullptr, nullptr, &pairs.raw, &mix, learning_rate, want_cost ? &c : nullptr));
+        return c;
+    }
 
     // training from an HBM-resident corpus (cunvsm_amd.h): the corpus goes to the device once, a batch is then [n] window
     // references — (document, first token inside the document) as interleaved uint32, 8 bytes per window — and every call below
