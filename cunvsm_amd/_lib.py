@@ -22,6 +22,7 @@ LEX_JM, LEX_DIRICHLET = 0, 1
 NORM_STANDARDIZE, NORM_MINMAX, NORM_NONE = 0, 1, 2
 LEXICAL_MAX_QUERY_TERMS = 1024
 ENSEMBLE_MAX_TOP_K = 1024
+FEEDBACK_MAX_DOCS = 1024
 
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "DEVICE", 4: "STATE", 5: "NO_DEVICE"}
 
@@ -104,6 +105,10 @@ class NvsmLexicalOptions(C.Structure):
 
 class NvsmEnsembleOptions(C.Structure):
     _fields_ = [("alpha", C.c_float), ("normalizer", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class NvsmFeedbackOptions(C.Structure):
+    _fields_ = [("fb_docs", C.c_int32), ("fb_terms", C.c_int32), ("orig_weight", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
 class NvsmNeighborQueries(C.Structure):
@@ -290,6 +295,12 @@ def lib():
         "nvsm_lexical_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), vp, vp, vp]),
         "nvsm_rank_ensemble": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmEnsembleOptions),
                                          P(NvsmJudgments), vp, vp, vp, vp]),
+        "nvsm_feedback_options_default": (None, [P(NvsmFeedbackOptions)]),
+        "nvsm_lexical_rank_weighted": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), vp, vp, vp]),
+        "nvsm_relevance_model": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), P(NvsmFeedbackOptions), vp, vp, vp]),
+        "nvsm_lexical_rank_prf": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), P(NvsmFeedbackOptions), vp, vp, vp]),
+        "nvsm_rank_ensemble_prf": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmFeedbackOptions),
+                                             P(NvsmEnsembleOptions), P(NvsmJudgments), vp, vp, vp, vp]),
         "nvsm_neighbor_options_default": (None, [P(NvsmNeighborOptions)]),
         "nvsm_neighbors": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNeighborOptions), vp, vp, vp]),
         "nvsm_similarity": (C.c_int, [vp, C.c_int32, vp, vp, i64, C.c_int32, vp]),

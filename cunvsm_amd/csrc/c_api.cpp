@@ -358,6 +358,39 @@ int nvsm_rank_ensemble(nvsm_model* m, const nvsm_queries* queries, const nvsm_ra
     return guarded_on(m, [&] { m->impl.rank_ensemble(*queries, *rank_opt, *lex, *ens, judgments, metrics, doc_ids, scores, counts); });
 }
 
+void nvsm_feedback_options_default(nvsm_feedback_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->fb_docs = 10; o->fb_terms = 10; o->orig_weight = 0.5f;
+}
+int nvsm_lexical_rank_weighted(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, int64_t* doc_ids, float* scores,
+                               int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(lex); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    NVSM_REQUIRE(queries->word_weights);
+    return guarded_on(m, [&] { m->impl.lexical_rank_weighted(*queries, *lex, doc_ids, scores, counts); });
+}
+int nvsm_relevance_model(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, const nvsm_feedback_options* fb,
+                         int64_t* term_ids, float* term_probs, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(lex); NVSM_REQUIRE(fb); NVSM_REQUIRE(term_ids); NVSM_REQUIRE(term_probs);
+    NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.relevance_model(*queries, *lex, *fb, term_ids, term_probs, counts); });
+}
+int nvsm_lexical_rank_prf(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, const nvsm_feedback_options* fb,
+                          int64_t* doc_ids, float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(lex); NVSM_REQUIRE(fb); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores);
+    NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.lexical_rank_prf(*queries, *lex, *fb, doc_ids, scores, counts); });
+}
+int nvsm_rank_ensemble_prf(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                           const nvsm_feedback_options* fb, const nvsm_ensemble_options* ens, const nvsm_judgments* judgments,
+                           double* metrics, int64_t* doc_ids, float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(rank_opt); NVSM_REQUIRE(lex); NVSM_REQUIRE(fb); NVSM_REQUIRE(ens);
+    NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    if (judgments) NVSM_REQUIRE(metrics);
+    if (metrics) NVSM_REQUIRE(judgments);
+    return guarded_on(m, [&] { m->impl.rank_ensemble_prf(*queries, *rank_opt, *lex, *fb, *ens, judgments, metrics, doc_ids, scores, counts); });
+}
+
 void nvsm_neighbor_options_default(nvsm_neighbor_options* o) {
     if (!o) return;
     std::memset(o, 0, sizeof(*o));

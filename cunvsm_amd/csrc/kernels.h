@@ -579,13 +579,30 @@ void launch_lex_set_slots(int* slot_of, const int* terms, int n, bool set, hipSt
 // scores[q][d - d0] for q < Q, d in [d0, d0 + S): Σ over the query's terms j in [qoff[q], qoff[q + 1]) — in that order, fp64, narrowed
 // once — of log((1 − param)·tf/len + c0[j]) (NVSM_LEX_JM) or log((tf + c0[j]) / (len + param)) (NVSM_LEX_DIRICHLET); -inf when no
 // term of q occurs in d. tslot[j]: the term's slot < num_slots <= kLexSlots; base[j] = log(c0[j]).
+// weight null: the sum as it stands (nvsm_lexical_rank's bits). weight given (nvsm_lexical_rank_weighted): Σ_j weight[j]·log(...),
+// each product rounded on its own, in the same order.
 struct LexScoreArgs {
     const int* tokens; const int64_t* doc_offsets; const int* slot_of;
     int64_t d0; int S; int Q; int num_slots; int method; double param;
     const int* qoff; const int* tslot; const double* c0; const double* base;
     float* scores; int64_t ld;
+    const double* weight;
 };
 void launch_lex_score(const LexScoreArgs& a, hipStream_t s);
+// relevance model of a round's queries (nvsm_relevance_model). Query q < Q has the feedback documents
+// fb_ids[q][0 .. fb_counts[q]) in rank order with the first pass's scores fb_scores[q][...] (rows fb_docs long, fb_docs <= kFeedbackMaxDocs).
+// acc [Q][V] doubles and cnt [Q][V] ints are zero before and cnt is zero behind; acc[q][t] = Σ_i ω_i·tf(t, d_i)/len(d_i) added in rank
+// order, sum_w[q] = Σ_i ω_i in rank order, ω_i = exp(s_i − s_0). Integer atomics only.
+constexpr int kFeedbackMaxDocs = 1024;     // the ω of a query: 8 KiB of LDS (NVSM_FEEDBACK_MAX_DOCS)
+struct LexRmArgs {
+    const int* tokens; const int64_t* doc_offsets;
+    const int* fb_ids; const float* fb_scores; const int* fb_counts; int fb_docs;
+    int64_t V; double* acc; int* cnt; double* sum_w;
+};
+void launch_lex_rm_accumulate(const LexRmArgs& a, int Q, hipStream_t s);
+// scores[q][t − t0] = float(acc[q][t] / sum_w[q]) where acc[q][t] > 0 and the narrowed value is > 0, else -inf, for t in [t0, t0 + S);
+// acc is zeroed behind
+void launch_lex_rm_narrow(double* acc, const double* sum_w, int64_t V, int64_t t0, int S, int Q, float* scores, int64_t ld, hipStream_t s);
 // launch_rank_write for keys that may carry -inf scores: ids / scores [Q][k] up to the first -inf or padding key, counts [Q] likewise
 void launch_lex_write(const unsigned long long* keys, int64_t npad, int Q, int k, int64_t n_all, int64_t* ids, float* scores,
                       int64_t* counts, hipStream_t s);

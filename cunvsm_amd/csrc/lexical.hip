@@ -9,6 +9,9 @@
 //                         a barrier a fixed lane visits the terms of one query IN QUERY ORDER, adds their logs in fp64 in that order
 //                         and stores the sum narrowed to fp32, -inf when no term of the query occurs in the document. Then the
 //                         counters are zeroed. A document longer than the workgroup is looped over.
+//                         lex_score_kernel<true> multiplies every term by its weight (nvsm_lexical_rank_weighted); <false> is the
+//                         kernel nvsm_lexical_rank always had
+//   lex_rm_accumulate_kernel, lex_rm_narrow_kernel   the relevance model of pseudo-relevance feedback
 //   lex_write_kernel      launch_rank_write for slabs that hold -inf entries: what is retrieved ends at the first -inf
 //   fuse_lists_kernel     one workgroup per query: normalises two ranked lists over their returned entries, matches the documents
 //                         both hold by a bitonic sort of (id, list, position) keys, computes the fused fp64 scores and sorts
@@ -42,6 +45,14 @@ __global__ __launch_bounds__(256) void lex_set_slots_kernel(int* __restrict__ sl
     if (i < n) slot_of[terms[i]] = set ? i : -1;
 }
 
+// w·a rounded on its own: the weighted sum is that of plain fp64 operations, whatever the compiler would contract
+__device__ __forceinline__ double lex_weighted(double w, double a) {
+#pragma clang fp contract(off)
+    return w * a;
+}
+
+// WEIGHTED false: nvsm_lexical_rank's kernel as it always was; true: every term times its weight (nvsm_lexical_rank_weighted)
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void lex_score_kernel(LexScoreArgs a) {
     __shared__ int tf[kLexSlots];
     for (int i = threadIdx.x; i < kLexSlots; i += 256) tf[i] = 0;
@@ -62,19 +73,75 @@ __global__ __launch_bounds__(256) void lex_score_kernel(LexScoreArgs a) {
             bool any = false;
             for (int j = a.qoff[q]; j < a.qoff[q + 1]; ++j) {
                 const int t = tf[a.tslot[j]];
+                double term;
                 if (t > 0) {
                     any = true;
-                    sum += a.method == NVSM_LEX_DIRICHLET ? log((static_cast<double>(t) + a.c0[j]) / (len + a.param))
+                    term = a.method == NVSM_LEX_DIRICHLET ? log((static_cast<double>(t) + a.c0[j]) / (len + a.param))
                                                           : log(jm_scale * static_cast<double>(t) + a.c0[j]);
                 } else {
-                    sum += a.base[j] - log_den;
+                    term = a.base[j] - log_den;
                 }
+                sum += WEIGHTED ? lex_weighted(a.weight[j], term) : term;
             }
             a.scores[static_cast<size_t>(q) * a.ld + (d - a.d0)] = any ? static_cast<float>(sum) : -__builtin_inff();
         }
         __syncthreads();
         for (int i = threadIdx.x; i < a.num_slots; i += 256) tf[i] = 0;
         __syncthreads();
+    }
+}
+
+// ---- relevance model ---------------------------------------------------------------------------------------------
+// One workgroup per query. The feedback documents are walked in rank order, one at a time: every token counts itself into the query's
+// cnt[term] (integer atomics), behind a barrier every token takes the count back with an exchange, and the one lane that receives it
+// adds ω·c/len to acc[term] with a plain load and store. Whichever lane that is, the adds of a term happen in rank order: a repeated
+// call returns the same bits. (The barriers order the workgroup's global accesses: all its waves share one CU's vector cache.)
+__global__ __launch_bounds__(256) void lex_rm_accumulate_kernel(LexRmArgs a) {
+    __shared__ double omega[kFeedbackMaxDocs];
+    const int q = blockIdx.x;
+    int n = a.fb_counts[q];
+    n = n < 0 ? 0 : (n > a.fb_docs ? a.fb_docs : n);
+    const int* ids = a.fb_ids + static_cast<size_t>(q) * a.fb_docs;
+    const float* sc = a.fb_scores + static_cast<size_t>(q) * a.fb_docs;
+    double* acc = a.acc + static_cast<size_t>(q) * a.V;
+    int* cnt = a.cnt + static_cast<size_t>(q) * a.V;
+    for (int i = threadIdx.x; i < n; i += 256) omega[i] = i == 0 ? 1.0 : exp(static_cast<double>(sc[i]) - static_cast<double>(sc[0]));
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < n; ++i) sum += omega[i];
+        a.sum_w[q] = sum;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int64_t d = ids[i];
+        const int64_t lo = a.doc_offsets[d], hi = a.doc_offsets[d + 1];
+        const double len = static_cast<double>(hi - lo);
+        const double w = omega[i];
+        for (int64_t p = lo + threadIdx.x; p < hi; p += 256) atomicAdd(&cnt[a.tokens[p]], 1);
+        __syncthreads();
+        for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+            const int t = a.tokens[p];
+            const int c = atomicExch(&cnt[t], 0);
+            if (c > 0) acc[t] += w * (static_cast<double>(c) / len);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void lex_rm_narrow_kernel(double* __restrict__ acc, const double* __restrict__ sum_w, int64_t V, int64_t t0,
+                                                            int S, float* __restrict__ scores, int64_t ld) {
+    const int q = blockIdx.y;
+    const double total = sum_w[q];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < S; i += gridDim.x * 256) {
+        double* cell = acc + static_cast<size_t>(q) * V + t0 + i;
+        const double v = *cell;
+        float f = -__builtin_inff();
+        if (v > 0.0) {
+            const float pi = static_cast<float>(v / total);
+            if (pi > 0.f) f = pi;
+            *cell = 0.0;
+        }
+        scores[static_cast<size_t>(q) * ld + i] = f;
     }
 }
 
@@ -254,7 +321,18 @@ void launch_lex_score(const LexScoreArgs& a, hipStream_t s) {
     if (a.S <= 0 || a.Q <= 0) return;
     // (grid-strided: enough workgroups to fill the device several times over, not one per document of a large slab)
     const int grid = static_cast<int>(a.S < 8192 ? a.S : 8192);
-    NVSM_LAUNCH(lex_score_kernel, dim3(grid), dim3(256), 0, s, a);
+    if (a.weight) NVSM_LAUNCH(lex_score_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    else NVSM_LAUNCH(lex_score_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+}
+
+void launch_lex_rm_accumulate(const LexRmArgs& a, int Q, hipStream_t s) {
+    if (Q > 0) NVSM_LAUNCH(lex_rm_accumulate_kernel, dim3(Q), dim3(256), 0, s, a);
+}
+
+void launch_lex_rm_narrow(double* acc, const double* sum_w, int64_t V, int64_t t0, int S, int Q, float* scores, int64_t ld, hipStream_t s) {
+    if (Q <= 0 || S <= 0) return;
+    const int gx = (S + 255) / 256 < 256 ? (S + 255) / 256 : 256;
+    NVSM_LAUNCH(lex_rm_narrow_kernel, dim3(gx, Q), dim3(256), 0, s, acc, sum_w, V, t0, S, scores, ld);
 }
 
 void launch_lex_write(const unsigned long long* keys, int64_t npad, int Q, int k, int64_t n_all, int64_t* ids, float* scores,

@@ -173,6 +173,15 @@ class Model {
     void lexical_rank(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts);
     void rank_ensemble(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_ensemble_options& ens,
                        const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
+    // weighted queries and pseudo-relevance feedback (include/cunvsm_amd.h; lexical.hip)
+    void lexical_rank_weighted(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts);
+    void relevance_model(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, int64_t* term_ids,
+                         float* term_probs, int64_t* counts);
+    void lexical_rank_prf(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, int64_t* doc_ids,
+                          float* scores, int64_t* counts);
+    void rank_ensemble_prf(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb,
+                           const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
+                           int64_t* counts);
     void evaluate(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_judgments& j, double* metrics, int64_t* doc_ids,
                   float* scores, int64_t* counts);
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
@@ -469,7 +478,10 @@ class Model {
         DevBuf<int64_t> joff;                      //           ... their offsets,
         DevBuf<double> jconst, metrics;            //           ... R / idcg / idcg@c per query, and the metric rows
         DevBuf<int> lex_slot_of, lex_terms, lex_qoff, lex_tslot;      // lexical: term -> slot [num_words] (-1 between rounds), a round's terms
-        DevBuf<double> lex_c0, lex_base;                              //          ... and their constants
+        DevBuf<double> lex_c0, lex_base, lex_weight;                  //          ... and their constants (lex_weight: weighted queries only)
+        DevBuf<double> rm_acc, rm_sum;                                // relevance model: acc [round][num_words] and cnt likewise (zero between
+        DevBuf<int> rm_cnt, rm_ids, rm_counts;                        //   rounds), Σω [round], a round's feedback lists [round][fb_docs]
+        DevBuf<float> rm_scores;
         DevBuf<int64_t> fuse_ids, fuse_counts, fuse_out_ids, fuse_out_counts;      // ensemble: both lists of a round [2][round][k], the fused list
         DevBuf<float> fuse_scores, fuse_out_scores;
     };
@@ -487,7 +499,18 @@ class Model {
     // the rounds of rank and evaluate (ev null: rank); null result pointers are not copied to
     void rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts, EvalPlan* ev);
     void lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex) const;      // the refusals of nvsm_lexical_rank, before anything runs
-    void lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts);
+    // weights null: nvsm_lexical_rank's rounds; given ([offsets[num_queries]] floats next to word_ids): the weighted scorer
+    void lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const float* weights, int64_t* doc_ids, float* scores, int64_t* counts);
+    void weights_check(const nvsm_queries& q) const;
+    void feedback_check(const nvsm_feedback_options& fb) const;                   // behind lexical_check: the corpus is there
+    // first pass + relevance model into host lists [Q][fb_terms] (the rounds of nvsm_relevance_model, behind its checks and rank_join)
+    void relevance_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, int64_t* term_ids,
+                          float* term_probs, int64_t* counts);
+    struct ExpandedQueries;                 // the RM3 queries of a call, built on the host in fp64 (ranking.cpp)
+    void expand_queries(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, ExpandedQueries& out);
+    void ensemble_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                         const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
+                         int64_t* counts);
     void rank_join();                       // the handle's four streams waited for on the host; the words table's pending stamps settled
     struct RowSpace { const float* rows; int64_t count; int dim; const TableState* table; };      // rows null: the projected vocabulary
     RowSpace row_space(int space) const;

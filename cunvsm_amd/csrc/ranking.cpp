@@ -414,10 +414,11 @@ void Model::lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex
 void Model::lexical_rank(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts) {
     lexical_check(q, lex);
     rank_join();
-    lexical_rounds(q, lex, doc_ids, scores, counts);
+    lexical_rounds(q, lex, nullptr, doc_ids, scores, counts);
 }
 
-void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts) {
+void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const float* weights, int64_t* doc_ids, float* scores,
+                           int64_t* counts) {
     Corpus& c = *corpus_;
     const int64_t Dc = c.num_documents, N = c.num_tokens, Q = q.num_queries, V = cfg_.num_words;
     const int k = lex.top_k;
@@ -439,14 +440,14 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
                                                    : (lex.param == 0.f ? static_cast<double>(N) / static_cast<double>(Dc) : static_cast<double>(lex.param));
     bool bad_word = false;
     std::vector<int> terms, qoff, tslot;
-    std::vector<double> c0, base;
+    std::vector<double> c0, base, wt;
     std::vector<std::pair<int64_t, int>> slot_of;      // (term, slot) of the round, kept sorted by term
 
     for (int64_t q0 = 0; q0 < Q;) {
         RankLayout l = rank_layout(Dc, k, Q - q0, score_floats());
         // ---- the round's queries: as many of the l.qn as their distinct remaining terms leave room for (at least one: lexical_check);
         // the slabs stay those of the layout, the scratch is sized by the queries taken
-        terms.clear(); tslot.clear(); c0.clear(); base.clear(); slot_of.clear();
+        terms.clear(); tslot.clear(); c0.clear(); base.clear(); wt.clear(); slot_of.clear();
         qoff.assign(1, 0);
         int64_t taken = 0;
         for (; taken < l.qn; ++taken) {
@@ -456,6 +457,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
                 const int64_t t = q.word_ids[j];
                 if (t < 0 || t >= V) { bad_word = true; continue; }      // the index contract: matches nothing, reported at the end
                 if (c.cf[static_cast<size_t>(t)] == 0) continue;
+                if (weights && weights[j] == 0.f) continue;               // a weighted query: a term of weight 0 is dropped
                 auto it = std::lower_bound(slot_of.begin(), slot_of.end(), std::make_pair(t, -1));
                 int slot;
                 if (it != slot_of.end() && it->first == t) {
@@ -470,6 +472,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
                 tslot.push_back(slot);
                 c0.push_back(param * p);
                 base.push_back(std::log(param * p));
+                if (weights) wt.push_back(static_cast<double>(weights[j]));
             }
             if (!fits) {      // this query opens the next round: take back what it added
                 for (size_t s = terms_before; s < terms.size(); ++s) {
@@ -477,6 +480,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
                     slot_of.erase(it);
                 }
                 terms.resize(terms_before); tslot.resize(entries_before); c0.resize(entries_before); base.resize(entries_before);
+                if (weights) wt.resize(entries_before);
                 break;
             }
             qoff.push_back(static_cast<int>(tslot.size()));
@@ -489,6 +493,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
         grow(r.lex_tslot, std::max<size_t>(nent, 1));
         grow(r.lex_c0, std::max<size_t>(nent, 1));
         grow(r.lex_base, std::max<size_t>(nent, 1));
+        if (weights) grow(r.lex_weight, std::max<size_t>(nent, 1));
         // (the main stream is idle here: every round ends with a wait)
         if (nslots > 0) NVSM_HIP_CHECK(hipMemcpy(r.lex_terms.p, terms.data(), static_cast<size_t>(nslots) * sizeof(int), hipMemcpyHostToDevice));
         NVSM_HIP_CHECK(hipMemcpy(r.lex_qoff.p, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -496,6 +501,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
             NVSM_HIP_CHECK(hipMemcpy(r.lex_tslot.p, tslot.data(), nent * sizeof(int), hipMemcpyHostToDevice));
             NVSM_HIP_CHECK(hipMemcpy(r.lex_c0.p, c0.data(), nent * sizeof(double), hipMemcpyHostToDevice));
             NVSM_HIP_CHECK(hipMemcpy(r.lex_base.p, base.data(), nent * sizeof(double), hipMemcpyHostToDevice));
+            if (weights) NVSM_HIP_CHECK(hipMemcpy(r.lex_weight.p, wt.data(), nent * sizeof(double), hipMemcpyHostToDevice));
         }
         round_grow(l, k);
         LexScoreArgs a{};
@@ -503,10 +509,11 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
         a.Q = static_cast<int>(qn); a.num_slots = nslots; a.method = lex.method; a.param = param;
         a.qoff = r.lex_qoff.p; a.tslot = r.lex_tslot.p; a.c0 = r.lex_c0.p; a.base = r.lex_base.p;
         a.ld = l.ld;
+        a.weight = weights ? r.lex_weight.p : nullptr;
         round_slabs(l, Dc, k, [&](int64_t d0, int Ss) {
             if (d0 == 0) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);      // (behind round_slabs' grows)
             a.scores = r.scores.p; a.d0 = d0; a.S = Ss;
-            RankProf scope(prof, "lex_score", stream_);
+            RankProf scope(prof, weights ? "lex_score_weighted" : "lex_score", stream_);
             launch_lex_score(a, stream_);
         });
         launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
@@ -518,13 +525,183 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
     if (bad_word) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a query word id is outside [0, num_words)");
 }
 
+// ---- weighted queries and pseudo-relevance feedback (include/cunvsm_amd.h nvsm_lexical_rank_weighted / nvsm_relevance_model /
+// nvsm_lexical_rank_prf; kernels: lexical.hip) -------------------------------------------------------------------------
+// The first pass is nvsm_lexical_rank's rounds at top_k = fb_docs into host lists. A round of the relevance model takes the lists of as
+// many queries as 12·num_words bytes each fit the score slab's budget (at least one), accumulates them (one workgroup per query),
+// narrows the accumulators slab by slab into the score slab and selects over the vocabulary with nvsm_rank's selection, sort and
+// launch_lex_write: rows = num_words, top_k = fb_terms. The expanded queries are built on the host and go through the weighted rounds.
+void Model::weights_check(const nvsm_queries& q) const {
+    if (!q.word_weights) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: queries->word_weights");
+    for (int64_t j = 0; j < q.offsets[q.num_queries]; ++j) {
+        if (!std::isfinite(q.word_weights[j])) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a word weight is not finite");
+        if (q.word_weights[j] < 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a word weight is negative");
+    }
+}
+
+void Model::feedback_check(const nvsm_feedback_options& fb) const {
+    if (fb.fb_docs < 1 || fb.fb_docs > std::min<int64_t>(corpus_->num_documents, kFeedbackMaxDocs))
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "fb_docs must be in [1, min(num_documents of the corpus, NVSM_FEEDBACK_MAX_DOCS)]");
+    if (fb.fb_terms < 1 || fb.fb_terms > cfg_.num_words) throw Error(NVSM_ERR_INVALID_ARGUMENT, "fb_terms must be in [1, num_words]");
+    if (!(fb.orig_weight >= 0.f && fb.orig_weight <= 1.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "orig_weight must be in [0, 1]");
+    check_row_count(cfg_.num_words, "the relevance model supports fewer than 2^31 words");
+}
+
+void Model::lexical_rank_weighted(const nvsm_queries& q, const nvsm_lexical_options& lex, int64_t* doc_ids, float* scores, int64_t* counts) {
+    lexical_check(q, lex);
+    weights_check(q);
+    rank_join();
+    lexical_rounds(q, lex, q.word_weights, doc_ids, scores, counts);
+}
+
+void Model::relevance_model(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, int64_t* term_ids,
+                            float* term_probs, int64_t* counts) {
+    lexical_check(q, lex);
+    feedback_check(fb);
+    rank_join();
+    relevance_rounds(q, lex, fb, term_ids, term_probs, counts);
+}
+
+void Model::relevance_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, int64_t* term_ids,
+                             float* term_probs, int64_t* counts) {
+    Corpus& c = *corpus_;
+    const int64_t Q = q.num_queries, V = cfg_.num_words;
+    const int nd = fb.fb_docs, kt = fb.fb_terms;
+    // ---- the first pass: nvsm_lexical_rank at top_k = fb_docs (a word id out of range ends the call here)
+    nvsm_lexical_options first = lex;
+    first.top_k = nd;
+    const size_t cells = static_cast<size_t>(std::max<int64_t>(Q, 1)) * nd;
+    std::vector<int64_t> ids(cells), cnt(static_cast<size_t>(Q) + 1);
+    std::vector<float> sc(cells);
+    lexical_rounds(q, first, nullptr, ids.data(), sc.data(), cnt.data());
+
+    RankScratch& r = rank_;
+    const int64_t fit = std::max<int64_t>(1, score_floats() * 4 / (12 * V));      // queries whose acc and cnt fit the slab's budget
+    std::vector<int> ids32, cnt32;
+    for (int64_t q0 = 0; q0 < Q;) {
+        RankLayout l = rank_layout(V, kt, Q - q0, score_floats());
+        const int64_t qn = l.qn = std::min(l.qn, fit);       // (the slabs stay those of the layout, the scratch is sized by the queries taken)
+        if (r.rm_acc.n < static_cast<size_t>(qn * V)) {      // zeroed once: the kernels leave both zero behind them
+            r.rm_acc.alloc(static_cast<size_t>(qn * V), true);
+            r.rm_cnt.alloc(static_cast<size_t>(qn * V), true);
+        }
+        grow(r.rm_sum, static_cast<size_t>(kRankChunk));
+        grow(r.rm_counts, static_cast<size_t>(kRankChunk));
+        grow(r.rm_ids, static_cast<size_t>(qn) * nd);
+        grow(r.rm_scores, static_cast<size_t>(qn) * nd);
+        ids32.resize(static_cast<size_t>(qn) * nd);
+        cnt32.resize(static_cast<size_t>(qn));
+        for (int64_t i = 0; i < qn; ++i) {
+            const int n = static_cast<int>(cnt[static_cast<size_t>(q0 + i)]);
+            cnt32[static_cast<size_t>(i)] = n;
+            for (int t = 0; t < nd; ++t) ids32[static_cast<size_t>(i) * nd + t] = t < n ? static_cast<int>(ids[static_cast<size_t>(q0 + i) * nd + t]) : 0;
+        }
+        // (the main stream is idle here: the first pass, and every round, end with a wait)
+        NVSM_HIP_CHECK(hipMemcpy(r.rm_ids.p, ids32.data(), ids32.size() * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.rm_scores.p, sc.data() + q0 * nd, static_cast<size_t>(qn) * nd * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.rm_counts.p, cnt32.data(), cnt32.size() * sizeof(int), hipMemcpyHostToDevice));
+        LexRmArgs a{};
+        a.tokens = c.tokens.p; a.doc_offsets = c.offsets.p;
+        a.fb_ids = r.rm_ids.p; a.fb_scores = r.rm_scores.p; a.fb_counts = r.rm_counts.p; a.fb_docs = nd;
+        a.V = V; a.acc = r.rm_acc.p; a.cnt = r.rm_cnt.p; a.sum_w = r.rm_sum.p;
+        { RankProf scope(prof, "lex_rm", stream_); launch_lex_rm_accumulate(a, static_cast<int>(qn), stream_); }
+        round_grow(l, kt);
+        round_slabs(l, V, kt, [&](int64_t t0, int Ss) {
+            RankProf scope(prof, "lex_rm_narrow", stream_);
+            launch_lex_rm_narrow(r.rm_acc.p, r.rm_sum.p, V, t0, Ss, static_cast<int>(qn), r.scores.p, l.ld, stream_);
+        });
+        round_sort(l, [&] { launch_lex_write(r.keys.p, l.npad, static_cast<int>(qn), kt, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_); });
+        round_results(q0, qn, kt, term_ids, term_probs, counts);
+        q0 += qn;
+    }
+    raise_device_error();
+}
+
+struct Model::ExpandedQueries {
+    std::vector<int64_t> word_ids, offsets;
+    std::vector<float> weights;
+    nvsm_queries view() const {
+        nvsm_queries x{};
+        x.word_ids = word_ids.data(); x.word_weights = weights.data(); x.offsets = offsets.data();
+        x.num_queries = static_cast<int64_t>(offsets.size()) - 1;
+        return x;
+    }
+};
+
+// the RM3 queries of the call: first pass, relevance model, and the weights in plain fp64 (a division, a difference, a product, a
+// division: nothing a compiler could contract, so the numpy restatement produces the same float32 weights); refuses an expanded query of more than kLexSlots distinct terms
+void Model::expand_queries(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, ExpandedQueries& out) {
+    const int64_t Q = q.num_queries, V = cfg_.num_words;
+    const int kt = fb.fb_terms;
+    const size_t cells = static_cast<size_t>(std::max<int64_t>(Q, 1)) * kt;
+    std::vector<int64_t> terms(cells), n_terms(static_cast<size_t>(Q) + 1);
+    std::vector<float> probs(cells);
+    relevance_rounds(q, lex, fb, terms.data(), probs.data(), n_terms.data());
+    const std::vector<int64_t>& cf = corpus_->cf;      // (made by the first pass at the latest)
+    const double o64 = static_cast<double>(fb.orig_weight);
+    out.word_ids.clear(); out.weights.clear();
+    out.offsets.assign(1, 0);
+    for (int64_t i = 0; i < Q; ++i) {
+        int64_t L = 0;
+        for (int64_t j = q.offsets[i]; j < q.offsets[i + 1]; ++j) {
+            const int64_t t = q.word_ids[j];
+            if (t >= 0 && t < V && cf[static_cast<size_t>(t)] > 0) ++L;
+        }
+        if (L > 0) {
+            const double each = o64 / static_cast<double>(L);
+            for (int64_t j = q.offsets[i]; j < q.offsets[i + 1]; ++j) {
+                const int64_t t = q.word_ids[j];
+                if (!(t >= 0 && t < V && cf[static_cast<size_t>(t)] > 0)) continue;
+                out.word_ids.push_back(t);
+                out.weights.push_back(static_cast<float>(each));
+            }
+            const int64_t n = n_terms[static_cast<size_t>(i)];
+            const float* pi = probs.data() + static_cast<size_t>(i) * kt;
+            double S = 0.0;
+            for (int64_t e = 0; e < n; ++e) S += static_cast<double>(pi[e]);
+            for (int64_t e = 0; e < n; ++e) {
+                const double num = (1.0 - o64) * static_cast<double>(pi[e]);
+                out.word_ids.push_back(terms[static_cast<size_t>(i) * kt + e]);
+                out.weights.push_back(static_cast<float>(num / S));
+            }
+        }
+        out.offsets.push_back(static_cast<int64_t>(out.word_ids.size()));
+    }
+    const nvsm_queries x = out.view();
+    lexical_check(x, lex);      // the distinct terms of every expanded query against the round's counters
+}
+
+void Model::lexical_rank_prf(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, int64_t* doc_ids,
+                             float* scores, int64_t* counts) {
+    lexical_check(q, lex);
+    feedback_check(fb);
+    rank_join();
+    ExpandedQueries x;
+    expand_queries(q, lex, fb, x);
+    lexical_rounds(x.view(), lex, x.weights.data(), doc_ids, scores, counts);
+}
+
 // ---- fusion of nvsm_rank's list with the lexical one (include/cunvsm_amd.h nvsm_rank_ensemble; fuse_lists_kernel) ----------------
 // Both rankings are made by their own calls' rounds (whose sizes differ) into host lists; a round of fusion takes kRankChunk queries'
 // lists back up, fuses them on the device and, with judgments, runs nvsm_evaluate's kernel on the fused ids where they lie.
 void Model::rank_ensemble(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_ensemble_options& ens,
                           const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores, int64_t* counts) {
+    ensemble_rounds(q, opt, lex, nullptr, ens, j, metrics, doc_ids, scores, counts);
+}
+
+void Model::rank_ensemble_prf(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb,
+                              const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
+                              int64_t* counts) {
+    ensemble_rounds(q, opt, lex, &fb, ens, j, metrics, doc_ids, scores, counts);
+}
+
+// fb null: list B is nvsm_lexical_rank's; given: nvsm_lexical_rank_prf's
+void Model::ensemble_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                            const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
+                            int64_t* counts) {
     const int64_t Q = q.num_queries;
     lexical_check(q, lex);
+    if (fb) feedback_check(*fb);
     if (ens.normalizer != NVSM_NORM_STANDARDIZE && ens.normalizer != NVSM_NORM_MINMAX && ens.normalizer != NVSM_NORM_NONE)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown score normalizer");
     if (!(ens.alpha >= 0.f && ens.alpha <= 1.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "alpha must be in [0, 1]");
@@ -541,7 +718,13 @@ void Model::rank_ensemble(const nvsm_queries& q, const nvsm_rank_options& opt, c
     std::vector<int64_t> ids_a(cells), ids_b(cells), cnt_a(static_cast<size_t>(Q) + 1), cnt_b(static_cast<size_t>(Q) + 1);
     std::vector<float> sc_a(cells), sc_b(cells);
     rank_rounds(q, opt, ids_a.data(), sc_a.data(), cnt_a.data(), nullptr);
-    lexical_rounds(q, lex, ids_b.data(), sc_b.data(), cnt_b.data());
+    if (fb) {
+        ExpandedQueries x;
+        expand_queries(q, lex, *fb, x);
+        lexical_rounds(x.view(), lex, x.weights.data(), ids_b.data(), sc_b.data(), cnt_b.data());
+    } else {
+        lexical_rounds(q, lex, nullptr, ids_b.data(), sc_b.data(), cnt_b.data());
+    }
 
     RankScratch& r = rank_;
     const size_t chunk_cells = static_cast<size_t>(kRankChunk) * k;

@@ -14,7 +14,8 @@
 // The last stage of rank-cranfield-collection.sh — a query-likelihood run and its fusion with the NVSM run (py/combine_runs.py
 // --alpha) — is --qlm / --ensemble_alpha: the collection goes to HBM as the token arena the trainer would upload (token_arena.hpp:
 // IndexSource's term mapping and out-of-vocabulary rule, documents in model id order) and nvsm_lexical_rank / nvsm_rank_ensemble do
-// the rest. The lexical model is over the MODEL's vocabulary, not Indri's.
+// the rest. The lexical model is over the MODEL's vocabulary, not Indri's. --qlm_prf makes the lexical run, and with it
+// the fusion, the reference's "QLM w/ PRF": nvsm_lexical_rank_prf / nvsm_rank_ensemble_prf (RM3).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -41,9 +42,9 @@ namespace {
 std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs, FLAGS_qlm, FLAGS_qlm_param, FLAGS_qlm_run_out,
     FLAGS_ensemble_alpha, FLAGS_score_normalizer;
 bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
-    FLAGS_l2norm_phrase, FLAGS_help;
-double FLAGS_bias_coefficient;
-int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers;
+    FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf;
+double FLAGS_bias_coefficient, FLAGS_qlm_fb_orig_weight;
+int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers, FLAGS_qlm_fb_docs, FLAGS_qlm_fb_terms;
 
 void define_flags(Flags* f) {
     f->define_string("index", &FLAGS_index, "", "TREC-text collection file or Indri repository directory, as given to cuNVSMTrainModel.");
@@ -78,6 +79,11 @@ void define_flags(Flags* f) {
                      "the query-likelihood ranking (weight 1 - alpha), up to 2 x top_k documents per topic, and the printed means are the fused list's.");
     f->define_string("score_normalizer", &FLAGS_score_normalizer, "standardize", "standardize | minmax | none: how --ensemble_alpha normalises each "
                      "list's scores per topic before mixing them.");
+    f->define_bool("qlm_prf", &FLAGS_qlm_prf, false, "With --qlm: pseudo-relevance feedback (RM3). Every topic is expanded with the most probable "
+                   "terms of its best documents' relevance model; the --qlm_run_out runs and the --ensemble_alpha fusion use the expanded ranking.");
+    f->define_int64("qlm_fb_docs", &FLAGS_qlm_fb_docs, 10, "With --qlm_prf: feedback documents per topic.");
+    f->define_int64("qlm_fb_terms", &FLAGS_qlm_fb_terms, 10, "With --qlm_prf: expansion terms per topic.");
+    f->define_double("qlm_fb_orig_weight", &FLAGS_qlm_fb_orig_weight, 0.5, "With --qlm_prf: weight of the original query in the expanded one, in [0, 1].");
     f->define_bool("help", &FLAGS_help, false, "Print the options and exit.");
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
     f->define_int64("v", &FLAGS_v, 0, "Verbosity of VLOG messages.");
@@ -184,6 +190,21 @@ int run(int argc, char** argv) {
     } else {
         NVSM_CHECK(!with_ensemble && FLAGS_qlm_run_out.empty() && FLAGS_qlm_param == "auto" && FLAGS_score_normalizer == "standardize")
             << "--qlm_param, --qlm_run_out, --ensemble_alpha and --score_normalizer need --qlm.";
+    }
+    nvsm_feedback_options fb;
+    nvsm_feedback_options_default(&fb);
+    const bool with_prf = FLAGS_qlm_prf;
+    if (with_prf) {
+        NVSM_CHECK(with_qlm) << "--qlm_prf needs --qlm.";
+        NVSM_CHECK(FLAGS_qlm_fb_docs >= 1 && FLAGS_qlm_fb_docs <= NVSM_FEEDBACK_MAX_DOCS) << "--qlm_fb_docs must be in [1, " << NVSM_FEEDBACK_MAX_DOCS << "].";
+        NVSM_CHECK(FLAGS_qlm_fb_terms >= 1 && FLAGS_qlm_fb_terms <= 2147483647) << "--qlm_fb_terms must be at least 1.";
+        NVSM_CHECK(FLAGS_qlm_fb_orig_weight >= 0.0 && FLAGS_qlm_fb_orig_weight <= 1.0) << "--qlm_fb_orig_weight must be in [0, 1].";
+        fb.fb_docs = static_cast<int32_t>(FLAGS_qlm_fb_docs);
+        fb.fb_terms = static_cast<int32_t>(FLAGS_qlm_fb_terms);
+        fb.orig_weight = static_cast<float>(FLAGS_qlm_fb_orig_weight);
+    } else {
+        NVSM_CHECK(FLAGS_qlm_fb_docs == 10 && FLAGS_qlm_fb_terms == 10 && FLAGS_qlm_fb_orig_weight == 0.5)
+            << "--qlm_fb_docs, --qlm_fb_terms and --qlm_fb_orig_weight need --qlm_prf.";
     }
     if (with_ensemble) {
         char* end = nullptr;
@@ -386,6 +407,7 @@ int run(int argc, char** argv) {
             NVSM_LOG(INFO) << "Run outputted to " << path << ".";
         };
         lex.top_k = static_cast<int32_t>(k);
+        fb.fb_docs = static_cast<int32_t>(std::min<int64_t>(fb.fb_docs, num_entities));      // clipped to the collection, as --top_k is
         if (with_qlm && !FLAGS_qlm_run_out.empty()) {
             const std::string qlm_path = FLAGS_qlm_run_out + "-" + basename_of(topic_path);
             if (exists(qlm_path)) {
@@ -393,7 +415,8 @@ int run(int argc, char** argv) {
             } else {
                 std::vector<int64_t> lex_ids(static_cast<size_t>(Q * k) + 1), lex_counts(static_cast<size_t>(Q) + 1);
                 std::vector<float> lex_scores(static_cast<size_t>(Q * k) + 1);
-                NVSM_CALL(nvsm_lexical_rank(model, &queries, &lex, lex_ids.data(), lex_scores.data(), lex_counts.data()));
+                if (with_prf) NVSM_CALL(nvsm_lexical_rank_prf(model, &queries, &lex, &fb, lex_ids.data(), lex_scores.data(), lex_counts.data()));
+                else NVSM_CALL(nvsm_lexical_rank(model, &queries, &lex, lex_ids.data(), lex_scores.data(), lex_counts.data()));
                 write_run(qlm_path, lex_ids, lex_scores, lex_counts, k);
             }
         }
@@ -401,8 +424,12 @@ int run(int argc, char** argv) {
             nvsm_judgments judgments{};
             judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
             judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());
-            NVSM_CALL(nvsm_rank_ensemble(model, &queries, &opt, &lex, &ens, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr, doc_ids.data(),
-                                         scores.data(), counts.data()));
+            if (with_prf)
+                NVSM_CALL(nvsm_rank_ensemble_prf(model, &queries, &opt, &lex, &fb, &ens, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr,
+                                                 doc_ids.data(), scores.data(), counts.data()));
+            else
+                NVSM_CALL(nvsm_rank_ensemble(model, &queries, &opt, &lex, &ens, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr,
+                                             doc_ids.data(), scores.data(), counts.data()));
         } else if (qrels) {      // ranking and metrics in ONE call: the metrics are computed from each round's ranked ids where they lie
             nvsm_judgments judgments{};
             judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();

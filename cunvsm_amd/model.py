@@ -320,6 +320,10 @@ class Queries:
                     raise ValueError("weights[%d] sum to zero" % i)
             self.word_weights = np.ascontiguousarray(np.concatenate(wrows) if wrows else np.zeros(0, np.float32), dtype=np.float32)
 
+    def rows(self):
+        """the queries as lists of word ids again"""
+        return [self.word_ids[self.offsets[i]:self.offsets[i + 1]] for i in range(self.num_queries)]
+
     def as_struct(self):
         return NvsmQueries(self.word_ids.ctypes.data, None if self.word_weights is None else self.word_weights.ctypes.data,
                            self.offsets.ctypes.data, self.num_queries)
@@ -456,6 +460,51 @@ def ensemble_options(alpha=0.5, normalizer="standardize"):
         raise ValueError("alpha = %r outside [0, 1]" % (alpha,))
     opt.alpha, opt.normalizer = float(alpha), int(normalizer)
     return opt
+
+
+def feedback_options(fb_docs=10, fb_terms=10, orig_weight=0.5):
+    """nvsm_feedback_options from keywords; raises ValueError for what the ABI would refuse without a device. fb_docs against the
+    corpus and fb_terms against the vocabulary are checked by the library, which holds them."""
+    opt = _lib.NvsmFeedbackOptions()
+    if not 1 <= int(fb_docs) <= _lib.FEEDBACK_MAX_DOCS:
+        raise ValueError("fb_docs = %d outside [1, %d]" % (int(fb_docs), _lib.FEEDBACK_MAX_DOCS))
+    if int(fb_terms) < 1:
+        raise ValueError("fb_terms = %d is smaller than 1" % int(fb_terms))
+    if not 0.0 <= float(orig_weight) <= 1.0:
+        raise ValueError("orig_weight = %r outside [0, 1]" % (orig_weight,))
+    opt.fb_docs, opt.fb_terms, opt.orig_weight = int(fb_docs), int(fb_terms), float(orig_weight)
+    return opt
+
+
+def as_feedback_options(feedback):
+    """feedback given as an NvsmFeedbackOptions, a dict of feedback_options' keywords, a (fb_docs, fb_terms, orig_weight) tuple, or True
+    for the defaults"""
+    if isinstance(feedback, _lib.NvsmFeedbackOptions):
+        return feedback
+    if feedback is True:
+        return feedback_options()
+    if isinstance(feedback, dict):
+        return feedback_options(**feedback)
+    return feedback_options(*feedback)
+
+
+def weighted_queries(queries, weights):
+    """Queries whose per-word weights are those of the weighted lexical scorer: float32, each finite and >= 0 (a weight 0 drops its
+    term, so a query's weights may well sum to zero — unlike rank()'s averaging weights)."""
+    q = Queries(queries)
+    rows = [np.asarray(w, dtype=np.float32).ravel() for w in weights]
+    if len(rows) != q.num_queries:
+        raise ValueError("weights holds %d lists, expected one per query = %d" % (len(rows), q.num_queries))
+    for i, w in enumerate(rows):
+        n = int(q.offsets[i + 1] - q.offsets[i])
+        if w.size != n:
+            raise ValueError("weights[%d] holds %d values, query %d has %d words" % (i, w.size, i, n))
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("weights[%d] holds a value that is negative or not finite" % i)
+    q.word_weights = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0, np.float32), dtype=np.float32)
+    if q.word_weights.size == 0:
+        q.word_weights = np.zeros(1, np.float32)      # (the ABI wants a pointer even where there is nothing to read)
+    return q
 
 
 SPACES = {"words": _lib.SPACE_WORDS, "projected_words": _lib.SPACE_PROJECTED_WORDS, "entities": _lib.SPACE_ENTITIES}
@@ -754,31 +803,67 @@ class Model:
         return (result, ids, scores, counts) if return_ranking else result
 
     # -- query-likelihood ranking over the uploaded corpus, and its fusion with rank()'s list --------
-    def lexical_rank(self, queries, method="jm", param=None, top_k=1000):
+    def lexical_rank(self, queries, method="jm", param=None, top_k=1000, weights=None):
         """nvsm_lexical_rank: the top_k documents of the uploaded corpus per query under the query-likelihood model with
         Jelinek-Mercer ("jm", param = lambda) or Dirichlet ("dirichlet", param = mu) smoothing; param None = auto (lambda 0.5,
         mu the average document length). Returns (ids [Q, k], scores [Q, k], counts [Q]) as rank() does; a document is
-        retrieved only if it holds a query term, so counts[q] may be smaller than top_k."""
-        q = queries if isinstance(queries, Queries) else Queries(queries)
+        retrieved only if it holds a query term, so counts[q] may be smaller than top_k. weights (per query a list of float32
+        weights >= 0, one per word): nvsm_lexical_rank_weighted, the score is the weighted sum of the terms' logs and a term of
+        weight 0 is dropped."""
+        if weights is not None:
+            q = weighted_queries(queries.rows() if isinstance(queries, Queries) else queries, weights)
+        else:
+            q = queries if isinstance(queries, Queries) else Queries(queries)
         opt = lexical_options(method, param, top_k)
         k = opt.top_k
         ids = np.empty((q.num_queries, k), dtype=np.int64)
         scores = np.empty((q.num_queries, k), dtype=np.float32)
         counts = np.empty(q.num_queries, dtype=np.int64)
         st = q.as_struct()
-        check(lib().nvsm_lexical_rank(self._h, C.byref(st), C.byref(opt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        call = lib().nvsm_lexical_rank if weights is None else lib().nvsm_lexical_rank_weighted
+        check(call(self._h, C.byref(st), C.byref(opt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids, scores, counts
+
+    def relevance_model(self, queries, fb_docs=10, fb_terms=10, method="jm", param=None):
+        """nvsm_relevance_model: per query the fb_terms words of largest probability under the relevance model of its fb_docs best
+        documents (the unweighted lexical_rank at top_k = fb_docs; include/cunvsm_amd.h has the formula). Returns
+        (term ids [Q, fb_terms] int64, probabilities [Q, fb_terms] float32, counts [Q]); slots beyond counts[q] hold (-1, -inf)."""
+        q = queries if isinstance(queries, Queries) else Queries(queries)
+        opt = lexical_options(method, param, 1)
+        fb = feedback_options(fb_docs, fb_terms)
+        ids = np.empty((q.num_queries, fb.fb_terms), dtype=np.int64)
+        probs = np.empty((q.num_queries, fb.fb_terms), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        check(lib().nvsm_relevance_model(self._h, C.byref(st), C.byref(opt), C.byref(fb), ids.ctypes.data, probs.ctypes.data, counts.ctypes.data))
+        return ids, probs, counts
+
+    def lexical_rank_prf(self, queries, fb_docs=10, fb_terms=10, orig_weight=0.5, method="jm", param=None, top_k=1000):
+        """nvsm_lexical_rank_prf: lexical_rank of the RM3 query — the original terms with weight orig_weight / L each, then the
+        relevance model's expansion terms sharing 1 - orig_weight in proportion to their probabilities. Returns what lexical_rank does."""
+        q = queries if isinstance(queries, Queries) else Queries(queries)
+        opt = lexical_options(method, param, top_k)
+        fb = feedback_options(fb_docs, fb_terms, orig_weight)
+        k = opt.top_k
+        ids = np.empty((q.num_queries, k), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        check(lib().nvsm_lexical_rank_prf(self._h, C.byref(st), C.byref(opt), C.byref(fb), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
 
     def rank_ensemble(self, queries, alpha=0.5, normalizer="standardize", judgments=None, top_k=1000, method="jm", param=None,
-                      cutoffs=(5, 10, 20, 100, 1000), weights=None, **opts):
+                      cutoffs=(5, 10, 20, 100, 1000), weights=None, feedback=None, **opts):
         """nvsm_rank_ensemble: rank()'s list and lexical_rank()'s list of every query, each normalised over its returned
         entries ("standardize" | "minmax" | "none") and fused with weights alpha and 1 - alpha (include/cunvsm_amd.h has the
         formula). Returns (ids [Q, 2k], scores [Q, 2k], counts [Q]); with judgments, (metrics, ids, scores, counts) where
-        metrics is evaluate()'s dict computed on the fused list. opts: as rank()."""
+        metrics is evaluate()'s dict computed on the fused list. feedback (True, a dict of fb_docs / fb_terms / orig_weight, such a
+        tuple, or an NvsmFeedbackOptions): nvsm_rank_ensemble_prf, the lexical list is lexical_rank_prf()'s. opts: as rank()."""
         q = queries if isinstance(queries, Queries) else Queries(queries, weights)
         ropt = rank_options(self.cfg.num_entities, top_k, **opts)
         lopt = lexical_options(method, param, top_k)
         eopt = ensemble_options(alpha, normalizer)
+        fopt = None if feedback is None or feedback is False else as_feedback_options(feedback)
         k = ropt.top_k
         ids = np.empty((q.num_queries, 2 * k), dtype=np.int64)
         scores = np.empty((q.num_queries, 2 * k), dtype=np.float32)
@@ -795,10 +880,13 @@ class Model:
             names = eval_metric_names(cut.tolist())
             metrics = np.empty((q.num_queries, len(names)), dtype=np.float64)
             js = j.as_struct(cut)
-        check(lib().nvsm_rank_ensemble(
-            self._h, C.byref(st), C.byref(ropt), C.byref(lopt), C.byref(eopt), None if js is None else C.byref(js),
-            None if js is None else (metrics.ctypes.data if metrics.size else _EMPTY_F64.ctypes.data),
-            ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        tail = (C.byref(eopt), None if js is None else C.byref(js),
+                None if js is None else (metrics.ctypes.data if metrics.size else _EMPTY_F64.ctypes.data),
+                ids.ctypes.data, scores.ctypes.data, counts.ctypes.data)
+        if fopt is None:
+            check(lib().nvsm_rank_ensemble(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), *tail))
+        else:
+            check(lib().nvsm_rank_ensemble_prf(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), C.byref(fopt), *tail))
         if js is None:
             return ids, scores, counts
         result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}

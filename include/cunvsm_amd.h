@@ -468,7 +468,8 @@ int nvsm_evaluate(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_op
  * over Indri's. With D_c = num_documents, N = num_tokens, len(d) = doc_offsets[d + 1] − doc_offsets[d], tf(t, d) = occurrences of
  * word t in document d, cf(t) = occurrences of t in the arena and p(t) = cf(t) / N, a query is the nvsm_queries list of word ids
  * t_1 .. t_L:
- *   duplicates      a word repeated in a query contributes once per occurrence. word_weights are not looked at.
+ *   duplicates      a word repeated in a query contributes once per occurrence. word_weights are not looked at
+ *                   (nvsm_lexical_rank_weighted, below, honours them).
  *   absent terms    a query term with cf(t) = 0 is dropped. A query with no remaining terms, or without words, retrieves nothing:
  *                   counts[q] = 0, ids -1, scores -inf, as in nvsm_rank.
  *   NVSM_LEX_JM         s(q, d) = Σ_j log((1 − λ)·tf(t_j, d) / len(d) + λ·p(t_j)), λ in (0, 1) the weight of the collection model
@@ -504,7 +505,44 @@ int nvsm_evaluate(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_op
  * what it did before they existed, and its nvsm_describe text is unchanged. NVSM_ERR_INVALID_ARGUMENT before anything runs, each
  * with a sentence: no corpus uploaded; unknown method or normaliser; λ outside (0, 1); μ < 0; alpha outside [0, 1]; top_k out of
  * range; unequal top_ks; candidates given; null arguments, by name. A word id outside [0, num_words) follows the index contract:
- * it matches nothing and the call returns NVSM_ERR_INVALID_ARGUMENT. Pseudo-relevance feedback is out of scope.
+ * it matches nothing and the call returns NVSM_ERR_INVALID_ARGUMENT.
+ *
+ * WEIGHTED QUERIES AND PSEUDO-RELEVANCE FEEDBACK (nvsm_lexical_rank_weighted, nvsm_relevance_model, nvsm_lexical_rank_prf,
+ * nvsm_rank_ensemble_prf) — the "QLM w/ PRF" runs of rank-cranfield-collection.sh, which the reference takes from Indri (--prf)
+ * through a package outside its tree. There is no program text to follow: the contract is this one, after Lavrenko's relevance model
+ * in its RM3 form. cf, p(t), len(d), tf, the smoothing methods and "auto" mean what they mean above.
+ *   weighted query likelihood   the query terms t_1 .. t_L carry float32 weights w_j >= 0 in queries->word_weights (required). A term
+ *                   with cf = 0 or w_j = 0 is dropped; a query with nothing left retrieves nothing. s(q, d) = Σ_j w_j·a_j(d), a_j the
+ *                   Jelinek-Mercer or Dirichlet log term above; the sum runs in query order in fp64 (every product rounded on its own)
+ *                   and is narrowed to float32 ONCE. Retrieved set: the documents that hold at least one remaining term. Order: score
+ *                   descending, ties by ascending id; a repeated call returns the same bits. Accuracy: every a_j <= 0 and w_j >= 0, so
+ *                   nothing cancels: |score − the fp64 sum| <= 2^-23·|the fp64 sum| — tighter than nvsm_lexical_rank's bound on
+ *                   purpose: fp64 evaluation is part of THIS contract. nvsm_lexical_rank keeps its own bound and its bits. (Weights all
+ *                   1 return nvsm_lexical_rank's bits; a power-of-two weight on every term scales its scores exactly.)
+ *   relevance model  per query: (1) the UNWEIGHTED first pass (nvsm_lexical_rank; queries->word_weights are not looked at) with
+ *                   top_k = fb_docs returns d_0 .. d_{n−1} with float32 scores s_0 >= ..., n <= fb_docs; (2) ω_i = exp(double(s_i) −
+ *                   double(s_0)); (3) π(t) = (Σ_i ω_i·tf(t, d_i) / len(d_i)) / Σ_i ω_i, both sums over the documents in rank order in
+ *                   fp64, no document smoothing; π is narrowed to float32; (4) the expansion terms are the fb_terms terms with the
+ *                   largest float32 π > 0, ties by ascending word id; counts[q] says how many there are, slots behind hold (-1, -inf).
+ *                   Accuracy: |π − its fp64 value| <= 2^-23·π + 2^-149 (the narrowing; the fp64 sum of at most fb_docs positive terms
+ *                   is right to a few of its own ulps). With n = 1 no exp is involved (ω = 1) and π(t) is float32(tf / len) exactly.
+ *   expanded query  with o64 = double(orig_weight) and L the number of the query's remaining terms (cf > 0; repeated words count once
+ *                   per occurrence): those terms first, in query order, each with weight float32(o64 / L); then the expansion terms in
+ *                   rank order, each with weight float32(((1.0 − o64)·double(π_i)) / S), S = Σ_i double(π_i) summed in rank order.
+ *                   A term in both groups appears twice. Plain fp64 operations. (Indri's #combine is a mean and its #weight normalises:
+ *                   hence o / L and π_i / S.) Expansion terms are not filtered against the original query nor against a stop list: the
+ *                   vocabulary is the model's. A query without remaining terms has no feedback documents and stays empty.
+ *   nvsm_lexical_rank_prf   is BY DEFINITION nvsm_lexical_rank_weighted of the expanded query at lex->top_k: the same bits.
+ *   nvsm_rank_ensemble_prf  is nvsm_rank_ensemble with list B taken from nvsm_lexical_rank_prf; everything else is the same code path.
+ * Document smoothing inside the relevance model (Indri's fbMu) is out of scope. nvsm_relevance_model checks lex->top_k as the other
+ * calls do but ranks at fb_docs. All four calls are synchronous, touch no parameter, optimiser state, RNG state or lazy bookkeeping,
+ * allocate on first use (the relevance model's scratch, 12 bytes per word and query of a round, comes out of the same budget as the
+ * score slab), and leave nvsm_describe unchanged. NVSM_ERR_INVALID_ARGUMENT before anything runs, each with a sentence: what
+ * nvsm_lexical_rank refuses; null arguments by name, queries->word_weights among them for the weighted call; a weight that is negative
+ * or not finite; fb_docs outside [1, min(num_documents, NVSM_FEEDBACK_MAX_DOCS)]; fb_terms outside [1, num_words]; orig_weight outside
+ * [0, 1]. An EXPANDED query of more than NVSM_LEXICAL_MAX_QUERY_TERMS distinct terms is NVSM_ERR_UNSUPPORTED; it is known behind the
+ * relevance model and refused there, before the second pass and before any result is written. A word id out of range fails the PRF
+ * calls behind their first pass, with nothing written.
  */
 enum { NVSM_LEX_JM = 0, NVSM_LEX_DIRICHLET = 1 };
 enum { NVSM_NORM_STANDARDIZE = 0, NVSM_NORM_MINMAX = 1, NVSM_NORM_NONE = 2 };
@@ -533,6 +571,28 @@ int nvsm_lexical_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_lex
 int nvsm_rank_ensemble(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
                        const nvsm_ensemble_options* ens, const nvsm_judgments* judgments, double* metrics,
                        int64_t* doc_ids, float* scores, int64_t* counts);
+#define NVSM_FEEDBACK_MAX_DOCS 1024
+typedef struct {
+    int32_t fb_docs;              /* feedback documents per query: 1 .. min(num_documents, NVSM_FEEDBACK_MAX_DOCS) */
+    int32_t fb_terms;             /* expansion terms per query: 1 .. num_words */
+    float   orig_weight;          /* weight of the original query in the expanded one, in [0, 1] */
+    int32_t reserved[5];
+} nvsm_feedback_options;
+/* fb_docs 10, fb_terms 10, orig_weight 0.5 */
+void nvsm_feedback_options_default(nvsm_feedback_options* opt);
+/* nvsm_lexical_rank with queries->word_weights honoured (required); results as nvsm_lexical_rank */
+int nvsm_lexical_rank_weighted(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex,
+                               int64_t* doc_ids, float* scores, int64_t* counts);
+/* term_ids, term_probs [num_queries][fb_terms], counts [num_queries], all host; (-1, -inf) beyond counts[q] */
+int nvsm_relevance_model(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, const nvsm_feedback_options* fb,
+                         int64_t* term_ids, float* term_probs, int64_t* counts);
+/* results as nvsm_lexical_rank */
+int nvsm_lexical_rank_prf(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, const nvsm_feedback_options* fb,
+                          int64_t* doc_ids, float* scores, int64_t* counts);
+/* arguments and results as nvsm_rank_ensemble */
+int nvsm_rank_ensemble_prf(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                           const nvsm_feedback_options* fb, const nvsm_ensemble_options* ens, const nvsm_judgments* judgments,
+                           double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
 
 /*
  * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query

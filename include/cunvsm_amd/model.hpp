@@ -255,6 +255,64 @@ class Model {
         return e;
     }
 
+    // nvsm_lexical_rank_weighted: lexical_rank with a float32 weight >= 0 per query word (one per word id; a weight 0 drops its term)
+    Ranking lexical_rank_weighted(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const std::vector<float>& word_weights,
+                                  const nvsm_lexical_options& lex) {
+        static const float none = 0.f;      // (the ABI wants a pointer even where there is nothing to read)
+        nvsm_queries q = queries_of(word_ids, offsets, &word_weights);
+        if (!q.word_weights) q.word_weights = &none;
+        Ranking r;
+        r.top_k = lex.top_k;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(lex.top_k > 0 ? lex.top_k : 0);
+        r.doc_ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_lexical_rank_weighted(h_, &q, &lex, r.doc_ids.data(), r.scores.data(), r.counts.data()));
+        r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+    // nvsm_relevance_model: per query the fb.fb_terms most probable words under the relevance model of its fb.fb_docs best documents
+    struct RelevanceModel { std::vector<int64_t> term_ids; std::vector<float> term_probs; std::vector<int64_t> counts; int32_t fb_terms; };
+    RelevanceModel relevance_model(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_lexical_options& lex,
+                                   const nvsm_feedback_options& fb) {
+        const nvsm_queries q = queries_of(word_ids, offsets, nullptr);
+        RelevanceModel r;
+        r.fb_terms = fb.fb_terms;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(fb.fb_terms > 0 ? fb.fb_terms : 0);
+        r.term_ids.resize(n ? n : 1); r.term_probs.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_relevance_model(h_, &q, &lex, &fb, r.term_ids.data(), r.term_probs.data(), r.counts.data()));
+        r.term_ids.resize(n); r.term_probs.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+    // nvsm_lexical_rank_prf: lexical_rank of the RM3 query (cunvsm_amd.h has the expansion)
+    Ranking lexical_rank_prf(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_lexical_options& lex,
+                             const nvsm_feedback_options& fb) {
+        const nvsm_queries q = queries_of(word_ids, offsets, nullptr);
+        Ranking r;
+        r.top_k = lex.top_k;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(lex.top_k > 0 ? lex.top_k : 0);
+        r.doc_ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_lexical_rank_prf(h_, &q, &lex, &fb, r.doc_ids.data(), r.scores.data(), r.counts.data()));
+        r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+    // nvsm_rank_ensemble_prf: rank_ensemble with the lexical list taken from lexical_rank_prf
+    Evaluation rank_ensemble_prf(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                                 const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, const nvsm_ensemble_options& ens,
+                                 const nvsm_judgments* judgments = nullptr, const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        Evaluation e;
+        e.width = judgments ? NVSM_EVAL_FIXED + 3 * (judgments->num_cutoffs > 0 ? judgments->num_cutoffs : 0) : 0;
+        e.ranking.top_k = 2 * opt.top_k;
+        const size_t Q = static_cast<size_t>(q.num_queries);
+        const size_t n = Q * 2 * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        e.metrics.resize(Q * static_cast<size_t>(e.width) + 1);
+        e.ranking.doc_ids.resize(n ? n : 1); e.ranking.scores.resize(n ? n : 1); e.ranking.counts.resize(Q + 1);
+        check(nvsm_rank_ensemble_prf(h_, &q, &opt, &lex, &fb, &ens, judgments, judgments ? e.metrics.data() : nullptr, e.ranking.doc_ids.data(),
+                                     e.ranking.scores.data(), e.ranking.counts.data()));
+        e.metrics.resize(Q * static_cast<size_t>(e.width));
+        e.ranking.doc_ids.resize(n); e.ranking.scores.resize(n); e.ranking.counts.resize(Q);
+        return e;
+    }
+
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
     // 362-430): queries are row ids of `source_space`, or vectors [n][dim] of the searched space (neighbors_of_vectors)
     struct Neighbors { std::vector<int64_t> ids; std::vector<float> scores; std::vector<int64_t> counts; int32_t top_k; };
