@@ -149,6 +149,17 @@ class TablePassArgs(C.Structure):
         ("prev_n", C.c_int64), ("prev_keys", C.c_void_p),
         ("path", C.POINTER(C.c_int)), ("chunk", C.POINTER(C.c_int)), ("num_chunks", C.POINTER(C.c_int)),
         ("max_chunks", C.POINTER(C.c_int)), ("max_chunks2", C.POINTER(C.c_int)), ("arrive_left", C.POINTER(C.c_int)),
+        ("stamp", C.c_void_p), ("lazy_decay", C.c_void_p), ("now", C.c_int), ("stamp_out", C.c_void_p),
+    ]
+
+
+class LazyRefreshArgs(C.Structure):
+    """nvsm_debug_lazy_refresh_args (include/cunvsm_amd_test_hooks.h)."""
+    _fields_ = [
+        ("rows", C.c_int64), ("dim", C.c_int),
+        ("P", C.c_void_p), ("m", C.c_void_p), ("sc", C.c_void_p), ("sc_snapshot", C.c_void_p),
+        ("stamp", C.c_void_p), ("stamp_out", C.c_void_p), ("list", C.c_void_p), ("n_list", C.c_int64),
+        ("now", C.c_int), ("s_m", C.c_float), ("s_v", C.c_float), ("decay", C.c_void_p), ("scalars_only", C.c_int),
     ]
 
 
@@ -231,6 +242,8 @@ class _Library:
                 "nvsm_debug_dt_time": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), P(C.c_float)]),
                 "nvsm_debug_sort": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, P(C.c_float)]),
                 "nvsm_debug_gather_mean": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, vp]),
+                "nvsm_debug_gather_mean_lazy": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
+                "nvsm_debug_lazy_refresh": (C.c_int, [P(LazyRefreshArgs)]),
             }.items():
                 fn = getattr(H, hook)
                 fn.restype = res

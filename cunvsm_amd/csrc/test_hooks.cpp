@@ -15,6 +15,14 @@ using cunvsm::Error;
 using cunvsm::guarded_hook;
 using cunvsm::guarded_on;
 
+// kernels.h "lazy dense decay": nobody falls further behind than the factor ring is long - and the row pass and the gather do not
+// clamp: a row further behind would read a stale slot of the ring
+static void require_lags(const char* who, const int32_t* stamp, int64_t rows, int now) {
+    for (int64_t r = 0; r < rows; ++r)
+        if (stamp[r] < 0 || stamp[r] > now || now - stamp[r] > cunvsm::kLazyHistory)
+            throw Error(NVSM_ERR_INVALID_ARGUMENT, std::string(who) + ": a row lags further behind than the lazy decay contract allows");
+}
+
 extern "C" {
 
 int nvsm_debug_set_table_pass_form(int one_launch) { cunvsm::set_table_pass_one_launch(one_launch != 0); return NVSM_OK; }
@@ -391,7 +399,7 @@ int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* a) {
         using namespace cunvsm;
         const int64_t rows = a->rows, n = a->n, prev_n = a->prev_keys ? a->prev_n : 0, cap = a->max_entries;
         const int dim = a->dim, kind = a->kind;
-        const bool adam = a->adam != 0, order = a->chunk_order != 0;
+        const bool adam = a->adam != 0, order = a->chunk_order != 0, lazy = a->stamp != nullptr;
         const bool uses_m = kind == ROW_ADAM_MV || kind == ROW_ADAM_SPARSE_ENT || kind == ROW_ADAM_DENSE || kind == ROW_ADAM_FULL;
         const bool uses_p = kind == ROW_SGD || kind == ROW_ADAGRAD_ENT || kind == ROW_ADAM_SPARSE_ENT || kind == ROW_ADAM_DENSE || kind == ROW_ADAM_FULL;
         const bool uses_sc = kind == ROW_ADAGRAD_ENT || kind == ROW_SCALAR_ACC || kind == ROW_ADAM_MV || kind == ROW_ADAM_SPARSE_ENT || kind == ROW_ADAM_DENSE;
@@ -403,6 +411,12 @@ int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* a) {
         if (a->table == 1 && a->src_scale) bad("src_scale belongs to the words table");
         for (int64_t i = 0; i < n; ++i) if (a->keys[i] < 0 || a->keys[i] >= rows) bad("key out of range");
         for (int64_t i = 0; i < prev_n; ++i) if (a->prev_keys[i] < 0 || a->prev_keys[i] >= rows) bad("previous key out of range");
+        if (lazy) {
+            if (kind == ROW_ADAM_DENSE || kind == ROW_ADAM_FULL || kind == ROW_SCALAR_ACC) throw Error(NVSM_ERR_UNSUPPORTED, "table_pass: the model never runs this kind with pending decay");
+            if (!a->lazy_decay || !a->stamp_out) bad("pending decay needs the factor ring and stamp_out");
+            if (prev_n > 0) bad("pending decay and a previous batch do not go together");
+            require_lags("table_pass", a->stamp, rows, a->now);
+        }
 
         // the form of the pass: these fields and the defaults, whatever the environment says
         Tuning t;
@@ -447,7 +461,13 @@ int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* a) {
         if (a->coef) { coef.alloc(nent); up(coef.p, a->coef, nent * sizeof(float)); }
         if (a->sq_src) { sq_src.alloc(a->num_src); up(sq_src.p, a->sq_src, sq_src.n * sizeof(float)); }
         if (a->src_scale) { src_scale.alloc(a->num_src); up(src_scale.p, a->src_scale, src_scale.n * sizeof(float)); }
-        const bool in_place = uses_sc && a->sc_out == a->sc_in;
+        const bool in_place = uses_sc && (lazy || a->sc_out == a->sc_in);      // (lazy: sc_in uploads the stored scalar, written in place)
+        DevBuf<int> stamp;
+        DevBuf<float> snapshot;
+        if (lazy) {
+            stamp.alloc(rows); up(stamp.p, a->stamp, rows * sizeof(int));
+            if (uses_sc) { snapshot.alloc(rows); NVSM_HIP_CHECK(hipMemset(snapshot.p, 0xFF, rows * sizeof(float))); }
+        }
         if (a->P) { P.alloc(RD); up(P.p, a->P, RD * sizeof(float)); }
         if (a->m) { m.alloc(RD); up(m.p, a->m, RD * sizeof(float)); }
         if (a->v) { v.alloc(RD); up(v.p, a->v, RD * sizeof(float)); }
@@ -496,11 +516,27 @@ int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* a) {
             r.div = static_cast<uint32_t>(a->div);
             r.div_magic = (uint64_t(1) << 37) / r.div + 1;
             r.P = tp; r.m = tm; r.v = tv; r.sc_in = si; r.sc_out = so; r.dim = dim;
-            if (uses_m) fill_adam_consts(r, a->bc, a->lambda);
+            if (uses_m || (kind == ROW_SGD && a->wide)) fill_adam_consts(r, a->bc, a->lambda);      // (the wide SGD pass is a copy of the moments pass's arguments)
             r.lr = a->lr; r.lambda = a->lambda; r.decay = a->decay; r.eps = 1e-6f;
             r.dense = a->dense != 0; r.wide = a->wide != 0;
             r.nt_m = a->nt & 1; r.nt_p = (a->nt >> 1) & 1;
+            if (lazy) {
+                // Model::lazy_begin_update, Model::lazy_scalar_snapshot
+                r.lazy = 1;
+                r.pending.stamp = stamp.p; r.pending.now = a->now; std::memcpy(r.pending.decay, a->lazy_decay, sizeof(r.pending.decay));
+                if (uses_sc) {
+                    LazyRefreshArgs f{};
+                    f.scalars_only = 1;
+                    f.sc = so; f.sc_snapshot = snapshot.p;
+                    f.stamp = stamp.p; f.rows = rows; f.dim = dim; f.now = a->now;
+                    f.s_m = 1.f; f.s_v = uses_m ? r.s_v : 1.f;
+                    f.list = c.touched; f.list_count = c.num_touched;
+                    launch_lazy_refresh(f, std::min<int64_t>(cnt, rows), s);
+                    r.sc_in = snapshot.p;
+                }
+            }
             const int path = launch_table_pass(c, r, s);
+            if (lazy) launch_stamp_rows(c, stamp.p, a->now + 1, std::min<int64_t>(cnt, rows), s);      // Model::lazy_end_update
             NVSM_HIP_CHECK(hipGetLastError());
             NVSM_HIP_CHECK(hipStreamSynchronize(s));
             return std::make_pair(path, c.chunk);
@@ -535,6 +571,7 @@ int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* a) {
         if (a->m) down(a->m, m.p, RD * sizeof(float));
         if (a->v) down(a->v, v.p, RD * sizeof(float));
         if (uses_sc) down(a->sc_out, in_place ? sc_in.p : sc_out.p, rows * sizeof(float));
+        if (lazy) down(a->stamp_out, stamp.p, rows * sizeof(int));
     });
 }
 
@@ -664,5 +701,82 @@ int nvsm_debug_gather_mean(int64_t num_rows, int dim, const float* table, const 
     });
 }
 
+int nvsm_debug_gather_mean_lazy(int64_t num_rows, int dim, const float* table, const int64_t* idx, const float* wts,
+                                int window, int64_t num_out, const int32_t* stamp, const float* decay, int now,
+                                float* out, float* table_out) {
+    NVSM_REQUIRE(table); NVSM_REQUIRE(idx); NVSM_REQUIRE(out); NVSM_REQUIRE(stamp); NVSM_REQUIRE(decay); NVSM_REQUIRE(table_out);
+    return guarded_hook([&] {
+        if (num_rows < 1 || num_rows >= (int64_t(1) << 31) || dim < 1 || window < 1 || num_out < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "gather_mean_lazy: bad sizes");
+        for (int64_t i = 0; i < num_out * window; ++i)
+            if (idx[i] < 0 || idx[i] >= num_rows) throw Error(NVSM_ERR_INVALID_ARGUMENT, "gather_mean_lazy: id out of range");
+        require_lags("gather_mean_lazy", stamp, num_rows, now);
+        cunvsm::DevBuf<float> T, W, O;
+        cunvsm::DevBuf<int64_t> I64;
+        cunvsm::DevBuf<int> I, S;
+        T.alloc(num_rows * dim); O.alloc(num_out * dim); I64.alloc(num_out * window); I.alloc(num_out * window); S.alloc(num_rows);
+        NVSM_HIP_CHECK(hipMemcpy(T.p, table, T.n * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(I64.p, idx, I64.n * sizeof(int64_t), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(S.p, stamp, S.n * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemset(O.p, 0xFF, O.n * sizeof(float)));
+        if (wts) { W.alloc(num_out * window); NVSM_HIP_CHECK(hipMemcpy(W.p, wts, W.n * sizeof(float), hipMemcpyHostToDevice)); }
+        cunvsm::LazyView view{};
+        view.stamp = S.p; view.now = now; std::memcpy(view.decay, decay, sizeof(view.decay));
+        cunvsm::launch_narrow_i64(I64.p, I.p, num_out * window, num_rows, nullptr, 0, nullptr);
+        cunvsm::launch_gather_mean(T.p, dim, I.p, wts ? W.p : nullptr, window, num_out, O.p, nullptr, &view);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(out, O.p, O.n * sizeof(float), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(table_out, T.p, T.n * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+// One launch_lazy_refresh on caller-supplied inputs (cunvsm_amd_test_hooks.h): the arguments of Model::lazy_refresh /
+// Model::lazy_scalar_snapshot, the list and its count on the device as Csr::touched / num_touched are.
+int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* a) {
+    NVSM_REQUIRE(a); NVSM_REQUIRE(a->P); NVSM_REQUIRE(a->stamp); NVSM_REQUIRE(a->stamp_out); NVSM_REQUIRE(a->decay);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        const int64_t rows = a->rows, nl = a->list ? a->n_list : 0;
+        const int dim = a->dim;
+        auto bad = [](const char* what) { throw Error(NVSM_ERR_INVALID_ARGUMENT, std::string("lazy_refresh: ") + what); };
+        if (rows < 1 || rows >= (int64_t(1) << 30) || dim < 1 || nl < 0 || nl > rows) bad("bad sizes");
+        if (a->sc_snapshot && !a->sc) bad("a snapshot needs the scalar");
+        std::vector<char> seen(a->list ? static_cast<size_t>(rows) : 0, 0);
+        for (int64_t i = 0; i < nl; ++i) {
+            if (a->list[i] < 0 || a->list[i] >= rows || seen[a->list[i]]) bad("list: row ids in [0, rows), none twice");
+            seen[a->list[i]] = 1;
+        }
+        require_lags("lazy_refresh", a->stamp, rows, a->now);
+        auto up = [](void* d, const void* h, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice)); };
+        auto down = [](void* h, const void* d, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost)); };
+        const size_t RD = static_cast<size_t>(rows + 1) * dim, R1 = static_cast<size_t>(rows) + 1;
+        DevBuf<float> P, m, sc, snap;
+        DevBuf<int> stamp, list, count;
+        P.alloc(RD); up(P.p, a->P, RD * sizeof(float));
+        if (a->m) { m.alloc(RD); up(m.p, a->m, RD * sizeof(float)); }
+        if (a->sc) { sc.alloc(R1); up(sc.p, a->sc, R1 * sizeof(float)); }
+        if (a->sc_snapshot) { snap.alloc(R1); NVSM_HIP_CHECK(hipMemset(snap.p, 0xFF, R1 * sizeof(float))); }
+        stamp.alloc(rows); up(stamp.p, a->stamp, rows * sizeof(int));
+        if (a->list) {
+            list.alloc(std::max<int64_t>(nl, 1)); up(list.p, a->list, nl * sizeof(int));
+            const int n32 = static_cast<int>(nl);
+            count.alloc(1); up(count.p, &n32, sizeof(int));
+        }
+        LazyRefreshArgs r{};
+        r.P = P.p; r.m = m.p; r.sc = sc.p; r.sc_snapshot = snap.p; r.scalars_only = a->scalars_only != 0;
+        r.stamp = stamp.p; r.list = list.p; r.list_count = count.p;
+        r.rows = rows; r.dim = dim; r.now = a->now; r.s_m = a->s_m; r.s_v = a->s_v;
+        std::memcpy(r.decay, a->decay, sizeof(r.decay));
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        launch_lazy_refresh(r, a->list ? nl : rows, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        down(a->P, P.p, RD * sizeof(float));
+        if (a->m) down(a->m, m.p, RD * sizeof(float));
+        if (a->sc) down(a->sc, sc.p, R1 * sizeof(float));
+        if (a->sc_snapshot) down(a->sc_snapshot, snap.p, R1 * sizeof(float));
+        down(a->stamp_out, stamp.p, rows * sizeof(int));
+    });
+}
 
 }  // extern "C"

@@ -61,7 +61,16 @@ int nvsm_debug_set_table_pass_form(int one_launch);
 /* ONE table pass of the update on caller-supplied inputs (tests/test_gpu_table_pass.py): the host arrays are uploaded, then the
  * product's own launchers run in the order model.cpp calls them - sort_pairs, launch_csr_build, launch_chunk_order when the
  * chunks get an order, launch_table_pass - on a workspace sized by the product's own arithmetic (csr_chunk_caps /
- * csr_chunk_entries, kernels.h), and the state is copied back. Lazy decay stays out (RowPassArgs::pending is empty).
+ * csr_chunk_entries, kernels.h), and the state is copied back.
+ * Lazy decay (tests/test_gpu_lazy_rows.py): with `stamp` given the hook does what Model::update_entities / update_words do for a
+ * lazy table, in their order - RowPassArgs::lazy = 1 and ::pending = (stamp, lazy_decay, now); for the kinds with a per-row scalar
+ * launch_lazy_refresh with scalars_only on the CSR's touched list into a snapshot buffer of the hook's own (0xFF bytes to begin
+ * with; s_v from fill_adam_consts for the Adam kinds, 1 otherwise), which the pass reads as sc_in while it writes the stored
+ * scalar in place (no ping-pong flip); launch_table_pass; launch_stamp_rows(now + 1). The stored scalar is what sc_in uploads, and
+ * sc_out receives it back for every row, visited or not; stamp_out receives the stamps. prev_keys must be null.
+ * Refused: NVSM_ERR_INVALID_ARGUMENT for a stamp that is negative, ahead of `now` or more than 128 updates (kLazyHistory) behind
+ * it - the row pass does not clamp, such a row would read a stale slot of the ring -; NVSM_ERR_UNSUPPORTED for the kinds the
+ * model never makes lazy (4 dense Adam, 5 full Adam) and for 6, the accumulator pass, which runs in front of the lazy pass proper.
  * The form of the pass comes from the fields below alone - a Tuning of the hook's own with every other switch at its default, and
  * the process-wide launch form put back on exit -, never from the environment.
  * Entry e (its position in `keys`) reads source row e / div of X and coefficient coef[e]: num_src * div >= max(n, prev_n), and
@@ -91,6 +100,11 @@ typedef struct nvsm_debug_table_pass_args {
     int* num_chunks;                 /* [2]: level-1 / level-2 chunks the CSR build reserved */
     int* max_chunks; int* max_chunks2;
     int* arrive_left;                /* arrival counters of the one-launch pass that are not back at zero after it */
+    /* lazy decay (null / 0 = none: the rows are current) */
+    const int32_t* stamp;            /* [rows]: updates applied to each row */
+    const float* lazy_decay;         /* [128]: factor of update u + 1 at [u % 128] */
+    int now;                         /* updates applied to the table */
+    int32_t* stamp_out;              /* out [rows]: the stamps after launch_stamp_rows(now + 1) */
 } nvsm_debug_table_pass_args;
 int nvsm_debug_table_pass(const nvsm_debug_table_pass_args* args);
 /* ONE launch_loss (csrc/loss_bn.hip) on caller-supplied inputs (tests/test_gpu_loss_shapes.py): the host arrays are uploaded, the
@@ -139,6 +153,31 @@ int nvsm_debug_dt_time(int M, int N, int rows, int slabs, int repeats, int which
 int nvsm_debug_sort(int64_t n, int bits, const int32_t* keys, int32_t* keys_out, int32_t* vals_out, int repeats, float* avg_ms);
 int nvsm_debug_gather_mean(int64_t num_rows, int dim, const float* table, const int64_t* idx, const float* wts,
                            int window, int64_t num_out, float* out);
+/* ... through a LazyView (stamp [num_rows], decay [128]: factor of update u + 1 at [u % 128], now): launch_gather_mean applies the
+ * factors a row sat out as it gathers the row and writes nothing back - table_out [num_rows][dim] receives the table after the
+ * launch. Refused as in nvsm_debug_loss: a stamp that is negative, ahead of `now` or more than 128 behind it; ids outside the table. */
+int nvsm_debug_gather_mean_lazy(int64_t num_rows, int dim, const float* table, const int64_t* idx, const float* wts,
+                                int window, int64_t num_out, const int32_t* stamp, const float* decay, int now,
+                                float* out, float* table_out);
+/* ONE launch_lazy_refresh (csrc/update.hip: lazy_refresh_kernel<1 / 4>, or lazy_scalar_snapshot_kernel with scalars_only) on
+ * caller-supplied inputs. P and m carry one guard row behind the table ([rows + 1][dim]), sc and sc_snapshot one guard element
+ * ([rows + 1]); everything is uploaded, the snapshot starts as 0xFF bytes, and everything comes back. `list` (n_list row ids, each
+ * in [0, rows), no id twice) goes to the device with its count, as Csr::touched / num_touched do; null = all rows.
+ * Refused with NVSM_ERR_INVALID_ARGUMENT: a stamp that is negative, ahead of `now` or more than 128 behind it. */
+typedef struct nvsm_debug_lazy_refresh_args {
+    int64_t rows; int dim;
+    float* P;                        /* in / out [rows + 1][dim] */
+    float* m;                        /* in / out [rows + 1][dim] or null */
+    float* sc;                       /* in / out [rows + 1] or null */
+    float* sc_snapshot;              /* out [rows + 1] or null */
+    const int32_t* stamp;            /* [rows] */
+    int32_t* stamp_out;              /* out [rows] */
+    const int32_t* list; int64_t n_list;
+    int now; float s_m, s_v;
+    const float* decay;              /* [128]: factor of update u + 1 at [u % 128] */
+    int scalars_only;
+} nvsm_debug_lazy_refresh_args;
+int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* args);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,15 @@ entries every partial sum - in any order, under any chunking, fused multiply-add
 granularity and therefore exact in float32 (Case.exactness() computes the margin from the case's own arrays). g and q of every row
 equal the sums computed here in float64, which are exact for the same reason; an entry that is dropped, counted twice or given to
 another row moves g by at least 1/4 whatever the row's length. The row formulas are then restated operation by operation in
-np.float32 - one rounding per operation, in the kernel's order (apply_row_formula_sc is compiled with fp contract off)."""
+np.float32 - one rounding per operation, in the kernel's order (apply_row_formula_sc is compiled with fp contract off).
+
+Lazy decay (tests/test_gpu_lazy_rows.py). A case with `lags` is a pass over a lazily decayed table (csrc/kernels.h "lazy dense
+decay"): row r has had stamp[r] = now - lags[r] updates applied, the table `now`, and ring[u % 128] holds the factor of update
+u + 1. The rows WITH entries first get the factors they sat out - refresh32: one float32 rounding per factor, ascending u; m by
+the constant S_M; the per-row scalar by scalar32 -, then the row formula above; rows without entries keep every bit and their
+stamp, the rows with entries are stamped now + 1. The factors are 1 - uniform(1e-4, 3e-2), all distinct, so that a wrong ring slot
+moves the result by at least 1e-4 relative, four thousand ulps (test_table_pass_reference.py asserts that every stale row of
+every case would show it)."""
 import numpy as np
 
 F32 = np.float32
@@ -33,6 +41,51 @@ ONE_M_B1 = F32(1.0 - float(F32(0.9)))
 ONE_M_B2 = F32(1.0 - float(F32(0.999)))
 S_M = F32(1.0 - float(ONE_M_B1))
 S_V = F32(1.0 - float(ONE_M_B2))
+LAZY_HISTORY = 128                               # kLazyHistory (csrc/kernels.h)
+LAZY_LAGS = (0, 1, 64, 127, 128)                 # the lags the table-pass cases lay their ladder out for
+LAZY_KINDS = (SGD, ADAGRAD_ENT, ADAM_MV, ADAM_SPARSE_ENT)
+SITE_ROW_PASS, SITE_BODY_SHORT, SITE_LONG_FINISH, SITE_ENTRY_WALK = "row_pass_kernel", "table_pass_body-short", "long-row-finish", "entry_walk_kernel"
+SITES = (SITE_ROW_PASS, SITE_BODY_SHORT, SITE_LONG_FINISH, SITE_ENTRY_WALK)      # the four call sites of refresh_row_state
+
+
+def lazy_ring(seed, ones=False):
+    """The factor ring of a case: 128 distinct factors of the magnitudes a training run produces (1 - lambda lr), or all ones (lambda = 0)."""
+    if ones:
+        return np.ones(LAZY_HISTORY, F32)
+    rs = np.random.RandomState(7000 + seed)
+    while True:      # (two of 128 draws round to the same float32 once in sixty rings: draw again)
+        ring = (1.0 - rs.uniform(1e-4, 3e-2, LAZY_HISTORY)).astype(F32)
+        if np.unique(ring).size == LAZY_HISTORY:
+            return ring
+
+
+def refresh32(x, stamp, now, ring, shift=0):
+    """Every row of x [rows][...] through the factors of the updates stamp[row] .. now - 1 it sat out: x = float32(x * ring[(u + shift)
+    % 128]) for ascending u, one rounding per factor. shift != 0 is the WRONG slot (the sensitivity condition of the CPU test)."""
+    x = np.array(x, F32, copy=True)
+    stamp = np.asarray(stamp, np.int64)
+    ring = np.asarray(ring, F32)
+    assert x.shape[0] == stamp.shape[0] and ring.shape == (LAZY_HISTORY,) and np.all(stamp <= now) and np.all(stamp >= 0)
+    tail = (1,) * (x.ndim - 1)
+    for k in range(int((now - stamp).max()) if stamp.size else 0):
+        u = stamp + k
+        on = u < now
+        x[on] = x[on] * ring[(u[on] + shift) % LAZY_HISTORY].reshape((-1,) + tail)
+    assert x.dtype == F32
+    return x
+
+
+def scalar32(v, lag, s):
+    """v[row] = float32(v[row] * s), lag[row] times; skipped altogether for s == 1, as the kernels skip it."""
+    v = np.array(v, F32, copy=True)
+    lag = np.asarray(lag, np.int64)
+    s = F32(s)
+    if s == F32(1.0):
+        return v
+    for k in range(int(lag.max()) if lag.size else 0):
+        on = lag > k
+        v[on] = v[on] * s
+    return v
 
 
 def chunk_entries(adam, dim, n):
@@ -75,12 +128,17 @@ class Case:
 
     def __init__(self, name, lengths, kind, table=0, dim=128, div=10, coef=True, src_scale=False, adam=False, max_entries=None,
                  dense=0, lam=0.0, one_launch=1, chunk_order=0, fill_in_bounds=0, entry_walk_min=ENTRY_WALK_DEFAULT_MIN,
-                 contiguous=False, prev_lengths=None, path=PATH_DENSE, chunk=CHUNK, wide=0, nt=0, seed=1):
+                 contiguous=False, prev_lengths=None, path=PATH_DENSE, chunk=CHUNK, wide=0, nt=0, seed=1, lags=None, now=0):
         self.name, self.lengths, self.kind, self.table, self.dim, self.div = name, list(lengths), kind, table, dim, div
         self.coef, self.src_scale, self.adam, self.dense, self.lam = coef, src_scale and table == 0, adam, dense, lam
         self.one_launch, self.chunk_order, self.fill_in_bounds, self.entry_walk_min = one_launch, chunk_order, fill_in_bounds, entry_walk_min
         self.contiguous, self.prev_lengths, self.path, self.chunk, self.wide, self.nt, self.seed = contiguous, prev_lengths, path, chunk, wide, nt, seed
         self.rows = len(self.lengths)
+        # lazy decay: lags per row (cut to `now`: a young table has no row further behind than it is old), None = the rows are current
+        self.lazy, self.now = lags is not None, int(now)
+        self.lags = np.minimum(np.asarray(lags, np.int64), self.now) if self.lazy else None
+        assert not self.lazy or (len(self.lags) == self.rows and kind in LAZY_KINDS and prev_lengths is None and self.lags.min() >= 0
+                                 and self.lags.max() <= LAZY_HISTORY)
         self.n = int(sum(self.lengths))
         self.prev_n = int(sum(prev_lengths)) if prev_lengths is not None else 0
         assert prev_lengths is None or len(prev_lengths) == self.rows
@@ -119,6 +177,9 @@ class Case:
         self.m = rs.standard_normal((rows, dim)).astype(F32) if self.kind in USES_M else None
         self.v = rs.uniform(0.5, 2.0, (rows, dim)).astype(F32) if self.kind == ADAM_FULL else None
         self.sc_base = rs.uniform(0.5, 2.0, rows) if self.kind in USES_SC else None
+        if self.lazy:
+            self.stamp = (self.now - self.lags).astype(np.int32)
+            self.ring = lazy_ring(self.seed, ones=self.decay == F32(1.0))
         return self
 
     def build(self):
@@ -133,7 +194,7 @@ class Case:
         return self
 
     def release(self):
-        for name in ("keys", "prev_keys", "X", "coefs", "sq_src", "scale", "P", "m", "v", "sc_base", "g", "q", "cnt", "sc_in"):
+        for name in ("keys", "prev_keys", "X", "coefs", "sq_src", "scale", "P", "m", "v", "sc_base", "g", "q", "cnt", "sc_in", "stamp", "ring", "_start"):
             self.__dict__.pop(name, None)
 
     def entry_terms(self):
@@ -193,9 +254,55 @@ class Case:
         """(rows that get the formula, rows whose P it rewrites): apply_row_formula_sc's touch_p in the three walks."""
         has = self.cnt > 0
         p_always = (self.decay != F32(1.0)) or self.kind in (ADAM_FULL, ADAM_DENSE)
-        if self.dense:
+        if self.dense and not self.lazy:      # (RowPassArgs::lazy: rows without entries are not visited, their decay stays pending)
             return np.ones(self.rows, bool), (np.ones(self.rows, bool) if p_always else has)
         return has, has
+
+    def refreshes(self):
+        """Which of P, m a lazy pass of this kind brings up to date (RowKindTraits: kUsesP, kUsesM): the moments pass of sparse Adam's
+        words update leaves P alone, the wide SGD pass behind it leaves m alone."""
+        return self.kind in USES_P, self.kind in USES_M
+
+    def start(self):
+        """What the row formula starts from - dict of P, m, sc: the inputs as they are, or (lazy) with the pending factors applied to
+        the rows with entries: P by the ring, m by S_M, the scalar by S_V (the Adam kinds; Adagrad's accumulator does not decay)."""
+        self.build()
+        if not self.lazy:
+            return dict(P=self.P, m=self.m, sc=self.sc_in)
+        if not hasattr(self, "_start"):
+            has = self.cnt > 0
+            ref_p, ref_m = self.refreshes()
+            P, m, sc = self.P, self.m, self.sc_in
+            if ref_p:
+                P = np.where(has[:, None], refresh32(self.P, self.stamp, self.now, self.ring), self.P)
+            if ref_m:
+                m = np.where(has[:, None], refresh32(self.m, self.stamp, self.now, np.full(LAZY_HISTORY, S_M, F32)), self.m)
+            if sc is not None:
+                sc = np.where(has, scalar32(self.sc_in, self.lags, S_V if self.kind in USES_M else F32(1.0)), self.sc_in)
+            self._start = dict(P=P, m=m, sc=sc)
+        return self._start
+
+    def stamps_after(self):
+        """The rows with entries carry this update, the others keep their stamp."""
+        self.build()
+        return np.where(self.cnt > 0, self.now + 1, self.stamp).astype(np.int32)
+
+    def sites(self, path=None, chunk=None):
+        """The call sites of refresh_row_state (csrc/update.hip) this case takes its rows with entries through - by the path and chunk
+        length it was built for, or by those a launch reported."""
+        path = self.path if path is None else path
+        chunk = self.chunk if chunk is None else chunk
+        short = any(0 < L <= chunk for L in self.lengths)
+        long_ = any(L > chunk for L in self.lengths)
+        out = set()
+        if not self.one_launch:
+            out.add(SITE_ROW_PASS)                       # the three-launch form: every row, short or long
+        else:
+            if long_:
+                out.add(SITE_LONG_FINISH)                # (also behind an entry walk: the chunk-only launch finishes those rows)
+            if short:
+                out.add(SITE_ENTRY_WALK if path == PATH_ENTRY_WALK else SITE_BODY_SHORT)
+        return out
 
     def reference32(self):
         """The state after the pass in np.float32 arithmetic: dict of P, m, v, sc (None where the kind has none)."""
@@ -204,23 +311,25 @@ class Case:
         vis, touch = self.visited()
         g, q, fc = self.g.astype(F32), self.q.astype(F32), self.cnt.astype(F32)
         assert np.array_equal(g.astype(np.float64), self.g) and np.array_equal(q.astype(np.float64), self.q)
-        P, m = self.P.copy(), (self.m.copy() if self.m is not None else None)
+        st = self.start()
+        sc_in = st["sc"]
+        P, m = st["P"].copy(), (st["m"].copy() if st["m"] is not None else None)
         v = self.v.copy() if self.v is not None else None
         lr, decay, bc = self.lr, self.decay, self.bc
         sc = None
-        if k in USES_SC:
-            sc = self.sc_in.copy() if k == SCALAR_ACC else np.full(self.rows, SENTINEL, F32)
+        if k in USES_SC:      # (a lazy pass writes the stored scalar in place: rows it does not visit keep what they hold)
+            sc = self.sc_in.copy() if (k == SCALAR_ACC or self.lazy) else np.full(self.rows, SENTINEL, F32)
         V, T = vis[:, None], touch[:, None]
         with np.errstate(all="ignore"):
             if k == SGD:
                 P = np.where(T, P * decay + lr * g, P)
             elif k == ADAGRAD_ENT:
-                acc = self.sc_in + q
+                acc = sc_in + q
                 sc = np.where(vis, acc, sc)
                 s = F32(1.0) / np.sqrt(acc + EPS)
                 P = np.where(T, P * decay + lr * (g * s[:, None]), P)
             elif k == SCALAR_ACC:
-                sc = np.where(vis, self.sc_in + q, sc)
+                sc = np.where(vis, sc_in + q, sc)
             elif k == ADAM_FULL:
                 mn = m * S_M + ONE_M_B1 * g
                 mn = mn + (-self.c_reg) * P
@@ -232,7 +341,7 @@ class Case:
             else:
                 mn = m * S_M + ONE_M_B1 * g
                 m = np.where(V, mn, m)
-                vn = self.sc_in * S_V + ONE_M_B2 * q
+                vn = sc_in * S_V + ONE_M_B2 * q
                 sc = np.where(vis, vn, sc)
                 denom = (np.sqrt(vn) + EPS)[:, None]
                 if k == ADAM_SPARSE_ENT:
@@ -252,7 +361,7 @@ class Case:
         k = self.kind
         assert k in SQRT_DIV_KINDS
         _, touch = self.visited()
-        P, g = self.P.astype(np.float64), self.g
+        P, g = self.start()["P"].astype(np.float64), self.g
         lr, decay, bc, eps = float(self.lr), float(self.decay), float(self.bc), float(EPS)
         with np.errstate(all="ignore"):
             if k == ADAGRAD_ENT:
@@ -424,9 +533,117 @@ def _cases():
         add("leftover-order-%s" % f, other[::-1], ADAM_MV, table=0, dim=32, div=10, adam=True, one_launch=one, chunk_order=1, prev_lengths=L64, seed=121)
         add("leftover-c32-%s" % f, [33, 0, 2 * K_FAN * 32 + 1, 32, K_FAN * 32 + 1, 0, 65, 1] + [0] * 10, SGD, table=0, dim=64, div=10, one_launch=one,
             chunk=32, prev_lengths=L32, seed=122)
+    out.extend(_lazy_cases())
     names = [c.name for c in out]
     assert len(set(names)) == len(names)
     return out
+
+
+# ---- lazy decay: a pass over a table whose rows carry pending factors (tests/test_gpu_lazy_rows.py) ----
+# kind variants of a lazy pass: (name, kind, extra arguments, tables it is run on)
+LAZY_VARIANTS = [("sgd", SGD, dict(), (0, 1)), ("sgd_wide", SGD, dict(wide=1, adam=True), (0, 0)), ("sgd_scale", SGD, dict(src_scale=True), (0, 0)),
+                 ("adagrad_ent", ADAGRAD_ENT, dict(), (1, 0)), ("adam_mv", ADAM_MV, dict(adam=True), (0, 1)),
+                 ("adam_sparse_ent", ADAM_SPARSE_ENT, dict(adam=True), (1, 0))]
+LAZY_NOWS = (5, 128, 421, 1000003)      # a young table (lags cut to 5, stamp 0 present); a full ring; a lag range across the wrap; a large count
+LAZY_DIMS = (3, 7, 12, 128, 256, 300)
+LAZY_FORMS = ("one", "three", "walk")   # list walk in one launch / in three; entry walk
+
+
+def lazy_layout(lengths_per_lag, lags=LAZY_LAGS, shallow=False):
+    """The lengths once per lag, then rows without entries, their lags cycling through the same set, until rows * 2 >= n: the pass
+    is split, as a lazy table's always is - or (shallow) until rows >= n, where launch_table_pass sets RowPassArgs::shallow, as it
+    does for every table much larger than the batch. Returns (lengths, lags per row)."""
+    lengths, row_lags = [], []
+    for lag in lags:
+        lengths += list(lengths_per_lag)
+        row_lags += [lag] * len(lengths_per_lag)
+    n = sum(lengths)
+    i = 0
+    while (1 if shallow else 2) * len(lengths) < n:
+        lengths.append(0)
+        row_lags.append(lags[i % len(lags)])
+        i += 1
+    return lengths, row_lags
+
+
+def lazy_chunk(variant_kw, dim, n):
+    return chunk_entries(variant_kw.get("adam", False), dim, n)
+
+
+def lazy_lengths(form, c, dim):
+    """List walk: the short ladder (up to kFan c + 1 for dim >= 256): a short row, c, c + 1, kFan c + 1, 2 kFan c + 1 - every boundary of
+    the chunk tree. Entry walk: the short-row lengths, between ones so that the rows straddle a wave's positions."""
+    if form == "walk":
+        return [L for L in (30, 31, 32, 33, 1, 47, 48, 49, 1, 1, 60, 61, 62, 63, 64, 1, 2, 3, 35, 5, 64, 7, 64, 64, 9) if L <= c]
+    s = short_ladder(c)
+    return [L for L in s if L <= K_FAN * c + 1] if dim >= 256 else s
+
+
+# per (walk, kind variant): every `now` at lambda > 0 - a ring of distinct factors, the tables alternating, the second of them a
+# shallow pass -, then lambda = 0 (a ring of ones: P must come back untouched by the refresh) once on either table
+LAZY_PLAN = [(now, 0.01, i % 2, i == 1) for i, now in enumerate(LAZY_NOWS)] + [(128, 0.0, 0, False), (421, 0.0, 1, True)]
+
+
+def lazy_variant(c):
+    return ("sgd_wide" if c.wide else "sgd_scale" if c.src_scale else "sgd") if c.kind == SGD else KIND_NAMES[c.kind]
+
+
+def _lazy_cases():
+    out = []
+    for fi, form in enumerate(LAZY_FORMS):
+        dims = [d for d in LAZY_DIMS if form != "walk" or d <= 256]      # (the entry walk takes rows of at most 128 column vectors)
+        for ki, (vname, kind, kw, tables) in enumerate(LAZY_VARIANTS):
+            for ji, (now, lam, ti, shallow) in enumerate(LAZY_PLAN):
+                dim = dims[(ki + ji + fi) % len(dims)]
+                table = tables[ti]
+                c = lazy_chunk(kw, dim, 1)                  # (n stays below the small-chunk limit: the chunk length follows kind and dim)
+                lengths, lags = lazy_layout(lazy_lengths(form, c, dim), shallow=shallow)
+                assert sum(lengths) <= CHUNK_SMALL_MAX_ENTRIES
+                walk = form == "walk"
+                out.append(Case("lazy-%s-%s-%s-dim%d-c%d-now%d-lam%s%s" % (form, vname, "words" if table == 0 else "ents", dim, c, now, "1" if lam else "0",
+                                                                         "-shallow" if shallow else ""),
+                                lengths, kind, table=table, dim=dim, div=(10, 1, 17)[(ki + ji) % 3], one_launch=0 if form == "three" else 1,
+                                dense=1, lam=lam, chunk=c, entry_walk_min=0 if walk else ENTRY_WALK_DEFAULT_MIN,
+                                path=PATH_ENTRY_WALK if walk else PATH_LIST_WALK, lags=lags, now=now, seed=200 + 36 * fi + 6 * ki + ji, **kw))
+    return out
+
+
+def lazy_coverage(cases, sites=None):
+    """{(site, axis, value)} the cases reach (sites: those of a launch's report, instead of the case's own). A kind whose pass
+    refreshes P counts for a `now` only with lambda > 0: with a ring of ones no slot can be told from another."""
+    got = set()
+    for c in cases:
+        variant = lazy_variant(c)
+        lam = bool(c.lam > 0)
+        axes = [("kind", variant), ("lambda", lam), ("table", c.table), ("dim", c.dim), ("chunk", c.chunk), ("now", c.now),
+                ("table-lambda", (c.table, lam)), ("kind-table-lambda", (variant, c.table, lam)), ("shallow", c.rows >= c.n)]
+        if lam or c.kind not in USES_P:
+            axes.append(("kind-now", (variant, c.now)))
+        for site in (c.sites() if sites is None else sites):
+            for axis, value in axes:
+                got.add((site, axis, value))
+    return got
+
+
+def lazy_coverage_wanted():
+    """Every value of every axis at every refresh site (the entry walk has no dim 300): kind, lambda, table, dim, chunk length, `now`,
+    shallow or not; every table with lambda > 0 and with lambda = 0, per kind too (on the tables the model runs it on); every kind at
+    every `now` with distinct factors."""
+    want = set()
+    for site in SITES:
+        for name, _, _, tables in LAZY_VARIANTS:
+            want.add((site, "kind", name))
+            for now in LAZY_NOWS:
+                want.add((site, "kind-now", (name, now)))
+            for t in set(tables):
+                for lam in (True, False):
+                    want.add((site, "kind-table-lambda", (name, t, lam)))
+        for axis, values in (("lambda", (True, False)), ("table", (0, 1)), ("chunk", (32, 64)), ("now", LAZY_NOWS), ("shallow", (True, False)),
+                             ("table-lambda", [(t, lam) for t in (0, 1) for lam in (True, False)]),
+                             ("dim", [d for d in LAZY_DIMS if site != SITE_ENTRY_WALK or d <= 256])):
+            for v in values:
+                want.add((site, axis, v))
+    return want
 
 
 CASES = _cases()

@@ -92,6 +92,37 @@ def test_config_struct_matches_header_size():
     assert C.sizeof(ca.NvsmBatch) == 48
 
 
+def test_hook_structs_match_their_ctypes_mirrors(tmp_path):
+    """The argument structs of include/cunvsm_amd_test_hooks.h against cunvsm_amd/_lib.py, field by field: size and every offset, as
+    the C compiler lays them out (a field added to one side only, or in another place, shifts everything behind it)."""
+    import subprocess
+    pairs = [("nvsm_debug_gemm_epilogue_args", ca._lib.GemmEpilogueArgs), ("nvsm_debug_table_pass_args", ca._lib.TablePassArgs),
+             ("nvsm_debug_loss_args", ca._lib.LossArgs), ("nvsm_debug_lazy_refresh_args", ca._lib.LazyRefreshArgs)]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "cunvsm_amd_test_hooks.h"', 'int main(void) {']
+    for cname, mirror in pairs:
+        lines.append('    printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        for field, _ in mirror._fields_:
+            lines.append('    printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, field, cname, field.rstrip("_")))
+    lines += ['    return 0;', '}']
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    got = dict(line.split() for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    for cname, mirror in pairs:
+        assert int(got[cname]) == C.sizeof(mirror), cname
+        for field, _ in mirror._fields_:
+            assert int(got["%s.%s" % (cname, field)]) == getattr(mirror, field).offset, (cname, field)
+    # the lazy-decay fields of the table pass stand at its end: callers that do not know them are unaffected
+    assert [f for f, _ in ca._lib.TablePassArgs._fields_][-4:] == ["stamp", "lazy_decay", "now", "stamp_out"]
+    with open(os.path.join(ROOT, "include", "cunvsm_amd_test_hooks.h")) as f:
+        header = f.read()
+    for cname, mirror in pairs:      # no field of the header is missing from the mirror: count the declarators of the struct's body
+        body = re.sub(r"/\*.*?\*/", "", header[header.index("typedef struct " + cname):header.index("} " + cname)], flags=re.S)
+        body = body[body.index("{") + 1:]
+        names = [d.strip().split()[-1].lstrip("*") for stmt in body.split(";") if stmt.strip() for d in stmt.split(",")]
+        assert names == [f.rstrip("_") for f, _ in mirror._fields_], cname
+
+
 def test_public_headers_compile(tmp_path):
     """include/cunvsm_amd.h is plain C (a cgo / JNI / ctypes binding can consume it); the C++ wrapper needs C++11 only."""
     import subprocess

@@ -12,7 +12,9 @@ that per case): one entry dropped, doubled or given to another row changes a row
 Asserted per case: the path launch_table_pass took and the chunk length; the CSR build's chunk counts against the row lengths and
 against the workspace's caps; the arrival counters back at zero; state that is only multiplied and added (P of SGD, m, the per-row
 scalar, v) bit for bit; P behind a sqrtf or a division within the allowance of table_pass_reference.Case.reference64; rows without
-entries untouched bit for bit (a pass that is not dense) or taken through the same formula with g = q = cnt = 0 (a dense one)."""
+entries untouched bit for bit (a pass that is not dense) or taken through the same formula with g = q = cnt = 0 (a dense one).
+A case with pending lazy decay (tests/test_gpu_lazy_rows.py runs those) also has its stamps compared, and its rows without entries
+must keep every bit of P, m, the stored scalar and the stamp, however stale they are."""
 import ctypes as C
 
 import numpy as np
@@ -29,16 +31,23 @@ def _ptr(a):
     return a.ctypes.data if a is not None else None
 
 
-def run_table_pass(case):
-    """The case through the hook: (state after the pass, what the hook reports)."""
+def run_table_pass(case, state=None):
+    """The case through the hook: (state after the pass, what the hook reports). state: P, m and stamps to start from instead of the
+    case's own (the second pass of a sequence)."""
     case.build()
-    P = case.P.copy()
-    m = case.m.copy() if case.m is not None else None
+    state = state or {}
+    P = state.get("P", case.P).copy()
+    m = state.get("m", case.m)      # (given to a kind that has no use for it, it must come back as it went in)
+    m = m.copy() if m is not None else None
     v = case.v.copy() if case.v is not None else None
     sc_in = sc_out = None
     if case.kind in tp.USES_SC:
         sc_in = case.sc_in.copy()
         sc_out = sc_in if case.kind == tp.SCALAR_ACC else np.full(case.rows, tp.SENTINEL, np.float32)      # the accumulator pass works in place
+    stamp = ring = stamp_out = None
+    if case.lazy:
+        stamp, ring = case.stamp.copy(), case.ring.copy()
+        stamp_out = np.full(case.rows, -7, np.int32)
     path, chunk, max1, max2, left = C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_int(-1), C.c_int(-1)
     num_chunks = (C.c_int * 2)(-1, -1)
     a = TablePassArgs(
@@ -50,11 +59,13 @@ def run_table_pass(case):
         fill_in_bounds=case.fill_in_bounds, entry_walk_min=case.entry_walk_min,
         prev_n=case.prev_n, prev_keys=_ptr(case.prev_keys),
         path=C.pointer(path), chunk=C.pointer(chunk), num_chunks=num_chunks, max_chunks=C.pointer(max1), max_chunks2=C.pointer(max2),
-        arrive_left=C.pointer(left))
+        arrive_left=C.pointer(left), stamp=_ptr(stamp), lazy_decay=_ptr(ring), now=case.now, stamp_out=_ptr(stamp_out))
     ca._lib.check(ca.lib().nvsm_debug_table_pass(C.byref(a)))
     report = dict(path=path.value, chunk=chunk.value, num_chunks=(num_chunks[0], num_chunks[1]), max_chunks=max1.value, max_chunks2=max2.value,
                   arrive_left=left.value)
-    return dict(P=P, m=m, v=v, sc=sc_out), report
+    if case.lazy:
+        assert np.array_equal(stamp, case.stamp) and np.array_equal(ring, case.ring), "the hook wrote to its inputs"
+    return dict(P=P, m=m, v=v, sc=sc_out, stamp=stamp_out), report
 
 
 def _rows_that_differ(got, want):
@@ -93,15 +104,27 @@ def check_case(case):
             np.flatnonzero(~ok.all(axis=1))[:8], lengths[np.flatnonzero(~ok.all(axis=1))[:8]], np.nanmax(err[over] / tol[over]) if over.any() else np.nan)
         _, touch = case.visited()
         np.testing.assert_array_equal(got["P"][~touch], case.P[~touch])
-        print("   P: worst error %.3f of the allowance" % float(np.max(err[tol > 0] / tol[tol > 0])) if (tol > 0).any() else "   P: untouched")
+        rep["p_share"] = float(np.max(err[tol > 0] / tol[tol > 0])) if (tol > 0).any() else 0.0
+        print("   P: worst error %.3f of the allowance" % rep["p_share"] if (tol > 0).any() else "   P: untouched")
     # ---- rows without entries of a pass that is not dense: nothing moves (also implied above; said once more, on the inputs) ----
-    if not case.dense:
+    if not case.dense or case.lazy:
         empty = lengths == 0
         for name, before in (("P", case.P), ("m", case.m), ("v", case.v)):
             if before is not None:
                 np.testing.assert_array_equal(got[name][empty], before[empty])
-        if got["sc"] is not None and case.kind != tp.SCALAR_ACC:
+        if got["sc"] is not None and case.kind != tp.SCALAR_ACC and not case.lazy:
             assert np.all(got["sc"][empty] == tp.SENTINEL)
+    # ---- pending lazy decay: the stamps; rows without entries keep the stored scalar and the stamp; a pass that has no use for P
+    #      (the moments pass of sparse Adam's words update) leaves all of it alone, stale rows included ----
+    if case.lazy:
+        empty = lengths == 0
+        np.testing.assert_array_equal(got["stamp"], case.stamps_after())
+        np.testing.assert_array_equal(got["stamp"][empty], case.stamp[empty])
+        if got["sc"] is not None:
+            np.testing.assert_array_equal(got["sc"][empty], case.sc_in[empty])
+        if case.kind not in tp.USES_P:
+            np.testing.assert_array_equal(got["P"], case.P)
+    return got, rep
 
 
 def _select(prefix):
