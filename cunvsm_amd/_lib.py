@@ -23,6 +23,7 @@ NORM_STANDARDIZE, NORM_MINMAX, NORM_NONE = 0, 1, 2
 LEXICAL_MAX_QUERY_TERMS = 1024
 ENSEMBLE_MAX_TOP_K = 1024
 FEEDBACK_MAX_DOCS = 1024
+SWEEP_MAX_ALPHAS = 1024
 
 STATUS = {0: "OK", 1: "INVALID_ARGUMENT", 2: "UNSUPPORTED", 3: "DEVICE", 4: "STATE", 5: "NO_DEVICE"}
 
@@ -109,6 +110,15 @@ class NvsmEnsembleOptions(C.Structure):
 
 class NvsmFeedbackOptions(C.Structure):
     _fields_ = [("fb_docs", C.c_int32), ("fb_terms", C.c_int32), ("orig_weight", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+class NvsmSweepOptions(C.Structure):
+    _fields_ = [("alphas", C.c_void_p), ("num_alphas", C.c_int32), ("normalizer", C.c_int32), ("depth", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
+class NvsmCvOptions(C.Structure):
+    _fields_ = [("measure", C.c_int32), ("num_folds", C.c_int32), ("fold_of", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
 class NvsmNeighborQueries(C.Structure):
@@ -314,6 +324,11 @@ def lib():
         "nvsm_lexical_rank_prf": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), P(NvsmFeedbackOptions), vp, vp, vp]),
         "nvsm_rank_ensemble_prf": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmFeedbackOptions),
                                              P(NvsmEnsembleOptions), P(NvsmJudgments), vp, vp, vp, vp]),
+        "nvsm_sweep_options_default": (None, [P(NvsmSweepOptions)]), "nvsm_cv_options_default": (None, [P(NvsmCvOptions)]),
+        "nvsm_ensemble_sweep": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmFeedbackOptions),
+                                          P(NvsmSweepOptions), P(NvsmJudgments), vp]),
+        "nvsm_rank_ensemble_cv": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmFeedbackOptions),
+                                            P(NvsmSweepOptions), P(NvsmCvOptions), P(NvsmJudgments), vp, vp, vp, vp, vp, vp, vp]),
         "nvsm_neighbor_options_default": (None, [P(NvsmNeighborOptions)]),
         "nvsm_neighbors": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNeighborOptions), vp, vp, vp]),
         "nvsm_similarity": (C.c_int, [vp, C.c_int32, vp, vp, i64, C.c_int32, vp]),

@@ -391,6 +391,35 @@ int nvsm_rank_ensemble_prf(nvsm_model* m, const nvsm_queries* queries, const nvs
     return guarded_on(m, [&] { m->impl.rank_ensemble_prf(*queries, *rank_opt, *lex, *fb, *ens, judgments, metrics, doc_ids, scores, counts); });
 }
 
+void nvsm_sweep_options_default(nvsm_sweep_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->normalizer = NVSM_NORM_STANDARDIZE;
+}
+void nvsm_cv_options_default(nvsm_cv_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->measure = NVSM_EVAL_AP; o->num_folds = 20;
+}
+int nvsm_ensemble_sweep(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                        const nvsm_feedback_options* fb, const nvsm_sweep_options* sweep, const nvsm_judgments* judgments, double* metrics) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(rank_opt); NVSM_REQUIRE(lex); NVSM_REQUIRE(sweep); NVSM_REQUIRE(judgments);
+    NVSM_REQUIRE(metrics);
+    return guarded_on(m, [&] { m->impl.ensemble_sweep(*queries, *rank_opt, *lex, fb, *sweep, *judgments, metrics); });
+}
+int nvsm_rank_ensemble_cv(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                          const nvsm_feedback_options* fb, const nvsm_sweep_options* sweep, const nvsm_cv_options* cv,
+                          const nvsm_judgments* judgments, float* fold_alpha, double* fold_train_measure, int64_t* doc_ids, float* scores,
+                          int64_t* counts, double* metrics, double* sweep_metrics) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(rank_opt); NVSM_REQUIRE(lex); NVSM_REQUIRE(sweep); NVSM_REQUIRE(cv);
+    NVSM_REQUIRE(judgments); NVSM_REQUIRE(fold_alpha); NVSM_REQUIRE(fold_train_measure); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores);
+    NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] {
+        m->impl.rank_ensemble_cv(*queries, *rank_opt, *lex, fb, *sweep, *cv, *judgments, fold_alpha, fold_train_measure, doc_ids, scores, counts,
+                                 metrics, sweep_metrics);
+    });
+}
+
 void nvsm_neighbor_options_default(nvsm_neighbor_options* o) {
     if (!o) return;
     std::memset(o, 0, sizeof(*o));

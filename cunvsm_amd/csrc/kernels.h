@@ -612,8 +612,22 @@ struct FuseArgs {
     const int64_t* ids_b; const float* scores_b; const int64_t* counts_b;
     int k; int npad; float alpha; int normalizer;
     int64_t* out_ids; float* out_scores; int64_t* out_counts;
+    const float* query_alpha;      // null: every query at `alpha`; given [Q]: query q at query_alpha[q] (nvsm_rank_ensemble_cv)
 };
 void launch_fuse_lists(const FuseArgs& a, int Q, hipStream_t s);
+// the alpha sweep of the fusion (fuse_sweep_kernel; include/cunvsm_amd.h nvsm_ensemble_sweep): the two lists of f
+// (f.alpha, f.out_* are not looked at) matched and normalised once per workgroup, then for every alpha of the workgroup's strip the
+// fused order of fuse_lists_kernel and eval_metrics_kernel's row of its first min(depth, count) entries (depth 0: all), all in LDS.
+// e: the call's judgments as launch_eval_metrics reads them, e.q0 the round's first query; table [num_alphas][total_queries][width]
+// doubles on the device, width = NVSM_EVAL_FIXED + 3 e.num_cutoffs. Grid: (queries of the round, strips of kFuseSweepStrip alphas).
+constexpr int kFuseSweepStrip = 8;         // alphas one workgroup sweeps behind one id match
+constexpr int kFuseSweepMaxAlphas = 1024;  // NVSM_SWEEP_MAX_ALPHAS
+struct FuseSweepArgs {
+    FuseArgs f; EvalArgs e;
+    const float* alphas; int num_alphas; int depth;
+    double* table; int64_t total_queries;
+};
+void launch_fuse_sweep(const FuseSweepArgs& a, int Q, hipStream_t s);
 
 
 }  // namespace cunvsm

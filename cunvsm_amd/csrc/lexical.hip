@@ -16,6 +16,8 @@
 //   fuse_lists_kernel     one workgroup per query: normalises two ranked lists over their returned entries, matches the documents
 //                         both hold by a bitonic sort of (id, list, position) keys, computes the fused fp64 scores and sorts
 //                         (fused score, id)
+//   fuse_sweep_kernel     fuse_lists_kernel's match once per workgroup, then per alpha of a strip the fused order and the metric row
+//                         of its first `depth` entries, all in LDS (nvsm_ensemble_sweep)
 // No float atomics anywhere: a repeated call returns the same bits. All arena offsets are 64-bit.
 //
 // Arithmetic of a term: fp64 throughout (allowed by the contract, and the accurate log the contract asks for). With tf = 0 — nearly
@@ -26,6 +28,7 @@
 #include "../../include/cunvsm_amd.h"
 #include "kernels.h"
 #include "device_utils.h"
+#include "eval_row.h"
 
 namespace cunvsm {
 
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(256) void fuse_lists_kernel(FuseArgs a) {
     }
     __syncthreads();
     fuse_sort<false, false>(sk, nullptr, n2);
-    const double wA = static_cast<double>(a.alpha), wB = 1.0 - wA;
+    const double wA = static_cast<double>(a.query_alpha ? a.query_alpha[q] : a.alpha), wB = 1.0 - wA;
     for (int i = threadIdx.x; i < n2; i += 256) {
         const unsigned long long key = sk[i];
         unsigned long long out = 0ull;
@@ -299,6 +302,102 @@ __global__ __launch_bounds__(256) void fuse_lists_kernel(FuseArgs a) {
     }
     __syncthreads();
     if (threadIdx.x == 0) a.out_counts[q] = fused_count;
+}
+
+// ---- the alpha sweep ----------------------------------------------------------------------------------------------
+// fuse_lists_kernel's match and normalisation once, then per alpha of the workgroup's strip its fused keys, its pair sort, and
+// eval_metrics_kernel's row of the sorted ids where they lie in LDS. What depends on alpha is the key, one sort and the row.
+//   LDS per entry slot: 8 B  the (id, list, position) key, overwritten by the entry's normalised score once its neighbours are read
+//                       8 B  fused key        4 B  ~id next to it        4 B  id        1 B  kind
+//   kind: 0 padding, or list B's entry of a document list A holds; 1 in list A only; 2 in list B only; 3 list A's entry of a document
+//   whose list B entry is the next slot. One double per ENTRY is enough: both lists together hold at most npad entries.
+__global__ __launch_bounds__(256) void fuse_sweep_kernel(FuseSweepArgs s) {
+#pragma clang fp contract(off)
+    extern __shared__ unsigned long long fuse_lds[];
+    const FuseArgs& a = s.f;
+    const int n2 = a.npad;                               // a power of two >= 2 k
+    unsigned long long* sk = fuse_lds;                   // [n2] (id, list, position) ascending; then the bits of the normalised scores
+    unsigned long long* fk = fuse_lds + n2;              // [n2] fused score keys, descending
+    unsigned* fid = reinterpret_cast<unsigned*>(fuse_lds + 2 * n2);      // [n2] ~id next to them
+    unsigned* did = fid + n2;                            // [n2] id of the slot's document
+    unsigned char* kind = reinterpret_cast<unsigned char*>(did + n2);    // [n2]
+    __shared__ FuseStats stats[2];
+    __shared__ int num_docs;
+    const int q = blockIdx.x, k = a.k;
+    const int64_t* idA = a.ids_a + static_cast<size_t>(q) * k;
+    const int64_t* idB = a.ids_b + static_cast<size_t>(q) * k;
+    const float* scA = a.scores_a + static_cast<size_t>(q) * k;
+    const float* scB = a.scores_b + static_cast<size_t>(q) * k;
+    int nA = static_cast<int>(a.counts_a[q]), nB = static_cast<int>(a.counts_b[q]);
+    nA = nA < 0 ? 0 : (nA > k ? k : nA);
+    nB = nB < 0 ? 0 : (nB > k ? k : nB);
+    if (threadIdx.x == 0) { stats[0] = fuse_stats(scA, nA); num_docs = 0; }
+    if (threadIdx.x == 64) stats[1] = fuse_stats(scB, nB);
+    for (int i = threadIdx.x; i < n2; i += 256) {
+        unsigned long long key = ~0ull;
+        if (i < nA) key = (static_cast<unsigned long long>(idA[i]) << 32) | static_cast<unsigned long long>(i);
+        else if (i >= k && i - k < nB) key = (static_cast<unsigned long long>(idB[i - k]) << 32) | 0x80000000ull | static_cast<unsigned long long>(i - k);
+        sk[i] = key;
+    }
+    __syncthreads();
+    fuse_sort<false, false>(sk, nullptr, n2);
+    for (int i = threadIdx.x; i < n2; i += 256) {
+        const unsigned long long key = sk[i];
+        unsigned id = 0u;
+        unsigned char kd = 0;
+        if (key != ~0ull) {
+            id = static_cast<unsigned>(key >> 32);
+            const bool dup = i > 0 && static_cast<unsigned>(sk[i - 1] >> 32) == id && sk[i - 1] != ~0ull;
+            if (!dup) {
+                if ((key & 0x80000000ull) != 0) kd = 2;
+                else kd = (i + 1 < n2 && sk[i + 1] != ~0ull && static_cast<unsigned>(sk[i + 1] >> 32) == id) ? 3 : 1;
+                atomicAdd(&num_docs, 1);      // (an integer count: its order does not matter)
+            }
+        }
+        did[i] = id;
+        kind[i] = kd;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n2; i += 256) {      // every entry's normalised score in place of its key
+        const unsigned long long key = sk[i];
+        double v = 0.0;
+        if (key != ~0ull) {
+            const int pos = static_cast<int>(key & 0x7fffffffull);
+            v = (key & 0x80000000ull) != 0 ? fuse_normalise(scB[pos], stats[1], a.normalizer) : fuse_normalise(scA[pos], stats[0], a.normalizer);
+        }
+        sk[i] = static_cast<unsigned long long>(__double_as_longlong(v));
+    }
+    __syncthreads();
+    const int64_t gq = s.e.q0 + q;
+    const int width = NVSM_EVAL_FIXED + 3 * s.e.num_cutoffs;
+    const int n = s.depth > 0 && s.depth < num_docs ? s.depth : num_docs;
+    const int a_end = (blockIdx.y + 1) * kFuseSweepStrip < s.num_alphas ? (blockIdx.y + 1) * kFuseSweepStrip : s.num_alphas;
+    for (int ai = blockIdx.y * kFuseSweepStrip; ai < a_end; ++ai) {
+        const double wA = static_cast<double>(s.alphas[ai]), wB = 1.0 - wA;
+        for (int i = threadIdx.x; i < n2; i += 256) {
+            const int kd = kind[i];
+            unsigned long long out = 0ull;
+            if (kd != 0) {
+                const double v = __longlong_as_double(static_cast<long long>(sk[i]));
+                double f;
+                if (kd == 2) {
+                    f = wB * v;
+                } else {
+                    f = wA * v;
+                    if (kd == 3) f = (f + wB * __longlong_as_double(static_cast<long long>(sk[i + 1]))) / 2.0;
+                }
+                out = fuse_key(f);
+            }
+            fk[i] = out;
+            fid[i] = 0xffffffffu - did[i];
+        }
+        __syncthreads();
+        fuse_sort<true, true>(fk, fid, n2);
+        if (threadIdx.x < 64)      // one wave, as eval_metrics_kernel: the row of the first n sorted ids
+            eval_row(s.e, gq, n, static_cast<int>(threadIdx.x), [fid](int r) { return static_cast<int>(0xffffffffu - fid[r]); },
+                     s.table + (static_cast<int64_t>(ai) * s.total_queries + gq) * width);
+        __syncthreads();      // (the next alpha overwrites the keys the wave reads)
+    }
 }
 
 int grid_for(int64_t n) { return stream_grid(n, 256); }
@@ -346,6 +445,14 @@ void launch_fuse_lists(const FuseArgs& a, int Q, hipStream_t s) {
     if (Q <= 0) return;
     const size_t lds = static_cast<size_t>(a.npad) * (2 * sizeof(unsigned long long) + sizeof(unsigned));
     NVSM_LAUNCH(fuse_lists_kernel, dim3(Q), dim3(256), lds, s, a);
+}
+
+static size_t fuse_sweep_lds_bytes(int npad) { return (static_cast<size_t>(npad) * (2 * sizeof(unsigned long long) + 2 * sizeof(unsigned) + 1) + 7) / 8 * 8; }
+
+void launch_fuse_sweep(const FuseSweepArgs& a, int Q, hipStream_t s) {
+    if (Q <= 0 || a.num_alphas <= 0) return;
+    const int strips = (a.num_alphas + kFuseSweepStrip - 1) / kFuseSweepStrip;
+    NVSM_LAUNCH(fuse_sweep_kernel, dim3(Q, strips), dim3(256), fuse_sweep_lds_bytes(a.f.npad), s, a);
 }
 
 }  // namespace cunvsm

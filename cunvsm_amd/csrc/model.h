@@ -184,6 +184,12 @@ class Model {
                            int64_t* counts);
     void evaluate(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_judgments& j, double* metrics, int64_t* doc_ids,
                   float* scores, int64_t* counts);
+    // supervised fusion (include/cunvsm_amd.h; lexical.hip fuse_sweep_kernel); fb null: list B is lexical_rank's
+    void ensemble_sweep(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                        const nvsm_sweep_options& sw, const nvsm_judgments& j, double* table);
+    void rank_ensemble_cv(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                          const nvsm_sweep_options& sw, const nvsm_cv_options& cv, const nvsm_judgments& j, float* fold_alpha,
+                          double* fold_train_measure, int64_t* doc_ids, float* scores, int64_t* counts, double* metrics, double* sweep_metrics);
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
     // 362-430), and the similarity of pairs of rows (ranking.cpp)
     void neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts);
@@ -484,6 +490,8 @@ class Model {
         DevBuf<float> rm_scores;
         DevBuf<int64_t> fuse_ids, fuse_counts, fuse_out_ids, fuse_out_counts;      // ensemble: both lists of a round [2][round][k], the fused list
         DevBuf<float> fuse_scores, fuse_out_scores;
+        DevBuf<float> fuse_alpha, sweep_alphas;    // supervised fusion: a round's per-query alphas; the call's grid
+        DevBuf<double> sweep_table;                //                    ... and its metric table [alphas][queries][width]
     };
     RankScratch rank_;
     int64_t score_floats() const { return static_cast<int64_t>(tune_.rank_slab_mb) << 18; }      // the score slab: 256 MB unless NVSM_RANK_SLAB_MB says otherwise
@@ -511,6 +519,19 @@ class Model {
     void ensemble_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
                          const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
                          int64_t* counts);
+    // what the fused calls share (ranking.cpp): the refusals of nvsm_rank_ensemble(_prf) for every alpha of the call, both rankings
+    // once, a round's lists on the device, and the fusion of the call's queries at one alpha or at one alpha per query
+    struct EnsembleLists;
+    void ensemble_check(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                        int normalizer, const float* alphas, int64_t num_alphas);
+    void ensemble_lists(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                        EnsembleLists& l);
+    FuseArgs ensemble_upload(const EnsembleLists& l, int64_t q0, int64_t qn, int normalizer);
+    void fuse_rounds(const nvsm_queries& q, const EnsembleLists& l, int normalizer, float alpha, const float* query_alpha, const EvalPlan* plan,
+                     int64_t* doc_ids, float* scores, int64_t* counts);
+    void sweep_check(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                     const nvsm_sweep_options& sw, const nvsm_judgments& j, double* table, EvalPlan& plan);
+    void sweep_rounds(const nvsm_queries& q, const EnsembleLists& l, const nvsm_sweep_options& sw, const EvalPlan& plan, double* table);
     void rank_join();                       // the handle's four streams waited for on the host; the words table's pending stamps settled
     struct RowSpace { const float* rows; int64_t count; int dim; const TableState* table; };      // rows null: the projected vocabulary
     RowSpace row_space(int space) const;
@@ -558,5 +579,11 @@ class Model {
     void allgather(const void* send, void* recv, size_t bytes, hipStream_t s);      // recv: world_size x bytes, rank-major
     void gather_update_inputs();
 };
+
+// The k-fold choice of nvsm_rank_ensemble_cv (ranking.cpp): a pure host function of the sweep table [A][Q][width]. Per fold f the
+// alpha whose column `measure`, averaged over the queries with fold_of[q] != f (added in ascending q, divided once), is largest, on
+// a tie the largest alpha; fold_index[f] its position in `alphas`. A fold nobody is in: (NaN, 0, -1).
+void cv_select(const double* table, int64_t A, int64_t Q, int width, int measure, const float* alphas, const int32_t* fold_of, int F,
+               float* fold_alpha, double* fold_train, int* fold_index);
 
 }  // namespace cunvsm

@@ -695,79 +695,251 @@ void Model::rank_ensemble_prf(const nvsm_queries& q, const nvsm_rank_options& op
     ensemble_rounds(q, opt, lex, &fb, ens, j, metrics, doc_ids, scores, counts);
 }
 
-// fb null: list B is nvsm_lexical_rank's; given: nvsm_lexical_rank_prf's
-void Model::ensemble_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
-                            const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
-                            int64_t* counts) {
-    const int64_t Q = q.num_queries;
+// both host lists of a call [Q][k] (+ counts), as the two rankings returned them
+struct Model::EnsembleLists {
+    int k = 0;
+    std::vector<int64_t> ids_a, ids_b, cnt_a, cnt_b;
+    std::vector<float> sc_a, sc_b;
+};
+
+// the refusals of nvsm_rank_ensemble(_prf), in their order, for every fused call; alphas [num_alphas]: the weights the call fuses with
+void Model::ensemble_check(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                           int normalizer, const float* alphas, int64_t num_alphas) {
     lexical_check(q, lex);
     if (fb) feedback_check(*fb);
-    if (ens.normalizer != NVSM_NORM_STANDARDIZE && ens.normalizer != NVSM_NORM_MINMAX && ens.normalizer != NVSM_NORM_NONE)
+    if (normalizer != NVSM_NORM_STANDARDIZE && normalizer != NVSM_NORM_MINMAX && normalizer != NVSM_NORM_NONE)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown score normalizer");
-    if (!(ens.alpha >= 0.f && ens.alpha <= 1.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "alpha must be in [0, 1]");
+    for (int64_t i = 0; i < num_alphas; ++i)
+        if (!(alphas[i] >= 0.f && alphas[i] <= 1.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "alpha must be in [0, 1]");
     if (opt.top_k != lex.top_k) throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_opt->top_k and lex->top_k must be equal");
     if (opt.candidates || opt.candidate_offsets) throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_opt->candidates must be NULL: the ensemble ranks every document");
     check_similarity(opt.similarity);
     check_top_k(opt.top_k, cfg_.num_entities, "top_k must be in [1, num_entities]");
     rank_check(q, opt);
     if (opt.top_k > kFuseMaxTopK) throw Error(NVSM_ERR_UNSUPPORTED, "the ensemble supports top_k up to NVSM_ENSEMBLE_MAX_TOP_K");
-    EvalPlan plan;
-    if (j) { plan.request = j; plan.metrics = metrics; eval_plan(plan, Q); }
-    const int k = opt.top_k;
-    const size_t cells = static_cast<size_t>(std::max<int64_t>(Q, 1)) * k;
-    std::vector<int64_t> ids_a(cells), ids_b(cells), cnt_a(static_cast<size_t>(Q) + 1), cnt_b(static_cast<size_t>(Q) + 1);
-    std::vector<float> sc_a(cells), sc_b(cells);
-    rank_rounds(q, opt, ids_a.data(), sc_a.data(), cnt_a.data(), nullptr);
+}
+
+// list A: nvsm_rank's; list B: nvsm_lexical_rank's (fb null) or nvsm_lexical_rank_prf's — once per call
+void Model::ensemble_lists(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                           EnsembleLists& l) {
+    const int64_t Q = q.num_queries;
+    l.k = opt.top_k;
+    const size_t cells = static_cast<size_t>(std::max<int64_t>(Q, 1)) * l.k;
+    l.ids_a.resize(cells); l.ids_b.resize(cells); l.sc_a.resize(cells); l.sc_b.resize(cells);
+    l.cnt_a.resize(static_cast<size_t>(Q) + 1); l.cnt_b.resize(static_cast<size_t>(Q) + 1);
+    rank_rounds(q, opt, l.ids_a.data(), l.sc_a.data(), l.cnt_a.data(), nullptr);
     if (fb) {
         ExpandedQueries x;
         expand_queries(q, lex, *fb, x);
-        lexical_rounds(x.view(), lex, x.weights.data(), ids_b.data(), sc_b.data(), cnt_b.data());
+        lexical_rounds(x.view(), lex, x.weights.data(), l.ids_b.data(), l.sc_b.data(), l.cnt_b.data());
     } else {
-        lexical_rounds(q, lex, nullptr, ids_b.data(), sc_b.data(), cnt_b.data());
+        lexical_rounds(q, lex, nullptr, l.ids_b.data(), l.sc_b.data(), l.cnt_b.data());
     }
+}
 
+// the lists of queries [q0, q0 + qn) of a round (qn <= kRankChunk) on the device, as the fusion kernels read them
+FuseArgs Model::ensemble_upload(const EnsembleLists& l, int64_t q0, int64_t qn, int normalizer) {
     RankScratch& r = rank_;
+    const int k = l.k;
     const size_t chunk_cells = static_cast<size_t>(kRankChunk) * k;
     grow(r.fuse_ids, 2 * chunk_cells);
     grow(r.fuse_scores, 2 * chunk_cells);
     grow(r.fuse_counts, static_cast<size_t>(2 * kRankChunk));
+    const size_t n = static_cast<size_t>(qn) * k;
+    // (the main stream is idle here: both rankings, and every round, end with a wait)
+    NVSM_HIP_CHECK(hipMemcpy(r.fuse_ids.p, l.ids_a.data() + q0 * k, n * sizeof(int64_t), hipMemcpyHostToDevice));
+    NVSM_HIP_CHECK(hipMemcpy(r.fuse_ids.p + chunk_cells, l.ids_b.data() + q0 * k, n * sizeof(int64_t), hipMemcpyHostToDevice));
+    NVSM_HIP_CHECK(hipMemcpy(r.fuse_scores.p, l.sc_a.data() + q0 * k, n * sizeof(float), hipMemcpyHostToDevice));
+    NVSM_HIP_CHECK(hipMemcpy(r.fuse_scores.p + chunk_cells, l.sc_b.data() + q0 * k, n * sizeof(float), hipMemcpyHostToDevice));
+    NVSM_HIP_CHECK(hipMemcpy(r.fuse_counts.p, l.cnt_a.data() + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
+    NVSM_HIP_CHECK(hipMemcpy(r.fuse_counts.p + kRankChunk, l.cnt_b.data() + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
+    FuseArgs f{};
+    f.ids_a = r.fuse_ids.p; f.scores_a = r.fuse_scores.p; f.counts_a = r.fuse_counts.p;
+    f.ids_b = r.fuse_ids.p + chunk_cells; f.scores_b = r.fuse_scores.p + chunk_cells; f.counts_b = r.fuse_counts.p + kRankChunk;
+    f.k = k; f.npad = static_cast<int>(pow2_at_least(2 * k)); f.normalizer = normalizer;
+    return f;
+}
+
+// the fused lists of the call, round by round. query_alpha null: every query at `alpha`; given [Q]: query i at query_alpha[i].
+// plan given: nvsm_evaluate's kernel on the fused ids where they lie, the rows into plan->metrics.
+void Model::fuse_rounds(const nvsm_queries& q, const EnsembleLists& l, int normalizer, float alpha, const float* query_alpha, const EvalPlan* plan,
+                        int64_t* doc_ids, float* scores, int64_t* counts) {
+    const int64_t Q = q.num_queries;
+    const int k = l.k;
+    RankScratch& r = rank_;
+    const size_t chunk_cells = static_cast<size_t>(kRankChunk) * k;
     grow(r.fuse_out_ids, 2 * chunk_cells);
     grow(r.fuse_out_scores, 2 * chunk_cells);
     grow(r.fuse_out_counts, static_cast<size_t>(kRankChunk));
+    if (query_alpha) grow(r.fuse_alpha, static_cast<size_t>(kRankChunk));
     EvalArgs ea{};
-    if (j) ea = eval_upload(plan, Q, 2 * k);
+    if (plan) ea = eval_upload(*plan, Q, 2 * k);
     for (int64_t q0 = 0; q0 < Q; q0 += kRankChunk) {
         const int64_t qn = std::min(kRankChunk, Q - q0);
-        const size_t n = static_cast<size_t>(qn) * k;
-        // (the main stream is idle here: both rankings, and every round, end with a wait)
-        NVSM_HIP_CHECK(hipMemcpy(r.fuse_ids.p, ids_a.data() + q0 * k, n * sizeof(int64_t), hipMemcpyHostToDevice));
-        NVSM_HIP_CHECK(hipMemcpy(r.fuse_ids.p + chunk_cells, ids_b.data() + q0 * k, n * sizeof(int64_t), hipMemcpyHostToDevice));
-        NVSM_HIP_CHECK(hipMemcpy(r.fuse_scores.p, sc_a.data() + q0 * k, n * sizeof(float), hipMemcpyHostToDevice));
-        NVSM_HIP_CHECK(hipMemcpy(r.fuse_scores.p + chunk_cells, sc_b.data() + q0 * k, n * sizeof(float), hipMemcpyHostToDevice));
-        NVSM_HIP_CHECK(hipMemcpy(r.fuse_counts.p, cnt_a.data() + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
-        NVSM_HIP_CHECK(hipMemcpy(r.fuse_counts.p + kRankChunk, cnt_b.data() + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
-        FuseArgs f{};
-        f.ids_a = r.fuse_ids.p; f.scores_a = r.fuse_scores.p; f.counts_a = r.fuse_counts.p;
-        f.ids_b = r.fuse_ids.p + chunk_cells; f.scores_b = r.fuse_scores.p + chunk_cells; f.counts_b = r.fuse_counts.p + kRankChunk;
-        f.k = k; f.npad = static_cast<int>(pow2_at_least(2 * k)); f.alpha = ens.alpha; f.normalizer = ens.normalizer;
+        const size_t n = static_cast<size_t>(qn) * 2 * k;      // entries of the round's fused lists
+        FuseArgs f = ensemble_upload(l, q0, qn, normalizer);
+        f.alpha = alpha;
+        if (query_alpha) {
+            NVSM_HIP_CHECK(hipMemcpy(r.fuse_alpha.p, query_alpha + q0, static_cast<size_t>(qn) * sizeof(float), hipMemcpyHostToDevice));
+            f.query_alpha = r.fuse_alpha.p;
+        }
         f.out_ids = r.fuse_out_ids.p; f.out_scores = r.fuse_out_scores.p; f.out_counts = r.fuse_out_counts.p;
         { RankProf scope(prof, "fuse_lists", stream_); launch_fuse_lists(f, static_cast<int>(qn), stream_); }
-        if (j) {
+        if (plan) {
             RankProf scope(prof, "rank_eval", stream_);
             ea.ids = r.fuse_out_ids.p; ea.counts = r.fuse_out_counts.p; ea.q0 = q0;
             launch_eval_metrics(ea, static_cast<int>(qn), stream_);
         }
-        NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * 2 * k, r.fuse_out_ids.p, 2 * n * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * 2 * k, r.fuse_out_scores.p, 2 * n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(doc_ids + q0 * 2 * k, r.fuse_out_ids.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(scores + q0 * 2 * k, r.fuse_out_scores.p, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
         NVSM_HIP_CHECK(hipMemcpyAsync(counts + q0, r.fuse_out_counts.p, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
         NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
     }
-    if (j && Q > 0) {
-        NVSM_HIP_CHECK(hipMemcpy(metrics, r.metrics.p, static_cast<size_t>(Q) * plan.width * sizeof(double), hipMemcpyDeviceToHost));
+    if (plan && Q > 0) {
+        double* metrics = plan->metrics;
+        NVSM_HIP_CHECK(hipMemcpy(metrics, r.metrics.p, static_cast<size_t>(Q) * plan->width * sizeof(double), hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < Q; ++i)      // a query without words gets all zeros, as in nvsm_evaluate
-            if (q.offsets[i + 1] == q.offsets[i]) std::fill(metrics + i * plan.width, metrics + (i + 1) * plan.width, 0.0);
+            if (q.offsets[i + 1] == q.offsets[i]) std::fill(metrics + i * plan->width, metrics + (i + 1) * plan->width, 0.0);
     }
     raise_device_error();
+}
+
+// fb null: list B is nvsm_lexical_rank's; given: nvsm_lexical_rank_prf's
+void Model::ensemble_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                            const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
+                            int64_t* counts) {
+    ensemble_check(q, opt, lex, fb, ens.normalizer, &ens.alpha, 1);
+    EvalPlan plan;
+    if (j) { plan.request = j; plan.metrics = metrics; eval_plan(plan, q.num_queries); }
+    EnsembleLists l;
+    ensemble_lists(q, opt, lex, fb, l);
+    fuse_rounds(q, l, ens.normalizer, ens.alpha, nullptr, j ? &plan : nullptr, doc_ids, scores, counts);
+}
+
+// ---- supervised fusion: the alpha sweep and the k-fold choice (include/cunvsm_amd.h nvsm_ensemble_sweep / nvsm_rank_ensemble_cv;
+// fuse_sweep_kernel) ------------------------------------------------------------------------------------------------
+// Both rankings once; a round takes kRankChunk queries' lists up once and one launch sweeps every alpha over them; the table
+// [num_alphas][Q][width] stays on the device until the last round.
+void Model::sweep_check(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                        const nvsm_sweep_options& sw, const nvsm_judgments& j, double* table, EvalPlan& plan) {
+    if (!sw.alphas) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: sweep->alphas");
+    if (sw.num_alphas < 1 || sw.num_alphas > NVSM_SWEEP_MAX_ALPHAS)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "sweep->num_alphas must be in [1, NVSM_SWEEP_MAX_ALPHAS]");
+    if (sw.depth < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "sweep->depth is negative");
+    ensemble_check(q, opt, lex, fb, sw.normalizer, sw.alphas, sw.num_alphas);
+    plan.request = &j;
+    plan.metrics = table;
+    eval_plan(plan, q.num_queries);
+}
+
+void Model::sweep_rounds(const nvsm_queries& q, const EnsembleLists& l, const nvsm_sweep_options& sw, const EvalPlan& plan, double* table) {
+    const int64_t Q = q.num_queries, A = sw.num_alphas;
+    if (Q == 0) return;
+    RankScratch& r = rank_;
+    const size_t cells = static_cast<size_t>(A) * Q * plan.width;
+    grow(r.sweep_alphas, static_cast<size_t>(kFuseSweepMaxAlphas));
+    grow(r.sweep_table, cells);
+    NVSM_HIP_CHECK(hipMemcpy(r.sweep_alphas.p, sw.alphas, static_cast<size_t>(A) * sizeof(float), hipMemcpyHostToDevice));
+    FuseSweepArgs s{};
+    // the judgments and their constants as launch_eval_metrics reads them. Of what eval_upload returns the sweep kernel looks at jids,
+    // jgrades, joff, consts, the cutoffs and q0 only: its ids are in LDS and its rows go to `table`, so ids, counts, k and metrics stay
+    // unused here (eval_upload also makes sure rank_.metrics holds Q rows, which this call never writes)
+    s.e = eval_upload(plan, Q, 2 * l.k);
+    s.alphas = r.sweep_alphas.p; s.num_alphas = static_cast<int>(A); s.depth = sw.depth;
+    s.table = r.sweep_table.p; s.total_queries = Q;
+    for (int64_t q0 = 0; q0 < Q; q0 += kRankChunk) {
+        const int64_t qn = std::min(kRankChunk, Q - q0);
+        s.f = ensemble_upload(l, q0, qn, sw.normalizer);
+        s.e.q0 = q0;
+        { RankProf scope(prof, "fuse_sweep", stream_); launch_fuse_sweep(s, static_cast<int>(qn), stream_); }
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));      // (the next round's lists overwrite this one's)
+    }
+    NVSM_HIP_CHECK(hipMemcpy(table, r.sweep_table.p, cells * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < Q; ++i) {      // a query without words gets all zeros, as in nvsm_evaluate
+        if (q.offsets[i + 1] != q.offsets[i]) continue;
+        for (int64_t a = 0; a < A; ++a) std::fill(table + (a * Q + i) * plan.width, table + (a * Q + i + 1) * plan.width, 0.0);
+    }
+    raise_device_error();
+}
+
+void Model::ensemble_sweep(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                           const nvsm_sweep_options& sw, const nvsm_judgments& j, double* table) {
+    EvalPlan plan;
+    sweep_check(q, opt, lex, fb, sw, j, table, plan);
+    EnsembleLists l;
+    ensemble_lists(q, opt, lex, fb, l);
+    sweep_rounds(q, l, sw, plan, table);
+}
+
+// the k-fold choice: a pure host function of the sweep table (DESIGN.md §17 "Selection"; declared in model.h)
+void cv_select(const double* table, int64_t A, int64_t Q, int width, int measure, const float* alphas, const int32_t* fold_of, int F,
+               float* fold_alpha, double* fold_train, int* fold_index) {
+    for (int f = 0; f < F; ++f) {
+        int64_t held = 0;
+        for (int64_t i = 0; i < Q; ++i) held += fold_of[i] == f;
+        fold_index[f] = -1;
+        if (held == 0) { fold_alpha[f] = std::nanf(""); fold_train[f] = 0.0; continue; }
+        const double n_train = static_cast<double>(Q - held);
+        double best = 0.0;
+        for (int64_t a = 0; a < A; ++a) {
+            double sum = 0.0;      // ascending query index, plain sequential additions, one division
+            for (int64_t i = 0; i < Q; ++i)
+                if (fold_of[i] != f) sum += table[(a * Q + i) * width + measure];
+            const double mean = sum / n_train;
+            // Python's max() over (value, alpha) tuples: the larger value, on a tie the larger alpha
+            if (fold_index[f] < 0 || mean > best || (mean == best && alphas[a] > alphas[fold_index[f]])) { best = mean; fold_index[f] = static_cast<int>(a); }
+        }
+        fold_alpha[f] = alphas[fold_index[f]];
+        fold_train[f] = best;
+    }
+}
+
+void Model::rank_ensemble_cv(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
+                             const nvsm_sweep_options& sw, const nvsm_cv_options& cv, const nvsm_judgments& j, float* fold_alpha,
+                             double* fold_train_measure, int64_t* doc_ids, float* scores, int64_t* counts, double* metrics, double* sweep_metrics) {
+    const int64_t Q = q.num_queries;
+    EvalPlan plan;
+    double none = 0.0;            // (eval_plan asks for a pointer; the table's size is known behind the checks)
+    sweep_check(q, opt, lex, fb, sw, j, sweep_metrics ? sweep_metrics : &none, plan);
+    const int F = cv.num_folds;
+    if (F < 2 || F > Q) throw Error(NVSM_ERR_INVALID_ARGUMENT, "cv->num_folds must be in [2, num_queries]");
+    if (cv.measure < 0 || cv.measure >= plan.width) throw Error(NVSM_ERR_INVALID_ARGUMENT, "cv->measure is no column of the metric row");
+    if (cv.measure == NVSM_EVAL_NUM_RET || cv.measure == NVSM_EVAL_NUM_REL || cv.measure == NVSM_EVAL_NUM_REL_RET)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "cv->measure: num_ret, num_rel and num_rel_ret are not offered as training measures");
+    std::vector<int32_t> fold(static_cast<size_t>(Q));
+    if (cv.fold_of) {
+        std::vector<int64_t> size(static_cast<size_t>(F), 0);
+        for (int64_t i = 0; i < Q; ++i) {
+            if (cv.fold_of[i] < 0 || cv.fold_of[i] >= F) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a cv->fold_of entry is outside [0, num_folds)");
+            fold[static_cast<size_t>(i)] = cv.fold_of[i];
+            ++size[static_cast<size_t>(cv.fold_of[i])];
+        }
+        for (int f = 0; f < F; ++f)
+            if (size[static_cast<size_t>(f)] == Q) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a fold holds every query: its training set is empty");
+    } else {      // sklearn's un-shuffled KFold: contiguous, the first Q % F folds one query longer
+        int64_t i = 0;
+        for (int f = 0; f < F; ++f)
+            for (int64_t c = Q / F + (f < Q % F ? 1 : 0); c > 0; --c) fold[static_cast<size_t>(i++)] = f;
+    }
+    const int64_t A = sw.num_alphas;
+    std::vector<double> own;      // the table, where the caller does not want it
+    if (!sweep_metrics) {
+        own.resize(static_cast<size_t>(A) * Q * plan.width);
+        sweep_metrics = own.data();
+    }
+    EnsembleLists l;
+    ensemble_lists(q, opt, lex, fb, l);
+    sweep_rounds(q, l, sw, plan, sweep_metrics);
+    std::vector<int> index(static_cast<size_t>(F));
+    cv_select(sweep_metrics, A, Q, plan.width, cv.measure, sw.alphas, fold.data(), F, fold_alpha, fold_train_measure, index.data());
+    std::vector<float> query_alpha(static_cast<size_t>(Q));
+    for (int64_t i = 0; i < Q; ++i) query_alpha[static_cast<size_t>(i)] = fold_alpha[fold[static_cast<size_t>(i)]];
+    fuse_rounds(q, l, sw.normalizer, 0.f, query_alpha.data(), nullptr, doc_ids, scores, counts);
+    if (metrics)      // the returned lists cut at depth: by definition the sweep's rows at the chosen alphas
+        for (int64_t i = 0; i < Q; ++i) {
+            const int64_t a = index[static_cast<size_t>(fold[static_cast<size_t>(i)])];
+            std::copy(sweep_metrics + (a * Q + i) * plan.width, sweep_metrics + (a * Q + i + 1) * plan.width, metrics + i * plan.width);
+        }
 }
 
 // ---- nearest neighbours (include/cunvsm_amd.h nvsm_neighbors / nvsm_similarity) ---------------------------------

@@ -4,6 +4,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <random>
 #include <sstream>
 
 #include "base.hpp"
@@ -127,6 +128,38 @@ std::vector<float> self_information(const ModelMappings& maps, const std::vector
         w.push_back(static_cast<float>(-std::log(static_cast<double>(tf) / static_cast<double>(maps.total_terms))));
     }
     return w;
+}
+
+std::vector<int32_t> ensemble_folds(int64_t n, int64_t num_folds, uint64_t seed) {
+    std::vector<int64_t> order(static_cast<size_t>(n > 0 ? n : 0));
+    for (size_t i = 0; i < order.size(); ++i) order[i] = static_cast<int64_t>(i);
+    if (seed > 0) {
+        std::minstd_rand0 rng(static_cast<std::minstd_rand0::result_type>(seed));
+        for (int64_t i = n - 1; i >= 1; --i) {
+            const int64_t j = static_cast<int64_t>(rng() % static_cast<uint64_t>(i + 1));
+            std::swap(order[static_cast<size_t>(i)], order[static_cast<size_t>(j)]);
+        }
+    }
+    std::vector<int32_t> fold_of(order.size(), 0);
+    if (num_folds < 1) return fold_of;
+    int64_t at = 0;
+    for (int64_t f = 0; f < num_folds; ++f)
+        for (int64_t c = n / num_folds + (f < n % num_folds ? 1 : 0); c > 0 && at < n; --c) fold_of[static_cast<size_t>(order[static_cast<size_t>(at++)])] = static_cast<int32_t>(f);
+    return fold_of;
+}
+
+bool ensemble_measure(const std::string& name, const std::vector<std::string>& names, int32_t* column, int32_t* depth) {
+    *depth = 0;
+    for (size_t i = 3; i < names.size(); ++i)
+        if (names[i] == name) { *column = static_cast<int32_t>(i); return true; }
+    static const std::string kCut = "map_cut_";
+    if (name.compare(0, kCut.size(), kCut) != 0 || name.size() == kCut.size() || name.size() > kCut.size() + 9) return false;
+    if (name.find_first_not_of("0123456789", kCut.size()) != std::string::npos) return false;
+    const long d = std::strtol(name.c_str() + kCut.size(), nullptr, 10);
+    if (d < 1) return false;
+    for (size_t i = 3; i < names.size(); ++i)
+        if (names[i] == "map") { *column = static_cast<int32_t>(i); *depth = static_cast<int32_t>(d); return true; }
+    return false;
 }
 
 }  // namespace nvsm_host

@@ -56,4 +56,13 @@ bool query_terms(IndexInterface* index, const ModelMappings& maps, const std::st
 // -log(tf / total_terms) in double, then float (py/nvsm/base.py:297-301)
 std::vector<float> self_information(const ModelMappings& maps, const std::vector<int64_t>& model_terms);
 
+// The folds of --ensemble_qrel: fold_of[i] of the i-th kept topic. The topics are permuted — seed > 0: a Fisher-Yates pass driven by
+// std::minstd_rand0(seed), for i = n - 1 down to 1: j = rng() % (i + 1), swap positions i and j; seed 0: topic-file order — and
+// the permuted sequence is cut into num_folds contiguous folds, the first n % num_folds of them one topic longer.
+std::vector<int32_t> ensemble_folds(int64_t n, int64_t num_folds, uint64_t seed);
+
+// --ensemble_measure: a name of `names` (the printed metrics; not num_ret, num_rel, num_rel_ret) -> its column, depth 0; or
+// map_cut_<d> -> the column of map, depth d. false: neither.
+bool ensemble_measure(const std::string& name, const std::vector<std::string>& names, int32_t* column, int32_t* depth);
+
 }  // namespace nvsm_host

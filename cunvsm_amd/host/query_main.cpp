@@ -16,6 +16,8 @@
 // IndexSource's term mapping and out-of-vocabulary rule, documents in model id order) and nvsm_lexical_rank / nvsm_rank_ensemble do
 // the rest. The lexical model is over the MODEL's vocabulary, not Indri's. --qlm_prf makes the lexical run, and with it
 // the fusion, the reference's "QLM w/ PRF": nvsm_lexical_rank_prf / nvsm_rank_ensemble_prf (RM3).
+// py/combine_runs.py's supervised mode (--qrel --num_folds --alpha_stepsize) is --ensemble_qrel: the fusion's weight is chosen per fold
+// of the topics on a grid by nvsm_rank_ensemble_cv.
 #include <sys/stat.h>
 
 #include <cmath>
@@ -40,11 +42,11 @@ using namespace nvsm_host;
 namespace {
 
 std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs, FLAGS_qlm, FLAGS_qlm_param, FLAGS_qlm_run_out,
-    FLAGS_ensemble_alpha, FLAGS_score_normalizer;
+    FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure;
 bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
     FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf;
-double FLAGS_bias_coefficient, FLAGS_qlm_fb_orig_weight;
-int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers, FLAGS_qlm_fb_docs, FLAGS_qlm_fb_terms;
+double FLAGS_bias_coefficient, FLAGS_qlm_fb_orig_weight, FLAGS_alpha_stepsize;
+int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers, FLAGS_qlm_fb_docs, FLAGS_qlm_fb_terms, FLAGS_num_folds, FLAGS_ensemble_seed;
 
 void define_flags(Flags* f) {
     f->define_string("index", &FLAGS_index, "", "TREC-text collection file or Indri repository directory, as given to cuNVSMTrainModel.");
@@ -79,6 +81,18 @@ void define_flags(Flags* f) {
                      "the query-likelihood ranking (weight 1 - alpha), up to 2 x top_k documents per topic, and the printed means are the fused list's.");
     f->define_string("score_normalizer", &FLAGS_score_normalizer, "standardize", "standardize | minmax | none: how --ensemble_alpha normalises each "
                      "list's scores per topic before mixing them.");
+    f->define_string("ensemble_qrel", &FLAGS_ensemble_qrel, "", "With --qlm, instead of --ensemble_alpha (the two exclude each other): qrel file names "
+                     "(blank-separated). The weight alpha is chosen by cross-validation over the topics: every alpha of the grid 0, stepsize, "
+                     "2 x stepsize, ... < 1 is evaluated, and each fold's topics are fused with the alpha whose mean --ensemble_measure over the "
+                     "OTHER folds' topics is largest (ties: the largest alpha). <run_out> holds the fused lists; the printed means are theirs.");
+    f->define_int64("num_folds", &FLAGS_num_folds, 20, "With --ensemble_qrel: folds of the ranked topics, 2 .. their number.");
+    f->define_double("alpha_stepsize", &FLAGS_alpha_stepsize, 0.05, "With --ensemble_qrel: step of the alpha grid; at most 1024 points.");
+    f->define_string("ensemble_measure", &FLAGS_ensemble_measure, "map_cut_1000", "With --ensemble_qrel: the training measure, a name of the printed "
+                     "metrics (map, ndcg, P_5, ...) or map_cut_<d>: map over the first d entries of the fused list, and the printed metrics are then "
+                     "those of the lists cut at d.");
+    f->define_int64("ensemble_seed", &FLAGS_ensemble_seed, 1, "With --ensemble_qrel: the folds are contiguous runs of the ranked topics after a "
+                    "permutation. seed s > 0: a Fisher-Yates pass driven by std::minstd_rand0(s) — for i = n - 1 down to 1, j = rng() % (i + 1), "
+                    "swap topics i and j. seed 0: topic-file order. (The reference shuffles with an unseeded generator.)");
     f->define_bool("qlm_prf", &FLAGS_qlm_prf, false, "With --qlm: pseudo-relevance feedback (RM3). Every topic is expanded with the most probable "
                    "terms of its best documents' relevance model; the --qlm_run_out runs and the --ensemble_alpha fusion use the expanded ranking.");
     f->define_int64("qlm_fb_docs", &FLAGS_qlm_fb_docs, 10, "With --qlm_prf: feedback documents per topic.");
@@ -170,7 +184,9 @@ int run(int argc, char** argv) {
     const std::vector<int32_t> cutoffs = parse_cutoffs(FLAGS_cutoffs);
 
     // ---- --qlm / --ensemble_alpha (rank-cranfield-collection.sh's last stage)
-    const bool with_qlm = !FLAGS_qlm.empty(), with_ensemble = !FLAGS_ensemble_alpha.empty();
+    const bool with_qlm = !FLAGS_qlm.empty(), with_ensemble = !FLAGS_ensemble_alpha.empty(), with_cv = !FLAGS_ensemble_qrel.empty();
+    const bool with_fusion = with_ensemble || with_cv;
+    NVSM_CHECK(!(with_ensemble && with_cv)) << "--ensemble_alpha and --ensemble_qrel are mutually exclusive: the weight is either given or chosen by cross-validation.";
     nvsm_lexical_options lex;
     nvsm_lexical_options_default(&lex);
     nvsm_ensemble_options ens;
@@ -186,10 +202,28 @@ int run(int argc, char** argv) {
                 NVSM_LOG(FATAL) << "--qlm_param: '" << FLAGS_qlm_param << "' is neither auto, nor a lambda in (0, 1) (jm), nor a mu > 0 (dirichlet).";
             lex.param = static_cast<float>(v);
         }
-        NVSM_CHECK(with_ensemble || !FLAGS_qlm_run_out.empty()) << "--qlm needs --qlm_run_out or --ensemble_alpha: nothing would be written.";
+        NVSM_CHECK(with_fusion || !FLAGS_qlm_run_out.empty()) << "--qlm needs --qlm_run_out, --ensemble_alpha or --ensemble_qrel: nothing would be written.";
     } else {
-        NVSM_CHECK(!with_ensemble && FLAGS_qlm_run_out.empty() && FLAGS_qlm_param == "auto" && FLAGS_score_normalizer == "standardize")
-            << "--qlm_param, --qlm_run_out, --ensemble_alpha and --score_normalizer need --qlm.";
+        NVSM_CHECK(!with_fusion && FLAGS_qlm_run_out.empty() && FLAGS_qlm_param == "auto" && FLAGS_score_normalizer == "standardize")
+            << "--qlm_param, --qlm_run_out, --ensemble_alpha, --ensemble_qrel and --score_normalizer need --qlm.";
+    }
+    std::vector<float> cv_alphas;
+    int32_t cv_measure = NVSM_EVAL_AP, cv_depth = 0;
+    if (with_cv) {
+        NVSM_CHECK(FLAGS_qrels.empty()) << "--ensemble_qrel evaluates the fused lists with its own judgments: leave --qrels out.";
+        NVSM_CHECK(FLAGS_num_folds >= 2 && FLAGS_num_folds <= 2147483647) << "--num_folds must be at least 2.";
+        NVSM_CHECK(FLAGS_ensemble_seed >= 0 && FLAGS_ensemble_seed <= 2147483646) << "--ensemble_seed must be in [0, 2147483646].";
+        NVSM_CHECK(FLAGS_alpha_stepsize > 0.0 && FLAGS_alpha_stepsize <= 1.0 && std::ceil(1.0 / FLAGS_alpha_stepsize) <= NVSM_SWEEP_MAX_ALPHAS)
+            << "--alpha_stepsize must be in (0, 1] and give at most " << NVSM_SWEEP_MAX_ALPHAS << " alphas.";
+        // np.arange(0.0, 1.0, stepsize): ceil(1 / stepsize) points i * stepsize in double, narrowed to float32
+        const int64_t points = static_cast<int64_t>(std::ceil(1.0 / FLAGS_alpha_stepsize));
+        for (int64_t i = 0; i < points; ++i) cv_alphas.push_back(static_cast<float>(static_cast<double>(i) * FLAGS_alpha_stepsize));
+        if (!ensemble_measure(FLAGS_ensemble_measure, metric_names(cutoffs), &cv_measure, &cv_depth))
+            NVSM_LOG(FATAL) << "--ensemble_measure: '" << FLAGS_ensemble_measure << "' is neither a printed metric (num_ret, num_rel and num_rel_ret "
+                               "are not offered) nor map_cut_<depth>.";
+    } else {
+        NVSM_CHECK(FLAGS_num_folds == 20 && FLAGS_alpha_stepsize == 0.05 && FLAGS_ensemble_measure == "map_cut_1000" && FLAGS_ensemble_seed == 1)
+            << "--num_folds, --alpha_stepsize, --ensemble_measure and --ensemble_seed need --ensemble_qrel.";
     }
     nvsm_feedback_options fb;
     nvsm_feedback_options_default(&fb);
@@ -235,6 +269,7 @@ int run(int argc, char** argv) {
     NVSM_CHECK(!(with_qlm && candidate_qrels)) << "--qlm ranks every document: with it --top_k is a number or 'all', not qrel files.";
     std::unique_ptr<Qrels> qrels;
     if (!FLAGS_qrels.empty()) qrels.reset(new Qrels(read_qrels(split_blanks(FLAGS_qrels))));
+    if (with_cv) qrels.reset(new Qrels(read_qrels(split_blanks(FLAGS_ensemble_qrel))));
 
     // ---- the index
     std::unique_ptr<IndexInterface> index;
@@ -385,7 +420,7 @@ int run(int argc, char** argv) {
         nvsm_queries queries;
         queries.word_ids = word_ids.data(); queries.word_weights = FLAGS_self_information ? word_weights.data() : nullptr;
         queries.offsets = word_off.data(); queries.num_queries = Q;
-        const int64_t run_width = with_ensemble ? 2 * k : k;               // entries per topic of <run_out>: the fused list is a union
+        const int64_t run_width = with_fusion ? 2 * k : k;               // entries per topic of <run_out>: the fused list is a union
         std::vector<int64_t> doc_ids(static_cast<size_t>(Q * run_width) + 1), counts(static_cast<size_t>(Q) + 1);
         std::vector<float> scores(static_cast<size_t>(Q * run_width) + 1);
         std::vector<double> metrics(static_cast<size_t>(Q) * width + 1);
@@ -420,7 +455,29 @@ int run(int argc, char** argv) {
                 write_run(qlm_path, lex_ids, lex_scores, lex_counts, k);
             }
         }
-        if (with_ensemble) {      // both rankings, their fusion and, with --qrels, the fused list's metrics in ONE call
+        if (with_cv) {      // both rankings once, the sweep of the grid, the choice per fold and the fused lists in ONE call
+            nvsm_judgments judgments{};
+            judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
+            judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());
+            nvsm_sweep_options sweep;
+            nvsm_sweep_options_default(&sweep);
+            sweep.alphas = cv_alphas.data(); sweep.num_alphas = static_cast<int32_t>(cv_alphas.size());
+            sweep.normalizer = ens.normalizer; sweep.depth = cv_depth;
+            const std::vector<int32_t> fold_of = ensemble_folds(Q, FLAGS_num_folds, static_cast<uint64_t>(FLAGS_ensemble_seed));
+            nvsm_cv_options cv;
+            nvsm_cv_options_default(&cv);
+            cv.measure = cv_measure; cv.num_folds = static_cast<int32_t>(FLAGS_num_folds); cv.fold_of = fold_of.data();
+            std::vector<float> fold_alpha(static_cast<size_t>(FLAGS_num_folds));
+            std::vector<double> fold_train(static_cast<size_t>(FLAGS_num_folds));
+            NVSM_CALL(nvsm_rank_ensemble_cv(model, &queries, &opt, &lex, with_prf ? &fb : nullptr, &sweep, &cv, &judgments, fold_alpha.data(),
+                                            fold_train.data(), doc_ids.data(), scores.data(), counts.data(), metrics.data(), nullptr));
+            char line[160];
+            for (int64_t f = 0; f < FLAGS_num_folds; ++f) {
+                std::snprintf(line, sizeof(line), "Fold %lld: best_alpha=%.2f train %s=%.4f", static_cast<long long>(f),
+                              static_cast<double>(fold_alpha[static_cast<size_t>(f)]), FLAGS_ensemble_measure.c_str(), fold_train[static_cast<size_t>(f)]);
+                NVSM_LOG(INFO) << line;
+            }
+        } else if (with_ensemble) {      // both rankings, their fusion and, with --qrels, the fused list's metrics in ONE call
             nvsm_judgments judgments{};
             judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
             judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());

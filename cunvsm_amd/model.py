@@ -462,6 +462,41 @@ def ensemble_options(alpha=0.5, normalizer="standardize"):
     return opt
 
 
+def alpha_grid(stepsize):
+    """The reference's grid of fusion weights, np.arange(0.0, 1.0, stepsize) restated: ceil(1.0 / stepsize) points computed in
+    fp64, alpha_i = float32(i * stepsize); 1.0 itself is excluded. More than SWEEP_MAX_ALPHAS points are refused."""
+    step = float(stepsize)
+    if not (np.isfinite(step) and 0.0 < step <= 1.0):
+        raise ValueError("stepsize = %r outside (0, 1]" % (stepsize,))
+    n = int(np.ceil(1.0 / step))
+    if n > _lib.SWEEP_MAX_ALPHAS:
+        raise ValueError("stepsize = %r gives %d alphas, at most %d" % (stepsize, n, _lib.SWEEP_MAX_ALPHAS))
+    return (np.arange(n, dtype=np.float64) * step).astype(np.float32)
+
+
+def sweep_alphas(alphas):
+    """The alphas of Model.ensemble_sweep as a float32 array; raises ValueError for what nvsm_ensemble_sweep would refuse."""
+    a = np.ascontiguousarray(np.asarray(alphas, dtype=np.float32).ravel())
+    if not 1 <= a.size <= _lib.SWEEP_MAX_ALPHAS:
+        raise ValueError("%d alphas, expected 1 to %d" % (a.size, _lib.SWEEP_MAX_ALPHAS))
+    if not (np.isfinite(a).all() and a.min() >= 0.0 and a.max() <= 1.0):
+        raise ValueError("an alpha is outside [0, 1] or not finite")
+    return a
+
+
+def sweep_options(alphas, normalizer="standardize", depth=0):
+    """nvsm_sweep_options over a float32 array the caller keeps alive; raises ValueError for what the ABI would refuse."""
+    opt = _lib.NvsmSweepOptions()
+    if isinstance(normalizer, str):
+        if normalizer not in NORMALIZERS:
+            raise ValueError("unknown normalizer %r (one of %s)" % (normalizer, sorted(NORMALIZERS)))
+        normalizer = NORMALIZERS[normalizer]
+    if int(depth) < 0:
+        raise ValueError("depth = %d is negative" % int(depth))
+    opt.alphas, opt.num_alphas, opt.normalizer, opt.depth = alphas.ctypes.data, int(alphas.size), int(normalizer), int(depth)
+    return opt
+
+
 def feedback_options(fb_docs=10, fb_terms=10, orig_weight=0.5):
     """nvsm_feedback_options from keywords; raises ValueError for what the ABI would refuse without a device. fb_docs against the
     corpus and fb_terms against the vocabulary are checked by the library, which holds them."""
@@ -891,6 +926,91 @@ class Model:
             return ids, scores, counts
         result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}
         return result, ids, scores, counts
+
+    # -- supervised fusion: the alpha sweep and the k-fold choice of alpha --------
+    def _sweep_arguments(self, queries, judgments, alphas, normalizer, depth, top_k, method, param, cutoffs, weights, feedback, opts):
+        q = queries if isinstance(queries, Queries) else Queries(queries, weights)
+        if judgments is None:
+            raise ValueError("judgments are required")
+        j = judgments if isinstance(judgments, Judgments) else Judgments(judgments)
+        if j.num_queries != q.num_queries:
+            raise ValueError("judgments holds %d lists, expected one per query = %d" % (j.num_queries, q.num_queries))
+        if j.doc_ids.size and (j.doc_ids.min() < -1 or j.doc_ids.max() >= self.cfg.num_entities):
+            raise ValueError("a judged document id is outside [-1, num_entities = %d)" % self.cfg.num_entities)
+        a = sweep_alphas(alphas)
+        sopt = sweep_options(a, normalizer, depth)
+        ropt = rank_options(self.cfg.num_entities, top_k, **opts)
+        lopt = lexical_options(method, param, top_k)
+        fopt = None if feedback is None or feedback is False else as_feedback_options(feedback)
+        cut = eval_cutoffs(cutoffs)
+        return q, j, a, sopt, ropt, lopt, fopt, cut
+
+    def ensemble_sweep(self, queries, judgments, alphas, normalizer="standardize", depth=0, top_k=1000, method="jm", param=None,
+                       cutoffs=(5, 10, 20, 100, 1000), weights=None, feedback=None, **opts):
+        """nvsm_ensemble_sweep: rank()'s and lexical_rank()'s (feedback: lexical_rank_prf()'s) lists made once, then the metrics of
+        their fusion at every alpha of `alphas` (float32 in [0, 1], at most SWEEP_MAX_ALPHAS), over the first `depth` entries of each
+        fused list (0: all). Returns a dict of float64 arrays [A, Q] keyed as evaluate()'s; with depth 0 row [a] holds the bits
+        rank_ensemble(alpha=alphas[a], judgments=...) returns."""
+        q, j, a, sopt, ropt, lopt, fopt, cut = self._sweep_arguments(queries, judgments, alphas, normalizer, depth, top_k, method, param,
+                                                                      cutoffs, weights, feedback, opts)
+        names = eval_metric_names(cut.tolist())
+        table = np.empty((a.size, q.num_queries, len(names)), dtype=np.float64)
+        st, js = q.as_struct(), j.as_struct(cut)
+        check(lib().nvsm_ensemble_sweep(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), None if fopt is None else C.byref(fopt),
+                                        C.byref(sopt), C.byref(js), table.ctypes.data if table.size else _EMPTY_F64.ctypes.data))
+        return {name: np.ascontiguousarray(table[:, :, i]) for i, name in enumerate(names)}
+
+    def rank_ensemble_cv(self, queries, judgments, alphas=None, stepsize=0.05, num_folds=20, measure="map", depth=1000, fold_of=None,
+                         normalizer="standardize", top_k=1000, method="jm", param=None, cutoffs=(5, 10, 20, 100, 1000), weights=None,
+                         feedback=None, return_sweep=False, **opts):
+        """nvsm_rank_ensemble_cv, the reference's combine_runs.py --qrel: ensemble_sweep over `alphas` (None: alpha_grid(stepsize)),
+        then per fold the alpha with the best mean `measure` (a key of the metric dict) over the queries outside the fold — on a tie the
+        largest alpha — fuses the fold's queries. fold_of: per query its fold in [0, num_folds), None: contiguous folds in query order.
+        Returns (fold_alphas [F] float32, fold_train_measures [F] float64, metrics, ids [Q, 2k], scores [Q, 2k], counts [Q]); metrics is
+        evaluate()'s dict of the returned lists cut at depth; with return_sweep the sweep's dict [A, Q] follows."""
+        if alphas is None:
+            alphas = alpha_grid(stepsize)
+        q, j, a, sopt, ropt, lopt, fopt, cut = self._sweep_arguments(queries, judgments, alphas, normalizer, depth, top_k, method, param,
+                                                                      cutoffs, weights, feedback, opts)
+        names = eval_metric_names(cut.tolist())
+        if measure not in names:
+            raise ValueError("unknown measure %r (one of %s)" % (measure, names))
+        if names.index(measure) < _lib.EVAL_AP:
+            raise ValueError("measure %r is not offered as a training measure" % (measure,))
+        Q, F = q.num_queries, int(num_folds)
+        if not 2 <= F <= Q:
+            raise ValueError("num_folds = %d outside [2, num_queries = %d]" % (F, Q))
+        copt = _lib.NvsmCvOptions()
+        copt.measure, copt.num_folds = names.index(measure), F
+        folds = None
+        if fold_of is not None:
+            folds = np.ascontiguousarray(np.asarray(fold_of, dtype=np.int64).ravel())
+            if folds.size != Q:
+                raise ValueError("fold_of holds %d entries, expected one per query = %d" % (folds.size, Q))
+            if folds.min() < 0 or folds.max() >= F:
+                raise ValueError("a fold_of entry is outside [0, num_folds = %d)" % F)
+            if np.bincount(folds, minlength=F).max() == Q:
+                raise ValueError("a fold holds every query: its training set is empty")
+            folds = folds.astype(np.int32)
+            copt.fold_of = folds.ctypes.data
+        k = ropt.top_k
+        fold_alpha = np.empty(F, dtype=np.float32)
+        fold_train = np.empty(F, dtype=np.float64)
+        ids = np.empty((Q, 2 * k), dtype=np.int64)
+        scores = np.empty((Q, 2 * k), dtype=np.float32)
+        counts = np.empty(Q, dtype=np.int64)
+        metrics = np.empty((Q, len(names)), dtype=np.float64)
+        table = np.empty((a.size, Q, len(names)), dtype=np.float64) if return_sweep else None
+        st, js = q.as_struct(), j.as_struct(cut)
+        check(lib().nvsm_rank_ensemble_cv(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), None if fopt is None else C.byref(fopt),
+                                          C.byref(sopt), C.byref(copt), C.byref(js), fold_alpha.ctypes.data, fold_train.ctypes.data,
+                                          ids.ctypes.data, scores.ctypes.data, counts.ctypes.data, metrics.ctypes.data,
+                                          None if table is None else table.ctypes.data))
+        result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}
+        out = (fold_alpha, fold_train, result, ids, scores, counts)
+        if return_sweep:
+            out += ({name: np.ascontiguousarray(table[:, :, i]) for i, name in enumerate(names)},)
+        return out
 
     # -- nearest neighbours in word, projected-word and document space (py/nvsm/base.py:106-162, 325-353, 362-430) ----
     def neighbors(self, space, ids=None, vectors=None, source=None, top_k=30, exclude_self=False, similarity="cosine",

@@ -595,6 +595,64 @@ int nvsm_rank_ensemble_prf(nvsm_model* m, const nvsm_queries* queries, const nvs
                            double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
 
 /*
+ * SUPERVISED FUSION (nvsm_ensemble_sweep, nvsm_rank_ensemble_cv) — py/combine_runs.py --qrel --num_folds --alpha_stepsize, the mode
+ * rank-cranfield-collection.sh takes its "NVSM + QLM" figures from: the fusion is evaluated on a grid of weights alpha, and for each of
+ * k folds of the queries the alpha with the best training measure fuses the held-out queries.
+ *   sweep      list A and list B are made ONCE per call, exactly as nvsm_rank_ensemble makes them (fb NULL: list B is
+ *              nvsm_lexical_rank's) or as nvsm_rank_ensemble_prf does (fb given), with the same refusals and the same bits.
+ *              metrics[a][q][:] is nvsm_evaluate's row of the list fused at alpha = alphas[a], over its first min(depth, count)
+ *              entries; depth = 0: the whole list. With a cut, num_ret is the cut length and every other formula applies to the cut
+ *              list unchanged (depth 1000: ap is trec_eval's map_cut_1000). With depth = 0 or depth >= 2·top_k every row equals BIT FOR
+ *              BIT the row nvsm_rank_ensemble(_prf) returns for that alpha. Alphas are float32 in [0, 1], in any order, repeats
+ *              allowed (equal alphas give equal rows), 1 <= num_alphas <= NVSM_SWEEP_MAX_ALPHAS. A query without words has all-zero
+ *              rows. judgments are required.
+ *   folds      cv->fold_of[q] in [0, num_folds) names the fold of query q. NULL: contiguous folds in query order, fold f holding
+ *              num_queries / num_folds + 1 queries when f < num_queries % num_folds, else num_queries / num_folds (sklearn's KFold
+ *              without shuffling). 2 <= num_folds <= num_queries. With fold_of given a fold may be empty: its outputs are
+ *              (NaN, 0). A fold that holds every query (its training set is empty) is refused.
+ *   choice     the training measure of (fold f, alpha a) is the mean over the queries NOT in f of column cv->measure of the sweep row
+ *              (NVSM_EVAL_AP, NVSM_EVAL_NDCG, a cutoff column, ...; num_ret, num_rel and num_rel_ret are refused): the queries are added
+ *              in ascending query index as plain sequential fp64 additions, then divided once by their number. A pure host function
+ *              of the sweep table's bits. The alpha of the largest training measure is chosen; on an exact tie the LARGEST alpha value
+ *              (Python's max() over (value, alpha) tuples).
+ *   result     every query's list is what nvsm_rank_ensemble(_prf) returns for alpha = fold_alpha[fold of q], bit for bit in ids,
+ *              scores and counts; metrics (may be NULL) [num_queries][width] are the sweep's rows of those lists, cut at depth;
+ *              sweep_metrics (may be NULL) receives the sweep table.
+ * Both calls are synchronous, touch no parameter, optimiser state, RNG state or lazy bookkeeping, and allocate on first use
+ * (nvsm_describe of a handle that never makes them is unchanged). NVSM_ERR_INVALID_ARGUMENT before anything runs, each with a
+ * sentence: everything nvsm_rank_ensemble(_prf) refuses; NULL alphas, judgments, metrics (and the cv call's required outputs), by name;
+ * num_alphas out of range; an alpha outside [0, 1] or not finite; depth < 0; num_folds out of range; a fold_of entry out of range; an
+ * unknown or not offered measure. top_k > NVSM_ENSEMBLE_MAX_TOP_K is NVSM_ERR_UNSUPPORTED.
+ */
+#define NVSM_SWEEP_MAX_ALPHAS 1024
+typedef struct {
+    const float* alphas;          /* [num_alphas], each in [0, 1] */
+    int32_t num_alphas;           /* 1 .. NVSM_SWEEP_MAX_ALPHAS */
+    int32_t normalizer;           /* NVSM_NORM_* */
+    int32_t depth;                /* the metrics look at the first depth entries of a fused list; 0 = all */
+    int32_t reserved[5];
+} nvsm_sweep_options;
+typedef struct {
+    int32_t measure;              /* a column of the metric row: NVSM_EVAL_AP, ..., NVSM_EVAL_FIXED + 3 j + {0, 1, 2} */
+    int32_t num_folds;            /* 2 .. num_queries */
+    const int32_t* fold_of;       /* [num_queries], or NULL: contiguous folds in query order */
+    int32_t reserved[4];
+} nvsm_cv_options;
+/* alphas NULL (the caller sets them), NVSM_NORM_STANDARDIZE, depth 0 */
+void nvsm_sweep_options_default(nvsm_sweep_options* opt);
+/* NVSM_EVAL_AP, 20 folds, fold_of NULL: what rank-cranfield-collection.sh passes */
+void nvsm_cv_options_default(nvsm_cv_options* opt);
+/* metrics [num_alphas][num_queries][NVSM_EVAL_FIXED + 3 * num_cutoffs] doubles, host; fb may be NULL */
+int nvsm_ensemble_sweep(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                        const nvsm_feedback_options* fb, const nvsm_sweep_options* sweep, const nvsm_judgments* judgments, double* metrics);
+/* fold_alpha, fold_train_measure [num_folds]; doc_ids / scores [num_queries][2 * top_k], counts [num_queries]; metrics
+ * [num_queries][width] or NULL; sweep_metrics as nvsm_ensemble_sweep's metrics or NULL; all host; fb may be NULL */
+int nvsm_rank_ensemble_cv(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                          const nvsm_feedback_options* fb, const nvsm_sweep_options* sweep, const nvsm_cv_options* cv,
+                          const nvsm_judgments* judgments, float* fold_alpha, double* fold_train_measure,
+                          int64_t* doc_ids, float* scores, int64_t* counts, double* metrics, double* sweep_metrics);
+
+/*
  * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query
  * library does with the same parameters (py/nvsm/base.py). Semantics, pinned by the reference:
  *   space        NVSM_SPACE_WORDS: the rows of W, dimension word_repr_size — NVSM.related_terms (base.py:325-342) and

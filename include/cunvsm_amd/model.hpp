@@ -313,6 +313,63 @@ class Model {
         return e;
     }
 
+    // nvsm_ensemble_sweep: both rankings once, then the metric rows [alphas][num_queries][width] of their fusion at every alpha over
+    // the first `depth` entries of the fused lists (0: all). fb null: the lexical list is lexical_rank's, else lexical_rank_prf's.
+    struct Sweep { std::vector<double> metrics; int32_t width; int32_t num_alphas; };
+    Sweep ensemble_sweep(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                         const nvsm_lexical_options& lex, const std::vector<float>& alphas, const nvsm_judgments& judgments,
+                         int32_t normalizer = NVSM_NORM_STANDARDIZE, int32_t depth = 0, const nvsm_feedback_options* fb = nullptr,
+                         const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        nvsm_sweep_options sw;
+        nvsm_sweep_options_default(&sw);
+        sw.alphas = alphas.data(); sw.num_alphas = static_cast<int32_t>(alphas.size()); sw.normalizer = normalizer; sw.depth = depth;
+        Sweep s;
+        s.width = NVSM_EVAL_FIXED + 3 * (judgments.num_cutoffs > 0 ? judgments.num_cutoffs : 0);
+        s.num_alphas = sw.num_alphas;
+        const size_t n = alphas.size() * static_cast<size_t>(q.num_queries) * static_cast<size_t>(s.width);
+        s.metrics.resize(n + 1);
+        check(nvsm_ensemble_sweep(h_, &q, &opt, &lex, fb, &sw, &judgments, s.metrics.data()));
+        s.metrics.resize(n);
+        return s;
+    }
+    // nvsm_rank_ensemble_cv: the sweep, per fold the alpha with the best training measure, and every query fused at its fold's alpha.
+    // fold_of null: contiguous folds in query order. The evaluation holds the fused lists and their metric rows cut at `depth`.
+    struct CrossValidation { std::vector<float> fold_alpha; std::vector<double> fold_train_measure; Evaluation evaluation; Sweep sweep; };
+    CrossValidation rank_ensemble_cv(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                                     const nvsm_lexical_options& lex, const std::vector<float>& alphas, const nvsm_judgments& judgments,
+                                     int32_t num_folds = 20, int32_t measure = NVSM_EVAL_AP, int32_t normalizer = NVSM_NORM_STANDARDIZE,
+                                     int32_t depth = 1000, const std::vector<int32_t>* fold_of = nullptr,
+                                     const nvsm_feedback_options* fb = nullptr, const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        nvsm_sweep_options sw;
+        nvsm_sweep_options_default(&sw);
+        sw.alphas = alphas.data(); sw.num_alphas = static_cast<int32_t>(alphas.size()); sw.normalizer = normalizer; sw.depth = depth;
+        nvsm_cv_options cv;
+        nvsm_cv_options_default(&cv);
+        cv.measure = measure; cv.num_folds = num_folds; cv.fold_of = fold_of ? fold_of->data() : nullptr;
+        CrossValidation c;
+        Evaluation& e = c.evaluation;
+        e.width = c.sweep.width = NVSM_EVAL_FIXED + 3 * (judgments.num_cutoffs > 0 ? judgments.num_cutoffs : 0);
+        c.sweep.num_alphas = sw.num_alphas;
+        e.ranking.top_k = 2 * opt.top_k;
+        const size_t Q = static_cast<size_t>(q.num_queries);
+        const size_t n = Q * 2 * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        const size_t F = static_cast<size_t>(num_folds > 0 ? num_folds : 0);
+        c.fold_alpha.resize(F + 1); c.fold_train_measure.resize(F + 1);
+        e.metrics.resize(Q * static_cast<size_t>(e.width) + 1);
+        c.sweep.metrics.resize(alphas.size() * Q * static_cast<size_t>(e.width) + 1);
+        e.ranking.doc_ids.resize(n ? n : 1); e.ranking.scores.resize(n ? n : 1); e.ranking.counts.resize(Q + 1);
+        check(nvsm_rank_ensemble_cv(h_, &q, &opt, &lex, fb, &sw, &cv, &judgments, c.fold_alpha.data(), c.fold_train_measure.data(),
+                                    e.ranking.doc_ids.data(), e.ranking.scores.data(), e.ranking.counts.data(), e.metrics.data(),
+                                    c.sweep.metrics.data()));
+        c.fold_alpha.resize(F); c.fold_train_measure.resize(F);
+        e.metrics.resize(Q * static_cast<size_t>(e.width));
+        c.sweep.metrics.resize(alphas.size() * Q * static_cast<size_t>(e.width));
+        e.ranking.doc_ids.resize(n); e.ranking.scores.resize(n); e.ranking.counts.resize(Q);
+        return c;
+    }
+
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
     // 362-430): queries are row ids of `source_space`, or vectors [n][dim] of the searched space (neighbors_of_vectors)
     struct Neighbors { std::vector<int64_t> ids; std::vector<float> scores; std::vector<int64_t> counts; int32_t top_k; };
