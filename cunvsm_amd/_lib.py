@@ -133,6 +133,14 @@ class NvsmNeighborOptions(C.Structure):
     ]
 
 
+class NvsmNgramOptions(C.Structure):
+    _fields_ = [
+        ("max_cardinality", C.c_int32), ("similarity", C.c_int32), ("top_k", C.c_int32), ("bias_coefficient", C.c_float),
+        ("activation", C.c_int32), ("reserved0", C.c_int32), ("vocabulary", C.c_void_p), ("vocabulary_size", C.c_int64),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 class GemmEpilogueArgs(C.Structure):
     """nvsm_debug_gemm_epilogue_args (include/cunvsm_amd_test_hooks.h)."""
     _fields_ = [
@@ -254,6 +262,7 @@ class _Library:
                 "nvsm_debug_gather_mean": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, vp]),
                 "nvsm_debug_gather_mean_lazy": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
                 "nvsm_debug_lazy_refresh": (C.c_int, [P(LazyRefreshArgs)]),
+                "nvsm_debug_ngram_rows": (C.c_int, [vp, i64, C.c_int, vp, C.c_float, C.c_int, i64, i64, vp, i64, i64]),
             }.items():
                 fn = getattr(H, hook)
                 fn.restype = res
@@ -332,6 +341,9 @@ def lib():
         "nvsm_neighbor_options_default": (None, [P(NvsmNeighborOptions)]),
         "nvsm_neighbors": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNeighborOptions), vp, vp, vp]),
         "nvsm_similarity": (C.c_int, [vp, C.c_int32, vp, vp, i64, C.c_int32, vp]),
+        "nvsm_ngram_options_default": (None, [P(NvsmNgramOptions)]),
+        "nvsm_ngram_rows": (i64, [i64, C.c_int32]),
+        "nvsm_ngram_search": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNgramOptions), vp, vp, vp, vp]),
         "nvsm_set_stream": (C.c_int, [vp, vp]), "nvsm_synchronize": (C.c_int, [vp]),
         "nvsm_describe": (C.c_int, [vp, C.c_int64, C.c_char_p, C.c_int64]),
         "nvsm_comm_unique_id": (C.c_int, [vp]), "nvsm_comm_init": (C.c_int, [vp, vp]),

@@ -435,6 +435,20 @@ int nvsm_similarity(nvsm_model* m, int32_t space, const int64_t* a, const int64_
     return guarded_on(m, [&] { m->impl.similarity(space, a, b, n, similarity, out); });
 }
 
+void nvsm_ngram_options_default(nvsm_ngram_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->max_cardinality = 1; o->similarity = NVSM_SIM_COSINE; o->top_k = 20;
+    o->bias_coefficient = 1.f; o->activation = NVSM_ACT_MODEL;
+}
+int64_t nvsm_ngram_rows(int64_t vocabulary_size, int32_t max_cardinality) { return cunvsm::ngram_row_count(vocabulary_size, max_cardinality); }
+int nvsm_ngram_search(nvsm_model* m, const nvsm_neighbor_queries* queries, const nvsm_ngram_options* opt, int64_t* phrase_rows, int64_t* terms,
+                      float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(opt); NVSM_REQUIRE(phrase_rows); NVSM_REQUIRE(terms); NVSM_REQUIRE(scores);
+    NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.ngram_search(*queries, *opt, phrase_rows, terms, scores, counts); });
+}
+
 int nvsm_set_stream(nvsm_model* m, void* s) { NVSM_REQUIRE(m); return guarded_on(m, [&] { m->impl.set_stream(static_cast<hipStream_t>(s)); }); }
 int nvsm_describe(nvsm_model* m, int64_t batch, char* buf, int64_t buf_bytes) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(buf);

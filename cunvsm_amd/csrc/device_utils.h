@@ -4,7 +4,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/cunvsm_amd.h"
+
 namespace cunvsm {
+
+// f(pre + c·b) of Model::infer without batch normalisation (cpp/model.cu:125-128): the one bias-and-activation expression of the
+// retrieval calls, shared by rank_bias_act_kernel (rank.hip) and ngram_rows_kernel (ngram.hip) so that a value that went through
+// either is the same bits. c = 0 leaves the bias out altogether (py/query.py's quirk); act: NVSM_TANH, NVSM_HARD_TANH, else identity;
+// clip_min / clip_max: the nextafter-widened hard_tanh bounds (cuda_utils.h:91-96).
+__device__ __forceinline__ float rank_bias_act(float v, float b, float c, int act, float clip_min, float clip_max) {
+    if (c != 0.f) v += c * b;
+    if (act == NVSM_TANH) v = tanhf(v);
+    else if (act == NVSM_HARD_TANH) v = fminf(fmaxf(v, clip_min), clip_max);
+    return v;
+}
 
 template <int V>
 __device__ __forceinline__ void ldv(const float* __restrict__ p, float (&x)[V]) {

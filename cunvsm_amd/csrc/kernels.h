@@ -555,6 +555,16 @@ void launch_rank_exclude_self(float* scores, int64_t ld_scores, int64_t d_begin,
 void launch_rank_pair_sim(const float* table, int dim, const int64_t* a, const int64_t* b, int64_t n, float* out, int cosine,
                           const LazyView& lazy, hipStream_t s);
 
+// ---- n-grams of terms in document space (ngram.hip; include/cunvsm_amd.h nvsm_ngram_search; py/nvsm/base.py:106-162) ----
+// rows of the stack of phrase projections over m words: m for max_cardinality 1, m + m(m − 1)/2 for 2; -1 where that is not below
+// 2^31 (the selection keys' limit), for m < 1 and for any other cardinality. Host arithmetic only.
+int64_t ngram_row_count(int64_t m, int max_cardinality);
+// out[i][de], i < S = phrase row p0 + i: f(G[a] + c·b) for the 1-gram a = p0 + i < m, f(0.5·(G[a] + G[b]) + c·b) for the 2-gram
+// (a, b) of row m + a·(2m − a − 1)/2 + (b − a − 1); G [m][de] = T·W[s_i] on the device, f and c as launch_rank_bias_act (the same
+// __device__ expression). The slab may straddle the 1-gram / 2-gram boundary and begin inside a run of one a; rows outside the
+// stack throw before anything is launched.
+void launch_ngram_rows(const float* G, int m, int de, const float* bias, float c, int act, int64_t p0, int S, float* out, hipStream_t s);
+
 // ---- retrieval metrics of a round's ranking (eval.hip; include/cunvsm_amd.h nvsm_evaluate) ----
 // One wave per query of the round. ids [Q][k] / counts [Q]: what launch_rank_write left. Judged documents of ALL queries of the
 // call: jids ascending per query (no -1 entries), jgrades next to them, joff [queries of the call + 1]; consts

@@ -193,6 +193,9 @@ class Model {
     // nearest neighbours among the word rows, the projected vocabulary or the document rows (py/nvsm/base.py:106-162, 325-353,
     // 362-430), and the similarity of pairs of rows (ranking.cpp)
     void neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts);
+    // phrase_rows / scores [Q][top_k], terms [Q][top_k][max_cardinality], counts [Q], host (nvsm_ngram_search)
+    void ngram_search(const nvsm_neighbor_queries& q, const nvsm_ngram_options& opt, int64_t* phrase_rows, int64_t* terms, float* scores,
+                      int64_t* counts);
     void similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out);
 
     void set_stream(hipStream_t s);
@@ -480,6 +483,8 @@ class Model {
         DevBuf<char> sel_ws;
         DevBuf<float> panel, pslab, pair_out;      // neighbours: the query panel [round][dim], one slab of the projected vocabulary
         DevBuf<int64_t> self;                      //             ... the queries' own rows (exclude_self)
+        DevBuf<float> ngram_g;                     // n-grams: G [m][de] = T·W[S] of the call,
+        DevBuf<int64_t> ngram_vocab;               //          ... and S on the device
         DevBuf<int> jids, jgrades;                 // evaluate: the call's judged ids (ascending per query) and grades,
         DevBuf<int64_t> joff;                      //           ... their offsets,
         DevBuf<double> jconst, metrics;            //           ... R / idcg / idcg@c per query, and the metric rows
@@ -536,6 +541,8 @@ class Model {
     struct RowSpace { const float* rows; int64_t count; int dim; const TableState* table; };      // rows null: the projected vocabulary
     RowSpace row_space(int space) const;
     void project_words(const int64_t* ids_dev, int64_t first, int64_t n, float c, int act, float* out);      // out [n][de] = f(T·W[id] + c·b)
+    void neighbor_queries_check(const nvsm_neighbor_queries& q, int dim) const;      // the query refusals nvsm_neighbors and nvsm_ngram_search share
+    void neighbor_panel(const nvsm_neighbor_queries& q, int64_t q0, int64_t qn, int dim, float c, int act, int cosine);      // rank_.panel, rank_.qinv of a round
     void rank_project(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, int64_t qn);      // rank_.proj [qn][de], on the main stream
 
     bool have_forward_ = false, have_grads_ = false;

@@ -89,11 +89,7 @@ __global__ __launch_bounds__(256) void rank_query_mean_kernel(const float* __res
 __global__ __launch_bounds__(256) void rank_bias_act_kernel(float* __restrict__ y, const float* __restrict__ bias, float c, int act,
                                                             float clip_min, float clip_max, int64_t n, int de) {
     for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-        float v = y[i];
-        if (c != 0.f) v += c * bias[i % de];
-        if (act == NVSM_TANH) v = tanhf(v);
-        else if (act == NVSM_HARD_TANH) v = fminf(fmaxf(v, clip_min), clip_max);
-        y[i] = v;
+        y[i] = rank_bias_act(y[i], bias[i % de], c, act, clip_min, clip_max);
     }
 }
 

@@ -986,14 +986,9 @@ void Model::project_words(const int64_t* ids_dev, int64_t first, int64_t n, floa
     }
 }
 
-void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts) {
-    if (!known_space(opt.space)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space");
-    check_similarity(opt.similarity);
-    check_activation(opt.activation);
-    if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
-    const RowSpace sp = row_space(opt.space);
-    const int64_t R = sp.count, Q = q.num_queries;
-    const int dim = sp.dim;
+// the refusals of a nvsm_neighbor_queries against a searched space of dimension `dim`, in nvsm_neighbors' order
+void Model::neighbor_queries_check(const nvsm_neighbor_queries& q, int dim) const {
+    const int64_t Q = q.num_queries;
     if (Q < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_queries is negative");
     if ((q.ids != nullptr) == (q.vectors != nullptr)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries: exactly one of ids and vectors must be given");
     if (q.ids) {
@@ -1005,6 +1000,37 @@ void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_option
     } else if (q.dim != dim) {
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "queries->dim differs from the searched space's dimension");
     }
+}
+
+// a round's query panel rank_.panel [qn][dim] from the queries q0 .. q0 + qn of the call — host vectors, gathered rows of a table
+// (through its lazy view) or projected words (c, act) — and its inverse norms rank_.qinv
+void Model::neighbor_panel(const nvsm_neighbor_queries& q, int64_t q0, int64_t qn, int dim, float c, int act, int cosine) {
+    RankScratch& r = rank_;
+    grow(r.panel, static_cast<size_t>(kRankChunk) * dim);
+    grow(r.ids, static_cast<size_t>(kInferChunk));
+    grow(r.qinv, static_cast<size_t>(kInferChunk));
+    if (q.ids) NVSM_HIP_CHECK(hipMemcpy(r.ids.p, q.ids + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (q.vectors) {
+        NVSM_HIP_CHECK(hipMemcpy(r.panel.p, q.vectors + q0 * dim, static_cast<size_t>(qn) * dim * sizeof(float), hipMemcpyHostToDevice));
+    } else if (q.source_space == NVSM_SPACE_PROJECTED_WORDS) {
+        project_words(r.ids.p, 0, qn, c, act, r.panel.p);
+    } else {
+        const RowSpace src = row_space(q.source_space);
+        RankProf scope(prof, "nbr_gather", stream_);
+        launch_rank_gather_rows(src.rows, dim, r.ids.p, 0, qn, r.panel.p, lazy_view(*src.table), stream_);
+    }
+    { RankProf scope(prof, "nbr_gather", stream_); launch_rank_query_norm(r.panel.p, qn, dim, r.qinv.p, cosine, stream_); }
+}
+
+void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_options& opt, int64_t* ids, float* scores, int64_t* counts) {
+    if (!known_space(opt.space)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space");
+    check_similarity(opt.similarity);
+    check_activation(opt.activation);
+    if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
+    const RowSpace sp = row_space(opt.space);
+    const int64_t R = sp.count, Q = q.num_queries;
+    const int dim = sp.dim;
+    neighbor_queries_check(q, dim);
     if (opt.exclude_self && !(q.ids && q.source_space == opt.space))
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "exclude_self needs queries given as row ids of the searched space");
     check_top_k(opt.top_k, R, "top_k must be in [1, rows of the searched space]");
@@ -1025,26 +1051,13 @@ void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_option
         const RankLayout l = rank_layout(R, k, Q - q0, score_floats(), sp.rows ? 0 : proj_rows);      // (a projected slab is scratch of its own)
         const int64_t qn = l.qn;
         // ---- the round's query panel [qn][dim]
-        grow(r.panel, static_cast<size_t>(kRankChunk) * dim);
-        grow(r.ids, static_cast<size_t>(kInferChunk));
-        grow(r.qinv, static_cast<size_t>(kInferChunk));
         const int64_t* self = nullptr;
-        if (q.ids) NVSM_HIP_CHECK(hipMemcpy(r.ids.p, q.ids + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
         if (exclude) {      // (a copy of its own: r.ids serves project_words' identity lists further down)
             grow(r.self, static_cast<size_t>(2 * kPairChunk));
             NVSM_HIP_CHECK(hipMemcpy(r.self.p, q.ids + q0, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice));
             self = r.self.p;
         }
-        if (q.vectors) {
-            NVSM_HIP_CHECK(hipMemcpy(r.panel.p, q.vectors + q0 * dim, static_cast<size_t>(qn) * dim * sizeof(float), hipMemcpyHostToDevice));
-        } else if (q.source_space == NVSM_SPACE_PROJECTED_WORDS) {
-            project_words(r.ids.p, 0, qn, opt.bias_coefficient, act, r.panel.p);
-        } else {
-            const RowSpace src = row_space(q.source_space);
-            RankProf scope(prof, "nbr_gather", stream_);
-            launch_rank_gather_rows(src.rows, dim, r.ids.p, 0, qn, r.panel.p, lazy_view(*src.table), stream_);
-        }
-        { RankProf scope(prof, "nbr_gather", stream_); launch_rank_query_norm(r.panel.p, qn, dim, r.qinv.p, cosine, stream_); }
+        neighbor_panel(q, q0, qn, dim, opt.bias_coefficient, act, cosine);
         round_grow(l, k);
         round_slabs(l, R, k, [&](int64_t d0, int Ss) {
             const float* rows = sp.rows;
@@ -1068,6 +1081,98 @@ void Model::neighbors(const nvsm_neighbor_queries& q, const nvsm_neighbor_option
         q0 += qn;
     }
     raise_device_error();
+}
+
+// ---- n-grams of terms in document space (include/cunvsm_amd.h nvsm_ngram_search; kernel: ngram.hip) ---------------
+// TermBruteforcer (base.py:106-162) up to 2-grams. G = T·W[S] is made once per call with project_words (c = 0, identity: the words
+// table's lazy view applies as it does to the projected vocabulary); a slab of phrase rows is generated from G into the projected
+// slab's scratch and scanned there. Rounds, slabs, selection, sort and write are nvsm_neighbors'.
+namespace {
+// (a, b) of phrase row p >= m over m words: the run of a begins at a·(2m − a − 1)/2 behind the 1-grams
+void ngram_pair_of_row(int64_t p, int64_t m, int64_t* a_out, int64_t* b_out) {
+    const int64_t t = p - m;
+    auto start = [m](int64_t a) { return a * (2 * m - a - 1) / 2; };
+    const double w = static_cast<double>(2 * m - 1);
+    int64_t a = static_cast<int64_t>((w - std::sqrt(w * w - 8.0 * static_cast<double>(t))) * 0.5);
+    a = std::max<int64_t>(0, std::min(a, m - 2));
+    while (a > 0 && start(a) > t) --a;
+    while (a < m - 2 && start(a + 1) <= t) ++a;
+    *a_out = a;
+    *b_out = a + 1 + (t - start(a));
+}
+}  // namespace
+
+void Model::ngram_search(const nvsm_neighbor_queries& q, const nvsm_ngram_options& opt, int64_t* phrase_rows, int64_t* terms, float* scores,
+                         int64_t* counts) {
+    const int de = cfg_.entity_repr_size;
+    const int64_t V = cfg_.num_words, Q = q.num_queries;
+    if (opt.max_cardinality != 1 && opt.max_cardinality != 2) throw Error(NVSM_ERR_INVALID_ARGUMENT, "max_cardinality must be 1 or 2");
+    check_similarity(opt.similarity);
+    check_activation(opt.activation);
+    if (!std::isfinite(opt.bias_coefficient)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "bias_coefficient is not finite");
+    const int64_t* S = opt.vocabulary;
+    if (S) {
+        if (opt.vocabulary_size < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "vocabulary_size must be at least 1");
+        for (int64_t i = 0; i < opt.vocabulary_size; ++i) {
+            if (S[i] < 0 || S[i] >= V) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a vocabulary word id is outside [0, num_words)");
+            if (i > 0 && S[i] <= S[i - 1]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the vocabulary must be strictly ascending");
+        }
+    }
+    const int64_t m = S ? opt.vocabulary_size : V;
+    const int card = opt.max_cardinality;
+    const int64_t R = ngram_row_count(m, card);
+    if (R < 0) throw Error(NVSM_ERR_UNSUPPORTED, "n-gram search supports fewer than 2^31 phrase rows: at most 65535 words for 2-grams");
+    neighbor_queries_check(q, de);
+    check_top_k(opt.top_k, R, "top_k must be in [1, rows of the phrase stack (nvsm_ngram_rows)]");
+    const int k = opt.top_k;
+    const int cosine = opt.similarity == NVSM_SIM_COSINE;
+    const int act = opt.activation == NVSM_ACT_MODEL ? cfg_.nonlinearity : opt.activation;
+    const int64_t proj_rows = std::max<int64_t>(kSlabAlign, kProjSlabBytes / (static_cast<int64_t>(de) * 4) / kSlabAlign * kSlabAlign);
+    rank_join();
+    RankScratch& r = rank_;
+    LazyView none{};
+    none.stamp = nullptr;
+    // ---- G [m][de] = T·W[S], whole: what every phrase row of the call is made from
+    grow(r.ngram_g, static_cast<size_t>(m) * de);
+    if (S) {
+        grow(r.ngram_vocab, static_cast<size_t>(m));
+        NVSM_HIP_CHECK(hipMemcpy(r.ngram_vocab.p, S, static_cast<size_t>(m) * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    project_words(S ? r.ngram_vocab.p : nullptr, 0, m, 0.f, NVSM_ACT_IDENTITY, r.ngram_g.p);
+
+    for (int64_t q0 = 0; q0 < Q;) {
+        const RankLayout l = rank_layout(R, k, Q - q0, score_floats(), proj_rows);
+        const int64_t qn = l.qn;
+        neighbor_panel(q, q0, qn, de, opt.bias_coefficient, act, cosine);
+        round_grow(l, k);
+        round_slabs(l, R, k, [&](int64_t p0, int Ss) {
+            grow(r.pslab, static_cast<size_t>(l.S) * de);
+            {
+                RankProf scope(prof, "ngram_rows", stream_);
+                launch_ngram_rows(r.ngram_g.p, static_cast<int>(m), de, b_.p, opt.bias_coefficient, act, p0, Ss, r.pslab.p, stream_);
+            }
+            RankProf scope(prof, "ngram_scan", stream_);
+            prof.note(nbr_scan_uses_mfma(de) ? "ngram_scan_mfma" : "ngram_scan_plain");
+            launch_nbr_scan(r.pslab.p, de, 0, Ss, r.panel.p, static_cast<int>(qn), r.qinv.p, r.scores.p, l.ld, cosine, none, stream_);
+        });
+        round_sort(l, [&] {
+            launch_rank_write(r.keys.p, l.npad, static_cast<int>(qn), k, nullptr, std::min<int64_t>(l.n_keys, R), r.out_ids.p, r.out_scores.p,
+                              r.out_counts.p, stream_);
+        });
+        round_results(q0, qn, k, phrase_rows, scores, counts);
+        q0 += qn;
+    }
+    raise_device_error();
+    // ---- the words of every returned row: positions in S by the row formula, then model word ids
+    for (int64_t i = 0; i < Q * k; ++i) {
+        int64_t* t = terms + i * card;
+        const int64_t p = phrase_rows[i];
+        int64_t a = -1, b = -1;
+        if (p >= m) ngram_pair_of_row(p, m, &a, &b);
+        else if (p >= 0) a = p;
+        t[0] = a < 0 ? -1 : (S ? S[a] : a);
+        if (card == 2) t[1] = b < 0 ? -1 : (S ? S[b] : b);
+    }
 }
 
 void Model::similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out) {

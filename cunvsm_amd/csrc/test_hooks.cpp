@@ -730,6 +730,28 @@ int nvsm_debug_gather_mean_lazy(int64_t num_rows, int dim, const float* table, c
     });
 }
 
+// One launch_ngram_rows on caller-supplied inputs (cunvsm_amd_test_hooks.h): the caller's buffer goes up whole, guard rows and all,
+// the launch writes S rows from out_row0 on, and the buffer comes back whole.
+int nvsm_debug_ngram_rows(const float* G, int64_t m, int de, const float* bias, float c, int act, int64_t p0, int64_t S, float* out,
+                          int64_t out_rows, int64_t out_row0) {
+    NVSM_REQUIRE(G); NVSM_REQUIRE(bias); NVSM_REQUIRE(out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        const int64_t rows = m < 65536 ? ngram_row_count(m, 2) : -1;
+        if (rows < 0 || de < 1 || S < 1 || S >= (int64_t(1) << 31) || p0 < 0 || p0 + S > rows || out_row0 < 0 || out_row0 + S > out_rows)
+            throw Error(NVSM_ERR_INVALID_ARGUMENT, "ngram_rows: bad sizes");
+        DevBuf<float> g, b, o;
+        g.alloc(static_cast<size_t>(m) * de); b.alloc(static_cast<size_t>(de)); o.alloc(static_cast<size_t>(out_rows) * de);
+        NVSM_HIP_CHECK(hipMemcpy(g.p, G, g.n * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(b.p, bias, b.n * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(o.p, out, o.n * sizeof(float), hipMemcpyHostToDevice));
+        launch_ngram_rows(g.p, static_cast<int>(m), de, b.p, c, act, p0, static_cast<int>(S), o.p + out_row0 * de, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(out, o.p, o.n * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
 // One launch_lazy_refresh on caller-supplied inputs (cunvsm_amd_test_hooks.h): the arguments of Model::lazy_refresh /
 // Model::lazy_scalar_snapshot, the list and its count on the device as Csr::touched / num_touched are.
 int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* a) {

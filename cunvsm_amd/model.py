@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmNgramOptions, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -600,6 +600,120 @@ def neighbor_arguments(cfg, space, ids=None, vectors=None, source=None, top_k=30
     return q, opt, data
 
 
+# -- n-grams of terms in document space (TermBruteforcer, py/nvsm/base.py:106-162; nvsm_ngram_search) --------------------------
+NGRAM_MAX_ROWS = 1 << 31      # the phrase stack stays below it (the selection keys' limit): 65 535 words for 2-grams
+
+
+def ngram_rows(vocabulary_size, max_cardinality):
+    """Rows of the phrase stack over `vocabulary_size` words (nvsm_ngram_rows): m 1-grams, then the m(m - 1)/2 2-grams; -1 where
+    that is not below 2^31, for fewer than one word and for a cardinality outside {1, 2}. Needs no library."""
+    m, c = int(vocabulary_size), int(max_cardinality)
+    if m < 1 or c not in (1, 2):
+        return -1
+    rows = m if c == 1 else m + m * (m - 1) // 2
+    return rows if rows < NGRAM_MAX_ROWS else -1
+
+
+def ngram_encode(terms, vocabulary_size):
+    """Phrase rows of `terms` [..., 2] (or [..., 1]): POSITIONS in the vocabulary, (a, -1) a 1-gram, (a, b) with a < b a 2-gram, in
+    the order of np.vstack over itertools.combinations: row of (a, b) = m + a(2m - a - 1)/2 + (b - a - 1)."""
+    m = int(vocabulary_size)
+    t = np.asarray(terms, dtype=np.int64)
+    if t.ndim == 0 or t.shape[-1] not in (1, 2):
+        raise ValueError("terms must end in an axis of 1 or 2 positions")
+    a = t[..., 0]
+    b = t[..., 1] if t.shape[-1] == 2 else np.full_like(a, -1)
+    pair = b >= 0
+    if ((a < 0) | (a >= m)).any() or (pair & ((b <= a) | (b >= m))).any() or (b < -1).any():
+        raise ValueError("positions must satisfy 0 <= a < m, and b = -1 or a < b < m (m = %d)" % m)
+    return np.where(pair, m + a * (2 * m - a - 1) // 2 + (b - a - 1), a)
+
+
+def ngram_decode(phrase_rows, vocabulary_size, max_cardinality=2):
+    """The inverse of ngram_encode: positions [..., max_cardinality] int64 of phrase rows, -1 in unused slots (the second of a 1-gram,
+    both of a row of -1: a slot beyond counts[q])."""
+    m, c = int(vocabulary_size), int(max_cardinality)
+    rows = ngram_rows(m, c)
+    if rows < 0:
+        raise ValueError("no phrase stack for vocabulary_size = %d, max_cardinality = %d" % (m, c))
+    p = np.asarray(phrase_rows, dtype=np.int64)
+    if ((p < -1) | (p >= rows)).any():
+        raise ValueError("a phrase row is outside [-1, %d)" % rows)
+    out = np.full(p.shape + (c,), -1, np.int64)
+    one = (p >= 0) & (p < m)
+    out[..., 0][one] = p[one]
+    two = p >= m
+    if two.any():
+        t = p[two] - m
+        start = lambda a: a * (2 * m - a - 1) // 2      # noqa: E731
+        w = 2 * m - 1
+        a = ((w - np.sqrt(np.maximum(w * w - 8.0 * t, 0.0))) / 2).astype(np.int64).clip(0, m - 2)
+        for _ in range(4):      # the float estimate is off by one at most; integer fix-up against the runs' first rows
+            a = np.where(start(a) > t, a - 1, a)
+            a = np.where((a < m - 2) & (start(np.minimum(a + 1, m - 2)) <= t), a + 1, a)
+        out[..., 0][two] = a
+        out[..., 1][two] = a + 1 + (t - start(a))
+    return out
+
+
+def ngram_arguments(cfg, entity_ids=None, word_ids=None, vectors=None, vocabulary=None, max_cardinality=2, top_k=20, similarity="cosine",
+                    bias_coefficient=1.0, activation="model"):
+    """(nvsm_neighbor_queries, nvsm_ngram_options, vocabulary as int64 array or None, arrays to keep alive) from keywords; raises
+    ValueError for everything nvsm_ngram_search would refuse (no device needed)."""
+    if int(max_cardinality) not in (1, 2):
+        raise ValueError("max_cardinality = %r outside {1, 2}" % (max_cardinality,))
+    ropt = rank_options(1, None, bias_coefficient=bias_coefficient, activation=activation, similarity=similarity)
+    if ropt.similarity not in SIMILARITIES.values():
+        raise ValueError("unknown similarity %r" % (similarity,))
+    if ropt.activation not in ACTIVATIONS.values():
+        raise ValueError("unknown activation %r" % (activation,))
+    if not np.isfinite(ropt.bias_coefficient):
+        raise ValueError("bias_coefficient is not finite")
+    V, de = int(cfg.num_words), int(cfg.entity_repr_size)
+    voc = None
+    if vocabulary is not None:
+        if np.asarray(vocabulary).ndim != 1:
+            raise ValueError("vocabulary must be a flat list of word ids")
+        voc = np.ascontiguousarray(np.asarray(vocabulary, dtype=np.int64))
+        if voc.size < 1:
+            raise ValueError("vocabulary_size must be at least 1")
+        if voc.min() < 0 or voc.max() >= V:
+            raise ValueError("a vocabulary word id is outside [0, %d)" % V)
+        if (np.diff(voc) <= 0).any():
+            raise ValueError("the vocabulary must be strictly ascending")
+    m = V if voc is None else voc.size
+    rows = ngram_rows(m, max_cardinality)
+    if rows < 0:
+        raise ValueError("the phrase stack over %d words reaches the row limit 2^31 (at most 65535 words for 2-grams)" % m)
+    given = [x is not None for x in (entity_ids, word_ids, vectors)]
+    if sum(given) != 1:
+        raise ValueError("exactly one of entity_ids, word_ids and vectors must be given")
+    q = NvsmNeighborQueries()
+    if vectors is None:
+        ids = entity_ids if word_ids is None else word_ids
+        src, src_rows = (_lib.SPACE_ENTITIES, int(cfg.num_entities)) if word_ids is None else (_lib.SPACE_PROJECTED_WORDS, V)
+        if np.asarray(ids).ndim > 1:
+            raise ValueError("ids must be a flat list of row ids")
+        data = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).ravel())
+        if data.size and (data.min() < 0 or data.max() >= src_rows):
+            raise ValueError("a query row id is outside [0, %d)" % src_rows)
+        q.ids, q.vectors, q.num_queries, q.source_space, q.dim = data.ctypes.data, None, data.size, src, de
+    else:
+        data = np.ascontiguousarray(vectors, dtype=np.float32)
+        if data.ndim == 1:
+            data = data.reshape(1, -1)
+        if data.ndim != 2 or data.shape[1] != de:
+            raise ValueError("vectors has shape %s, expected [num_queries][dimension of document space = %d]" % (data.shape, de))
+        q.ids, q.vectors, q.num_queries, q.source_space, q.dim = None, data.ctypes.data, data.shape[0], _lib.SPACE_ENTITIES, de
+    if not 1 <= int(top_k) <= rows:
+        raise ValueError("top_k = %d outside [1, rows of the phrase stack = %d]" % (int(top_k), rows))
+    opt = NvsmNgramOptions()
+    opt.max_cardinality, opt.similarity, opt.top_k = int(max_cardinality), ropt.similarity, int(top_k)
+    opt.bias_coefficient, opt.activation = ropt.bias_coefficient, ropt.activation
+    opt.vocabulary, opt.vocabulary_size = (None, 0) if voc is None else (voc.ctypes.data, voc.size)
+    return q, opt, voc, data
+
+
 class Model:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -1061,6 +1175,25 @@ class Model:
         document rows (entity_ids) or to vectors of document space."""
         return self.neighbors("projected_words", ids=entity_ids, vectors=vectors, source=None if entity_ids is None else "entities",
                               top_k=top_k, **projection_opts)
+
+    def nearest_ngrams(self, entity_ids=None, word_ids=None, vectors=None, vocabulary=None, max_cardinality=2, top_k=20,
+                       similarity="cosine", bias_coefficient=1.0, activation="model"):
+        """TermBruteforcer up to 2-grams (base.py:106-162; nvsm_ngram_search): the 1- and 2-grams of `vocabulary` (strictly ascending
+        word ids; None: every word) whose projection f(T·mean(W[s_a], W[s_b]) + c·b) lies closest to document rows (entity_ids), to
+        projected words (word_ids) or to vectors of document space. Returns (phrase_rows [Q, k] int64, terms [Q, k, max_cardinality]
+        int64 model word ids with -1 in unused slots, scores [Q, k] float32, counts [Q] int64), by score descending, ties by ascending
+        phrase row (ngram_decode gives positions in the vocabulary); slots beyond counts[q] hold (-1, -1 ..., -inf)."""
+        q, opt, voc, keep = ngram_arguments(self.cfg, entity_ids, word_ids, vectors, vocabulary, max_cardinality, top_k, similarity,
+                                            bias_coefficient, activation)
+        k, c = opt.top_k, opt.max_cardinality
+        rows = np.empty((q.num_queries, k), dtype=np.int64)
+        terms = np.empty((q.num_queries, k, c), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        check(lib().nvsm_ngram_search(self._h, C.byref(q), C.byref(opt), rows.ctypes.data, terms.ctypes.data, scores.ctypes.data,
+                                      counts.ctypes.data))
+        del keep, voc
+        return rows, terms, scores, counts
 
     def related_documents(self, entity_ids, top_k=10, exclude_self=False):
         """Documents near documents (query_using_projected_query, base.py:362-430, with document rows as the queries)."""

@@ -658,8 +658,9 @@ int nvsm_rank_ensemble_cv(nvsm_model* m, const nvsm_queries* queries, const nvsm
  *   space        NVSM_SPACE_WORDS: the rows of W, dimension word_repr_size — NVSM.related_terms (base.py:325-342) and
  *                term_similarity (:344-353), cosine neighbours of a word among the word rows.
  *                NVSM_SPACE_PROJECTED_WORDS: row w is f(T·W[w] + c·b), dimension entity_repr_size — the vocabulary projected
- *                into document space, which TermBruteforcer (base.py:106-162, n-gram cardinality 1) searches for the terms
- *                closest to a document vector ("which terms describe this document"). NO batch normalisation;
+ *                into document space, which TermBruteforcer (base.py:106-162) searches for the terms closest to a document
+ *                vector ("which terms describe this document"); its n-grams of more than one term are nvsm_ngram_search's,
+ *                further down. NO batch normalisation;
  *                bias_coefficient and activation mean exactly what they mean in nvsm_rank_options, with the same defaults
  *                and the same quirk (c = 0 is what py/query.py computes; not "fixed" here).
  *                NVSM_SPACE_ENTITIES: the rows of E, dimension entity_repr_size — query_using_projected_query
@@ -705,6 +706,52 @@ int nvsm_neighbors(nvsm_model* m, const nvsm_neighbor_queries* queries, const nv
                    int64_t* ids, float* scores, int64_t* counts);
 /* a, b [n] host row ids of `space`; out [n] host */
 int nvsm_similarity(nvsm_model* m, int32_t space, const int64_t* a, const int64_t* b, int64_t n, int32_t similarity, float* out);
+
+/*
+ * N-grams of terms in document space — TermBruteforcer (py/nvsm/base.py:106-162) with max_ngram_cardinality up to 2: which
+ * terms, and which PAIRS of terms, describe a document or a query vector. Semantics, pinned by the reference:
+ *   vocabulary   S: vocabulary_size strictly ascending model word ids (host); NULL: all num_words words, which is what the
+ *                reference always takes. The subset is this library's addition: C(|V|, 2) phrases fit no other way.
+ *   phrase rows  the rows of the reference's np.vstack(reprs): first the m = |S| 1-grams in order, then the 2-grams (a, b),
+ *                a < b positions in S, in itertools.combinations order: row of (a, b) = m + a·(2m − a − 1)/2 + (b − a − 1).
+ *                R = m rows for max_cardinality 1, m + m(m − 1)/2 for 2 (nvsm_ngram_rows). R must stay below 2^31, the
+ *                selection keys' limit, i.e. m <= 65 535 for 2-grams: beyond it NVSM_ERR_UNSUPPORTED before anything runs.
+ *   row vector   f(T·mean(W[s_a], W[s_b]) + c·b) — Model::infer of the mean word vector, NO batch normalisation;
+ *                bias_coefficient and activation mean exactly what they mean in nvsm_rank_options, the c = 0 quirk included.
+ *                Evaluated as f(0.5·(G[a] + G[b]) + c·b) with G[i] = T·W[s_i] computed once per call (the projection is
+ *                linear in front of the bias); the 1-gram row is f(G[a] + c·b).
+ *   queries      a nvsm_neighbor_queries of dimension entity_repr_size: entity ids, projected-word ids or host vectors; the
+ *                dimension rule and the refusals are nvsm_neighbors' (projected-word queries take this call's c and activation).
+ *   score        NVSM_SIM_COSINE (the reference's 1 − cosine distance) or NVSM_SIM_DOT; a zero phrase or a zero query scores
+ *                0, never NaN.
+ *   result       per query the top_k phrase rows by score descending, ties by ASCENDING phrase row; terms[q][j][0 ..
+ *                max_cardinality) holds the model word ids of row phrase_rows[q][j], -1 in unused slots (the second of a
+ *                1-gram); slots beyond counts[q] hold (-1, -1 ..., -inf). A repeated call returns the same bits.
+ * Refused with a status code, in this order, the handle usable afterwards: max_cardinality outside {1, 2}; unknown
+ * similarity / activation; a bias_coefficient that is not finite; vocabulary_size < 1 (with a vocabulary), a vocabulary that
+ * is not strictly ascending or holds an id outside [0, num_words); the row limit; nvsm_neighbors' query refusals; top_k
+ * outside [1, R]. The call is synchronous; it runs behind everything earlier steps have queued (the side streams' tails
+ * included), flushes nothing and moves no stamp of a lazily decayed table: training goes on from exactly the same state.
+ */
+typedef struct {
+    int32_t        max_cardinality;   /* 1 or 2 */
+    int32_t        similarity;        /* NVSM_SIM_* */
+    int32_t        top_k;
+    float          bias_coefficient;  /* as nvsm_rank_options */
+    int32_t        activation;
+    int32_t        reserved0;
+    const int64_t* vocabulary;        /* [vocabulary_size] host, strictly ascending word ids, or NULL: every word */
+    int64_t        vocabulary_size;   /* ignored with vocabulary NULL */
+    int32_t        reserved[4];
+} nvsm_ngram_options;
+/* max_cardinality 1, NVSM_SIM_COSINE, top_k 20 (the reference's n_neighbors), bias_coefficient 1, NVSM_ACT_MODEL, vocabulary NULL */
+void nvsm_ngram_options_default(nvsm_ngram_options* opt);
+/* rows of the phrase stack over vocabulary_size words; -1 where that is not below 2^31, for vocabulary_size < 1 and for a
+ * max_cardinality outside {1, 2}. Host arithmetic only. */
+int64_t nvsm_ngram_rows(int64_t vocabulary_size, int32_t max_cardinality);
+/* phrase_rows, scores [num_queries][top_k], terms [num_queries][top_k][max_cardinality], counts [num_queries], all host */
+int nvsm_ngram_search(nvsm_model* m, const nvsm_neighbor_queries* queries, const nvsm_ngram_options* opt,
+                      int64_t* phrase_rows, int64_t* terms, float* scores, int64_t* counts);
 
 /* Streams. A handle issues its work on FOUR HIP streams of its own device: the main stream (highest priority: the step's
  * critical chain), two side streams (lowest priority: the batch → row-order sorts, and — in nvsm_step — the documents

@@ -395,6 +395,27 @@ class Model {
         return out;
     }
 
+    // TermBruteforcer up to 2-grams (py/nvsm/base.py:106-162; nvsm_ngram_search): the phrases of opt.vocabulary (NULL: every word)
+    // nearest to rows of `source_space` (entities or projected words), or to vectors [n][entity_repr_size] (ngram_search_of_vectors)
+    struct Ngrams {
+        std::vector<int64_t> phrase_rows, terms; std::vector<float> scores; std::vector<int64_t> counts;
+        int32_t top_k, max_cardinality;      // terms [n][top_k][max_cardinality], -1 in unused slots
+    };
+    Ngrams ngram_search(const std::vector<int64_t>& row_ids, int32_t source_space, const nvsm_ngram_options& opt) {
+        nvsm_neighbor_queries q;
+        q.ids = row_ids.data(); q.vectors = nullptr; q.num_queries = static_cast<int64_t>(row_ids.size());
+        q.source_space = source_space; q.dim = 0;
+        return ngrams_of(q, opt);
+    }
+    Ngrams ngram_search_of_vectors(const std::vector<float>& vectors, const nvsm_ngram_options& opt) {
+        const int32_t dim = cfg_.entity_repr_size;
+        if (dim < 1 || vectors.size() % static_cast<size_t>(dim) != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "vectors: a whole number of rows of entity_repr_size floats");
+        nvsm_neighbor_queries q;
+        q.ids = nullptr; q.vectors = vectors.data(); q.num_queries = static_cast<int64_t>(vectors.size() / static_cast<size_t>(dim));
+        q.source_space = NVSM_SPACE_ENTITIES; q.dim = dim;
+        return ngrams_of(q, opt);
+    }
+
     void synchronize() { check(nvsm_synchronize(h_)); }
     void comm_init(const char id[128]) { check(nvsm_comm_init(h_, id)); }
     nvsm_model* handle() { return h_; }
@@ -408,6 +429,17 @@ class Model {
         r.ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
         check(nvsm_neighbors(h_, &q, &opt, r.ids.data(), r.scores.data(), r.counts.data()));
         r.ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+    Ngrams ngrams_of(const nvsm_neighbor_queries& q, const nvsm_ngram_options& opt) {
+        Ngrams r;
+        r.top_k = opt.top_k; r.max_cardinality = opt.max_cardinality;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        const size_t c = static_cast<size_t>(opt.max_cardinality > 0 ? opt.max_cardinality : 0);
+        r.phrase_rows.resize(n ? n : 1); r.terms.resize(n * c + 1); r.scores.resize(n ? n : 1);
+        r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_ngram_search(h_, &q, &opt, r.phrase_rows.data(), r.terms.data(), r.scores.data(), r.counts.data()));
+        r.phrase_rows.resize(n); r.terms.resize(n * c); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
         return r;
     }
     static nvsm_queries queries_of(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const std::vector<float>* word_weights) {

@@ -145,6 +145,14 @@ int nvsm_debug_loss(const nvsm_debug_loss_args* args);
 /* nvsm_neighbors' scan through the plain kernel whatever the dimension (1) or by its own dispatch (0, the default): how
  * tools/bench_neighbors.py holds the MFMA scan with the tail chunk against the plain scan on the same table; process-wide */
 int nvsm_debug_neighbors_force_plain(int on);
+/* ONE launch of nvsm_ngram_search's phrase-row generator (csrc/ngram.hip launch_ngram_rows) on caller-supplied inputs: G [m][de]
+ * host (what the call makes as T·W[S]), bias [de], c and act (NVSM_TANH, NVSM_HARD_TANH, else identity) as launch_rank_bias_act
+ * takes them. The rows [p0, p0 + S) of the 1- and 2-gram stack over m words are written to out[out_row0 .. out_row0 + S); out
+ * [out_rows][de] is uploaded whole before the launch and comes back whole, so whatever the caller filled the other rows with must
+ * still be there.
+ * Refused with NVSM_ERR_INVALID_ARGUMENT: m outside [1, 65 535], rows outside the stack or outside out. */
+int nvsm_debug_ngram_rows(const float* G, int64_t m, int de, const float* bias, float c, int act, int64_t p0, int64_t S, float* out,
+                          int64_t out_rows, int64_t out_row0);
 /* the stable (row, entry) radix sort alone: keys of `bits` significant bits in, sorted keys + their original positions out */
 /* average ms per launch of a batch-sized projection product on device operands (extras: 1 = column statistics, 2 = row sums of squares) */
 int nvsm_debug_gemm_time(int b_layout, int M, int N, int K, int extras, int repeats, float* avg_ms);
