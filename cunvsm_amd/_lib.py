@@ -141,6 +141,19 @@ class NvsmNgramOptions(C.Structure):
     ]
 
 
+TSNE_MAX_ROWS = 32768
+TSNE_INIT_PCA, TSNE_INIT_GIVEN = 0, 1
+
+
+class NvsmTsneOptions(C.Structure):
+    _fields_ = [
+        ("space", C.c_int32), ("l2_normalize", C.c_int32), ("ids", C.c_void_p), ("num_rows", C.c_int64),
+        ("perplexity", C.c_float), ("early_exaggeration", C.c_float), ("learning_rate", C.c_float), ("min_grad_norm", C.c_float),
+        ("max_iter", C.c_int32), ("n_iter_without_progress", C.c_int32), ("init", C.c_int32), ("reserved0", C.c_int32),
+        ("init_embedding", C.c_void_p), ("reserved", C.c_int32 * 6),
+    ]
+
+
 class GemmEpilogueArgs(C.Structure):
     """nvsm_debug_gemm_epilogue_args (include/cunvsm_amd_test_hooks.h)."""
     _fields_ = [
@@ -263,6 +276,10 @@ class _Library:
                 "nvsm_debug_gather_mean_lazy": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
                 "nvsm_debug_lazy_refresh": (C.c_int, [P(LazyRefreshArgs)]),
                 "nvsm_debug_ngram_rows": (C.c_int, [vp, i64, C.c_int, vp, C.c_float, C.c_int, i64, i64, vp, i64, i64]),
+                "nvsm_debug_tsne_affinities": (C.c_int, [vp, i64, C.c_int, C.c_float, vp, vp]),
+                "nvsm_debug_tsne_gradient": (C.c_int, [vp, vp, i64, C.c_float, vp, P(C.c_double)]),
+                "nvsm_debug_tsne_pca": (C.c_int, [vp, i64, C.c_int, vp]),
+                "nvsm_debug_tsne_descent": (C.c_int, [vp, vp, i64, P(NvsmTsneOptions), C.c_int, P(C.c_double), P(C.c_int32)]),
             }.items():
                 fn = getattr(H, hook)
                 fn.restype = res
@@ -344,6 +361,8 @@ def lib():
         "nvsm_ngram_options_default": (None, [P(NvsmNgramOptions)]),
         "nvsm_ngram_rows": (i64, [i64, C.c_int32]),
         "nvsm_ngram_search": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNgramOptions), vp, vp, vp, vp]),
+        "nvsm_tsne_options_default": (None, [P(NvsmTsneOptions)]),
+        "nvsm_tsne": (C.c_int, [vp, P(NvsmTsneOptions), vp, P(C.c_double), P(C.c_int32)]),
         "nvsm_set_stream": (C.c_int, [vp, vp]), "nvsm_synchronize": (C.c_int, [vp]),
         "nvsm_describe": (C.c_int, [vp, C.c_int64, C.c_char_p, C.c_int64]),
         "nvsm_comm_unique_id": (C.c_int, [vp]), "nvsm_comm_init": (C.c_int, [vp, vp]),

@@ -449,6 +449,18 @@ int nvsm_ngram_search(nvsm_model* m, const nvsm_neighbor_queries* queries, const
     return guarded_on(m, [&] { m->impl.ngram_search(*queries, *opt, phrase_rows, terms, scores, counts); });
 }
 
+void nvsm_tsne_options_default(nvsm_tsne_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->space = NVSM_SPACE_ENTITIES;
+    o->perplexity = 30.f; o->early_exaggeration = 12.f; o->learning_rate = 0.f; o->min_grad_norm = 1e-7f;
+    o->max_iter = 1000; o->n_iter_without_progress = 300; o->init = NVSM_TSNE_INIT_PCA;
+}
+int nvsm_tsne(nvsm_model* m, const nvsm_tsne_options* opt, float* embedding, double* kl_divergence, int32_t* n_iter) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(opt); NVSM_REQUIRE(embedding); NVSM_REQUIRE(kl_divergence); NVSM_REQUIRE(n_iter);
+    return guarded_on(m, [&] { m->impl.tsne(*opt, embedding, kl_divergence, n_iter); });
+}
+
 int nvsm_set_stream(nvsm_model* m, void* s) { NVSM_REQUIRE(m); return guarded_on(m, [&] { m->impl.set_stream(static_cast<hipStream_t>(s)); }); }
 int nvsm_describe(nvsm_model* m, int64_t batch, char* buf, int64_t buf_bytes) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(buf);

@@ -565,6 +565,31 @@ int64_t ngram_row_count(int64_t m, int max_cardinality);
 // stack throw before anything is launched.
 void launch_ngram_rows(const float* G, int m, int de, const float* bias, float c, int act, int64_t p0, int S, float* out, hipStream_t s);
 
+// ---- exact t-SNE of table rows (tsne.hip; include/cunvsm_amd.h nvsm_tsne; py/visualize.py) ----
+// The n × n buffer P (squared distances, then conditional probabilities, then joint probabilities) has rows of tsne_ld(n) floats,
+// n rounded up to 4; every pointer below is a device pointer, and every sum has a fixed order (no atomics).
+int64_t tsne_ld(int64_t n);
+// the column slabs of tsne_forces_kernel at n rows: width wc (a multiple of 256, at most 4096) and their number; host arithmetic
+void tsne_force_layout(int n, int* wc, int* slabs);
+void launch_tsne_normalize(float* X, int n, int d, hipStream_t s);      // rows of X [n][d] divided by their norms, zero rows kept
+// X [n][d] -> P: distances (fp64 sums rounded to fp32), then sklearn's perplexity search per row (fp64): the conditional
+// probabilities, zero diagonal; rowsum [n] = their row sums (fp64)
+void launch_tsne_conditionals(const float* X, int n, int d, float perplexity, float* P, double* rowsum, hipStream_t s);
+// P in place: max((C + Cᵀ) / max(2ΣC, eps), eps) with a zero diagonal; total [1]: fp64 scratch
+void launch_tsne_joint(float* P, int n, const double* rowsum, double* total, hipStream_t s);
+// part [n][slabs][5] = (Σ P q dx, Σ P q dy, Σ q² dx, Σ q² dy, Σ q) per row and column slab, q = 1 / (1 + |y_i − y_j|²); z [1] = Σ q
+void launch_tsne_forces(const float* P, const float* Y, int n, float* part, double* z, hipStream_t s);
+// g = 4·(exaggeration·attractive − repulsive / Z) and sklearn's _gradient_descent step on Y, upd, gains [n][2]; gs [n][2] = the
+// gain-scaled gradient, graw [n][2] (may be null) = g
+void launch_tsne_update(const float* part, int n, const double* z, float exaggeration, float momentum, float learning_rate, float* Y,
+                        float* upd, float* gains, float* gs, float* graw, hipStream_t s);
+// klrow [n] = the rows of KL(e·P ‖ Q) at Y, fp64 throughout, with a Z of their own in z64 [1] (scratch); out [2] = (Σ klrow, |gs|)
+void launch_tsne_kl_rows(const float* P, const float* Y, int n, double* z64, float exaggeration, double* klrow, hipStream_t s);
+void launch_tsne_check(const double* klrow, const float* gs, int n, double* out, hipStream_t s);
+// PCA start: mean [d], cov [d][d] = XcᵀXc (fp64); Y0 [n][2] = fp32(Xc·Vᵀ) for V [2][d] (fp64)
+void launch_tsne_covariance(const float* X, int n, int d, double* mean, double* cov, hipStream_t s);
+void launch_tsne_project(const float* X, int n, int d, const double* mean, const double* V, float* Y0, hipStream_t s);
+
 // ---- retrieval metrics of a round's ranking (eval.hip; include/cunvsm_amd.h nvsm_evaluate) ----
 // One wave per query of the round. ids [Q][k] / counts [Q]: what launch_rank_write left. Judged documents of ALL queries of the
 // call: jids ascending per query (no -1 entries), jgrades next to them, joff [queries of the call + 1]; consts

@@ -126,6 +126,24 @@ struct RankLayout { int64_t qn, S, ld, n_keys, npad; };
 RankLayout rank_layout(int64_t rows, int64_t k, int64_t queries, int64_t score_floats, int64_t slab_cap = 0);      // slab_cap 0: none
 RankLayout rank_layout_candidates(const int64_t* offsets, int64_t queries);
 
+// ---- exact t-SNE (ranking.cpp; kernels: tsne.hip): the host side the product call and the test hooks share ----
+// device scratch of a run over n rows; P [n][tsne_ld(n)] is filled by launch_tsne_conditionals + launch_tsne_joint
+struct TsneScratch {
+    DevBuf<float> x, p, y, upd, gains, gs, part;
+    DevBuf<double> rows, pca;      // rows: rowsum [n] | klrow [n] | total, z, kl, |g|, the check's own z; pca: mean [d] | cov [d][d] | V [2][d]
+    DevBuf<int64_t> ids;
+    void grow_for(int64_t n, int d);
+};
+// Y0 [n][2] (device) = the rows X [n][d] (device) on their two leading principal axes, scaled to a standard deviation of 1e-4 in
+// column 0: covariance on the device in fp64, cyclic Jacobi on the host, signs by each axis' entry of largest magnitude (the lower
+// index on a tie). Throws NVSM_ERR_INVALID_ARGUMENT when that standard deviation is 0. Synchronous on s.
+void tsne_pca_start(const float* X, int n, int d, TsneScratch& w, float* Y0, hipStream_t s);
+// sklearn's two-phase _gradient_descent on Y [n][2] (device) for P in w.p: `exploration` iterations (momentum 0.5, P times
+// early_exaggeration, n_iter_without_progress 250), then up to max_iter (momentum 0.8). learning_rate resolved by the caller.
+// kl / n_iter: the error of the last evaluation and the index of the last iteration run. Synchronous on s.
+void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl, int32_t* n_iter,
+                  Profiler* prof, hipStream_t s);
+
 class Model {
  public:
     explicit Model(const nvsm_config& cfg);
@@ -197,6 +215,8 @@ class Model {
     void ngram_search(const nvsm_neighbor_queries& q, const nvsm_ngram_options& opt, int64_t* phrase_rows, int64_t* terms, float* scores,
                       int64_t* counts);
     void similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out);
+    // exact t-SNE of rows of E or W (py/visualize.py; nvsm_tsne): embedding [num_rows][2] host
+    void tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_divergence, int32_t* n_iter);
 
     void set_stream(hipStream_t s);
     int64_t step_deferred(const nvsm_batch& batch, const int64_t* entity_ids, float lr);
@@ -499,6 +519,7 @@ class Model {
         DevBuf<double> sweep_table;                //                    ... and its metric table [alphas][queries][width]
     };
     RankScratch rank_;
+    TsneScratch tsne_;      // allocated by the first nvsm_tsne, grown by a later call with more rows
     int64_t score_floats() const { return static_cast<int64_t>(tune_.rank_slab_mb) << 18; }      // the score slab: 256 MB unless NVSM_RANK_SLAB_MB says otherwise
     // one round behind its layout (ranking.cpp): scratch, the slabs through the caller's fill step, sort + the caller's write, results
     void round_grow(const RankLayout& l, int k);

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "model.h"
@@ -14,10 +15,11 @@ namespace cunvsm {
 
 namespace {
 
-struct RankProf {      // a profiler group around a few launches of the main stream
-    Profiler& p; hipStream_t s;
-    RankProf(Profiler& p_, const char* name, hipStream_t s_) : p(p_), s(s_) { p.begin(name, s); }
-    ~RankProf() { p.end(s); }
+struct RankProf {      // a profiler group around a few launches of the main stream; no profiler (the test hooks have none): nothing
+    Profiler* p; hipStream_t s;
+    RankProf(Profiler& p_, const char* name, hipStream_t s_) : p(&p_), s(s_) { p->begin(name, s); }
+    RankProf(Profiler* p_, const char* name, hipStream_t s_) : p(p_), s(s_) { if (p) p->begin(name, s); }
+    ~RankProf() { if (p) p->end(s); }
 };
 
 template <typename T>
@@ -1212,6 +1214,209 @@ void Model::similarity(int space, const int64_t* a, const int64_t* b, int64_t n,
         NVSM_HIP_CHECK(hipMemcpyAsync(out + i0, r.pair_out.p, static_cast<size_t>(cn) * sizeof(float), hipMemcpyDeviceToHost, stream_));
         NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
     }
+    raise_device_error();
+}
+
+// ---- exact t-SNE of table rows (include/cunvsm_amd.h nvsm_tsne; kernels: tsne.hip) --------------------------------
+// py/visualize.py's sklearn.manifold.TSNE with the exact gradient. The host keeps sklearn's control flow — two phases of
+// _gradient_descent, the error every 50th iteration, the stopping rules — and reads two doubles back at every check; everything
+// else stays on the device. tsne_pca_start and tsne_descent are free functions so that the test hooks run the same code.
+namespace {
+// eigenvectors of the symmetric A [d][d] (destroyed; its diagonal ends as the eigenvalues) as the COLUMNS of V: cyclic Jacobi
+void jacobi_eigen(std::vector<double>& A, int d, std::vector<double>& V) {
+    V.assign(static_cast<size_t>(d) * d, 0.0);
+    for (int i = 0; i < d; ++i) V[static_cast<size_t>(i) * d + i] = 1.0;
+    double fro = 0.0;
+    for (double a : A) fro += a * a;
+    for (int sweep = 0; sweep < 100; ++sweep) {
+        double off = 0.0;
+        for (int p = 0; p < d; ++p)
+            for (int q = p + 1; q < d; ++q) off += A[static_cast<size_t>(p) * d + q] * A[static_cast<size_t>(p) * d + q];
+        if (off <= 1e-32 * fro) return;
+        for (int p = 0; p < d - 1; ++p)
+            for (int q = p + 1; q < d; ++q) {
+                const double apq = A[static_cast<size_t>(p) * d + q];
+                if (apq == 0.0) continue;
+                const double theta = (A[static_cast<size_t>(q) * d + q] - A[static_cast<size_t>(p) * d + p]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+                for (int k = 0; k < d; ++k) {
+                    double* r = &A[static_cast<size_t>(k) * d];
+                    const double akp = r[p], akq = r[q];
+                    r[p] = c * akp - sn * akq;
+                    r[q] = sn * akp + c * akq;
+                }
+                double* rp = &A[static_cast<size_t>(p) * d];
+                double* rq = &A[static_cast<size_t>(q) * d];
+                for (int k = 0; k < d; ++k) {
+                    const double apk = rp[k], aqk = rq[k];
+                    rp[k] = c * apk - sn * aqk;
+                    rq[k] = sn * apk + c * aqk;
+                }
+                for (int k = 0; k < d; ++k) {
+                    double* r = &V[static_cast<size_t>(k) * d];
+                    const double vkp = r[p], vkq = r[q];
+                    r[p] = c * vkp - sn * vkq;
+                    r[q] = sn * vkp + c * vkq;
+                }
+            }
+    }
+    // cyclic Jacobi converges quadratically (a dozen sweeps at d = 1024); a matrix that is still not diagonal holds non-finite entries
+    throw Error(NVSM_ERR_INVALID_ARGUMENT, "PCA initialisation: the covariance of the rows has no eigen-decomposition (non-finite values?)");
+}
+}  // namespace
+
+void TsneScratch::grow_for(int64_t n, int d) {
+    int wc, slabs;
+    tsne_force_layout(static_cast<int>(n), &wc, &slabs);
+    grow(x, static_cast<size_t>(n) * d);
+    grow(p, static_cast<size_t>(n) * tsne_ld(n));
+    grow(y, static_cast<size_t>(2 * n)); grow(upd, static_cast<size_t>(2 * n)); grow(gains, static_cast<size_t>(2 * n)); grow(gs, static_cast<size_t>(2 * n));
+    grow(part, static_cast<size_t>(n) * slabs * 5);
+    grow(rows, static_cast<size_t>(2 * n + 5));
+    grow(pca, static_cast<size_t>(d) * (d + 3));
+    grow(ids, static_cast<size_t>(n));
+}
+
+void tsne_pca_start(const float* X, int n, int d, TsneScratch& w, float* Y0, hipStream_t s) {
+    double* mean = w.pca.p;
+    double* cov = mean + d;
+    double* V = cov + static_cast<size_t>(d) * d;
+    launch_tsne_covariance(X, n, d, mean, cov, s);
+    std::vector<double> A(static_cast<size_t>(d) * d), vecs;
+    NVSM_HIP_CHECK(hipMemcpyAsync(A.data(), cov, A.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    NVSM_HIP_CHECK(hipStreamSynchronize(s));
+    jacobi_eigen(A, d, vecs);
+    // the two largest eigenvalues (the lower index on a tie); with d = 1 the second axis is zero
+    int first = 0, second = -1;
+    for (int i = 1; i < d; ++i) if (A[static_cast<size_t>(i) * d + i] > A[static_cast<size_t>(first) * d + first]) first = i;
+    for (int i = 0; i < d; ++i) {
+        if (i == first) continue;
+        if (second < 0 || A[static_cast<size_t>(i) * d + i] > A[static_cast<size_t>(second) * d + second]) second = i;
+    }
+    std::vector<double> axes(static_cast<size_t>(2) * d, 0.0);
+    const int pick[2] = {first, second};
+    for (int c = 0; c < 2; ++c) {
+        if (pick[c] < 0) continue;
+        int big = 0;
+        for (int t = 0; t < d; ++t) {
+            axes[static_cast<size_t>(c) * d + t] = vecs[static_cast<size_t>(t) * d + pick[c]];
+            if (std::fabs(axes[static_cast<size_t>(c) * d + t]) > std::fabs(axes[static_cast<size_t>(c) * d + big])) big = t;
+        }
+        if (axes[static_cast<size_t>(c) * d + big] < 0.0)
+            for (int t = 0; t < d; ++t) axes[static_cast<size_t>(c) * d + t] = -axes[static_cast<size_t>(c) * d + t];
+    }
+    NVSM_HIP_CHECK(hipMemcpyAsync(V, axes.data(), axes.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_tsne_project(X, n, d, mean, V, Y0, s);
+    std::vector<float> y(static_cast<size_t>(2) * n);
+    NVSM_HIP_CHECK(hipMemcpyAsync(y.data(), Y0, y.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    NVSM_HIP_CHECK(hipStreamSynchronize(s));
+    // np.std of column 0 (population), then Y0 / std · 1e-4
+    double m = 0.0, var = 0.0;
+    for (int i = 0; i < n; ++i) m += static_cast<double>(y[static_cast<size_t>(2) * i]);
+    m /= n;
+    for (int i = 0; i < n; ++i) { const double c = static_cast<double>(y[static_cast<size_t>(2) * i]) - m; var += c * c; }
+    const double sd = std::sqrt(var / n);
+    if (!(sd > 0.0) || !std::isfinite(sd))
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "PCA initialisation: the rows have no spread along their first principal axis (all rows identical?)");
+    for (float& v : y) v = static_cast<float>(static_cast<double>(v) / sd * 1e-4);
+    NVSM_HIP_CHECK(hipMemcpyAsync(Y0, y.data(), y.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    NVSM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl, int32_t* n_iter,
+                  Profiler* prof, hipStream_t s) {
+    double* klrow = w.rows.p + n;
+    double* z = w.rows.p + 2 * static_cast<size_t>(n) + 1;
+    double* out = z + 1;
+    const std::vector<float> ones(static_cast<size_t>(2) * n, 1.f);
+    double error = std::numeric_limits<double>::max();
+    // one _gradient_descent: iterations it0 .. max_iter − 1; returns the index of the last one that ran (it0 − 1: none did)
+    auto phase = [&](int it0, int max_iter, float momentum, float exaggeration, int without_progress) {
+        NVSM_HIP_CHECK(hipMemsetAsync(w.upd.p, 0, ones.size() * sizeof(float), s));
+        NVSM_HIP_CHECK(hipMemcpyAsync(w.gains.p, ones.data(), ones.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        double best_error = std::numeric_limits<double>::max();
+        int best_iter = it0, last = it0 - 1;
+        for (int i = it0; i < max_iter; ++i) {
+            last = i;
+            const bool check = (i + 1) % 50 == 0, compute = check || i == max_iter - 1;
+            { RankProf scope(prof, "tsne_forces", s); launch_tsne_forces(w.p.p, w.y.p, n, w.part.p, z, s); }
+            if (compute) { RankProf scope(prof, "tsne_kl", s); launch_tsne_kl_rows(w.p.p, w.y.p, n, out + 2, exaggeration, klrow, s); }
+            {
+                RankProf scope(prof, "tsne_update", s);
+                launch_tsne_update(w.part.p, n, z, exaggeration, momentum, learning_rate, w.y.p, w.upd.p, w.gains.p, w.gs.p, nullptr, s);
+            }
+            if (!compute) continue;
+            double host[2];
+            { RankProf scope(prof, "tsne_kl", s); launch_tsne_check(klrow, w.gs.p, n, out, s); }
+            NVSM_HIP_CHECK(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, s));
+            NVSM_HIP_CHECK(hipStreamSynchronize(s));
+            error = host[0];
+            if (!check) continue;
+            if (error < best_error) { best_error = error; best_iter = i; }
+            else if (i - best_iter > without_progress) break;
+            if (host[1] <= static_cast<double>(opt.min_grad_norm)) break;
+        }
+        NVSM_HIP_CHECK(hipStreamSynchronize(s));      // (`ones` and `host` are this frame's)
+        return last;
+    };
+    int it = phase(0, exploration, 0.5f, opt.early_exaggeration, 250);
+    if (it + 1 < opt.max_iter) it = phase(it + 1, opt.max_iter, 0.8f, 1.f, opt.n_iter_without_progress);
+    *kl = error;
+    *n_iter = it;
+}
+
+void Model::tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_divergence, int32_t* n_iter) {
+    if (opt.space != NVSM_SPACE_ENTITIES && opt.space != NVSM_SPACE_WORDS)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space: t-SNE takes the rows of NVSM_SPACE_ENTITIES or NVSM_SPACE_WORDS");
+    const RowSpace sp = row_space(opt.space);
+    const int64_t n = (!opt.ids && opt.num_rows == 0) ? sp.count : opt.num_rows;
+    if (n < 2) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_rows must be at least 2");
+    if (!opt.ids && n > sp.count) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_rows exceeds the rows of the space");
+    if (opt.ids)
+        for (int64_t i = 0; i < n; ++i)
+            if (opt.ids[i] < 0 || opt.ids[i] >= sp.count) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a row id is outside the space");
+    if (n > NVSM_TSNE_MAX_ROWS) throw Error(NVSM_ERR_UNSUPPORTED, "t-SNE supports at most NVSM_TSNE_MAX_ROWS (32768) rows");
+    if (!std::isfinite(opt.perplexity) || !(opt.perplexity > 0.f) || !(opt.perplexity < static_cast<float>(n)))
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "perplexity must be finite, positive and below num_rows");
+    if (!std::isfinite(opt.early_exaggeration) || !(opt.early_exaggeration > 0.f))
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "early_exaggeration must be finite and positive");
+    if (!std::isfinite(opt.learning_rate)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "learning_rate is not finite");
+    if (!std::isfinite(opt.min_grad_norm)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "min_grad_norm is not finite");
+    if (opt.init == NVSM_TSNE_INIT_GIVEN && opt.init_embedding)
+        for (int64_t i = 0; i < 2 * n; ++i)
+            if (!std::isfinite(opt.init_embedding[i])) throw Error(NVSM_ERR_INVALID_ARGUMENT, "init_embedding holds a value that is not finite");
+    if (opt.max_iter < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "max_iter must be at least 1");
+    if (opt.n_iter_without_progress < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "n_iter_without_progress is negative");
+    if (opt.init != NVSM_TSNE_INIT_PCA && opt.init != NVSM_TSNE_INIT_GIVEN) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown init");
+    if (opt.init == NVSM_TSNE_INIT_GIVEN && !opt.init_embedding)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "NVSM_TSNE_INIT_GIVEN needs init_embedding");
+    const int d = sp.dim, rows = static_cast<int>(n);
+    rank_join();
+    TsneScratch& w = tsne_;
+    w.grow_for(n, d);
+    if (opt.ids) NVSM_HIP_CHECK(hipMemcpy(w.ids.p, opt.ids, static_cast<size_t>(n) * sizeof(int64_t), hipMemcpyHostToDevice));
+    {
+        RankProf scope(prof, "tsne_rows", stream_);
+        launch_rank_gather_rows(sp.rows, d, opt.ids ? w.ids.p : nullptr, 0, n, w.x.p, lazy_view(*sp.table), stream_);
+        if (opt.l2_normalize) launch_tsne_normalize(w.x.p, rows, d, stream_);
+    }
+    {
+        RankProf scope(prof, "tsne_affinities", stream_);
+        launch_tsne_conditionals(w.x.p, rows, d, opt.perplexity, w.p.p, w.rows.p, stream_);
+        launch_tsne_joint(w.p.p, rows, w.rows.p, w.rows.p + 2 * n, stream_);
+    }
+    if (opt.init == NVSM_TSNE_INIT_GIVEN) {
+        NVSM_HIP_CHECK(hipMemcpyAsync(w.y.p, opt.init_embedding, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyHostToDevice, stream_));
+    } else {
+        RankProf scope(prof, "tsne_pca", stream_);
+        tsne_pca_start(w.x.p, rows, d, w, w.y.p, stream_);
+    }
+    // sklearn's learning_rate='auto'
+    const float lr = opt.learning_rate > 0.f ? opt.learning_rate : std::max(static_cast<float>(n) / opt.early_exaggeration / 4.f, 50.f);
+    tsne_descent(w, rows, opt, lr, std::min(250, opt.max_iter), kl_divergence, n_iter, &prof, stream_);
+    NVSM_HIP_CHECK(hipMemcpyAsync(embedding, w.y.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
     raise_device_error();
 }
 

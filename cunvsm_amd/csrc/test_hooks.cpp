@@ -752,6 +752,107 @@ int nvsm_debug_ngram_rows(const float* G, int64_t m, int de, const float* bias, 
     });
 }
 
+// ---- nvsm_tsne's stages on caller-supplied inputs (cunvsm_amd_test_hooks.h): the product's launchers and its host functions
+// (kernels.h launch_tsne_*, model.h tsne_pca_start / tsne_descent) on a scratch of the hook's own
+namespace {
+void tsne_hook_sizes(int64_t n, int64_t d) {
+    if (n < 2 || n > NVSM_TSNE_MAX_ROWS || d < 1 || d > 4096) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne hook: bad sizes");
+}
+// host [rows][n] <-> device rows of tsne_ld(n) floats
+void tsne_hook_up(float* dev, const float* host, int64_t n, int64_t rows) {
+    NVSM_HIP_CHECK(hipMemcpy2D(dev, cunvsm::tsne_ld(n) * sizeof(float), host, n * sizeof(float), n * sizeof(float), rows, hipMemcpyHostToDevice));
+}
+void tsne_hook_down(float* host, const float* dev, int64_t n, int64_t rows) {
+    NVSM_HIP_CHECK(hipMemcpy2D(host, n * sizeof(float), dev, cunvsm::tsne_ld(n) * sizeof(float), n * sizeof(float), rows, hipMemcpyDeviceToHost));
+}
+}  // namespace
+
+int nvsm_debug_tsne_affinities(const float* X, int64_t n, int d, float perplexity, float* P_out, float* cond_out) {
+    NVSM_REQUIRE(X); NVSM_REQUIRE(P_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_hook_sizes(n, d);
+        if (!(perplexity > 0.f) || !(perplexity < static_cast<float>(n))) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne hook: bad perplexity");
+        const int64_t ld = tsne_ld(n);
+        DevBuf<float> x, p, c;
+        DevBuf<double> w;
+        x.alloc(static_cast<size_t>(n) * d); p.alloc(static_cast<size_t>(n + 2) * ld); w.alloc(static_cast<size_t>(n) + 1);
+        if (cond_out) c.alloc(static_cast<size_t>(n) * ld);
+        NVSM_HIP_CHECK(hipMemcpy(x.p, X, x.n * sizeof(float), hipMemcpyHostToDevice));
+        tsne_hook_up(p.p, P_out, n, n + 2);      // the caller's guard rows 0 and n + 1 go up and must come back as they are
+        launch_tsne_conditionals(x.p, static_cast<int>(n), d, perplexity, p.p + ld, w.p, nullptr);
+        if (cond_out)      // (what the symmetrised P no longer shows)
+            NVSM_HIP_CHECK(hipMemcpyAsync(c.p, p.p + ld, static_cast<size_t>(n) * ld * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+        launch_tsne_joint(p.p + ld, static_cast<int>(n), w.p, w.p + n, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        tsne_hook_down(P_out, p.p, n, n + 2);
+        if (cond_out) tsne_hook_down(cond_out, c.p, n, n);
+    });
+}
+
+int nvsm_debug_tsne_gradient(const float* P, const float* Y, int64_t n, float exaggeration, float* grad_out, double* kl_out) {
+    NVSM_REQUIRE(P); NVSM_REQUIRE(Y); NVSM_REQUIRE(grad_out); NVSM_REQUIRE(kl_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_hook_sizes(n, 1);
+        TsneScratch w;
+        w.grow_for(n, 1);
+        DevBuf<float> graw;
+        graw.alloc(static_cast<size_t>(2 * n));
+        const int rows = static_cast<int>(n);
+        double* klrow = w.rows.p + n;
+        double* z = w.rows.p + 2 * n + 1;
+        tsne_hook_up(w.p.p, P, n, n);
+        NVSM_HIP_CHECK(hipMemcpy(w.y.p, Y, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemset(w.upd.p, 0, static_cast<size_t>(2 * n) * sizeof(float)));
+        NVSM_HIP_CHECK(hipMemset(w.gains.p, 0, static_cast<size_t>(2 * n) * sizeof(float)));
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        launch_tsne_forces(w.p.p, w.y.p, rows, w.part.p, z, nullptr);
+        launch_tsne_kl_rows(w.p.p, w.y.p, rows, z + 3, exaggeration, klrow, nullptr);
+        // a step of learning rate 0 on zero gains and updates: Y stays, graw is the gradient
+        launch_tsne_update(w.part.p, rows, z, exaggeration, 0.f, 0.f, w.y.p, w.upd.p, w.gains.p, w.gs.p, graw.p, nullptr);
+        launch_tsne_check(klrow, w.gs.p, rows, z + 1, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(grad_out, graw.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(kl_out, z + 1, sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int nvsm_debug_tsne_pca(const float* X, int64_t n, int d, float* Y0_out) {
+    NVSM_REQUIRE(X); NVSM_REQUIRE(Y0_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_hook_sizes(n, d);
+        TsneScratch w;
+        w.grow_for(n, d);
+        NVSM_HIP_CHECK(hipMemcpy(w.x.p, X, static_cast<size_t>(n) * d * sizeof(float), hipMemcpyHostToDevice));
+        tsne_pca_start(w.x.p, static_cast<int>(n), d, w, w.y.p, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipMemcpy(Y0_out, w.y.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int nvsm_debug_tsne_descent(const float* P, float* Y, int64_t n, const nvsm_tsne_options* opt, int exploration, double* kl_out,
+                            int32_t* n_iter_out) {
+    NVSM_REQUIRE(P); NVSM_REQUIRE(Y); NVSM_REQUIRE(opt); NVSM_REQUIRE(kl_out); NVSM_REQUIRE(n_iter_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_hook_sizes(n, 1);
+        if (opt->max_iter < 1 || opt->max_iter > 100000 || exploration < 1 || exploration > opt->max_iter || !(opt->learning_rate > 0.f) ||
+            !(opt->early_exaggeration > 0.f) || opt->n_iter_without_progress < 0)
+            throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne hook: bad options");
+        TsneScratch w;
+        w.grow_for(n, 1);
+        tsne_hook_up(w.p.p, P, n, n);
+        NVSM_HIP_CHECK(hipMemcpy(w.y.p, Y, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyHostToDevice));
+        tsne_descent(w, static_cast<int>(n), *opt, opt->learning_rate, exploration, kl_out, n_iter_out, nullptr, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipMemcpy(Y, w.y.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
 // One launch_lazy_refresh on caller-supplied inputs (cunvsm_amd_test_hooks.h): the arguments of Model::lazy_refresh /
 // Model::lazy_scalar_snapshot, the list and its count on the device as Csr::touched / num_touched are.
 int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* a) {

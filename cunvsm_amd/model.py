@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmNgramOptions, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmNgramOptions, NvsmTsneOptions, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -714,6 +714,73 @@ def ngram_arguments(cfg, entity_ids=None, word_ids=None, vectors=None, vocabular
     return q, opt, voc, data
 
 
+# -- exact t-SNE of document or word rows (py/visualize.py's sklearn.manifold.TSNE; nvsm_tsne) ----------------------------------
+def tsne_arguments(cfg, space="entities", ids=None, limit=None, l2_normalize=False, perplexity=30.0, early_exaggeration=12.0,
+                   learning_rate="auto", max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=0):
+    """(nvsm_tsne_options, number of rows, arrays to keep alive) from keywords; raises ValueError for what the ABI would refuse, in
+    its order (no device needed). ids: row ids in any order (visualize.py --filter_unclassified); limit: the first rows (--limit);
+    neither: every row. init: "pca", "random" (sklearn's 1e-4 · RandomState(random_state).standard_normal((n, 2))) or an [n][2] array."""
+    space, rows, _ = space_shape(cfg, space)
+    if space == _lib.SPACE_PROJECTED_WORDS:
+        raise ValueError("unknown space for t-SNE: \"entities\" or \"words\" (projected words are not served)")
+    if ids is not None and limit is not None:
+        raise ValueError("at most one of ids and limit may be given")
+    id_array = None
+    if ids is not None:
+        if np.asarray(ids).ndim > 1:
+            raise ValueError("ids must be a flat list of row ids")
+        id_array = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).ravel())
+        n = int(id_array.size)
+    else:
+        n = rows if limit is None else int(limit)
+    if n < 2:
+        raise ValueError("num_rows = %d: t-SNE needs at least 2 rows" % n)
+    if id_array is None and n > rows:
+        raise ValueError("limit = %d exceeds the rows of the space = %d" % (n, rows))
+    if id_array is not None and (id_array.min() < 0 or id_array.max() >= rows):
+        raise ValueError("a row id is outside [0, %d)" % rows)
+    if n > _lib.TSNE_MAX_ROWS:
+        raise ValueError("num_rows = %d above the limit of %d rows" % (n, _lib.TSNE_MAX_ROWS))
+    perplexity = float(np.float32(perplexity))
+    if not (np.isfinite(perplexity) and 0.0 < perplexity < n):
+        raise ValueError("perplexity = %r must be finite, positive and below num_rows = %d" % (perplexity, n))
+    early_exaggeration = float(np.float32(early_exaggeration))
+    if not (np.isfinite(early_exaggeration) and early_exaggeration > 0.0):
+        raise ValueError("early_exaggeration = %r must be finite and positive" % early_exaggeration)
+    if isinstance(learning_rate, str):
+        if learning_rate != "auto":
+            raise ValueError("learning_rate must be a number or \"auto\"")
+        learning_rate = 0.0
+    elif not float(learning_rate) > 0.0 or not np.isfinite(float(learning_rate)):
+        raise ValueError("learning_rate = %r must be finite and positive (or \"auto\")" % (learning_rate,))
+    if not np.isfinite(float(min_grad_norm)):
+        raise ValueError("min_grad_norm is not finite")
+    given = None
+    if isinstance(init, str):
+        if init not in ("pca", "random"):
+            raise ValueError("unknown init %r (\"pca\", \"random\" or an [n][2] array)" % init)
+        if init == "random":
+            given = (1e-4 * np.random.RandomState(random_state).standard_normal(size=(n, 2))).astype(np.float32)
+    else:
+        given = np.ascontiguousarray(init, dtype=np.float32)
+        if given.shape != (n, 2):
+            raise ValueError("init has shape %s, expected (%d, 2)" % (given.shape, n))
+        if not np.isfinite(given).all():
+            raise ValueError("init holds a value that is not finite")
+    if int(max_iter) < 1:
+        raise ValueError("max_iter = %d must be at least 1" % int(max_iter))
+    if int(n_iter_without_progress) < 0:
+        raise ValueError("n_iter_without_progress is negative")
+    opt = NvsmTsneOptions()
+    opt.space, opt.l2_normalize = space, int(bool(l2_normalize))
+    opt.ids, opt.num_rows = (None if id_array is None else id_array.ctypes.data), n
+    opt.perplexity, opt.early_exaggeration, opt.learning_rate, opt.min_grad_norm = perplexity, early_exaggeration, float(learning_rate), float(min_grad_norm)
+    opt.max_iter, opt.n_iter_without_progress = int(max_iter), int(n_iter_without_progress)
+    opt.init = _lib.TSNE_INIT_PCA if given is None else _lib.TSNE_INIT_GIVEN
+    opt.init_embedding = None if given is None else given.ctypes.data
+    return opt, n, (id_array, given)
+
+
 class Model:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -1194,6 +1261,19 @@ class Model:
                                       counts.ctypes.data))
         del keep, voc
         return rows, terms, scores, counts
+
+    def tsne(self, space="entities", ids=None, limit=None, l2_normalize=False, perplexity=30.0, early_exaggeration=12.0,
+             learning_rate="auto", max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=0):
+        """py/visualize.py's sklearn.manifold.TSNE(n_components=2, init='pca', random_state=0) with the exact gradient, on the device
+        (nvsm_tsne): the rows `ids` of `space` ("entities" | "words"), its first `limit` rows, or all of them. Returns
+        (embedding [n, 2] float32, kl_divergence, n_iter) as sklearn's embedding_, kl_divergence_ and n_iter_."""
+        opt, n, keep = tsne_arguments(self.cfg, space, ids, limit, l2_normalize, perplexity, early_exaggeration, learning_rate, max_iter,
+                                      n_iter_without_progress, min_grad_norm, init, random_state)
+        embedding = np.empty((n, 2), dtype=np.float32)
+        kl, it = C.c_double(0.0), C.c_int32(0)
+        check(lib().nvsm_tsne(self._h, C.byref(opt), embedding.ctypes.data, C.byref(kl), C.byref(it)))
+        del keep
+        return embedding, kl.value, it.value
 
     def related_documents(self, entity_ids, top_k=10, exclude_self=False):
         """Documents near documents (query_using_projected_query, base.py:362-430, with document rows as the queries)."""

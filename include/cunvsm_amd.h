@@ -753,6 +753,64 @@ int64_t nvsm_ngram_rows(int64_t vocabulary_size, int32_t max_cardinality);
 int nvsm_ngram_search(nvsm_model* m, const nvsm_neighbor_queries* queries, const nvsm_ngram_options* opt,
                       int64_t* phrase_rows, int64_t* terms, float* scores, int64_t* counts);
 
+/*
+ * Exact t-SNE of document or word rows — what py/visualize.py asks sklearn.manifold.TSNE(n_components=2, init='pca',
+ * random_state=0) for, with the EXACT gradient (sklearn's method='exact'; its default is the Barnes-Hut approximation) on the
+ * device. Semantics, pinned by scikit-learn 1.7:
+ *   rows         ids: num_rows host row ids of `space`, any order (--filter_unclassified passes the sorted indices of the
+ *                classified documents), or NULL: rows 0 .. num_rows − 1 (--limit); num_rows 0 with ids NULL: every row.
+ *                Gathered through the lazy view; with l2_normalize every row is divided by its norm (a zero row stays zero).
+ *   affinities   squared Euclidean distances (fp64 sums rounded to fp32, as sklearn hands them on), sklearn's
+ *                _binary_search_perplexity per row in fp64 (at most 100 steps, tolerance 1e-5), then
+ *                P = max((C + Cᵀ) / max(ΣC + ΣCᵀ, eps), eps), eps = 2.220446049250313e-16, zero diagonal, stored as fp32.
+ *   start        NVSM_TSNE_INIT_PCA: the centred rows on their two leading principal axes, each axis' sign chosen so that its
+ *                entry of largest magnitude is positive (svd_flip on V; the lower index on a tie), scaled to a standard
+ *                deviation of 1e-4 in the first column. The axes come from an fp64 covariance and a Jacobi eigensolver, NOT
+ *                from sklearn's randomised SVD: the start agrees with sklearn's to rounding, not bit for bit.
+ *                NVSM_TSNE_INIT_GIVEN: init_embedding as it is (sklearn's 'random' is 1e-4 · standard normal draws).
+ *   descent      sklearn's _gradient_descent twice: min(250, max_iter) iterations with momentum 0.5 and P times
+ *                early_exaggeration (n_iter_without_progress 250), then up to max_iter with momentum 0.8; gains, update and
+ *                the best error start afresh in the second phase. The error is evaluated every 50th iteration of a phase and
+ *                on its last; a phase ends when i − best_iter > n_iter_without_progress or the norm of the gain-scaled gradient
+ *                is <= min_grad_norm. Y is never re-centred.
+ *   result       kl_divergence: the error of the last evaluation (sklearn's kl_divergence_); n_iter: the index of the last
+ *                iteration that ran (sklearn's n_iter_: max_iter − 1 for a run that max_iter ends). Where the second phase has
+ *                no iteration left (max_iter <= 250, which sklearn refuses) both are the first phase's.
+ * NVSM_SPACE_PROJECTED_WORDS is not served: a caller can project words with nvsm_neighbors' machinery but pass no vectors through
+ * this call yet.
+ * Refused with a status code before anything runs, in this order, the handle usable afterwards: a space other than entities or
+ * words; num_rows < 2 (after the default is resolved) or, with ids NULL, beyond the space's rows; an id out of range; num_rows >
+ * NVSM_TSNE_MAX_ROWS (NVSM_ERR_UNSUPPORTED); a perplexity that is not finite, not positive or not below num_rows; a non-finite or
+ * non-positive early_exaggeration; a non-finite learning_rate, min_grad_norm or init_embedding entry; max_iter < 1 or
+ * n_iter_without_progress < 0; an unknown init, or NVSM_TSNE_INIT_GIVEN without an array. Rows that are all identical have no
+ * principal axes: NVSM_TSNE_INIT_PCA then fails with NVSM_ERR_INVALID_ARGUMENT.
+ * The call is synchronous; it runs behind everything earlier steps have queued (the side streams' tails included), flushes
+ * nothing and moves no stamp of a lazily decayed table: training goes on from exactly the same state. A repeated call returns
+ * the same bits. Device scratch (n² floats for P) is allocated by the first call and grown by a later one with more rows.
+ */
+#define NVSM_TSNE_MAX_ROWS 32768          /* P is n*n floats: 4 GiB at the cap */
+enum { NVSM_TSNE_INIT_PCA = 0, NVSM_TSNE_INIT_GIVEN = 1 };
+typedef struct {
+    int32_t        space;                    /* NVSM_SPACE_ENTITIES (visualize.py) or NVSM_SPACE_WORDS */
+    int32_t        l2_normalize;             /* --l2_normalize */
+    const int64_t* ids;                      /* [num_rows] host row ids, any order, or NULL: rows 0 .. num_rows-1 (--limit) */
+    int64_t        num_rows;
+    float          perplexity;               /* 30 */
+    float          early_exaggeration;       /* 12 */
+    float          learning_rate;            /* <= 0: sklearn's 'auto', max(n / early_exaggeration / 4, 50) */
+    float          min_grad_norm;            /* 1e-7 */
+    int32_t        max_iter;                 /* 1000; >= 1 (exploration = min(250, max_iter)) */
+    int32_t        n_iter_without_progress;  /* 300 */
+    int32_t        init;                     /* NVSM_TSNE_INIT_* */
+    int32_t        reserved0;
+    const float*   init_embedding;           /* [num_rows][2] host, with NVSM_TSNE_INIT_GIVEN */
+    int32_t        reserved[6];
+} nvsm_tsne_options;
+/* entities, no normalisation, ids NULL, num_rows 0 = every row, the values above, PCA */
+void nvsm_tsne_options_default(nvsm_tsne_options* opt);
+/* embedding [num_rows][2] host; kl_divergence and n_iter as sklearn's kl_divergence_ and n_iter_ */
+int nvsm_tsne(nvsm_model* m, const nvsm_tsne_options* opt, float* embedding, double* kl_divergence, int32_t* n_iter);
+
 /* Streams. A handle issues its work on FOUR HIP streams of its own device: the main stream (highest priority: the step's
  * critical chain), two side streams (lowest priority: the batch → row-order sorts, and — in nvsm_step — the documents
  * update and the ∂T GEMM + projection update, which keep running after nvsm_step has returned and are joined by the next

@@ -416,6 +416,24 @@ class Model {
         return ngrams_of(q, opt);
     }
 
+    // exact t-SNE of document or word rows (py/visualize.py; nvsm_tsne): opt.ids / opt.num_rows choose the rows (nvsm_tsne_options_default:
+    // every document); embedding [rows][2], kl_divergence and n_iter as sklearn's kl_divergence_ and n_iter_
+    struct Tsne { std::vector<float> embedding; double kl_divergence; int32_t n_iter; };
+    Tsne tsne(const nvsm_tsne_options& opt) {
+        int64_t n = opt.num_rows;
+        if (!opt.ids && n == 0) n = opt.space == NVSM_SPACE_WORDS ? cfg_.num_words : cfg_.num_entities;
+        Tsne r;
+        r.embedding.resize(static_cast<size_t>(n > 0 ? 2 * n : 0) + 1);
+        r.kl_divergence = 0.0; r.n_iter = 0;
+        check(nvsm_tsne(h_, &opt, r.embedding.data(), &r.kl_divergence, &r.n_iter));
+        r.embedding.resize(static_cast<size_t>(2 * n));
+        return r;
+    }
+    Tsne tsne(const std::vector<int64_t>& row_ids, nvsm_tsne_options opt) {
+        opt.ids = row_ids.data(); opt.num_rows = static_cast<int64_t>(row_ids.size());
+        return tsne(opt);
+    }
+
     void synchronize() { check(nvsm_synchronize(h_)); }
     void comm_init(const char id[128]) { check(nvsm_comm_init(h_, id)); }
     nvsm_model* handle() { return h_; }

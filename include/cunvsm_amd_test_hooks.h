@@ -153,6 +153,23 @@ int nvsm_debug_neighbors_force_plain(int on);
  * Refused with NVSM_ERR_INVALID_ARGUMENT: m outside [1, 65 535], rows outside the stack or outside out. */
 int nvsm_debug_ngram_rows(const float* G, int64_t m, int de, const float* bias, float c, int act, int64_t p0, int64_t S, float* out,
                           int64_t out_rows, int64_t out_row0);
+/* nvsm_tsne's stages on caller-supplied host inputs, through the product's own launchers (csrc/tsne.hip) and host functions
+ * (csrc/ranking.cpp tsne_pca_start / tsne_descent). Sizes: 2 <= n <= NVSM_TSNE_MAX_ROWS, 1 <= d <= 4096, else
+ * NVSM_ERR_INVALID_ARGUMENT.
+ * affinities: X [n][d] -> the joint probabilities P in rows 1 .. n of P_out [n + 2][n]; P_out is uploaded whole before the launches
+ *   and comes back whole, so rows 0 and n + 1 must return as the caller filled them. cond_out [n][n] (may be NULL): the
+ *   conditional probabilities the perplexity search left, which the symmetrised P no longer shows.
+ * gradient: for P [n][n] and Y [n][2], grad_out [n][2] = 4·(e·attractive − repulsive / Z) as tsne_update_kernel forms it and
+ *   *kl_out = KL(e·P ‖ Q) as the convergence check evaluates it; Y is left as it is.
+ * pca: Y0_out [n][2] = nvsm_tsne's NVSM_TSNE_INIT_PCA start of the rows X [n][d]; identical rows are refused.
+ * descent: the two-phase loop on P [n][n] from Y [n][2] (overwritten with the result): opt's early_exaggeration, learning_rate
+ *   (> 0: no 'auto' here), min_grad_norm, max_iter and n_iter_without_progress, and `exploration` (1 .. max_iter) iterations in the
+ *   first phase, which the C ABI fixes at min(250, max_iter). */
+int nvsm_debug_tsne_affinities(const float* X, int64_t n, int d, float perplexity, float* P_out, float* cond_out);
+int nvsm_debug_tsne_gradient(const float* P, const float* Y, int64_t n, float exaggeration, float* grad_out, double* kl_out);
+int nvsm_debug_tsne_pca(const float* X, int64_t n, int d, float* Y0_out);
+int nvsm_debug_tsne_descent(const float* P, float* Y, int64_t n, const nvsm_tsne_options* opt, int exploration, double* kl_out,
+                            int32_t* n_iter_out);
 /* the stable (row, entry) radix sort alone: keys of `bits` significant bits in, sorted keys + their original positions out */
 /* average ms per launch of a batch-sized projection product on device operands (extras: 1 = column statistics, 2 = row sums of squares) */
 int nvsm_debug_gemm_time(int b_layout, int M, int N, int K, int extras, int repeats, float* avg_ms);
