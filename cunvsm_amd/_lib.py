@@ -121,6 +121,20 @@ class NvsmCvOptions(C.Structure):
     _fields_ = [("measure", C.c_int32), ("num_folds", C.c_int32), ("fold_of", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+IDF_ROBERTSON, IDF_OKAPI = 0, 1
+STAGE_TFIDF, STAGE_LEXICAL = 0, 1
+RERANK_MAX_DEPTH = 4096
+
+
+class NvsmTfidfOptions(C.Structure):
+    _fields_ = [("k1", C.c_float), ("b", C.c_float), ("idf", C.c_int32), ("top_k", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class NvsmRerankOptions(C.Structure):
+    _fields_ = [("first_stage", C.c_int32), ("depth", C.c_int32), ("tfidf", C.POINTER(NvsmTfidfOptions)),
+                ("lexical", C.POINTER(NvsmLexicalOptions)), ("reserved", C.c_int32 * 4)]
+
+
 class NvsmNeighborQueries(C.Structure):
     _fields_ = [("ids", C.c_void_p), ("vectors", C.c_void_p), ("num_queries", C.c_int64), ("source_space", C.c_int32), ("dim", C.c_int32)]
 
@@ -275,7 +289,8 @@ class _Library:
                 "nvsm_debug_gather_mean": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, vp]),
                 "nvsm_debug_gather_mean_lazy": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, vp, vp, C.c_int, vp, vp]),
                 "nvsm_debug_lazy_refresh": (C.c_int, [P(LazyRefreshArgs)]),
-                "nvsm_debug_ngram_rows": (C.c_int, [vp, i64, C.c_int, vp, C.c_float, C.c_int, i64, i64, vp, i64, i64]),
+                "nvsm_debug_lex_df": (C.c_int, [vp, i64, vp, i64, i64, i64, vp]),
+                "nvsm_debug_ngram_rows":(C.c_int, [vp, i64, C.c_int, vp, C.c_float, C.c_int, i64, i64, vp, i64, i64]),
                 "nvsm_debug_tsne_affinities": (C.c_int, [vp, i64, C.c_int, C.c_float, vp, vp]),
                 "nvsm_debug_tsne_gradient": (C.c_int, [vp, vp, i64, C.c_float, vp, P(C.c_double)]),
                 "nvsm_debug_tsne_pca": (C.c_int, [vp, i64, C.c_int, vp]),
@@ -355,6 +370,9 @@ def lib():
                                           P(NvsmSweepOptions), P(NvsmJudgments), vp]),
         "nvsm_rank_ensemble_cv": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmFeedbackOptions),
                                             P(NvsmSweepOptions), P(NvsmCvOptions), P(NvsmJudgments), vp, vp, vp, vp, vp, vp, vp]),
+        "nvsm_tfidf_options_default": (None, [P(NvsmTfidfOptions)]), "nvsm_rerank_options_default": (None, [P(NvsmRerankOptions)]),
+        "nvsm_tfidf_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmTfidfOptions), vp, vp, vp]),
+        "nvsm_rerank": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmRerankOptions), P(NvsmJudgments), vp, vp, vp, vp]),
         "nvsm_neighbor_options_default": (None, [P(NvsmNeighborOptions)]),
         "nvsm_neighbors": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNeighborOptions), vp, vp, vp]),
         "nvsm_similarity": (C.c_int, [vp, C.c_int32, vp, vp, i64, C.c_int32, vp]),

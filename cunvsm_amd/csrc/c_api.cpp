@@ -391,6 +391,30 @@ int nvsm_rank_ensemble_prf(nvsm_model* m, const nvsm_queries* queries, const nvs
     return guarded_on(m, [&] { m->impl.rank_ensemble_prf(*queries, *rank_opt, *lex, *fb, *ens, judgments, metrics, doc_ids, scores, counts); });
 }
 
+void nvsm_tfidf_options_default(nvsm_tfidf_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->idf = NVSM_IDF_ROBERTSON; o->top_k = 1000;
+}
+void nvsm_rerank_options_default(nvsm_rerank_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->first_stage = NVSM_STAGE_TFIDF; o->depth = 1000;
+}
+int nvsm_tfidf_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_tfidf_options* opt, int64_t* doc_ids, float* scores,
+                    int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(opt); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.tfidf_rank(*queries, *opt, doc_ids, scores, counts); });
+}
+int nvsm_rerank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_rerank_options* rr,
+                const nvsm_judgments* judgments, double* metrics, int64_t* doc_ids, float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(rank_opt); NVSM_REQUIRE(rr);
+    if (judgments) NVSM_REQUIRE(metrics);
+    if (metrics) NVSM_REQUIRE(judgments);
+    if (!metrics) { NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts); }
+    return guarded_on(m, [&] { m->impl.rerank(*queries, *rank_opt, *rr, judgments, metrics, doc_ids, scores, counts); });
+}
+
 void nvsm_sweep_options_default(nvsm_sweep_options* o) {
     if (!o) return;
     std::memset(o, 0, sizeof(*o));

@@ -641,6 +641,27 @@ void launch_lex_rm_narrow(double* acc, const double* sum_w, int64_t V, int64_t t
 // launch_rank_write for keys that may carry -inf scores: ids / scores [Q][k] up to the first -inf or padding key, counts [Q] likewise
 void launch_lex_write(const unsigned long long* keys, int64_t npad, int Q, int k, int64_t n_all, int64_t* ids, float* scores,
                       int64_t* counts, hipStream_t s);
+// ---- TF-IDF first stage and re-ranking of its candidates (lexical.hip; include/cunvsm_amd.h nvsm_tfidf_rank / nvsm_rerank)
+// df[t] += documents d < num_documents with tf(t, d) >= 1, exactly: the documents in slabs of `slab` (1 .. 2^31 − 1), bits
+// [num_words][lex_df_row_words(slab)] words, zero before (behind a slab that is not the last they are zero again; behind the last they
+// are not). df zeroed by the caller. Integer atomics only.
+int64_t lex_df_row_words(int64_t slab);
+void launch_lex_df(const int* tokens, const int64_t* doc_offsets, int64_t num_documents, int64_t slab, unsigned* bits,
+                   unsigned long long* df, hipStream_t s);
+// scores[q][d - d0] as launch_lex_score lays them out: Σ over the query's terms j with tf > 0 — in query order, fp64, every operation
+// rounded on its own, narrowed once — of (idf[j]·(tf·(k1 + 1))) / (tf + k1·((1 − b) + b·(len / avgdl))), times weight[j] where weight
+// is given; -inf when no term of q occurs in d. idf[j]: evaluated by the host, once per term.
+struct TfidfScoreArgs {
+    const int* tokens; const int64_t* doc_offsets; const int* slot_of;
+    int64_t d0; int S; int Q; int num_slots; double k1, b, avgdl;
+    const int* qoff; const int* tslot; const double* idf; const double* weight;
+    float* scores; int64_t ld;
+};
+void launch_tfidf_score(const TfidfScoreArgs& a, hipStream_t s);
+// the hand-over of nvsm_rerank: cand[off[q] .. off[q + 1]) = the ids of query q's first off[q + 1] − off[q] sorted keys (rows of
+// npad), ascending, for q < Q; off [Q + 1] on the device; nsort: a power of two >= every list, <= kRerankMaxDepth (LDS: 4 B per slot)
+constexpr int kRerankMaxDepth = 4096;      // NVSM_RERANK_MAX_DEPTH
+void launch_rerank_gather(const unsigned long long* keys, int64_t npad, const int64_t* off, int* cand, int Q, int nsort, hipStream_t s);
 // two ranked lists [Q][k] (+ counts) -> their fused list [Q][2 k] (+ counts); npad: a power of two >= 2 k; k <= kFuseMaxTopK
 struct FuseArgs {
     const int64_t* ids_a; const float* scores_a; const int64_t* counts_a;

@@ -12,6 +12,11 @@
 //                         lex_score_kernel<true> multiplies every term by its weight (nvsm_lexical_rank_weighted); <false> is the
 //                         kernel nvsm_lexical_rank always had
 //   lex_rm_accumulate_kernel, lex_rm_narrow_kernel   the relevance model of pseudo-relevance feedback
+//   lex_df_kernel         df(t): documents in slabs over a bit table [num_words][slab / 32]; a token ORs its document's bit and the lane
+//                         that found it clear counts the document; <false> takes the bits away again behind a slab
+//   tfidf_score_kernel    lex_score_kernel's frame with the BM25 term idf·tf·(k1 + 1) / (tf + K) (nvsm_tfidf_rank): no log on the device
+//   rerank_gather_kernel  a first-stage round's retrieved ids out of its sorted keys, ascending per query, into the candidate arrays
+//                         of rank_scan_cand_kernel (nvsm_rerank)
 //   lex_write_kernel      launch_rank_write for slabs that hold -inf entries: what is retrieved ends at the first -inf
 //   fuse_lists_kernel     one workgroup per query: normalises two ranked lists over their returned entries, matches the documents
 //                         both hold by a bitonic sort of (id, list, position) keys, computes the fused fp64 scores and sorts
@@ -23,6 +28,7 @@
 // Arithmetic of a term: fp64 throughout (allowed by the contract, and the accurate log the contract asks for). With tf = 0 — nearly
 // every (document, term) pair — the term is base[j] − log(den), base[j] = log(c0[j]) evaluated once per term by the host and
 // log(den) once per document: no log per pair.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include "../../include/cunvsm_amd.h"
@@ -92,6 +98,95 @@ __global__ __launch_bounds__(256) void lex_score_kernel(LexScoreArgs a) {
         for (int i = threadIdx.x; i < a.num_slots; i += 256) tf[i] = 0;
         __syncthreads();
     }
+}
+
+// ---- document frequencies, TF-IDF and the hand-over to the re-ranking stage ---------------------------------------
+// One wave per document of the slab, grid-strided, a document longer than the wave looped over; no barrier anywhere. Document j of
+// the slab owns bit j % 32 of word j / 32 in every term's row of `bits` ([V][W] words). MARK: every token ORs its document's bit
+// into its term's row, and the one lane that found the bit clear — whichever occurrence of the term in the document that is, across
+// the loop's chunks too — adds 1 to df[term]. Clear pass: every token ANDs the bit away again, so the table is zero for the next slab
+// without a memset of the whole table per slab. Integer atomics only: df does not depend on their order.
+template <bool MARK>
+__global__ __launch_bounds__(256) void lex_df_kernel(const int* __restrict__ tokens, const int64_t* __restrict__ doc_offsets, int64_t d0, int S,
+                                                     int64_t W, unsigned* __restrict__ bits, unsigned long long* __restrict__ df) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t j = blockIdx.x * 4ll + (threadIdx.x >> 6); j < S; j += static_cast<int64_t>(gridDim.x) * 4) {
+        const int64_t lo = doc_offsets[d0 + j], hi = doc_offsets[d0 + j + 1];
+        const unsigned bit = 1u << (j & 31);
+        for (int64_t i = lo + lane; i < hi; i += 64) {
+            const int t = tokens[i];
+            unsigned* word = bits + static_cast<size_t>(t) * W + (j >> 5);
+            if (MARK) {
+                if (!(atomicOr(word, bit) & bit)) atomicAdd(&df[t], 1ull);
+            } else {
+                atomicAnd(word, ~bit);
+            }
+        }
+    }
+}
+
+// a = (idf·(tf·(k1 + 1))) / (tf + K), K = k1·((1 − b) + b·(len / avgdl)) once per document; every operation rounded on its own
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void tfidf_score_kernel(TfidfScoreArgs a) {
+#pragma clang fp contract(off)
+    __shared__ int tf[kLexSlots];
+    for (int i = threadIdx.x; i < kLexSlots; i += 256) tf[i] = 0;
+    __syncthreads();
+    const double k1p = a.k1 + 1.0;
+    for (int64_t d = a.d0 + blockIdx.x; d < a.d0 + a.S; d += gridDim.x) {
+        const int64_t lo = a.doc_offsets[d], hi = a.doc_offsets[d + 1];
+        for (int64_t i = lo + threadIdx.x; i < hi; i += 256) {
+            const int slot = a.slot_of[a.tokens[i]];
+            if (slot >= 0) atomicAdd(&tf[slot], 1);
+        }
+        __syncthreads();
+        const double K = a.k1 * ((1.0 - a.b) + a.b * (static_cast<double>(hi - lo) / a.avgdl));
+        for (int q = threadIdx.x; q < a.Q; q += 256) {
+            double sum = 0.0;
+            bool any = false;
+            for (int j = a.qoff[q]; j < a.qoff[q + 1]; ++j) {
+                const int t = tf[a.tslot[j]];
+                if (t == 0) continue;      // (a term the document does not hold is worth exactly 0)
+                any = true;
+                const double tfd = static_cast<double>(t);
+                const double term = (a.idf[j] * (tfd * k1p)) / (tfd + K);
+                sum += WEIGHTED ? a.weight[j] * term : term;
+            }
+            a.scores[static_cast<size_t>(q) * a.ld + (d - a.d0)] = any ? static_cast<float>(sum) : -__builtin_inff();
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < a.num_slots; i += 256) tf[i] = 0;
+        __syncthreads();
+    }
+}
+
+// One workgroup per query of a first-stage round: the ids of the first n = off[q + 1] − off[q] sorted keys (what the round retrieved,
+// a prefix: launch_lex_write), ordered ascending by a bitonic sort in LDS (they are distinct), to cand[off[q] ..): the arrays
+// rank_scan_cand_kernel reads. nsort: a power of two >= every n, at most kRerankMaxDepth.
+__global__ __launch_bounds__(256) void rerank_gather_kernel(const unsigned long long* __restrict__ keys, int64_t npad,
+                                                            const int64_t* __restrict__ off, int* __restrict__ cand, int nsort) {
+    extern __shared__ unsigned rerank_ids[];
+    const int q = blockIdx.x;
+    const unsigned long long* g = keys + static_cast<size_t>(q) * npad;
+    int64_t n = off[q + 1] - off[q];
+    n = n < 0 ? 0 : (n > nsort ? nsort : n);
+    n = n > npad ? npad : n;
+    for (int i = threadIdx.x; i < nsort; i += 256)
+        rerank_ids[i] = i < n ? 0xffffffffu - static_cast<unsigned>(g[i] & 0xffffffffull) : 0xffffffffu;      // (padding sorts last)
+    __syncthreads();
+    for (int k = 2; k <= nsort; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int p = threadIdx.x; p < nsort / 2; p += 256) {
+                const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+                const int l = i | j;
+                const unsigned x = rerank_ids[i], y = rerank_ids[l];
+                if ((x <= y) != ((i & k) == 0)) { rerank_ids[i] = y; rerank_ids[l] = x; }
+            }
+            __syncthreads();
+        }
+    }
+    int* out = cand + off[q];
+    for (int i = threadIdx.x; i < n; i += 256) out[i] = static_cast<int>(rerank_ids[i]);
 }
 
 // ---- relevance model ---------------------------------------------------------------------------------------------
@@ -422,6 +517,35 @@ void launch_lex_score(const LexScoreArgs& a, hipStream_t s) {
     const int grid = static_cast<int>(a.S < 8192 ? a.S : 8192);
     if (a.weight) NVSM_LAUNCH(lex_score_kernel<true>, dim3(grid), dim3(256), 0, s, a);
     else NVSM_LAUNCH(lex_score_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+}
+
+int64_t lex_df_row_words(int64_t slab) { return (slab + 31) / 32; }
+
+void launch_lex_df(const int* tokens, const int64_t* doc_offsets, int64_t num_documents, int64_t slab, unsigned* bits,
+                   unsigned long long* df, hipStream_t s) {
+    if (slab < 1 || slab >= (int64_t(1) << 31)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lex_df: the slab must hold 1 .. 2^31 - 1 documents");
+    const int64_t W = lex_df_row_words(slab);
+    for (int64_t d0 = 0; d0 < num_documents; d0 += slab) {
+        const int S = static_cast<int>(std::min(slab, num_documents - d0));
+        const int grid = static_cast<int>(std::min<int64_t>((S + 3) / 4, 8192));
+        NVSM_LAUNCH(lex_df_kernel<true>, dim3(grid), dim3(256), 0, s, tokens, doc_offsets, d0, S, W, bits, df);
+        if (d0 + slab < num_documents)      // (behind the last slab the table is left as it is: its owner frees it)
+            NVSM_LAUNCH(lex_df_kernel<false>, dim3(grid), dim3(256), 0, s, tokens, doc_offsets, d0, S, W, bits, df);
+    }
+}
+
+void launch_tfidf_score(const TfidfScoreArgs& a, hipStream_t s) {
+    if (a.S <= 0 || a.Q <= 0) return;
+    const int grid = static_cast<int>(a.S < 8192 ? a.S : 8192);      // (grid-strided, as launch_lex_score)
+    if (a.weight) NVSM_LAUNCH(tfidf_score_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    else NVSM_LAUNCH(tfidf_score_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+}
+
+void launch_rerank_gather(const unsigned long long* keys, int64_t npad, const int64_t* off, int* cand, int Q, int nsort, hipStream_t s) {
+    if (Q <= 0) return;
+    if (nsort < 1 || nsort > kRerankMaxDepth || (nsort & (nsort - 1)) != 0)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "rerank_gather: nsort must be a power of two of at most NVSM_RERANK_MAX_DEPTH");
+    NVSM_LAUNCH(rerank_gather_kernel, dim3(Q), dim3(256), static_cast<size_t>(nsort) * sizeof(unsigned), s, keys, npad, off, cand, nsort);
 }
 
 void launch_lex_rm_accumulate(const LexRmArgs& a, int Q, hipStream_t s) {

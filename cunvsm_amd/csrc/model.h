@@ -202,6 +202,11 @@ class Model {
                            int64_t* counts);
     void evaluate(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_judgments& j, double* metrics, int64_t* doc_ids,
                   float* scores, int64_t* counts);
+    // TF-IDF first stage over the resident corpus, and nvsm_rank over its candidates handed over on the device (include/cunvsm_amd.h;
+    // lexical.hip); j and metrics both null or both given
+    void tfidf_rank(const nvsm_queries& q, const nvsm_tfidf_options& opt, int64_t* doc_ids, float* scores, int64_t* counts);
+    void rerank(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_rerank_options& rr, const nvsm_judgments* j, double* metrics,
+                int64_t* doc_ids, float* scores, int64_t* counts);
     // supervised fusion (include/cunvsm_amd.h; lexical.hip fuse_sweep_kernel); fb null: list B is lexical_rank's
     void ensemble_sweep(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
                         const nvsm_sweep_options& sw, const nvsm_judgments& j, double* table);
@@ -488,6 +493,7 @@ class Model {
         bool with_doc_weights = false, with_term_weights = false;
         size_t bytes = 0;
         std::vector<int64_t> cf;            // lexical ranking: occurrences of every word, made by the first lexical call (empty: not yet)
+        std::vector<int64_t> df;            // TF-IDF: documents holding every word, made by the first call that needs it (empty: not yet)
     };
     Corpus* corpus_ = nullptr;
     DevBuf<uint32_t> in_refs_[2];               // host references, one per staging set
@@ -534,7 +540,20 @@ class Model {
     void rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t* doc_ids, float* scores, int64_t* counts, EvalPlan* ev);
     void lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex) const;      // the refusals of nvsm_lexical_rank, before anything runs
     // weights null: nvsm_lexical_rank's rounds; given ([offsets[num_queries]] floats next to word_ids): the weighted scorer
-    void lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const float* weights, int64_t* doc_ids, float* scores, int64_t* counts);
+    // tfidf given: nvsm_tfidf_rank's scorer at lex.top_k (lex's method and param are not looked at). hand given: the round's retrieved
+    // ids go, ascending, where the candidate scan reads them (nvsm_rerank); counts must then be given
+    struct TfidfPlan { double k1, b, avgdl; int idf; };
+    struct Handover;                        // the candidate arrays of nvsm_rerank while the first stage fills them (ranking.cpp)
+    void lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const float* weights, int64_t* doc_ids, float* scores, int64_t* counts,
+                        const TfidfPlan* tfidf = nullptr, Handover* hand = nullptr);
+    void tfidf_check(const nvsm_queries& q, const nvsm_tfidf_options& opt) const;          // the refusals of nvsm_tfidf_rank, before anything runs
+    TfidfPlan tfidf_plan(const nvsm_tfidf_options& opt) const;
+    void corpus_df();                       // the df table of the corpus, made once (lex_df_kernel)
+    // one round of nvsm_rank over candidate lists that lie on the device as launch_rank_scan_candidates reads them
+    void rank_candidates_round(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, const RankLayout& l, const int* cand,
+                               const int64_t* cand_off, EvalArgs* ea, int64_t* doc_ids, float* scores, int64_t* counts);
+    // a query without words retrieves nothing: its result rows blanked, its metric row zero (metrics null: none)
+    void blank_wordless(const nvsm_queries& q, int k, int64_t* doc_ids, float* scores, int64_t* counts, double* metrics, int width) const;
     void weights_check(const nvsm_queries& q) const;
     void feedback_check(const nvsm_feedback_options& fb) const;                   // behind lexical_check: the corpus is there
     // first pass + relevance model into host lists [Q][fb_terms] (the rounds of nvsm_relevance_model, behind its checks and rank_join)

@@ -337,12 +337,7 @@ void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int
     for (int64_t q0 = 0; q0 < Q;) {
         const RankLayout l = by_candidates ? rank_layout_candidates(cand_off.data() + q0, Q - q0) : rank_layout(D, k, Q - q0, score_floats());
         const int64_t qn = l.qn;
-        rank_project(q, opt, q0, qn);
-        grow(r.qinv, static_cast<size_t>(kInferChunk));
-        round_grow(l, k);
-        const int64_t* cand_off_dev = nullptr;
-        { RankProf scope(prof, "rank_query", stream_); launch_rank_query_norm(r.proj.p, qn, de, r.qinv.p, cosine, stream_); }
-        if (by_candidates) {      // no slabs: the scan writes every list's keys, padded to npad
+        if (by_candidates) {      // the round's lists go up, then the round that nvsm_rerank shares
             const int64_t c0 = cand_off[q0], nc = cand_off[q0 + qn] - c0;
             std::vector<int64_t> off(static_cast<size_t>(qn) + 1);
             for (int64_t i = 0; i <= qn; ++i) off[static_cast<size_t>(i)] = cand_off[q0 + i] - c0;
@@ -351,19 +346,21 @@ void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int
             NVSM_HIP_CHECK(hipMemcpyAsync(r.cand_off.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
             if (nc > 0) NVSM_HIP_CHECK(hipMemcpyAsync(r.cand.p, cand.data() + c0, static_cast<size_t>(nc) * sizeof(int), hipMemcpyHostToDevice, stream_));
             NVSM_HIP_CHECK(hipStreamSynchronize(stream_));      // (`off` goes out of scope)
-            cand_off_dev = r.cand_off.p;
-            RankProf scope(prof, "rank_scan", stream_);
-            prof.note("rank_scan_candidates");
-            launch_rank_scan_candidates(ents_.P.p, de, r.proj.p, r.qinv.p, r.cand.p, r.cand_off.p, static_cast<int>(qn), l.npad, r.keys.p, cosine, view, stream_);
-        } else {
-            round_slabs(l, D, k, [&](int64_t d0, int Ss) {
-                RankProf scope(prof, "rank_scan", stream_);
-                prof.note(rank_scan_uses_mfma(de) ? "rank_scan_mfma" : "rank_scan_plain");
-                launch_rank_scan(ents_.P.p, de, d0, Ss, r.proj.p, static_cast<int>(qn), r.qinv.p, r.scores.p, l.ld, cosine, view, stream_);
-            });
+            rank_candidates_round(q, opt, q0, l, r.cand.p, r.cand_off.p, ev ? &ea : nullptr, doc_ids, scores, counts);
+            q0 += qn;
+            continue;
         }
+        rank_project(q, opt, q0, qn);
+        grow(r.qinv, static_cast<size_t>(kInferChunk));
+        round_grow(l, k);
+        { RankProf scope(prof, "rank_query", stream_); launch_rank_query_norm(r.proj.p, qn, de, r.qinv.p, cosine, stream_); }
+        round_slabs(l, D, k, [&](int64_t d0, int Ss) {
+            RankProf scope(prof, "rank_scan", stream_);
+            prof.note(rank_scan_uses_mfma(de) ? "rank_scan_mfma" : "rank_scan_plain");
+            launch_rank_scan(ents_.P.p, de, d0, Ss, r.proj.p, static_cast<int>(qn), r.qinv.p, r.scores.p, l.ld, cosine, view, stream_);
+        });
         round_sort(l, [&] {
-            launch_rank_write(r.keys.p, l.npad, static_cast<int>(qn), k, cand_off_dev, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
+            launch_rank_write(r.keys.p, l.npad, static_cast<int>(qn), k, nullptr, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
         });
         if (ev) {      // the round's metrics from the ranked ids where they lie: one wave per query
             RankProf scope(prof, "rank_eval", stream_);
@@ -375,23 +372,74 @@ void Model::rank_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, int
     }
     if (ev && Q > 0)
         NVSM_HIP_CHECK(hipMemcpy(ev->metrics, r.metrics.p, static_cast<size_t>(Q) * ev->width * sizeof(double), hipMemcpyDeviceToHost));
-    // a query without words retrieves nothing (the reference returns None)
-    for (int64_t i = 0; i < Q; ++i) {
+    blank_wordless(q, k, doc_ids, scores, counts, ev ? ev->metrics : nullptr, ev ? ev->width : 0);
+    raise_device_error();
+}
+
+// a query without words retrieves nothing (the reference returns None)
+void Model::blank_wordless(const nvsm_queries& q, int k, int64_t* doc_ids, float* scores, int64_t* counts, double* metrics, int width) const {
+    for (int64_t i = 0; i < q.num_queries; ++i) {
         if (q.offsets[i + 1] > q.offsets[i]) continue;
         if (counts) counts[i] = 0;
         for (int j = 0; j < k; ++j) {
             if (doc_ids) doc_ids[i * k + j] = -1;
             if (scores) scores[i * k + j] = -INFINITY;
         }
-        if (ev) std::fill(ev->metrics + i * ev->width, ev->metrics + (i + 1) * ev->width, 0.0);
+        if (metrics) std::fill(metrics + i * width, metrics + (i + 1) * width, 0.0);
     }
-    raise_device_error();
+}
+
+// no slabs: the scan writes every list's keys, padded to npad; then the sort, the write, the metrics and the results of the round
+void Model::rank_candidates_round(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, const RankLayout& l, const int* cand,
+                                  const int64_t* cand_off, EvalArgs* ea, int64_t* doc_ids, float* scores, int64_t* counts) {
+    RankScratch& r = rank_;
+    const int de = cfg_.entity_repr_size, k = opt.top_k;
+    const int cosine = opt.similarity == NVSM_SIM_COSINE;
+    const int64_t qn = l.qn;
+    rank_project(q, opt, q0, qn);
+    grow(r.qinv, static_cast<size_t>(kInferChunk));
+    round_grow(l, k);
+    { RankProf scope(prof, "rank_query", stream_); launch_rank_query_norm(r.proj.p, qn, de, r.qinv.p, cosine, stream_); }
+    {
+        RankProf scope(prof, "rank_scan", stream_);
+        prof.note("rank_scan_candidates");
+        launch_rank_scan_candidates(ents_.P.p, de, r.proj.p, r.qinv.p, cand, cand_off, static_cast<int>(qn), l.npad, r.keys.p, cosine,
+                                    lazy_view(ents_), stream_);
+    }
+    round_sort(l, [&] {
+        launch_rank_write(r.keys.p, l.npad, static_cast<int>(qn), k, cand_off, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_);
+    });
+    if (ea) {      // the round's metrics from the ranked ids where they lie: one wave per query
+        RankProf scope(prof, "rank_eval", stream_);
+        ea->ids = r.out_ids.p; ea->counts = r.out_counts.p; ea->q0 = q0;
+        launch_eval_metrics(*ea, static_cast<int>(qn), stream_);
+    }
+    round_results(q0, qn, k, doc_ids, scores, counts);
 }
 
 // ---- query-likelihood ranking over the resident corpus (include/cunvsm_amd.h nvsm_lexical_rank; kernels: lexical.hip) ----
 // Rounds, slabs, selection and sort are nvsm_rank's; what differs is who fills the score slab (launch_lex_score from the token arena)
 // and that a slab entry may be -inf — a document without any of the query's terms — which launch_lex_write leaves out and counts.
 // A round takes queries while their distinct remaining terms fit kLexSlots counters.
+//
+// nvsm_rerank's first stage hands every round over on the device: the round's counts are on the host behind round_results, the
+// offsets of its queries follow from them and go up behind those of the rounds before, and rerank_gather_kernel takes the retrieved
+// ids out of the round's sorted keys. `off` is sized for the chunk up front, so what the queued copies read stays where it is.
+struct Model::Handover {
+    int* cand = nullptr;                  // device: every query of the chunk has room for `depth` ids
+    int64_t* off_dev = nullptr;           // device [queries of the chunk + 1]; off_dev[0] = 0 is there already
+    std::vector<int64_t> off;             // the same on the host
+    int64_t done = 0;                     // queries handed over so far
+    int nsort = 1;                        // a power of two >= depth
+    void take(Model& m, const RankLayout& l, const int64_t* counts, int64_t qn) {
+        for (int64_t i = 0; i < qn; ++i) off[static_cast<size_t>(done + i + 1)] = off[static_cast<size_t>(done + i)] + counts[i];
+        NVSM_HIP_CHECK(hipMemcpyAsync(off_dev + done + 1, off.data() + done + 1, static_cast<size_t>(qn) * sizeof(int64_t), hipMemcpyHostToDevice, m.stream_));
+        RankProf scope(m.prof, "rerank_gather", m.stream_);
+        launch_rerank_gather(m.rank_.keys.p, l.npad, off_dev + done, cand, static_cast<int>(qn), nsort, m.stream_);
+        done += qn;
+    }
+};
+
 void Model::lexical_check(const nvsm_queries& q, const nvsm_lexical_options& lex) const {
     if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical ranking needs a corpus: call nvsm_corpus_upload first");
     if (lex.method != NVSM_LEX_JM && lex.method != NVSM_LEX_DIRICHLET) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown lexical method");
@@ -420,12 +468,14 @@ void Model::lexical_rank(const nvsm_queries& q, const nvsm_lexical_options& lex,
 }
 
 void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const float* weights, int64_t* doc_ids, float* scores,
-                           int64_t* counts) {
+                           int64_t* counts, const TfidfPlan* tfidf, Handover* hand) {
     Corpus& c = *corpus_;
     const int64_t Dc = c.num_documents, N = c.num_tokens, Q = q.num_queries, V = cfg_.num_words;
     const int k = lex.top_k;
     RankScratch& r = rank_;
-    if (c.cf.empty()) {      // one histogram pass over the arena, kept with the corpus (a new upload is a new Corpus)
+    if (tfidf) {
+        corpus_df();
+    } else if (c.cf.empty()) {      // one histogram pass over the arena, kept with the corpus (a new upload is a new Corpus)
         DevBuf<unsigned long long> cf;
         cf.alloc(static_cast<size_t>(V), true);
         { RankProf scope(prof, "lex_cf", stream_); launch_lex_cf(c.tokens.p, N, cf.p, stream_); }
@@ -440,6 +490,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
     }
     const double param = lex.method == NVSM_LEX_JM ? (lex.param == 0.f ? 0.5 : static_cast<double>(lex.param))
                                                    : (lex.param == 0.f ? static_cast<double>(N) / static_cast<double>(Dc) : static_cast<double>(lex.param));
+    const std::vector<int64_t>& held = tfidf ? c.df : c.cf;      // a term nobody holds is dropped: df = 0 exactly where cf = 0
     bool bad_word = false;
     std::vector<int> terms, qoff, tslot;
     std::vector<double> c0, base, wt;
@@ -458,7 +509,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
             for (int64_t j = q.offsets[q0 + taken]; j < q.offsets[q0 + taken + 1]; ++j) {
                 const int64_t t = q.word_ids[j];
                 if (t < 0 || t >= V) { bad_word = true; continue; }      // the index contract: matches nothing, reported at the end
-                if (c.cf[static_cast<size_t>(t)] == 0) continue;
+                if (held[static_cast<size_t>(t)] == 0) continue;
                 if (weights && weights[j] == 0.f) continue;               // a weighted query: a term of weight 0 is dropped
                 auto it = std::lower_bound(slot_of.begin(), slot_of.end(), std::make_pair(t, -1));
                 int slot;
@@ -470,10 +521,16 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
                     slot_of.insert(it, std::make_pair(t, slot));
                     terms.push_back(static_cast<int>(t));
                 }
-                const double p = static_cast<double>(c.cf[static_cast<size_t>(t)]) / static_cast<double>(N);
                 tslot.push_back(slot);
-                c0.push_back(param * p);
-                base.push_back(std::log(param * p));
+                if (tfidf) {      // the term's idf, once per term by the host, where the lexical scorer has c0 (base is not read)
+                    const double df = static_cast<double>(c.df[static_cast<size_t>(t)]), docs = static_cast<double>(Dc);
+                    c0.push_back(tfidf->idf == NVSM_IDF_OKAPI ? std::log((docs - df + 0.5) / (df + 0.5)) : std::log((docs + 1.0) / (df + 0.5)));
+                    base.push_back(0.0);
+                } else {
+                    const double p = static_cast<double>(c.cf[static_cast<size_t>(t)]) / static_cast<double>(N);
+                    c0.push_back(param * p);
+                    base.push_back(std::log(param * p));
+                }
                 if (weights) wt.push_back(static_cast<double>(weights[j]));
             }
             if (!fits) {      // this query opens the next round: take back what it added
@@ -512,8 +569,20 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
         a.qoff = r.lex_qoff.p; a.tslot = r.lex_tslot.p; a.c0 = r.lex_c0.p; a.base = r.lex_base.p;
         a.ld = l.ld;
         a.weight = weights ? r.lex_weight.p : nullptr;
+        TfidfScoreArgs ta{};
+        if (tfidf) {
+            ta.tokens = a.tokens; ta.doc_offsets = a.doc_offsets; ta.slot_of = a.slot_of;
+            ta.Q = a.Q; ta.num_slots = nslots; ta.k1 = tfidf->k1; ta.b = tfidf->b; ta.avgdl = tfidf->avgdl;
+            ta.qoff = a.qoff; ta.tslot = a.tslot; ta.idf = a.c0; ta.weight = a.weight; ta.ld = l.ld;
+        }
         round_slabs(l, Dc, k, [&](int64_t d0, int Ss) {
             if (d0 == 0) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);      // (behind round_slabs' grows)
+            if (tfidf) {
+                ta.scores = r.scores.p; ta.d0 = d0; ta.S = Ss;
+                RankProf scope(prof, "tfidf_score", stream_);
+                launch_tfidf_score(ta, stream_);
+                return;
+            }
             a.scores = r.scores.p; a.d0 = d0; a.S = Ss;
             RankProf scope(prof, weights ? "lex_score_weighted" : "lex_score", stream_);
             launch_lex_score(a, stream_);
@@ -521,10 +590,150 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
         launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
         round_sort(l, [&] { launch_lex_write(r.keys.p, l.npad, static_cast<int>(qn), k, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_); });
         round_results(q0, qn, k, doc_ids, scores, counts);
+        if (hand) hand->take(*this, l, counts + q0, qn);      // (the round's sorted keys still lie in r.keys)
         q0 += qn;
     }
     raise_device_error();
     if (bad_word) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a query word id is outside [0, num_words)");
+}
+
+// ---- TF-IDF first stage and re-ranking of its candidates (include/cunvsm_amd.h nvsm_tfidf_rank / nvsm_rerank; kernels: lexical.hip;
+// DESIGN.md §20) -------------------------------------------------------------------------------------------------------------------------
+// nvsm_tfidf_rank is lexical_rounds with another scorer: the same rounds, slot table, slabs, selection, sort and write.
+void Model::tfidf_check(const nvsm_queries& q, const nvsm_tfidf_options& opt) const {
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical ranking needs a corpus: call nvsm_corpus_upload first");
+    if (opt.idf != NVSM_IDF_ROBERTSON && opt.idf != NVSM_IDF_OKAPI) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown idf");
+    if (!std::isfinite(opt.k1) || opt.k1 < 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "k1 must be finite and positive, or 0 for auto");
+    if (!(opt.b >= 0.f && opt.b <= 1.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "b must be in (0, 1], or 0 for auto");
+    check_top_k(opt.top_k, corpus_->num_documents, "tfidf top_k must be in [1, num_documents of the corpus]");
+    check_row_count(corpus_->num_documents, "ranking supports fewer than 2^31 documents");
+    check_queries(q);
+    if (q.word_weights) weights_check(q);
+    std::vector<int64_t> one;
+    for (int64_t i = 0; i < q.num_queries; ++i) {
+        if (q.offsets[i + 1] - q.offsets[i] <= kLexSlots) continue;
+        one.assign(q.word_ids + q.offsets[i], q.word_ids + q.offsets[i + 1]);
+        std::sort(one.begin(), one.end());
+        if (std::unique(one.begin(), one.end()) - one.begin() > kLexSlots)
+            throw Error(NVSM_ERR_UNSUPPORTED, "a query has more than NVSM_LEXICAL_MAX_QUERY_TERMS distinct terms");
+    }
+}
+
+Model::TfidfPlan Model::tfidf_plan(const nvsm_tfidf_options& opt) const {
+    TfidfPlan p{};
+    p.k1 = opt.k1 == 0.f ? 1.2 : static_cast<double>(opt.k1);
+    p.b = opt.b == 0.f ? 0.75 : static_cast<double>(opt.b);
+    p.avgdl = static_cast<double>(corpus_->num_tokens) / static_cast<double>(corpus_->num_documents);      // (top_k >= 1: there are documents)
+    p.idf = opt.idf;
+    return p;
+}
+
+// One pass over the arena, kept with the corpus as the cf table is (a new upload is a new Corpus). The bit table comes out of the score
+// slab's budget: as many documents per slab as fit, at least 32.
+void Model::corpus_df() {
+    Corpus& c = *corpus_;
+    if (!c.df.empty()) return;
+    const int64_t V = cfg_.num_words, Dc = c.num_documents;
+    const int64_t slab = std::max<int64_t>(1, std::min(Dc, std::max<int64_t>(1, score_floats() / V) * 32));
+    DevBuf<unsigned long long> df;
+    DevBuf<unsigned> bits;
+    df.alloc(static_cast<size_t>(V), true);
+    bits.alloc(static_cast<size_t>(V * lex_df_row_words(slab)), true);
+    { RankProf scope(prof, "lex_df", stream_); launch_lex_df(c.tokens.p, c.offsets.p, Dc, slab, bits.p, df.p, stream_); }
+    std::vector<int64_t> host(static_cast<size_t>(V));
+    NVSM_HIP_CHECK(hipMemcpyAsync(host.data(), df.p, static_cast<size_t>(V) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    c.df.swap(host);
+}
+
+void Model::tfidf_rank(const nvsm_queries& q, const nvsm_tfidf_options& opt, int64_t* doc_ids, float* scores, int64_t* counts) {
+    tfidf_check(q, opt);
+    rank_join();
+    const TfidfPlan plan = tfidf_plan(opt);
+    nvsm_lexical_options rounds{};      // (what lexical_rounds reads of it in this form: top_k)
+    rounds.top_k = opt.top_k;
+    lexical_rounds(q, rounds, q.word_weights, doc_ids, scores, counts, &plan);
+}
+
+// nvsm_rerank: chunks of at most kInferChunk queries. The first stage's rounds of a chunk leave its candidate arrays on the device
+// (Handover), then the rounds of nvsm_rank over candidate lists run on them: their layout needs the lists' lengths, which are the
+// counts the first stage brought back. Both stages' rounds decide nothing about the bits: every (query, candidate) score and every
+// query's sort are on their own.
+void Model::rerank(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_rerank_options& rr, const nvsm_judgments* j, double* metrics,
+                   int64_t* doc_ids, float* scores, int64_t* counts) {
+    const int64_t D = cfg_.num_entities, Q = q.num_queries;
+    if (opt.candidates || opt.candidate_offsets)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "rank_opt->candidates must be NULL: the first stage names the candidates");
+    if (rr.first_stage != NVSM_STAGE_TFIDF && rr.first_stage != NVSM_STAGE_LEXICAL) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown first stage");
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical ranking needs a corpus: call nvsm_corpus_upload first");
+    if (rr.depth < 1 || rr.depth > corpus_->num_documents)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "depth must be in [1, min(num_documents of the corpus, NVSM_RERANK_MAX_DEPTH)]");
+    if (rr.depth > kRerankMaxDepth) throw Error(NVSM_ERR_UNSUPPORTED, "depth exceeds NVSM_RERANK_MAX_DEPTH");
+    if (rr.depth < opt.top_k) throw Error(NVSM_ERR_INVALID_ARGUMENT, "depth must not be smaller than rank_opt->top_k");
+    const bool by_tfidf = rr.first_stage == NVSM_STAGE_TFIDF;
+    nvsm_queries plain = q;      // the first stage is unweighted
+    plain.word_weights = nullptr;
+    nvsm_tfidf_options tf{};
+    nvsm_lexical_options lex{};
+    if (by_tfidf) {
+        if (rr.tfidf) tf = *rr.tfidf; else nvsm_tfidf_options_default(&tf);
+        tf.top_k = rr.depth;
+        tfidf_check(plain, tf);
+        lex.top_k = rr.depth;
+    } else {
+        if (rr.lexical) lex = *rr.lexical; else nvsm_lexical_options_default(&lex);
+        lex.top_k = rr.depth;
+        lexical_check(plain, lex);
+    }
+    check_similarity(opt.similarity);
+    check_top_k(opt.top_k, D, "top_k must be in [1, num_entities]");
+    check_row_count(D, "ranking supports fewer than 2^31 documents");
+    rank_check(q, opt);
+    EvalPlan plan;
+    EvalPlan* ev = nullptr;
+    if (j) {
+        plan.request = j;
+        plan.metrics = metrics;
+        eval_plan(plan, Q);
+        ev = &plan;
+    }
+    rank_join();
+    const TfidfPlan tplan = by_tfidf ? tfidf_plan(tf) : TfidfPlan{};
+    RankScratch& r = rank_;
+    const int k = opt.top_k;
+    EvalArgs ea{};
+    if (ev) ea = eval_upload(*ev, Q, k);
+    std::vector<int64_t> sub_off, first_counts;
+    for (int64_t c0 = 0; c0 < Q; c0 += kInferChunk) {
+        const int64_t cn = std::min(kInferChunk, Q - c0);
+        // ---- the first stage over the chunk's queries, handed over round by round
+        grow(r.cand_off, static_cast<size_t>(kInferChunk) + 1);
+        grow(r.cand, static_cast<size_t>(cn) * rr.depth);
+        Handover hand;
+        hand.cand = r.cand.p; hand.off_dev = r.cand_off.p;
+        hand.off.assign(static_cast<size_t>(cn) + 1, 0);
+        hand.nsort = static_cast<int>(pow2_at_least(rr.depth));
+        NVSM_HIP_CHECK(hipMemcpy(r.cand_off.p, hand.off.data(), sizeof(int64_t), hipMemcpyHostToDevice));      // off[0] = 0
+        sub_off.resize(static_cast<size_t>(cn) + 1);
+        for (int64_t i = 0; i <= cn; ++i) sub_off[static_cast<size_t>(i)] = q.offsets[c0 + i] - q.offsets[c0];
+        nvsm_queries sub{};
+        sub.word_ids = q.word_ids ? q.word_ids + q.offsets[c0] : nullptr;
+        sub.offsets = sub_off.data();
+        sub.num_queries = cn;
+        first_counts.assign(static_cast<size_t>(cn), 0);
+        lexical_rounds(sub, lex, nullptr, nullptr, nullptr, first_counts.data(), by_tfidf ? &tplan : nullptr, &hand);
+        // ---- nvsm_rank's rounds over the candidate lists where they lie: cand_off holds the chunk's absolute offsets, so a round
+        // that begins at query s reads them from cand_off + s against the one cand array
+        for (int64_t s = 0; s < cn;) {
+            const RankLayout l = rank_layout_candidates(hand.off.data() + s, cn - s);
+            rank_candidates_round(q, opt, c0 + s, l, r.cand.p, r.cand_off.p + s, ev ? &ea : nullptr, doc_ids, scores, counts);
+            s += l.qn;
+        }
+    }
+    if (ev && Q > 0)
+        NVSM_HIP_CHECK(hipMemcpy(ev->metrics, r.metrics.p, static_cast<size_t>(Q) * ev->width * sizeof(double), hipMemcpyDeviceToHost));
+    blank_wordless(q, k, doc_ids, scores, counts, ev ? ev->metrics : nullptr, ev ? ev->width : 0);
+    raise_device_error();
 }
 
 // ---- weighted queries and pseudo-relevance feedback (include/cunvsm_amd.h nvsm_lexical_rank_weighted / nvsm_relevance_model /

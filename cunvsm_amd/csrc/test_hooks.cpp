@@ -902,4 +902,40 @@ int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* a) {
     });
 }
 
+// launch_lex_df on a caller-supplied corpus at a caller-chosen slab (cunvsm_amd_test_hooks.h): what Model::corpus_df runs, with a bit
+// table of the hook's own. The corpus is checked on the host: the kernel indexes df and the bit table by token.
+int nvsm_debug_lex_df(const int32_t* tokens, int64_t num_tokens, const int64_t* doc_offsets, int64_t num_documents, int64_t num_words,
+                      int64_t slab, int64_t* df_out) {
+    NVSM_REQUIRE(doc_offsets); NVSM_REQUIRE(df_out);
+    if (num_tokens > 0) NVSM_REQUIRE(tokens);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        auto bad = [](const char* what) { throw Error(NVSM_ERR_INVALID_ARGUMENT, std::string("lex_df: ") + what); };
+        if (num_tokens < 0 || num_documents < 0 || num_documents >= (int64_t(1) << 31) || num_words < 1 || slab < 1 || slab >= (int64_t(1) << 31))
+            bad("bad sizes");
+        if (lex_df_row_words(slab) > (int64_t(1) << 28) / num_words) bad("the bit table would exceed 1 GiB");
+        if (doc_offsets[0] != 0) bad("doc_offsets must start at 0");
+        for (int64_t d = 0; d < num_documents; ++d)
+            if (doc_offsets[d + 1] < doc_offsets[d]) bad("doc_offsets must not decrease");
+        if (doc_offsets[num_documents] != num_tokens) bad("the last of doc_offsets must be num_tokens");
+        for (int64_t i = 0; i < num_tokens; ++i)
+            if (tokens[i] < 0 || tokens[i] >= num_words) bad("a token is outside [0, num_words)");
+        DevBuf<int> tok;
+        DevBuf<int64_t> off;
+        DevBuf<unsigned long long> df;
+        DevBuf<unsigned> bits;
+        tok.alloc(static_cast<size_t>(std::max<int64_t>(num_tokens, 1)), true);
+        off.alloc(static_cast<size_t>(num_documents) + 1);
+        df.alloc(static_cast<size_t>(num_words), true);
+        bits.alloc(static_cast<size_t>(num_words * lex_df_row_words(slab)), true);
+        if (num_tokens > 0) NVSM_HIP_CHECK(hipMemcpy(tok.p, tokens, static_cast<size_t>(num_tokens) * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(off.p, doc_offsets, (static_cast<size_t>(num_documents) + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        launch_lex_df(tok.p, off.p, num_documents, slab, bits.p, df.p, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(df_out, df.p, static_cast<size_t>(num_words) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    });
+}
+
 }  // extern "C"

@@ -10,7 +10,8 @@
 //   * the written score is the cosine similarity nvsm_rank returns; the reference writes cos - 1 through an external writer —
 //     the same ranking.
 //   * ties in a ranking are broken by ascending model document id, not by docno.
-//   * not offered: --rerank_exact_matching_documents, --num_workers, --l2norm_phrase (see --help).
+//   * not offered: --rerank_exact_matching_documents (its place is taken by --rerank tfidf, below), --num_workers, --l2norm_phrase
+//     (see --help).
 // The last stage of rank-cranfield-collection.sh — a query-likelihood run and its fusion with the NVSM run (py/combine_runs.py
 // --alpha) — is --qlm / --ensemble_alpha: the collection goes to HBM as the token arena the trainer would upload (token_arena.hpp:
 // IndexSource's term mapping and out-of-vocabulary rule, documents in model id order) and nvsm_lexical_rank / nvsm_rank_ensemble do
@@ -18,6 +19,9 @@
 // the fusion, the reference's "QLM w/ PRF": nvsm_lexical_rank_prf / nvsm_rank_ensemble_prf (RM3).
 // py/combine_runs.py's supervised mode (--qrel --num_folds --alpha_stepsize) is --ensemble_qrel: the fusion's weight is chosen per fold
 // of the topics on a grid by nvsm_rank_ensemble_cv.
+// py/query.py's --rerank_exact_matching_documents — a lexical first stage names each topic's candidates and the model ranks only those —
+// is --rerank tfidf | okapi | jm | dirichlet with --rerank_depth: nvsm_rerank over the same uploaded collection, the candidates handed
+// over on the device. --tfidf_run_out writes the TF-IDF first stage's own run (nvsm_tfidf_rank).
 #include <sys/stat.h>
 
 #include <cmath>
@@ -42,11 +46,12 @@ using namespace nvsm_host;
 namespace {
 
 std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs, FLAGS_qlm, FLAGS_qlm_param, FLAGS_qlm_run_out,
-    FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure;
+    FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure, FLAGS_rerank, FLAGS_tfidf_run_out;
 bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
     FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf;
 double FLAGS_bias_coefficient, FLAGS_qlm_fb_orig_weight, FLAGS_alpha_stepsize;
-int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers, FLAGS_qlm_fb_docs, FLAGS_qlm_fb_terms, FLAGS_num_folds, FLAGS_ensemble_seed;
+int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers, FLAGS_qlm_fb_docs, FLAGS_qlm_fb_terms, FLAGS_num_folds, FLAGS_ensemble_seed,
+    FLAGS_rerank_depth;
 
 void define_flags(Flags* f) {
     f->define_string("index", &FLAGS_index, "", "TREC-text collection file or Indri repository directory, as given to cuNVSMTrainModel.");
@@ -68,7 +73,7 @@ void define_flags(Flags* f) {
     f->define_bool("per_query", &FLAGS_per_query, false, "With --qrels: also print every evaluated topic's metrics.");
     f->define_int64("device", &FLAGS_device, 0, "HIP device ordinal.");
     f->define_bool("rerank_exact_matching_documents", &FLAGS_rerank_exact_matching_documents, false, "NOT OFFERED: it needs Indri's TF-IDF "
-                   "query environment, which does not exist here.");
+                   "query environment, which does not exist here. --rerank tfidf is the same retrieve-then-rerank over the model's vocabulary.");
     f->define_int64("num_workers", &FLAGS_num_workers, 0, "NOT OFFERED (accepted and ignored): every topic file is one GPU pass.");
     f->define_bool("l2norm_phrase", &FLAGS_l2norm_phrase, false, "NOT OFFERED: py/nvsm/base.py has no such argument (the reference's "
                    "py/query.py fails when it is given).");
@@ -98,6 +103,13 @@ void define_flags(Flags* f) {
     f->define_int64("qlm_fb_docs", &FLAGS_qlm_fb_docs, 10, "With --qlm_prf: feedback documents per topic.");
     f->define_int64("qlm_fb_terms", &FLAGS_qlm_fb_terms, 10, "With --qlm_prf: expansion terms per topic.");
     f->define_double("qlm_fb_orig_weight", &FLAGS_qlm_fb_orig_weight, 0.5, "With --qlm_prf: weight of the original query in the expanded one, in [0, 1].");
+    f->define_string("rerank", &FLAGS_rerank, "", "tfidf | okapi | jm | dirichlet: retrieve-then-rerank. A lexical first stage over the collection in the "
+                     "model's vocabulary (TF-IDF with Robertson's or Okapi's idf, or the query-likelihood model at its automatic parameter) retrieves "
+                     "--rerank_depth documents per topic and the model ranks only those; <run_out> and the printed means are the re-ranked lists. "
+                     "Excludes --ensemble_alpha, --ensemble_qrel and qrel files as --top_k.");
+    f->define_int64("rerank_depth", &FLAGS_rerank_depth, 1000, "With --rerank: candidates per topic, clipped to the collection; at most 4096.");
+    f->define_string("tfidf_run_out", &FLAGS_tfidf_run_out, "", "Prefix of the TF-IDF runs (Robertson's idf; Okapi's with --rerank okapi), written as "
+                     "<prefix>-<topic file> in TREC format, --top_k documents per topic (with --rerank: the --rerank_depth candidates).");
     f->define_bool("help", &FLAGS_help, false, "Print the options and exit.");
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
     f->define_int64("v", &FLAGS_v, 0, "Verbosity of VLOG messages.");
@@ -169,7 +181,8 @@ int run(int argc, char** argv) {
         std::cerr << usage;
         NVSM_LOG(FATAL) << "--index, --topics, the model and the run's name are required.";
     }
-    NVSM_CHECK(!FLAGS_rerank_exact_matching_documents) << "--rerank_exact_matching_documents is not offered: it needs Indri's TF-IDF query environment.";
+    NVSM_CHECK(!FLAGS_rerank_exact_matching_documents) << "--rerank_exact_matching_documents is not offered: it needs Indri's TF-IDF query environment. "
+                                                          "--rerank tfidf re-ranks a TF-IDF first stage over the model's vocabulary.";
     NVSM_CHECK(!FLAGS_l2norm_phrase) << "--l2norm_phrase is not offered: py/nvsm/base.py has no such argument.";
     if (FLAGS_num_workers != 0) NVSM_LOG(WARNING) << "--num_workers is ignored: every topic file is one GPU pass.";
     if (FLAGS_bias_coefficient != 0.0)
@@ -251,6 +264,28 @@ int run(int argc, char** argv) {
     else if (FLAGS_score_normalizer == "none") ens.normalizer = NVSM_NORM_NONE;
     else NVSM_LOG(FATAL) << "--score_normalizer: '" << FLAGS_score_normalizer << "' is none of standardize, minmax, none.";
 
+    // ---- --rerank / --tfidf_run_out (py/query.py:186-205, over the model's vocabulary)
+    const bool with_rerank = !FLAGS_rerank.empty(), with_tfidf_run = !FLAGS_tfidf_run_out.empty();
+    nvsm_tfidf_options tfidf;
+    nvsm_tfidf_options_default(&tfidf);
+    nvsm_lexical_options rerank_lex;
+    nvsm_lexical_options_default(&rerank_lex);
+    nvsm_rerank_options rerank;
+    nvsm_rerank_options_default(&rerank);
+    rerank.tfidf = &tfidf; rerank.lexical = &rerank_lex;
+    if (with_rerank) {
+        NVSM_CHECK(!with_fusion) << "--rerank and --ensemble_alpha / --ensemble_qrel are mutually exclusive: <run_out> holds either the re-ranked or the fused lists.";
+        if (FLAGS_rerank == "tfidf") { rerank.first_stage = NVSM_STAGE_TFIDF; tfidf.idf = NVSM_IDF_ROBERTSON; }
+        else if (FLAGS_rerank == "okapi") { rerank.first_stage = NVSM_STAGE_TFIDF; tfidf.idf = NVSM_IDF_OKAPI; }
+        else if (FLAGS_rerank == "jm") { rerank.first_stage = NVSM_STAGE_LEXICAL; rerank_lex.method = NVSM_LEX_JM; }
+        else if (FLAGS_rerank == "dirichlet") { rerank.first_stage = NVSM_STAGE_LEXICAL; rerank_lex.method = NVSM_LEX_DIRICHLET; }
+        else NVSM_LOG(FATAL) << "--rerank: '" << FLAGS_rerank << "' is none of tfidf, okapi, jm, dirichlet.";
+        NVSM_CHECK(FLAGS_rerank_depth >= 1 && FLAGS_rerank_depth <= NVSM_RERANK_MAX_DEPTH) << "--rerank_depth must be in [1, " << NVSM_RERANK_MAX_DEPTH << "].";
+    } else {
+        NVSM_CHECK(FLAGS_rerank_depth == 1000) << "--rerank_depth needs --rerank.";
+    }
+    const bool with_collection = with_qlm || with_rerank || with_tfidf_run;      // the token arena goes to the device
+
     // ---- --top_k (py/query.py:118-139)
     int64_t top_k = 1000;
     bool top_k_all = false;
@@ -267,6 +302,8 @@ int run(int argc, char** argv) {
         candidate_qrels.reset(new Qrels(read_qrels(paths)));
     }
     NVSM_CHECK(!(with_qlm && candidate_qrels)) << "--qlm ranks every document: with it --top_k is a number or 'all', not qrel files.";
+    NVSM_CHECK(!((with_rerank || with_tfidf_run) && candidate_qrels))
+        << "--rerank and --tfidf_run_out take their candidates from the collection: with them --top_k is a number or 'all', not qrel files.";
     std::unique_ptr<Qrels> qrels;
     if (!FLAGS_qrels.empty()) qrels.reset(new Qrels(read_qrels(split_blanks(FLAGS_qrels))));
     if (with_cv) qrels.reset(new Qrels(read_qrels(split_blanks(FLAGS_ensemble_qrel))));
@@ -324,8 +361,8 @@ int run(int argc, char** argv) {
     for (int i = 0; i < 4; ++i)
         NVSM_CALL(nvsm_set_param(model, kNames[i], arrays[static_cast<size_t>(i)].data.data(), static_cast<int64_t>(arrays[static_cast<size_t>(i)].data.size())));
 
-    if (with_qlm) {      // the collection as the trainer would upload it: model term ids, documents in model id order
-        NVSM_LOG(INFO) << "Uploading the collection for the query-likelihood model.";
+    if (with_collection) {      // the collection as the trainer would upload it: model term ids, documents in model id order
+        NVSM_LOG(INFO) << "Uploading the collection for the lexical models.";
         std::vector<std::pair<size_t, DOCID_T>> documents;
         for (int64_t d = 0; d < num_entities; ++d)
             if (maps.index_object_of[static_cast<size_t>(d)] >= 0)
@@ -413,6 +450,10 @@ int run(int argc, char** argv) {
         // judged documents of the topic — one call ranks every topic, so it asks for the largest and counts[] cuts each topic's list
         int64_t k = top_k_all ? num_entities : std::min(top_k, num_entities);
         if (candidate_qrels) k = std::max<int64_t>(1, std::min(most_candidates, num_entities));
+        if (with_rerank) {      // the depth clipped to the collection, as --top_k is; a topic has no more results than candidates
+            rerank.depth = static_cast<int32_t>(std::min<int64_t>(FLAGS_rerank_depth, num_entities));
+            k = std::min<int64_t>(k, rerank.depth);
+        }
         NVSM_CHECK(k <= 2147483647) << "--top_k is too large.";
         opt.top_k = static_cast<int32_t>(k);
         opt.candidates = candidate_qrels && !cand.empty() ? cand.data() : nullptr;
@@ -455,7 +496,29 @@ int run(int argc, char** argv) {
                 write_run(qlm_path, lex_ids, lex_scores, lex_counts, k);
             }
         }
-        if (with_cv) {      // both rankings once, the sweep of the grid, the choice per fold and the fused lists in ONE call
+        if (with_tfidf_run) {
+            const std::string tfidf_path = FLAGS_tfidf_run_out + "-" + basename_of(topic_path);
+            if (exists(tfidf_path)) {
+                NVSM_LOG(WARNING) << "Run for topics " << topic_path << " already exists (" << tfidf_path << "); skipping.";
+            } else {
+                const int64_t kt = with_rerank ? rerank.depth : k;      // with --rerank the run is the first stage's: its candidates
+                std::vector<int64_t> tf_ids(static_cast<size_t>(Q * kt) + 1), tf_counts(static_cast<size_t>(Q) + 1);
+                std::vector<float> tf_scores(static_cast<size_t>(Q * kt) + 1);
+                nvsm_tfidf_options own = tfidf;
+                own.top_k = static_cast<int32_t>(kt);
+                nvsm_queries plain = queries;      // a plain query string: --self_information shapes the model's query only
+                plain.word_weights = nullptr;
+                NVSM_CALL(nvsm_tfidf_rank(model, &plain, &own, tf_ids.data(), tf_scores.data(), tf_counts.data()));
+                write_run(tfidf_path, tf_ids, tf_scores, tf_counts, kt);
+            }
+        }
+        if (with_rerank) {      // first stage, hand-over, the model's ranking of the candidates and, with --qrels, its metrics in ONE call
+            nvsm_judgments judgments{};
+            judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
+            judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());
+            NVSM_CALL(nvsm_rerank(model, &queries, &opt, &rerank, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr, doc_ids.data(),
+                                  scores.data(), counts.data()));
+        } else if (with_cv) {      // both rankings once, the sweep of the grid, the choice per fold and the fused lists in ONE call
             nvsm_judgments judgments{};
             judgments.doc_ids = judged_ids.data(); judgments.grades = judged_grades.data(); judgments.offsets = judged_off.data();
             judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());

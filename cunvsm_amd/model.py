@@ -511,6 +511,30 @@ def feedback_options(fb_docs=10, fb_terms=10, orig_weight=0.5):
     return opt
 
 
+IDFS = {"robertson": _lib.IDF_ROBERTSON, "okapi": _lib.IDF_OKAPI}
+FIRST_STAGES = {"tfidf": _lib.STAGE_TFIDF, "lexical": _lib.STAGE_LEXICAL}
+
+
+def tfidf_options(k1=None, b=None, idf="robertson", top_k=1000):
+    """nvsm_tfidf_options from keywords (k1 / b None or "auto": 0 = auto 1.2 / 0.75); raises ValueError for what the ABI would refuse
+    without a device. top_k against the corpus is checked by the library, which holds it."""
+    opt = _lib.NvsmTfidfOptions()
+    if isinstance(idf, str):
+        if idf not in IDFS:
+            raise ValueError("unknown idf %r (one of %s)" % (idf, sorted(IDFS)))
+        idf = IDFS[idf]
+    k1v = 0.0 if k1 is None or k1 == "auto" else float(k1)
+    bv = 0.0 if b is None or b == "auto" else float(b)
+    if not (np.isfinite(k1v) and k1v >= 0.0):
+        raise ValueError("k1 = %r must be finite and positive" % (k1,))
+    if not 0.0 <= bv <= 1.0:
+        raise ValueError("b = %r outside (0, 1]" % (b,))
+    if int(top_k) < 1:
+        raise ValueError("top_k = %d is smaller than 1" % int(top_k))
+    opt.k1, opt.b, opt.idf, opt.top_k = k1v, bv, int(idf), int(top_k)
+    return opt
+
+
 def as_feedback_options(feedback):
     """feedback given as an NvsmFeedbackOptions, a dict of feedback_options' keywords, a (fb_docs, fb_terms, orig_weight) tuple, or True
     for the defaults"""
@@ -1103,6 +1127,69 @@ class Model:
             check(lib().nvsm_rank_ensemble(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), *tail))
         else:
             check(lib().nvsm_rank_ensemble_prf(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), C.byref(fopt), *tail))
+        if js is None:
+            return ids, scores, counts
+        result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}
+        return result, ids, scores, counts
+
+    # -- TF-IDF first-stage retrieval and re-ranking of its candidates on the device --------
+    def tfidf_rank(self, queries, k1=None, b=None, idf="robertson", top_k=1000, weights=None):
+        """nvsm_tfidf_rank: the top_k documents of the uploaded corpus per query under BM25's saturating tf with Robertson's
+        ("robertson") or Okapi's ("okapi") idf (include/cunvsm_amd.h has the formula); k1 / b None = auto (1.2 / 0.75). Returns
+        (ids [Q, k], scores [Q, k], counts [Q]) as lexical_rank() does. weights (per query a list of float32 weights >= 0, one
+        per word): every term times its weight, a term of weight 0 is dropped."""
+        if weights is not None:
+            q = weighted_queries(queries.rows() if isinstance(queries, Queries) else queries, weights)
+        else:
+            q = queries if isinstance(queries, Queries) else Queries(queries)
+        opt = tfidf_options(k1, b, idf, top_k)
+        k = opt.top_k
+        ids = np.empty((q.num_queries, k), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        if weights is None:
+            st.word_weights = None
+        check(lib().nvsm_tfidf_rank(self._h, C.byref(st), C.byref(opt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids, scores, counts
+
+    def rerank(self, queries, first_stage="tfidf", depth=1000, top_k=1000, judgments=None, cutoffs=(5, 10, 20, 100, 1000), weights=None,
+               k1=None, b=None, idf="robertson", method="jm", param=None, **opts):
+        """nvsm_rerank: rank() over the candidates the first stage retrieves at top_k = depth — tfidf_rank() ("tfidf": k1, b, idf) or
+        lexical_rank() ("lexical": method, param), unweighted — handed over on the device: bit for bit rank(candidates = the first
+        stage's ids). weights shape only the neural stage's query representation. Returns (ids [Q, top_k], scores, counts); with
+        judgments, (metrics, ids, scores, counts), metrics being evaluate()'s dict for those candidates. opts: as rank()."""
+        q = queries if isinstance(queries, Queries) else Queries(queries, weights)
+        if isinstance(first_stage, str):
+            if first_stage not in FIRST_STAGES:
+                raise ValueError("unknown first stage %r (one of %s)" % (first_stage, sorted(FIRST_STAGES)))
+            first_stage = FIRST_STAGES[first_stage]
+        ropt = rank_options(self.cfg.num_entities, top_k, **opts)
+        # (depth against the corpus, the cap and top_k is checked by the library, which holds the corpus)
+        topt = tfidf_options(k1, b, idf, int(depth))
+        lopt = lexical_options(method, param, int(depth))
+        rr = _lib.NvsmRerankOptions()
+        rr.first_stage, rr.depth = int(first_stage), int(depth)
+        rr.tfidf, rr.lexical = C.pointer(topt), C.pointer(lopt)
+        k = ropt.top_k
+        ids = np.empty((q.num_queries, k), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        js = metrics = names = cut = None
+        if judgments is not None:
+            j = judgments if isinstance(judgments, Judgments) else Judgments(judgments)
+            if j.num_queries != q.num_queries:
+                raise ValueError("judgments holds %d lists, expected one per query = %d" % (j.num_queries, q.num_queries))
+            if j.doc_ids.size and (j.doc_ids.min() < -1 or j.doc_ids.max() >= self.cfg.num_entities):
+                raise ValueError("a judged document id is outside [-1, num_entities = %d)" % self.cfg.num_entities)
+            cut = eval_cutoffs(cutoffs)
+            names = eval_metric_names(cut.tolist())
+            metrics = np.empty((q.num_queries, len(names)), dtype=np.float64)
+            js = j.as_struct(cut)
+        check(lib().nvsm_rerank(self._h, C.byref(st), C.byref(ropt), C.byref(rr), None if js is None else C.byref(js),
+                                None if js is None else (metrics.ctypes.data if metrics.size else _EMPTY_F64.ctypes.data),
+                                ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         if js is None:
             return ids, scores, counts
         result = {name: np.ascontiguousarray(metrics[:, i]) for i, name in enumerate(names)}

@@ -653,6 +653,77 @@ int nvsm_rank_ensemble_cv(nvsm_model* m, const nvsm_queries* queries, const nvsm
                           int64_t* doc_ids, float* scores, int64_t* counts, double* metrics, double* sweep_metrics);
 
 /*
+ * TF-IDF FIRST-STAGE RETRIEVAL AND RE-RANKING OF ITS CANDIDATES (nvsm_tfidf_rank, nvsm_rerank) — py/query.py
+ * --rerank_exact_matching_documents (query.py:186-205): Indri's TF-IDF query environment returns each topic's best 1000 documents and
+ * the neural model ranks only those (base.py's document_set). Indri is outside the reference's tree: there is no program text to
+ * follow, and the formula written here is the contract. D_c, N, len(d), tf and the corpus mean what they mean for nvsm_lexical_rank;
+ * df(t) is the number of documents d with tf(t, d) >= 1; avgdl = N / D_c, empty documents counted (as μ auto does).
+ *   term value      a_j(d) = idf(t_j) · tf·(k1 + 1) / (tf + k1·(1 − b + b·len(d) / avgdl)), tf = tf(t_j, d): BM25's saturating tf.
+ *   NVSM_IDF_ROBERTSON  idf = ln((D_c + 1) / (df + 0.5)): Robertson's tf × idf, which Indri's tfidf baseline documents. Always > 0.
+ *   NVSM_IDF_OKAPI      idf = ln((D_c − df + 0.5) / (df + 0.5)): negative for df > D_c / 2, reproduced as it is. Finite for every df in
+ *                   [1, D_c], so -inf stays free to mark "no term of the query in this document".
+ *   score           s(q, d) = Σ_j w_j·a_j(d) in query order; a repeated word contributes once per occurrence. w_j = 1 when
+ *                   queries->word_weights is NULL, else the float32 weights, each finite and >= 0 (refused otherwise); a term of
+ *                   weight 0 is dropped, and so is a term with df = 0. A query with nothing left, or without words, retrieves nothing.
+ *   retrieved set   the documents that hold at least one remaining term; counts[q] = min(top_k, matches), 1 <= top_k <= num_documents.
+ *   order           float32 score descending, ties by ascending id; slots behind hold (-1, -inf); a repeated call returns the same bits.
+ *   arithmetic      fp64 plain operations without contraction, every product rounded on its own:
+ *                   (idf·(tf·(k1 + 1))) / (tf + k1·((1 − b) + b·(len / avgdl))); the sum is narrowed to float32 ONCE. idf is evaluated
+ *                   once per term by the host, the length norm once per document: no log per (document, term) pair.
+ *   accuracy        |score − the exact value| <= 2^-23 · Σ_j |w_j·a_j|: one narrowing of an fp64 sum whose own error is orders of
+ *                   magnitude smaller. (Weights all 1 return the unweighted bits; a power-of-two weight on every term scales exactly.)
+ *   parameters      k1 finite and > 0, or 0 for auto 1.2; b in (0, 1], or 0 for auto 0.75.
+ * The df table is made by one pass over the arena at the first call that needs it after an upload (integer atomics only: exact,
+ * whatever their order) and kept with the corpus exactly as the cf table is: uploading or freeing a corpus drops it. A handle that
+ * never makes these calls allocates and launches nothing new, and its nvsm_describe text is unchanged. More than
+ * NVSM_LEXICAL_MAX_QUERY_TERMS distinct terms in a query is NVSM_ERR_UNSUPPORTED. NVSM_ERR_INVALID_ARGUMENT before anything runs, each
+ * with a sentence: no corpus uploaded; unknown idf; k1 or b out of range or NaN; top_k outside [1, num_documents]; a weight that is
+ * negative or not finite; null arguments by name; decreasing offsets. A word id out of range follows the index contract: it matches
+ * nothing and the call returns NVSM_ERR_INVALID_ARGUMENT.
+ *
+ * nvsm_rerank returns BY DEFINITION, bit for bit, what nvsm_rank returns with `candidates` set to the ids the first stage returns at
+ * top_k = depth, and with rank_opt's remaining fields. The first stage is nvsm_tfidf_rank (NVSM_STAGE_TFIDF, options rr->tfidf) or
+ * nvsm_lexical_rank (NVSM_STAGE_LEXICAL, options rr->lexical); a NULL pointer means that stage's defaults, and the stage's own top_k
+ * field is not looked at. The first stage is UNWEIGHTED: queries->word_weights shape only the neural stage's query representation
+ * (query.py builds a plain query string). Results are [num_queries][rank_opt->top_k], counts[q] = min(top_k, first-stage count). With
+ * judgments and metrics (both given or both NULL) the metrics are nvsm_evaluate's for those candidates; doc_ids, scores and counts may
+ * each be NULL when metrics are asked for. The candidate ids never leave the device: per round of the first stage only the per-query
+ * counts come back to the host (they size the second stage's rounds), and a kernel writes the retrieved ids, ascending, where the
+ * candidate scan reads them. Refusals, before anything runs: rank_opt->candidates must be NULL; depth in [1, min(num_documents,
+ * NVSM_RERANK_MAX_DEPTH)] (above the cap with enough documents: NVSM_ERR_UNSUPPORTED; a query's candidates are ordered in LDS);
+ * depth >= rank_opt->top_k; an unknown first stage; and everything either stage would refuse, in its words. Synchronous, behind
+ * everything queued, lazily decayed tables read through their view, no parameter, optimiser state, RNG state or lazy bookkeeping touched.
+ */
+enum { NVSM_IDF_ROBERTSON = 0, NVSM_IDF_OKAPI = 1 };
+typedef struct {
+    float   k1;                   /* > 0; 0 = auto 1.2 */
+    float   b;                    /* in (0, 1]; 0 = auto 0.75 */
+    int32_t idf;                  /* NVSM_IDF_* */
+    int32_t top_k;
+    int32_t reserved[4];
+} nvsm_tfidf_options;
+/* k1 0 (auto 1.2), b 0 (auto 0.75), NVSM_IDF_ROBERTSON, top_k 1000 */
+void nvsm_tfidf_options_default(nvsm_tfidf_options* opt);
+/* doc_ids, scores [num_queries][top_k], counts [num_queries], all host */
+int nvsm_tfidf_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_tfidf_options* opt,
+                    int64_t* doc_ids, float* scores, int64_t* counts);
+#define NVSM_RERANK_MAX_DEPTH 4096
+enum { NVSM_STAGE_TFIDF = 0, NVSM_STAGE_LEXICAL = 1 };
+typedef struct {
+    int32_t first_stage;          /* NVSM_STAGE_* */
+    int32_t depth;                /* candidates per query: 1 .. min(num_documents, NVSM_RERANK_MAX_DEPTH), >= rank_opt->top_k */
+    const nvsm_tfidf_options* tfidf;        /* NVSM_STAGE_TFIDF; NULL = defaults; its top_k is not looked at */
+    const nvsm_lexical_options* lexical;    /* NVSM_STAGE_LEXICAL; NULL = defaults; its top_k is not looked at */
+    int32_t reserved[4];
+} nvsm_rerank_options;
+/* NVSM_STAGE_TFIDF, depth 1000 (query.py:201), both pointers NULL */
+void nvsm_rerank_options_default(nvsm_rerank_options* opt);
+/* doc_ids, scores [num_queries][rank_opt->top_k], counts [num_queries], all host; judgments and metrics both given or both NULL:
+ * metrics [num_queries][NVSM_EVAL_FIXED + 3 * num_cutoffs]; with metrics each of doc_ids / scores / counts may be NULL */
+int nvsm_rerank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_rerank_options* rr,
+                const nvsm_judgments* judgments, double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
+
+/*
  * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query
  * library does with the same parameters (py/nvsm/base.py). Semantics, pinned by the reference:
  *   space        NVSM_SPACE_WORDS: the rows of W, dimension word_repr_size — NVSM.related_terms (base.py:325-342) and

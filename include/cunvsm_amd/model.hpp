@@ -255,6 +255,37 @@ class Model {
         return e;
     }
 
+    // nvsm_tfidf_rank: TF-IDF / BM25 ranking over the uploaded corpus (cunvsm_amd.h has the formula); word_weights null: every weight 1
+    Ranking tfidf_rank(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_tfidf_options& opt,
+                       const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        Ranking r;
+        r.top_k = opt.top_k;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        r.doc_ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_tfidf_rank(h_, &q, &opt, r.doc_ids.data(), r.scores.data(), r.counts.data()));
+        r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+    // nvsm_rerank: rank() over the candidates the first stage retrieves at top_k = rr.depth, handed over on the device. judgments
+    // null: no metrics (width 0).
+    Evaluation rerank(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                      const nvsm_rerank_options& rr, const nvsm_judgments* judgments = nullptr, const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        Evaluation e;
+        e.width = judgments ? NVSM_EVAL_FIXED + 3 * (judgments->num_cutoffs > 0 ? judgments->num_cutoffs : 0) : 0;
+        e.ranking.top_k = opt.top_k;
+        const size_t Q = static_cast<size_t>(q.num_queries);
+        const size_t n = Q * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        e.metrics.resize(Q * static_cast<size_t>(e.width) + 1);
+        e.ranking.doc_ids.resize(n ? n : 1); e.ranking.scores.resize(n ? n : 1); e.ranking.counts.resize(Q + 1);
+        check(nvsm_rerank(h_, &q, &opt, &rr, judgments, judgments ? e.metrics.data() : nullptr, e.ranking.doc_ids.data(),
+                          e.ranking.scores.data(), e.ranking.counts.data()));
+        e.metrics.resize(Q * static_cast<size_t>(e.width));
+        e.ranking.doc_ids.resize(n); e.ranking.scores.resize(n); e.ranking.counts.resize(Q);
+        return e;
+    }
+
     // nvsm_lexical_rank_weighted: lexical_rank with a float32 weight >= 0 per query word (one per word id; a weight 0 drops its term)
     Ranking lexical_rank_weighted(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const std::vector<float>& word_weights,
                                   const nvsm_lexical_options& lex) {

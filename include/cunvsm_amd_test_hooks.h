@@ -203,6 +203,12 @@ typedef struct nvsm_debug_lazy_refresh_args {
     int scalars_only;
 } nvsm_debug_lazy_refresh_args;
 int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* args);
+/* The document-frequency pass of nvsm_tfidf_rank alone (csrc/lexical.hip: launch_lex_df) on a caller-supplied corpus, the documents in
+ * slabs of `slab` (1 .. 2^31 - 1; it need not be a multiple of 32 nor divide num_documents): df_out [num_words] = documents that
+ * hold each word. The bit table [num_words][(slab + 31) / 32] is the hook's own. Refused with NVSM_ERR_INVALID_ARGUMENT: offsets that
+ * do not start at 0, decrease or do not end at num_tokens; a token outside [0, num_words). */
+int nvsm_debug_lex_df(const int32_t* tokens, int64_t num_tokens, const int64_t* doc_offsets, int64_t num_documents, int64_t num_words,
+                      int64_t slab, int64_t* df_out);
 
 #ifdef __cplusplus
 }
