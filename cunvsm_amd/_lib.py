@@ -58,6 +58,10 @@ class NvsmBatch(C.Structure):
     ]
 
 
+class NvsmFoldOptions(C.Structure):
+    _fields_ = [("first_document", C.c_int64), ("reserved", C.c_int32 * 6)]
+
+
 class NvsmPairBatch(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("weights", C.c_void_p), ("num_pairs", C.c_int64), ("on_device", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
@@ -339,6 +343,10 @@ def lib():
         "nvsm_update": (C.c_int, [vp, C.c_float, C.c_float]), "nvsm_get_cost": (C.c_int, [vp, P(C.c_float)]), "nvsm_get_cost_f64": (C.c_int, [vp, P(C.c_double)]),
         "nvsm_scaled_regularization_lambda": (C.c_float, [vp]),
         "nvsm_step": (C.c_int, [vp, P(NvsmBatch), vp, C.c_float, P(C.c_float)]),
+        "nvsm_fold_options_default": (None, [P(NvsmFoldOptions)]),
+        "nvsm_step_fold": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmFoldOptions), C.c_float, P(C.c_float)]),
+        "nvsm_fold_summation": (None, [P(C.c_int32), P(C.c_int32)]),
+        "nvsm_get_param_rows": (C.c_int, [vp, cp, i64, i64, vp]), "nvsm_set_param_rows": (C.c_int, [vp, cp, i64, i64, vp]),
         "nvsm_compute_cost_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture)]),
         "nvsm_step_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture), C.c_float, P(C.c_float)]),
         "nvsm_compute_cost_term_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture)]),

@@ -254,6 +254,27 @@ int nvsm_step(nvsm_model* m, const nvsm_batch* batch, const int64_t* entity_ids,
     return guarded_on(m, [&] { m->impl.step(*batch, entity_ids, lr, cost); });
 }
 
+void nvsm_fold_options_default(nvsm_fold_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+}
+void nvsm_fold_summation(int32_t* chunk_entries, int32_t* group_chunks) {
+    if (chunk_entries) *chunk_entries = cunvsm::kFoldChunk;
+    if (group_chunks) *group_chunks = cunvsm::kFoldGroup;
+}
+int nvsm_step_fold(nvsm_model* m, const nvsm_batch* batch, const int64_t* entity_ids, const nvsm_fold_options* opt, float lr, float* cost) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(batch); NVSM_REQUIRE(opt);
+    return guarded_on(m, [&] { m->impl.step_fold(*batch, entity_ids, opt->first_document, lr, cost); });
+}
+int nvsm_get_param_rows(nvsm_model* m, const char* name, int64_t first_row, int64_t rows, float* dst) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(name); NVSM_REQUIRE(dst);
+    return guarded_on(m, [&] { m->impl.get_param_rows(name, first_row, rows, dst); });
+}
+int nvsm_set_param_rows(nvsm_model* m, const char* name, int64_t first_row, int64_t rows, const float* src) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(name); NVSM_REQUIRE(src);
+    return guarded_on(m, [&] { m->impl.set_param_rows(name, first_row, rows, src); });
+}
+
 int nvsm_compute_cost_mixed(nvsm_model* m, const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch* pairs, const nvsm_mixture* mix) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(pairs);
     if (text) NVSM_REQUIRE(mix);

@@ -493,6 +493,26 @@ bool table_pass_one_launch();                 // what set_table_pass_one_launch 
 // the constants of an Adam row pass (β₁ = 0.9, β₂ = 0.999, ε = 1e-6) for bias correction bc and scaled λ sl (model.cpp)
 void fill_adam_consts(RowPassArgs& a, float bc, float sl);
 
+// ---- fold-in (fold.hip; include/cunvsm_amd.h nvsm_step_fold): the documents update on the rows [first, rows) only ----
+// Reads row_begin / row_end / sorted_key / sorted_entry of the documents CSR and its own partial buffers; the row formula and its
+// constants are RowPassArgs' (kind: ROW_SGD, ROW_ADAGRAD_ENT, ROW_ADAM_SPARSE_ENT, ROW_ADAM_DENSE, ROW_ADAM_FULL). The per-row scalar
+// state is updated in place (a wave owns its row). Rows below `first` are neither read nor written.
+constexpr int kFoldChunk = 64;      // entries per chunk of a row's sum (a row of more entries is cut over several waves)
+constexpr int kFoldGroup = 32;      // chunk sums per second-stage group (rows of more chunks get group sums first)
+struct FoldArgs {
+    const int* sorted_key; const int* sorted_entry; const int* row_begin; const int* row_end;
+    int64_t n, rows, first;             // entries of the batch, rows of the table, first row that trains
+    const float* X; const float* coefs; const float* sq_src;      // proj [B][dim], coef [n], pp [B] (null: the kind has no q)
+    uint64_t div_magic;                 // as RowPassArgs: src = (entry * div_magic) >> 37
+    float* P; float* m; float* v; float* sc;
+    int dim, kind, dense;
+    float lr, decay, lambda, one_m_b1, s_m, one_m_b2, s_v, bc, eps, c_reg;
+    float* partial; float* partial_q;   // [chunk_rows][dim], [chunk_rows]    } fold_partial_rows(max entries)
+    float* partial2; float* partial2_q; // [group_rows][dim], [group_rows]    }
+};
+void fold_partial_rows(int64_t max_entries, size_t* chunk_rows, size_t* group_rows);
+void launch_fold_update(const FoldArgs& f, hipStream_t s);
+
 // words, window > 1 (cpp/updates_adagrad.cu:83-97, cpp/updates_adam.cu:132-151)
 void launch_adagrad_scale(const float* acc, const int* idx, int window, int64_t B, float eps, float* scale, hipStream_t s);
 void launch_adam_u(const float* m, const float* v, int dim, const int* idx, int window, int64_t B, float bc, float eps,

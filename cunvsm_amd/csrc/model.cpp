@@ -1958,6 +1958,74 @@ void Model::update_entities(float lr, float sl, hipStream_t strm, hipEvent_t row
     lazy_end_update(t, c, strm);
 }
 
+// ---- fold-in (nvsm_step_fold; fold.hip) -------------------------------------------------------------------
+// compute_cost as it is — same kernels, same sampler, same loss word —, then update_entities' row formula and constants on the rows
+// [n0, num_entities) only, by fold.hip's kernels on the main stream. Nothing else of a step runs: with W, T and b fixed there is no
+// gradient upstream of the loss (no batch-norm backward, no dx / dT product, no words chain, no projection update, no plane re-cut).
+void Model::step_fold(const nvsm_batch& batch, const int64_t* entity_ids, int64_t n0, float lr, float* cost) {
+    if (cfg_.world_size > 1) throw Error(NVSM_ERR_UNSUPPORTED, "nvsm_step_fold: world_size > 1 is not supported");
+    if (cfg_.l2_normalize_entity_reprs) throw Error(NVSM_ERR_UNSUPPORTED, "nvsm_step_fold: l2_normalize_entity_reprs is not supported");
+    if (n0 < 0 || n0 > cfg_.num_entities)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "nvsm_step_fold: first_document must be in [0, num_entities]");
+    if (!(lr >= 0.f)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "learning_rate must be >= 0");
+    forward(ForwardRequest{&batch, nullptr, entity_ids});
+    const float sl = scaled_regularization_lambda();
+    TableState& t = ents_;
+    if (n0 < t.rows) {
+        RangeScope range_up("UpdateParameters");
+        // the main stream behind the CSR builds (the loss kernel in front of this has joined the previous documents update)
+        NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_ents_, 0));
+        NVSM_HIP_CHECK(hipStreamWaitEvent(stream_, ev_csr_, 0));
+        csr_joined_ents_ = csr_joined_words_ = true;
+        // A lazily decayed table: a fold step may not leave pending factors on frozen rows, so it adds none — no entry of the factor
+        // history, no update counted — and writes the new rows as they are. That is only right on rows that are current: the table is
+        // brought up to date once when a fold step follows an ordinary update (every stamp then equals updates_done, and stays so).
+        if (t.lazy && fold_current_at_ != t.updates_done) {
+            lazy_refresh(t, nullptr, stream_);
+            fold_current_at_ = t.updates_done;
+        }
+        if (!fold_partial_.p) {
+            size_t chunk_rows = 0, group_rows = 0;
+            fold_partial_rows(static_cast<int64_t>(cfg_.max_batch_size) * R_, &chunk_rows, &group_rows);
+            fold_partial_.alloc(chunk_rows * t.dim); fold_partial_q_.alloc(chunk_rows);
+            fold_partial2_.alloc(group_rows * t.dim); fold_partial2_q_.alloc(group_rows);
+        }
+        const Csr c = csr_of(t, B_ * R_);
+        RowPassArgs a{};      // the constants, exactly as update_entities sets them
+        a.lr = lr; a.lambda = sl; a.eps = 1e-6f;
+        a.decay = sl > 0.f ? static_cast<float>(1.0 - static_cast<double>(sl) * static_cast<double>(lr)) : 1.f;
+        a.sq_src = pp_.p;
+        switch (cfg_.update_method) {
+            case NVSM_SGD: a.kind = ROW_SGD; a.sq_src = nullptr; a.dense = sl > 0.f; break;
+            case NVSM_ADAGRAD: a.kind = ROW_ADAGRAD_ENT; a.dense = 1; break;
+            default: {
+                fill_adam_consts(a, adam_bc(t.t), sl);
+                t.t += 1;
+                a.dense = 1;
+                if (cfg_.adam_mode == NVSM_ADAM_DENSE_UPDATE) a.kind = ROW_ADAM_DENSE;
+                else if (cfg_.adam_mode == NVSM_ADAM_DENSE_UPDATE_DENSE_VARIANCE) { a.kind = ROW_ADAM_FULL; a.sq_src = nullptr; a.decay = 1.f; }
+                else a.kind = ROW_ADAM_SPARSE_ENT;
+            }
+        }
+        FoldArgs f{};
+        f.sorted_key = c.sorted_key; f.sorted_entry = c.sorted_entry; f.row_begin = c.row_begin; f.row_end = c.row_end;
+        f.n = c.n; f.rows = t.rows; f.first = n0;
+        f.X = proj_.p; f.coefs = coef_.p; f.sq_src = a.sq_src;
+        f.div_magic = (uint64_t(1) << 37) / static_cast<uint32_t>(R_) + 1;
+        f.P = t.P.p; f.m = t.m.p; f.v = t.vfull.p; f.sc = t.sc[t.sc_cur].p;
+        f.dim = t.dim; f.kind = a.kind; f.dense = a.dense;
+        f.lr = a.lr; f.decay = a.decay; f.lambda = a.lambda; f.one_m_b1 = a.one_m_b1; f.s_m = a.s_m; f.one_m_b2 = a.one_m_b2; f.s_v = a.s_v;
+        f.bc = a.bc; f.eps = a.eps; f.c_reg = a.c_reg;
+        f.partial = fold_partial_.p; f.partial_q = fold_partial_q_.p; f.partial2 = fold_partial2_.p; f.partial2_q = fold_partial2_q_.p;
+        {
+            PROF("fold_update");
+            launch_fold_update(f, stream_);
+        }
+        NVSM_HIP_CHECK(hipGetLastError());
+    }
+    if (cost) *cost = get_cost();
+}
+
 // what the LAST pass of an SGD / Adagrad words update looks like to the rows without entries (launch_untouched_rows): P *= decay
 RowPassArgs Model::final_words_pass_args(float lr, float sl) {
     RowPassArgs a{};
@@ -2837,6 +2905,30 @@ void Model::set_param(const std::string& name, const float* src, int64_t count) 
     lazy_flush_all();
     NVSM_HIP_CHECK(hipMemcpy(r.p, src, count * sizeof(float), hipMemcpyHostToDevice));
     planes_stale();
+}
+
+// rows of the two embedding tables and of their per-row optimiser state: [rows][dim] arrays, or one scalar per row
+Model::RowsRef Model::find_param_rows(const std::string& name, int64_t first_row, int64_t rows) {
+    const bool words = name.rfind("word_representations", 0) == 0, ents = name.rfind("entity_representations", 0) == 0;
+    ParamRef r = (words || ents) ? find_param(name) : ParamRef{nullptr, 0};
+    if (!r.p) throw Error(NVSM_ERR_INVALID_ARGUMENT, "not a table parameter with rows: " + name);
+    const TableState& t = words ? words_ : ents_;
+    const int64_t width = r.n / t.rows;      // dim, or 1 for the per-row scalars
+    if (first_row < 0 || rows < 0 || first_row > t.rows || rows > t.rows - first_row)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "row range outside the table for " + name);
+    return {r.p + first_row * width, rows, width};
+}
+void Model::get_param_rows(const std::string& name, int64_t first_row, int64_t rows, float* dst) {
+    RowsRef r = find_param_rows(name, first_row, rows);
+    synchronize();
+    lazy_flush_all();
+    if (r.rows > 0) NVSM_HIP_CHECK(hipMemcpy(dst, r.p, r.rows * r.width * sizeof(float), hipMemcpyDeviceToHost));
+}
+void Model::set_param_rows(const std::string& name, int64_t first_row, int64_t rows, const float* src) {
+    RowsRef r = find_param_rows(name, first_row, rows);
+    synchronize();
+    lazy_flush_all();
+    if (r.rows > 0) NVSM_HIP_CHECK(hipMemcpy(r.p, src, r.rows * r.width * sizeof(float), hipMemcpyHostToDevice));
 }
 
 void Model::increment_param(const std::string& name, int64_t index, float delta) {

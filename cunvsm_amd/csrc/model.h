@@ -161,6 +161,9 @@ class Model {
     double cost_f64() const { return cost_; }      // valid after get_cost()
     float scaled_regularization_lambda() const;
     void step(const nvsm_batch& batch, const int64_t* entity_ids, float lr, float* cost);
+    // fold-in (include/cunvsm_amd.h nvsm_step_fold; fold.hip): compute_cost, then the documents update on the rows
+    // [first_document, num_entities) alone — W, T, b and the rows below keep their logical values bit for bit
+    void step_fold(const nvsm_batch& batch, const int64_t* entity_ids, int64_t first_document, float lr, float* cost);
     // the entity-entity similarity objective alone (text null) or mixed into the text objective (TextEntityEntityEntity,
     // cpp/objective.cu:698-745): see "entity-entity pairs" below
     void compute_cost_mixed(const nvsm_batch* text, const int64_t* entity_ids, const nvsm_pair_batch& pairs, const nvsm_mixture* mix);
@@ -179,6 +182,9 @@ class Model {
     int64_t param_size(const std::string& name);
     void get_param(const std::string& name, float* dst, int64_t count);
     void set_param(const std::string& name, const float* src, int64_t count);
+    // rows [first_row, first_row + rows) of an embedding table or of its per-row optimiser state
+    void get_param_rows(const std::string& name, int64_t first_row, int64_t rows, float* dst);
+    void set_param_rows(const std::string& name, int64_t first_row, int64_t rows, const float* src);
     void increment_param(const std::string& name, int64_t index, float delta);
     int64_t tensor_size(const std::string& name);
     void get_tensor(const std::string& name, float* dst, int64_t count);
@@ -247,6 +253,10 @@ class Model {
  private:
     struct ParamRef { float* p; int64_t n; };
     ParamRef find_param(const std::string& name);
+    struct RowsRef { float* p; int64_t rows, width; };
+    RowsRef find_param_rows(const std::string& name, int64_t first_row, int64_t rows);      // throws unless a table's rows, in range
+    DevBuf<float> fold_partial_, fold_partial_q_, fold_partial2_, fold_partial2_q_;          // fold.hip's partial sums: allocated by the first fold step
+    int fold_current_at_ = -1;            // ents_.updates_done when a fold step last brought the lazily decayed documents table up to date
     void build_csr(TableState& t, const int* keys, int64_t n, hipStream_t s, int64_t n_pair_entries = 0);
     void alloc_table_csr(TableState& t, int64_t max_entries, bool chunk_order);
     Csr csr_of(TableState& t, int64_t n);

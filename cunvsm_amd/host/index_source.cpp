@@ -143,8 +143,8 @@ class IndexSource::WindowFeeder {
             for (size_t j = 0; j < window_; ++j) ids[j] = static_cast<WordIdxType>(src[j]);
             if (!term_weight_.empty())
                 for (size_t j = 0; j < window_; ++j) per_term[j] = term_weight_[static_cast<size_t>(src[j])];
-            owner_->push_window(ids.data(), term_weight_.empty() ? nullptr : per_term.data(), static_cast<ObjectIdxType>(ref.doc),
-                                instance_weight_[ref.doc], batch);
+            owner_->push_window(ids.data(), term_weight_.empty() ? nullptr : per_term.data(),
+                                static_cast<ObjectIdxType>(ref.doc + owner_->label_offset_), instance_weight_[ref.doc], batch);
         }
     }
 
@@ -260,10 +260,82 @@ IndexSource::IndexSource(IndexInterface* index, size_t window_size, RNG* rng, si
     if (weighting_strategy == AUTOMATIC_WEIGHTING) weighting_strategy = sampling_strategy == NONE ? INV_DOC_FREQUENCY : UNIFORM;
     choose_documents(documents_cutoff, document_list);
     choose_vocabulary(max_vocabulary_size, min_document_frequency, max_document_frequency, include_digits, term_blacklist);
+    start_feeder(shuffle, sampling_strategy, weighting_strategy, rng);
+}
+
+void IndexSource::start_feeder(bool shuffle, SamplingStrategy sampling_strategy, WeightingStrategy weighting_strategy, RNG* rng) {
     WindowFeeder::Order order = WindowFeeder::DOCUMENT_ORDER;
     if (shuffle) order = sampling_strategy == NONE ? WindowFeeder::ALL_WINDOWS_SHUFFLED : WindowFeeder::SAMPLED_POSITIONS_SHUFFLED;
     else NVSM_CHECK(sampling_strategy == NONE);                    // sampling positions without shuffling is refused (:873-875)
     feeder_.reset(new WindowFeeder(this, order, weighting_strategy == INV_DOC_FREQUENCY, rng));
+}
+
+static bool maps_index_term_zero(const std::vector<Metadata::TermInfo>& terms) {
+    for (const Metadata::TermInfo& t : terms) if (t.index_term_id == 0) return true;
+    return false;
+}
+
+IndexSource::IndexSource(IndexInterface* index, size_t window_size, RNG* rng, const FoldIn& fold, bool shuffle,
+                         SamplingStrategy sampling_strategy, WeightingStrategy weighting_strategy, TermWeightingStrategy term_weighting_strategy)
+    : DataSource(0, 0), index_(index), window_(window_size), oov_token_(maps_index_term_zero(fold.terms)), term_weighting_(term_weighting_strategy),
+      label_offset_(fold.label_offset) {
+    NVSM_CHECK(index_.get() != nullptr);
+    if (sampling_strategy == AUTOMATIC_SAMPLING) sampling_strategy = shuffle ? NGRAM_FREQUENCY : NONE;
+    if (weighting_strategy == AUTOMATIC_WEIGHTING) weighting_strategy = sampling_strategy == NONE ? INV_DOC_FREQUENCY : UNIFORM;
+    // the documents as given: local ids 0, 1, ... in the given order (labels add the offset)
+    NVSM_CHECK(!fold.documents.empty()) << "fold-in without documents";
+    index_document_length_.assign(fold.documents.size(), 0);
+    size_t length_sum = 0;
+    for (const DOCID_T d : fold.documents) {
+        const int64_t length = index_->documentLength(d);
+        NVSM_CHECK(length >= static_cast<int64_t>(window_)) << "document " << d << " is shorter than a window";
+        const size_t local = index_doc_of_.size();
+        index_doc_of_.emplace(local, d);
+        index_document_length_[local] = length;
+        length_sum += static_cast<size_t>(length);
+    }
+    corpus_size_ = index_doc_of_.size();
+    NVSM_CHECK(corpus_size_ == fold.documents.size()) << "a document is named twice";
+    mean_index_document_length_ = length_sum / static_cast<WeightType>(index_doc_of_.size());
+    // the vocabulary as given
+    NVSM_CHECK(!fold.terms.empty() && fold.total_terms > 0) << "fold-in without a vocabulary";
+    for (const Metadata::TermInfo& t : fold.terms) {
+        NVSM_CHECK(t.model_term_id >= 0 && t.term_frequency > 0) << "bad term " << t.index_term_id << " in the fold-in vocabulary";
+        NVSM_CHECK(model_term_of_.emplace(static_cast<TERMID_T>(t.index_term_id), static_cast<size_t>(t.model_term_id)).second);
+        NVSM_CHECK(index_term_of_.emplace(static_cast<size_t>(t.model_term_id), static_cast<TERMID_T>(t.index_term_id)).second);
+        frequency_of_model_term_.emplace(static_cast<size_t>(t.model_term_id), static_cast<int64_t>(t.term_frequency));
+    }
+    corpus_term_occurrences_ = static_cast<size_t>(fold.total_terms);
+    vocabulary_size_ = model_term_of_.size();
+    start_feeder(shuffle, sampling_strategy, weighting_strategy, rng);
+}
+
+std::vector<DOCID_T> fold_in_new_documents(IndexInterface* index, const Metadata& meta, const std::vector<std::string>* document_list,
+                                           size_t window_size) {
+    std::set<DOCID_T> known;
+    for (const Metadata::ObjectInfo& o : meta.object) known.insert(static_cast<DOCID_T>(o.index_object_id));
+    std::vector<DOCID_T> candidates;
+    if (document_list != nullptr) {
+        candidates = index->documentIDsFromDocno(*document_list);
+        NVSM_CHECK(candidates.size() == document_list->size());
+        std::sort(candidates.begin(), candidates.end());
+        candidates.erase(std::unique(candidates.begin(), candidates.end()), candidates.end());
+    } else {
+        for (DOCID_T d = index->documentBase(), end = index->documentMaximum(); d < end; ++d) candidates.push_back(d);
+    }
+    std::vector<DOCID_T> fresh;
+    size_t too_short = 0;
+    for (const DOCID_T d : candidates) {
+        if (known.count(d)) continue;
+        if (index->documentLength(d) < static_cast<int64_t>(window_size)) { ++too_short; continue; }
+        fresh.push_back(d);
+    }
+    if (fresh.empty())
+        NVSM_LOG(FATAL) << "fold-in: no new documents: the meta file names every document " << (document_list ? "of the document list" : "of the index")
+                        << " that is at least a window long (" << too_short << " are shorter).";
+    NVSM_LOG(INFO) << "Fold-in: " << fresh.size() << " new documents (" << too_short << " discarded as too short, " << known.size()
+                   << " already in the model).";
+    return fresh;
 }
 
 IndexSource::~IndexSource() {}
@@ -395,7 +467,7 @@ void IndexSource::extract_metadata(Metadata* metadata) const {                  
     metadata->total_terms = static_cast<int32_t>(corpus_term_occurrences_);
     for (const auto& d : index_doc_of_) {
         Metadata::ObjectInfo o;
-        o.model_object_id = static_cast<int32_t>(d.first);
+        o.model_object_id = static_cast<int32_t>(d.first + label_offset_);
         o.index_object_id = static_cast<int32_t>(d.second);
         metadata->object.push_back(o);
     }
@@ -409,7 +481,7 @@ std::map<std::string, int64_t> IndexSource::build_term_identifiers_map() const {
 
 std::map<std::string, int64_t> IndexSource::build_document_identifiers_map() const {   // :571-589
     std::map<std::string, int64_t> by_docno;
-    for (const auto& d : index_doc_of_) NVSM_CHECK(by_docno.emplace(index_->docno(d.second), static_cast<int64_t>(d.first)).second);
+    for (const auto& d : index_doc_of_) NVSM_CHECK(by_docno.emplace(index_->docno(d.second), static_cast<int64_t>(d.first + label_offset_)).second);
     return by_docno;
 }
 

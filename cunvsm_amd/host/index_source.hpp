@@ -20,6 +20,7 @@
 
 #include "data.hpp"
 #include "index.hpp"
+#include "metadata.hpp"
 
 namespace nvsm_host {
 
@@ -41,6 +42,20 @@ class IndexSource : public DataSource {
                 bool shuffle = false, SamplingStrategy sampling_strategy = AUTOMATIC_SAMPLING,
                 WeightingStrategy weighting_strategy = AUTOMATIC_WEIGHTING,
                 TermWeightingStrategy term_weighting_strategy = UNIFORM_TERM_WEIGHTING);
+    // Fold-in (cuNVSMTrainModel --fold_in): windows of a CHOSEN set of documents under a FIXED term mapping. Nothing is selected: the
+    // vocabulary is `terms` (a checkpoint's meta file: the same model term ids, its term frequencies and total_terms for the
+    // self-information weights; the out-of-vocabulary token exists exactly when index term 0 is mapped), the documents are
+    // `documents` (index ids, each at least a window long), and document i carries the label label_offset + i. Weighting, sampling
+    // and shuffling are what the constructor above does for a collection that consists of these documents. Takes ownership of `index`.
+    struct FoldIn {
+        std::vector<Metadata::TermInfo> terms;
+        int64_t total_terms = 0;
+        std::vector<DOCID_T> documents;
+        size_t label_offset = 0;
+    };
+    IndexSource(IndexInterface* index, size_t window_size, RNG* rng, const FoldIn& fold, bool shuffle = false,
+                SamplingStrategy sampling_strategy = AUTOMATIC_SAMPLING, WeightingStrategy weighting_strategy = AUTOMATIC_WEIGHTING,
+                TermWeightingStrategy term_weighting_strategy = UNIFORM_TERM_WEIGHTING);
     ~IndexSource() override;
 
     void reset() override;                 // next epoch: re-draws / re-shuffles with the shared generator
@@ -52,7 +67,8 @@ class IndexSource : public DataSource {
     int64_t term_id(const std::string& term) const;            // model term id or -1
     std::string term(int64_t model_term_id) const;
     const TermIdMapping& term_id_mapping() const { return model_term_of_; }
-    const DocumentIdMapping& document_id_mapping() const { return index_doc_of_; }
+    const DocumentIdMapping& document_id_mapping() const { return index_doc_of_; }      // keyed without the fold-in's label offset
+    size_t label_offset() const { return label_offset_; }
     const std::map<size_t, int64_t>& term_frequencies() const { return frequency_of_model_term_; }
     size_t window_size() const { return window_; }
     size_t total_num_terms() const { return corpus_term_occurrences_; }
@@ -102,7 +118,14 @@ class IndexSource : public DataSource {
     std::vector<int64_t> index_document_length_;           // by model document id
     std::map<TERMID_T, size_t> occurrences_;               // term occurrences inside the chosen documents (built on demand)
     bool occurrences_counted_ = false;
+    size_t label_offset_ = 0;              // fold-in: added to every label (and to the model ids of extract_metadata and the docno map)
+    void start_feeder(bool shuffle, SamplingStrategy sampling_strategy, WeightingStrategy weighting_strategy, RNG* rng);
     std::unique_ptr<WindowFeeder> feeder_;
 };
+
+// --fold_in: the documents a model is grown by — of `document_list` (docnos; null: every document of the index) those the meta file
+// does not name and that are at least a window long, in INDEX order whatever the list's. A docno the index does not know is fatal, and so is a result without documents.
+std::vector<DOCID_T> fold_in_new_documents(IndexInterface* index, const Metadata& meta, const std::vector<std::string>* document_list,
+                                           size_t window_size);
 
 }  // namespace nvsm_host

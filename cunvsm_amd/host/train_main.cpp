@@ -28,6 +28,13 @@
 //     8 bytes per window, slices of the epoch plan in page-locked memory — instead of as a 132-byte-per-window host batch
 //     (nvsm_step_windows_deferred). The epochs, the random stream, the skip rule, the log lines and every number are those of the run
 //     without the flag. Refused together with a similarity file, with --check_gradients and under data parallelism.
+//   * --fold_in <model_base>_<epoch>.hdf5: new documents are folded into a trained model. The vocabulary is the meta
+//     file's (no selection runs; --max_vocabulary_size, --min_document_frequency and --max_document_frequency are ignored), model
+//     documents [0, n_old) are the meta file's, the documents of the index (or of --document_list) it does not name follow in index
+//     order, windows come from the new documents only and every step is nvsm_step_fold with first_document = n_old. The new rows are
+//     Glorot draws of std::minstd_rand0(--seed) at the grown table's bound. Writes <output>_meta (terms unchanged, old objects then
+//     new ones) and <output>_<epoch>.hdf5. Refused with --device_corpus, data parallelism, either similarity weight,
+//     --l2_entity_normalization and --check_gradients.
 //   * extensions: --stopwords, --device, --sampler {host,device}, --allow_ragged_batches, and data parallelism over RCCL
 //     (--gpus N spawns one process per GPU; or --world_size / --rank [or WORLD_SIZE / RANK / LOCAL_RANK] under any launcher).
 #include <sys/stat.h>
@@ -51,6 +58,7 @@
 #include "index_source.hpp"
 #include "indri_index.hpp"
 #include "pair_source.hpp"
+#include "query_lib.hpp"
 #include "rendezvous.hpp"
 #include "trectext_index.hpp"
 
@@ -61,7 +69,7 @@ namespace {
 uint64_t FLAGS_num_epochs, FLAGS_document_cutoff, FLAGS_word_repr_size, FLAGS_entity_repr_size, FLAGS_batch_size, FLAGS_window_size,
     FLAGS_num_random_entities, FLAGS_seed, FLAGS_max_vocabulary_size, FLAGS_min_document_frequency;
 std::string FLAGS_document_list, FLAGS_term_blacklist, FLAGS_update_method, FLAGS_weighting, FLAGS_feature_weighting, FLAGS_nonlinearity,
-    FLAGS_output, FLAGS_stopwords, FLAGS_sampler, FLAGS_term_similarities;
+    FLAGS_output, FLAGS_stopwords, FLAGS_sampler, FLAGS_term_similarities, FLAGS_fold_in;
 double FLAGS_regularization_lambda, FLAGS_learning_rate, FLAGS_max_document_frequency, FLAGS_entity_similarity_weight,
     FLAGS_term_similarity_weight;
 bool FLAGS_bias_negative_samples, FLAGS_l2_phrase_normalization, FLAGS_l2_entity_normalization, FLAGS_batch_normalization,
@@ -130,6 +138,10 @@ void define_flags(Flags* f) {      // names, defaults and help strings of cpp/ma
     f->define_bool("device_corpus", &FLAGS_device_corpus, false, "Put the collection into GPU memory once and train from window references (8 bytes per "
                    "window) instead of host batches (132 bytes per window at window size 10). Same epochs, same random stream, same results. "
                    "Single GPU, text-entity objective only.");
+    f->define_string("fold_in", &FLAGS_fold_in, "", "Fold new documents into a trained model: <model_base>_<epoch>.hdf5 of a checkpoint whose "
+                     "<model_base>_meta lies next to it. The vocabulary, the word table, the projection and the rows of the checkpoint's documents stay "
+                     "as they are; the documents of the index (or of --document_list) that the meta file does not name get rows of their own, "
+                     "trained on their windows (nvsm_step_fold). The model flags must describe the checkpoint. Single GPU, text-entity objective only.");
     // glog's own options that the reference's scripts pass
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
     f->define_bool("alsologtostderr", &FLAGS_alsologtostderr, true, "Accepted for compatibility.");
@@ -200,6 +212,9 @@ class Trainer {
     // --device_corpus: the epochs are drawn from `source` as window references into the corpus uploaded to the model; the data source
     // handed to iterate_data is that same object (has_next / progress)
     void train_from_refs(IndexSource* source) { ref_source_ = source; }
+
+    // --fold_in: every training step is nvsm_step_fold with this first_document
+    void fold_from(int64_t first_document) { fold_first_ = first_document; }
 
     // DumpModelFn (cpp/main.cu:335-364) + write_to_hdf5 (include/cuNVSM/lse_hdf5_inl.h)
     void dump_model(size_t epoch, const std::string& identifier) {
@@ -316,6 +331,11 @@ class Trainer {
                     // gradients at ε = 1e-4; ε = 1e-2 keeps the same 10 % threshold meaningful for every parameter.
                     NVSM_CHECK(check_gradients(b, cost, 1e-2f, 1e-1f)) << "Gradient check failed.";
                     if (backpropagate) NVSM_CALL(nvsm_update(model_, tc_.learning_rate, nvsm_scaled_regularization_lambda(model_)));
+                } else if (backpropagate && fold_first_ >= 0) {
+                    nvsm_fold_options fo;
+                    nvsm_fold_options_default(&fo);
+                    fo.first_document = fold_first_;
+                    NVSM_CALL(nvsm_step_fold(model_, &b, nullptr, &fo, tc_.learning_rate, &cost));
                 } else if (backpropagate) {
                     // compute_cost → compute_gradients → update(lr, scaled λ) → get_cost (cpp/main.cu:405-444) as ONE call:
                     // same arithmetic, the independent halves of the backward pass overlapped on two streams
@@ -450,6 +470,7 @@ class Trainer {
     int world_size_, rank_;
     uint64_t windows_ = 0;
     IndexSource* ref_source_ = nullptr;
+    int64_t fold_first_ = -1;
     RepeatingPairSource* pair_source_ = nullptr;
     RNG* pair_rng_ = nullptr;
     bool term_pairs_ = false;
@@ -494,6 +515,18 @@ int run(int argc, char** argv) {
             NVSM_LOG(FATAL) << "--device_corpus cannot be combined with a similarity file: window references cover the text-entity objective only.";
         if (!FLAGS_term_similarities.empty() && FLAGS_term_similarity_weight != 0.0)
             NVSM_LOG(FATAL) << "--device_corpus cannot be combined with --term_similarities: window references cover the text-entity objective only.";
+    }
+
+    const bool fold_in = !FLAGS_fold_in.empty();
+    if (fold_in) {      // (before anything is spawned or indexed)
+        const char* ws = std::getenv("WORLD_SIZE");
+        if (FLAGS_device_corpus) NVSM_LOG(FATAL) << "--fold_in cannot be combined with --device_corpus: a fold-in trains from host batches.";
+        if (FLAGS_gpus > 1 || FLAGS_world_size > 1 || (FLAGS_world_size == 0 && ws && std::atoll(ws) > 1))
+            NVSM_LOG(FATAL) << "--fold_in is not implemented under data parallelism (--gpus / --world_size > 1).";
+        if (FLAGS_entity_similarity_weight != 0.0 || FLAGS_term_similarity_weight != 0.0)
+            NVSM_LOG(FATAL) << "--fold_in trains the text-entity objective only: --entity_similarity_weight and --term_similarity_weight must be 0.";
+        if (FLAGS_l2_entity_normalization) NVSM_LOG(FATAL) << "--fold_in cannot be combined with --l2_entity_normalization.";
+        if (FLAGS_check_gradients) NVSM_LOG(FATAL) << "--fold_in cannot be combined with --check_gradients: the frozen parameters have no gradient to check.";
     }
 
     // ---- data parallelism: --gpus N spawns the ranks; otherwise world size / rank come from the flags or the launcher's environment
@@ -663,10 +696,47 @@ int run(int argc, char** argv) {
         NVSM_LOG(INFO) << "Reading term blacklist from " << FLAGS_term_blacklist << ".";
         term_blacklist.reset(read_strings<IndexSource::TermBlacklist>(FLAGS_term_blacklist));
     }
-    IndexSource* index_source = new IndexSource(
-        index.release(), tc.window_size, &rng, FLAGS_max_vocabulary_size, FLAGS_min_document_frequency, max_document_frequency,
-        FLAGS_document_cutoff, FLAGS_include_oov, false /* include_digits */, document_list.get(), term_blacklist.get(),
-        !tc.no_shuffle, AUTOMATIC_SAMPLING, WEIGHTING_STRATEGIES.at(FLAGS_weighting), FEATURE_WEIGHTING_STRATEGIES.at(FLAGS_feature_weighting));
+    // --fold_in: the checkpoint — its meta file is the vocabulary and the documents [0, n_old) —, then a source over the new documents
+    Metadata old_meta;
+    std::vector<Hdf5Array> old_params;
+    int64_t n_old = 0;
+    IndexSource* index_source = nullptr;
+    if (fold_in) {
+        static const char* kNames[4] = {"word_representations-representations", "entity_representations-representations",
+                                        "word_entity_mapping-transform", "word_entity_mapping-bias"};
+        const ModelPath where = split_model_path(FLAGS_fold_in);
+        {
+            std::ifstream f(where.meta_path, std::ios::binary);
+            std::stringstream wire;
+            wire << f.rdbuf();
+            NVSM_CHECK(f.good() && old_meta.ParseFromString(wire.str())) << "cannot parse " << where.meta_path;
+        }
+        old_params = read_hdf5(FLAGS_fold_in, {kNames[0], kNames[1], kNames[2], kNames[3]});
+        const Hdf5Array &W = old_params[0], &E = old_params[1], &T = old_params[2], &b = old_params[3];
+        n_old = static_cast<int64_t>(E.dim0);
+        if (W.dim1 != FLAGS_word_repr_size) NVSM_LOG(FATAL) << FLAGS_fold_in << " holds " << W.dim1 << "-dimensional word rows: --word_repr_size " << FLAGS_word_repr_size << " does not describe it.";
+        if (E.dim1 != FLAGS_entity_repr_size) NVSM_LOG(FATAL) << FLAGS_fold_in << " holds " << E.dim1 << "-dimensional document rows: --entity_repr_size " << FLAGS_entity_repr_size << " does not describe it.";
+        if (T.dim0 != W.dim1 || T.dim1 != E.dim1) NVSM_LOG(FATAL) << FLAGS_fold_in << ": the transform is " << T.dim0 << " x " << T.dim1 << ", expected " << W.dim1 << " x " << E.dim1;
+        if (b.dim0 * b.dim1 != E.dim1) NVSM_LOG(FATAL) << FLAGS_fold_in << ": the bias holds " << b.dim0 * b.dim1 << " values, expected " << E.dim1;
+        if (W.dim0 != old_meta.term_size()) NVSM_LOG(FATAL) << FLAGS_fold_in << " holds " << W.dim0 << " word rows, " << where.meta_path << " names " << old_meta.term_size() << " terms.";
+        if (E.dim0 != old_meta.object_size()) NVSM_LOG(FATAL) << FLAGS_fold_in << " holds " << E.dim0 << " document rows, " << where.meta_path << " names " << old_meta.object_size() << " objects.";
+        (void)build_mappings(old_meta, static_cast<int64_t>(W.dim0), n_old);      // ids unique and inside the tables, or fatal
+        for (size_t i = 0; i < old_meta.object.size(); ++i)
+            NVSM_CHECK(old_meta.object[i].model_object_id == static_cast<int32_t>(i)) << where.meta_path << " does not list its objects in model order";
+        NVSM_LOG(INFO) << "Folding into " << FLAGS_fold_in << " (epoch " << where.epoch << "): the vocabulary is the meta file's (" << old_meta.term_size()
+                       << " terms); --max_vocabulary_size, --min_document_frequency and --max_document_frequency are ignored.";
+        IndexSource::FoldIn fold;
+        fold.terms = old_meta.term; fold.total_terms = old_meta.total_terms;
+        fold.documents = fold_in_new_documents(index.get(), old_meta, document_list.get(), tc.window_size);
+        fold.label_offset = static_cast<size_t>(n_old);
+        index_source = new IndexSource(index.release(), tc.window_size, &rng, fold, !tc.no_shuffle, AUTOMATIC_SAMPLING,
+                                       WEIGHTING_STRATEGIES.at(FLAGS_weighting), FEATURE_WEIGHTING_STRATEGIES.at(FLAGS_feature_weighting));
+    } else {
+        index_source = new IndexSource(
+            index.release(), tc.window_size, &rng, FLAGS_max_vocabulary_size, FLAGS_min_document_frequency, max_document_frequency,
+            FLAGS_document_cutoff, FLAGS_include_oov, false /* include_digits */, document_list.get(), term_blacklist.get(),
+            !tc.no_shuffle, AUTOMATIC_SAMPLING, WEIGHTING_STRATEGIES.at(FLAGS_weighting), FEATURE_WEIGHTING_STRATEGIES.at(FLAGS_feature_weighting));
+    }
     // construct_data_source<TextEntityEntityEntity::Objective> (:281-306): the docno -> model document id map of the index source,
     // then the shuffled pair source (its first shuffle draws from `rng` HERE, behind the index source's and before the model's
     // initialisation) inside RepeatingSource(-1)
@@ -698,6 +768,11 @@ int run(int argc, char** argv) {
 
     Metadata meta;
     data_source->extract_metadata(&meta);
+    if (fold_in) {      // the grown model: the terms unchanged, the old objects followed by the new ones
+        Metadata grown = old_meta;
+        for (const Metadata::ObjectInfo& o : meta.object) grown.object.push_back(o);
+        meta = grown;
+    }
     const size_t vocabulary_size = meta.term_size(), corpus_size = meta.object_size();
     NVSM_CHECK(vocabulary_size > 0);
     NVSM_CHECK(corpus_size > 0);
@@ -751,10 +826,30 @@ int run(int argc, char** argv) {
     }
     // model.initialize(rng): the SAME generator the data source has just drawn from (cpp/main.cu:497-520)
     NVSM_CALL(nvsm_rng_set_state(model, rng_state(rng)));
-    NVSM_CALL(nvsm_initialize_from_rng_state(model));
+    if (fold_in) {
+        // the checkpoint as it is, and Glorot's U(-a, a) for the new rows at the bound of the GROWN table (what nvsm_initialize
+        // uses for such a model), drawn from std::minstd_rand0(seed) in row-major order
+        const Hdf5Array &W = old_params[0], &E = old_params[1], &T = old_params[2], &b = old_params[3];
+        NVSM_CHECK(static_cast<size_t>(n_old) < corpus_size);
+        NVSM_CALL(nvsm_set_param(model, "word_representations-representations", W.data.data(), static_cast<int64_t>(W.data.size())));
+        NVSM_CALL(nvsm_set_param(model, "word_entity_mapping-transform", T.data.data(), static_cast<int64_t>(T.data.size())));
+        NVSM_CALL(nvsm_set_param(model, "word_entity_mapping-bias", b.data.data(), static_cast<int64_t>(b.data.size())));
+        NVSM_CALL(nvsm_set_param_rows(model, "entity_representations-representations", 0, n_old, E.data.data()));
+        const size_t de = static_cast<size_t>(FLAGS_entity_repr_size), fresh_rows = corpus_size - static_cast<size_t>(n_old);
+        std::vector<float> fresh(fresh_rows * de);
+        RNG draw(static_cast<RNG::result_type>(FLAGS_seed));
+        const float max = std::sqrt(6.0 / static_cast<double>(de + corpus_size));
+        for (float& x : fresh) x = 2 * max * (std::generate_canonical<float, 1>(draw) - 0.5);
+        NVSM_CALL(nvsm_set_param_rows(model, "entity_representations-representations", n_old, static_cast<int64_t>(fresh_rows), fresh.data()));
+        std::vector<Hdf5Array>().swap(old_params);
+    } else {
+        NVSM_CALL(nvsm_initialize_from_rng_state(model));
+    }
     NVSM_CALL(nvsm_synchronize(model));
     const uint64_t num_parameters = vocabulary_size * FLAGS_word_repr_size + corpus_size * FLAGS_entity_repr_size +
                                     FLAGS_entity_repr_size * FLAGS_word_repr_size + FLAGS_entity_repr_size;
+    if (fold_in)
+        NVSM_LOG(INFO) << "Fold-in: documents [0, " << n_old << ") are frozen, documents [" << n_old << ", " << corpus_size << ") train.";
     NVSM_LOG(INFO) << "Initialized cuNVSM with " << num_parameters << " parameters for training on " << vocabulary_size << " words and "
                    << corpus_size << " objects.";
 
@@ -787,6 +882,7 @@ int run(int argc, char** argv) {
     Trainer trainer(model, tc, static_cast<int64_t>(vocabulary_size), static_cast<int64_t>(corpus_size),
                     static_cast<int>(FLAGS_word_repr_size), static_cast<int>(FLAGS_entity_repr_size), world_size, rank);
     if (FLAGS_device_corpus) trainer.train_from_refs(index_source);
+    if (fold_in) trainer.fold_from(n_old);
     if (train_pairs)
         trainer.train_pairs(pair_source.get(), &rng, static_cast<float>(1.0 - FLAGS_entity_similarity_weight), static_cast<float>(FLAGS_entity_similarity_weight));
     if (train_terms)

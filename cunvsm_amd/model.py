@@ -805,6 +805,60 @@ def tsne_arguments(cfg, space="entities", ids=None, limit=None, l2_normalize=Fal
     return opt, n, (id_array, given)
 
 
+def fold_summation():
+    """(chunk_entries, group_chunks) of nvsm_step_fold's summation order (nvsm_fold_summation)."""
+    c, g = C.c_int32(), C.c_int32()
+    lib().nvsm_fold_summation(C.byref(c), C.byref(g))
+    return c.value, g.value
+
+
+def minstd_canonical(seed, count):
+    """`count` draws of std::generate_canonical<float, 1>(std::minstd_rand0(seed)) as float32 — the generator nvsm_initialize draws
+    Glorot's uniforms from (x' = 16807 x mod 2^31 - 1; (x' - 1) / 2^31 in float, a result of 1 stepped down to the float below)."""
+    m, a = 2147483647, 16807
+    x = int(seed) % m
+    if x == 0:
+        x = 1
+    block = min(int(count), 1 << 16)
+    pows = np.empty(block, dtype=np.uint64)
+    p = 1
+    for i in range(block):
+        p = p * a % m
+        pows[i] = p
+    out = np.empty(int(count), dtype=np.float32)
+    done = 0
+    while done < count:
+        n = min(block, count - done)
+        xs = (np.uint64(x) * pows[:n]) % np.uint64(m)
+        out[done:done + n] = (xs - np.uint64(1)).astype(np.float32) / np.float32(2147483648.0)
+        x = int(xs[-1])
+        done += n
+    np.minimum(out, np.nextafter(np.float32(1), np.float32(0)), out=out)
+    return out
+
+
+def grow_documents(params, new_rows, seed):
+    """The four tensors of a model with `new_rows` more documents, for a fold-in (Model.step_fold): W, T and b as they are, the old
+    rows of E copied, the new rows Glorot's U(-a, a) with a = sqrt(6 / (entity_repr_size + num_entities)) at the GROWN num_entities
+    — the bound nvsm_initialize uses for the whole table of such a model —, drawn from std::minstd_rand0(seed) in row-major order.
+    `params`: name -> array for the four PARAM_NAMES (Model.get_data())."""
+    if new_rows < 0:
+        raise ValueError("new_rows must be >= 0")
+    if int(seed) <= 0:
+        raise ValueError("seed must be > 0")
+    out = {n: np.ascontiguousarray(params[n], dtype=np.float32).ravel().copy() for n in PARAM_NAMES}
+    de = out["word_entity_mapping-bias"].size
+    old = out["entity_representations-representations"]
+    if old.size % de:
+        raise ValueError("the documents table holds no whole rows of %d values" % de)
+    n_total = old.size // de + int(new_rows)
+    bound = np.float32(np.sqrt(6.0 / float(de + n_total)))
+    u = minstd_canonical(seed, int(new_rows) * de)
+    fresh = (np.float64(np.float32(2) * bound) * (u.astype(np.float64) - 0.5)).astype(np.float32)
+    out["entity_representations-representations"] = np.concatenate([old, fresh])
+    return out
+
+
 class Model:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -878,6 +932,22 @@ class Model:
         c = C.c_float()
         check(lib().nvsm_step(self._h, C.byref(st), None if ids is None else ids.ctypes.data, learning_rate,
                               C.byref(c) if want_cost else None))
+        return c.value if want_cost else None
+
+    def step_fold(self, batch, learning_rate, first_document, entity_ids=None, want_cost=True):
+        """nvsm_step_fold: compute_cost, then the documents update on rows [first_document, num_entities) alone; W, T, b and the
+        rows below stay bit for bit as they are. Returns the cost (what compute_cost + get_cost return) unless want_cost is False."""
+        ids = None
+        if entity_ids is not None:
+            ids = np.ascontiguousarray(entity_ids, dtype=np.int64)
+        st = self._checked(batch, ids)
+        self._keep = (batch, ids)
+        opt = _lib.NvsmFoldOptions()
+        lib().nvsm_fold_options_default(C.byref(opt))
+        opt.first_document = int(first_document)
+        c = C.c_float()
+        check(lib().nvsm_step_fold(self._h, C.byref(st), None if ids is None else ids.ctypes.data, C.byref(opt), learning_rate,
+                                   C.byref(c) if want_cost else None))
         return c.value if want_cost else None
 
     # -- training from an HBM-resident corpus: window references instead of batches -------------------------------
@@ -1396,6 +1466,28 @@ class Model:
     def set_param(self, name, value):
         v = np.ascontiguousarray(value, dtype=np.float32).ravel()
         check(lib().nvsm_set_param(self._h, name.encode(), v.ctypes.data, v.size))
+
+    def _row_width(self, name):
+        n = C.c_int64()
+        check(lib().nvsm_param_size(self._h, name.encode(), C.byref(n)))
+        rows = self.cfg.num_words if name.startswith("word_representations") else self.cfg.num_entities
+        return max(1, n.value // rows)
+
+    def get_param_rows(self, name, first_row, rows):
+        """nvsm_get_param_rows: rows [first_row, first_row + rows) of an embedding table or of its per-row optimiser state, as
+        [rows, width] float32 (width 1 for the per-row scalars)."""
+        out = np.empty((max(int(rows), 0), self._row_width(name)), dtype=np.float32)
+        buf = out if out.size else np.empty(1, dtype=np.float32)      # (an empty range still passes a buffer: NULL is refused)
+        check(lib().nvsm_get_param_rows(self._h, name.encode(), int(first_row), int(rows), buf.ctypes.data))
+        return out
+
+    def set_param_rows(self, name, first_row, value):
+        """nvsm_set_param_rows: `value` ([rows, width] or flat) replaces the rows from first_row on."""
+        v = np.ascontiguousarray(value, dtype=np.float32).ravel()
+        width = self._row_width(name)
+        if v.size % width:
+            raise ValueError("%d values are no whole rows of width %d" % (v.size, width))
+        check(lib().nvsm_set_param_rows(self._h, name.encode(), int(first_row), v.size // width, v.ctypes.data))
 
     def get_data(self):
         """ModelBase::get_data() (cpp/model.cu:64-93): the four tensors the HDF5 writer dumps."""

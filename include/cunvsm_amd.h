@@ -195,6 +195,48 @@ float nvsm_scaled_regularization_lambda(nvsm_model* m);
 int nvsm_step(nvsm_model* m, const nvsm_batch* batch, const int64_t* entity_ids, float learning_rate, float* cost);
 
 /*
+ * DOCUMENT FOLD-IN (nvsm_step_fold). The model is transductive: a document exists for nvsm_rank only if it had a
+ * row of E when training started. Folding new documents in trains THEIR rows against a frozen model: the word table, the
+ * projection, the bias and rows [0, first_document) of the documents table stay as they are; rows [first_document, num_entities)
+ * train with the configured objective, sampler and optimiser. (The caller creates the handle with the grown num_entities and loads
+ * it: old rows copied, new rows drawn — nvsm_set_param_rows below. A live handle's tables do not grow.)
+ *   forward, loss  exactly nvsm_compute_cost(batch, entity_ids): the same kernels, the same sampler — negatives are drawn over all
+ *                  documents, frozen and new alike — and *cost is bit for bit what nvsm_compute_cost + nvsm_get_cost return from the
+ *                  same state.
+ *   not run        batch-norm backward, the dx and dT products, the words update, the projection update, the re-cut of T's planes.
+ *   update         row r >= first_document gets nvsm_step's documents update restricted to those rows: g_r = Σ coef·proj and q_r
+ *                  over the entries of the batch whose id is r, then the optimiser's row formula with the constants nvsm_step would
+ *                  use (decay 1 − λ/B·lr, Adam's bias correction at the documents table's step counter, which advances by one). A new
+ *                  row without entries gets what a dense pass gives it (decay of the row, of m and of the row's scalar under Adam).
+ *                  Entries with id < first_document contribute to the loss and to nothing else.
+ *   frozen state   rows < first_document of E and of its m / v / a, all of W, T, b and their optimiser state keep their LOGICAL
+ *                  values (what nvsm_get_param returns) bit for bit, whatever λ and the Adam mode. On a lazily decayed documents table
+ *                  the first fold step behind an ordinary one brings the table up to date; fold steps add no pending factors.
+ *                  Ordinary steps and fold steps may be interleaved freely.
+ *   reproducible   no float atomics. A row's sum runs over its entries in ascending entry order in an association that depends on
+ *                  the row's entry count alone (nvsm_fold_summation: chunks of chunk_entries entries, each an fma chain from 0;
+ *                  the chunk sums of a row added left to right; rows of more than group_chunks chunks: groups of group_chunks chunk
+ *                  sums first, then the group sums left to right) — not on the grid, on max_batch_size or on the other rows.
+ * NVSM_ERR_UNSUPPORTED (the handle stays usable): world_size > 1; l2_normalize_entity_reprs. NVSM_ERR_INVALID_ARGUMENT: first_document
+ * outside [0, num_entities]; a negative learning rate. first_document == num_entities is valid: nothing trains, the cost is produced.
+ * cost may be NULL (the call then does not wait). The index contract above holds for ids.
+ */
+typedef struct {
+    int64_t first_document;   /* rows [0, first_document) of the documents table are frozen; rows [first_document, num_entities) train */
+    int32_t reserved[6];
+} nvsm_fold_options;
+void nvsm_fold_options_default(nvsm_fold_options* opt);          /* first_document = 0 */
+int nvsm_step_fold(nvsm_model* m, const nvsm_batch* batch, const int64_t* entity_ids, const nvsm_fold_options* opt, float learning_rate,
+                   float* cost);
+void nvsm_fold_summation(int32_t* chunk_entries, int32_t* group_chunks);      /* the constants of the summation order; either may be NULL */
+/* Rows [first_row, first_row + rows) of an embedding table ("word_representations-representations",
+ * "entity_representations-representations") or of its per-row optimiser state ("<param>/m", "/v", "/a"): host arrays of rows x width
+ * floats, width the table's dimension or 1 for a per-row scalar. Same waits and the same flush of a lazily decayed table as
+ * nvsm_get_param / nvsm_set_param. A range outside the table, or any other parameter name, is NVSM_ERR_INVALID_ARGUMENT. */
+int nvsm_get_param_rows(nvsm_model* m, const char* name, int64_t first_row, int64_t rows, float* host_dst);
+int nvsm_set_param_rows(nvsm_model* m, const char* name, int64_t first_row, int64_t rows, const float* host_src);
+
+/*
  * The entity-entity similarity objective (RepresentationSimilarity::Objective on ENTITY_REPRS, cpp/objective.cu:485-696) and its
  * mixture with the text objective (TextEntityEntityEntity, cpp/objective.cu:698-745) — what the reference trains when
  * cuNVSMTrainModel gets document-document similarities as its second argument (PRODUCT_SUBSTITUTABILITY.md).

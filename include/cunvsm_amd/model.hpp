@@ -94,6 +94,16 @@ class Model {
         return c;
     }
 
+    // document fold-in (nvsm_step_fold): compute_cost, then the documents update on rows [first_document, num_entities) alone
+    float step_fold(const Batch& batch, float learning_rate, int64_t first_document, bool want_cost = true) {
+        nvsm_fold_options opt;
+        nvsm_fold_options_default(&opt);
+        opt.first_document = first_document;
+        float c = 0.f;
+        check(nvsm_step_fold(h_, &batch.raw, nullptr, &opt, learning_rate, want_cost ? &c : nullptr));
+        return c;
+    }
+
     // the entity-entity similarity objective mixed into the text objective with weights (text_weight, pair_weight)
     // (TextEntityEntityEntity, cpp/objective.cu:698-745), or alone (text == nullptr): compute_gradients / update / get_cost follow
     void compute_cost_mixed(const Batch* text, const PairBatch& pairs, float text_weight = 0.5f, float pair_weight = 0.5f,
@@ -174,6 +184,9 @@ class Model {
         }
         return out;
     }
+    // rows [first_row, first_row + rows) of an embedding table or of its per-row optimiser state; v holds rows x width floats
+    void get_param_rows(const std::string& name, int64_t first_row, int64_t rows, std::vector<float>* v) { check(nvsm_get_param_rows(h_, name.c_str(), first_row, rows, v->data())); }
+    void set_param_rows(const std::string& name, int64_t first_row, int64_t rows, const std::vector<float>& v) { check(nvsm_set_param_rows(h_, name.c_str(), first_row, rows, v.data())); }
     void set_param(const std::string& name, const std::vector<float>& v) { check(nvsm_set_param(h_, name.c_str(), v.data(), static_cast<int64_t>(v.size()))); }
 
     // Storage::increment_parameter (cpp/storage.cu:123-131) — the gradient checker's poke
