@@ -62,6 +62,17 @@ class NvsmFoldOptions(C.Structure):
     _fields_ = [("first_document", C.c_int64), ("reserved", C.c_int32 * 6)]
 
 
+INDEX_AUTO, INDEX_ALWAYS, INDEX_NEVER = 0, 1, 2
+
+
+class NvsmIndexOptions(C.Structure):
+    _fields_ = [("use", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class NvsmIndexInfo(C.Structure):
+    _fields_ = [("num_postings", C.c_int64), ("bytes", C.c_int64), ("max_df", C.c_int64), ("use", C.c_int32), ("reserved", C.c_int32 * 9)]
+
+
 class NvsmPairBatch(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("weights", C.c_void_p), ("num_pairs", C.c_int64), ("on_device", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
@@ -352,6 +363,10 @@ def lib():
         "nvsm_compute_cost_term_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture)]),
         "nvsm_step_term_mixed": (C.c_int, [vp, P(NvsmBatch), vp, P(NvsmPairBatch), P(NvsmMixture), C.c_float, P(C.c_float)]),
         "nvsm_corpus_upload": (C.c_int, [vp, P(NvsmCorpus)]),
+        "nvsm_index_options_default": (None, [P(NvsmIndexOptions)]),
+        "nvsm_corpus_index": (C.c_int, [vp, P(NvsmIndexOptions), P(NvsmIndexInfo)]),
+        "nvsm_corpus_index_free": (C.c_int, [vp]),
+        "nvsm_corpus_postings": (C.c_int, [vp, i64, i64, vp, vp, P(i64)]),
         "nvsm_compute_cost_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp]),
         "nvsm_step_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp, C.c_float, P(C.c_float)]),
         "nvsm_step_windows_deferred": (C.c_int, [vp, P(NvsmWindowBatch), vp, C.c_float, P(i64)]),

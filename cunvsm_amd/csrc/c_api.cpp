@@ -313,7 +313,24 @@ int nvsm_corpus_upload(nvsm_model* m, const nvsm_corpus* corpus) {
     NVSM_REQUIRE(m);
     return guarded_on(m, [&] { m->impl.corpus_upload(corpus); });
 }
-int nvsm_compute_cost_windows(nvsm_model* m, const nvsm_window_batch* windows, const int64_t* entity_ids) {
+void nvsm_index_options_default(nvsm_index_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->use = NVSM_INDEX_AUTO;
+}
+int nvsm_corpus_index(nvsm_model* m, const nvsm_index_options* opt, nvsm_index_info* info) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(opt);
+    return guarded_on(m, [&] { m->impl.corpus_index(*opt, info); });
+}
+int nvsm_corpus_index_free(nvsm_model* m) {
+    NVSM_REQUIRE(m);
+    return guarded_on(m, [&] { m->impl.corpus_index_free(); });
+}
+int nvsm_corpus_postings(nvsm_model* m, int64_t word_id, int64_t capacity, int64_t* doc_ids, int32_t* tfs, int64_t* count) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(count);
+    return guarded_on(m, [&] { m->impl.corpus_postings(word_id, capacity, doc_ids, tfs, count); });
+}
+int nvsm_compute_cost_windows(nvsm_model* m,const nvsm_window_batch* windows, const int64_t* entity_ids) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(windows);
     return guarded_on(m, [&] { m->impl.compute_cost_windows(*windows, entity_ids); });
 }

@@ -705,5 +705,32 @@ struct FuseSweepArgs {
 };
 void launch_fuse_sweep(const FuseSweepArgs& a, int Q, hipStream_t s);
 
+// ---- inverted index of the uploaded corpus (index.hip; include/cunvsm_amd.h nvsm_corpus_index) ----
+// The build behind sort_pairs(keys = tokens, vals_in = nullptr): term [n] the sorted tokens, pos [n] their arena positions.
+// launch_index_docs: pos[i] -> the document of that position, in place (doc_offsets [num_documents + 1], the last one n).
+void launch_index_docs(int* pos, int64_t n, const int64_t* doc_offsets, int64_t num_documents, hipStream_t s);
+// heads = entries whose (term, document) differs from their predecessor's. tile_sums [index_tiles(n) + 1]: every tile's heads, then
+// (a second launch, one workgroup) their exclusive prefixes with the total P behind them
+int64_t index_tiles(int64_t n);
+void launch_index_scan(const int* term, const int* doc, int64_t n, int* tile_sums, hipStream_t s);
+// post_doc [P], head_pos [P + 1] (a posting's first entry; head_pos[P] = n), post_off / tok_off [V + 1]: a term's first posting and
+// first sorted entry (df and cf are their differences). Every element has exactly one writer.
+void launch_index_write(const int* term, const int* doc, int64_t n, int64_t V, const int* tile_sums, int* head_pos, int* post_doc,
+                        int64_t* post_off, int64_t* tok_off, hipStream_t s);
+void launch_index_tf(const int* head_pos, int64_t P, int* post_tf, hipStream_t s);      // post_tf[p] = head_pos[p + 1] − head_pos[p]
+// The postings form of launch_lex_score / launch_tfidf_score: the same scores [Q][ld] of the slab [d0, d0 + S), the same bits.
+// terms [num_slots]: the round's distinct terms by slot; entries as LexScoreArgs' (qoff, tslot, c0 = idf for TF-IDF, base, weight);
+// entry_query [num_entries]: the query of an entry; first [num_entries]: 1 where the entry is the first of its term in its query;
+// lo / hi [num_slots]: scratch, a term's postings inside the slab. max_df: the longest list among the round's terms (sizes the grid).
+struct PostingsArgs {
+    const int64_t* post_off; const int* post_doc; const int* post_tf; const int64_t* doc_offsets;
+    const int* terms; int num_slots; int64_t* lo; int64_t* hi;
+    int64_t d0; int S; int Q; int num_entries; int method; double param; double k1, b, avgdl;
+    const int* qoff; const int* tslot; const int* entry_query; const int* first;
+    const double* c0; const double* base; const double* weight;
+    float* scores; int64_t ld;
+};
+void launch_postings_fill(const PostingsArgs& a, int64_t max_df, bool tfidf, hipStream_t s);
+
 
 }  // namespace cunvsm

@@ -248,6 +248,10 @@ class Model {
     Profiler prof;
     const nvsm_config& config() const { return cfg_; }
     const Tuning& tune() const { return tune_; }
+    // the inverted index of the uploaded corpus (include/cunvsm_amd.h nvsm_corpus_index; ranking.cpp)
+    void corpus_index(const nvsm_index_options& opt, nvsm_index_info* info);
+    void corpus_index_free();
+    void corpus_postings(int64_t word_id, int64_t capacity, int64_t* doc_ids, int32_t* tfs, int64_t* count);
     std::string describe(int64_t batch) const;      // which kernel each product of a step takes at `batch` windows, table modes, switches off their defaults
 
  private:
@@ -504,6 +508,14 @@ class Model {
         size_t bytes = 0;
         std::vector<int64_t> cf;            // lexical ranking: occurrences of every word, made by the first lexical call (empty: not yet)
         std::vector<int64_t> df;            // TF-IDF: documents holding every word, made by the first call that needs it (empty: not yet)
+        // the inverted index (index.hip), made by nvsm_corpus_index and dropped with the corpus: post_off [V + 1],
+        // post_doc / post_tf [P] (at least one element)
+        bool indexed = false;
+        int index_use = 0;                  // NVSM_INDEX_*
+        DevBuf<int64_t> post_off;
+        DevBuf<int> post_doc, post_tf;
+        std::vector<int64_t> host_post_off; // post_off on the host: df, and the bounds nvsm_corpus_postings copies between
+        int64_t num_postings = 0, index_bytes = 0, max_df = 0;
     };
     Corpus* corpus_ = nullptr;
     DevBuf<uint32_t> in_refs_[2];               // host references, one per staging set
@@ -526,6 +538,8 @@ class Model {
         DevBuf<double> jconst, metrics;            //           ... R / idcg / idcg@c per query, and the metric rows
         DevBuf<int> lex_slot_of, lex_terms, lex_qoff, lex_tslot;      // lexical: term -> slot [num_words] (-1 between rounds), a round's terms
         DevBuf<double> lex_c0, lex_base, lex_weight;                  //          ... and their constants (lex_weight: weighted queries only)
+        DevBuf<int> post_query, post_first;                           // postings fill (indexed corpora only): an entry's query, first-of-its-term flag
+        DevBuf<int64_t> post_lo, post_hi;                             //          ... and a term's postings inside the slab
         DevBuf<double> rm_acc, rm_sum;                                // relevance model: acc [round][num_words] and cnt likewise (zero between
         DevBuf<int> rm_cnt, rm_ids, rm_counts;                        //   rounds), Σω [round], a round's feedback lists [round][fb_docs]
         DevBuf<float> rm_scores;
@@ -559,6 +573,7 @@ class Model {
     void tfidf_check(const nvsm_queries& q, const nvsm_tfidf_options& opt) const;          // the refusals of nvsm_tfidf_rank, before anything runs
     TfidfPlan tfidf_plan(const nvsm_tfidf_options& opt) const;
     void corpus_df();                       // the df table of the corpus, made once (lex_df_kernel)
+    void index_build(Corpus& c);            // the postings of the corpus and, where still empty, its cf and df (ranking.cpp; index.hip)
     // one round of nvsm_rank over candidate lists that lie on the device as launch_rank_scan_candidates reads them
     void rank_candidates_round(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, const RankLayout& l, const int* cand,
                                const int64_t* cand_off, EvalArgs* ea, int64_t* doc_ids, float* scores, int64_t* counts);

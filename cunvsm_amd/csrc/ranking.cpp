@@ -49,6 +49,17 @@ void check_activation(int a) {
 void check_top_k(int64_t k, int64_t rows, const char* refusal) { if (k < 1 || k > rows) throw Error(NVSM_ERR_INVALID_ARGUMENT, refusal); }
 void check_row_count(int64_t rows, const char* refusal) { if (rows >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, refusal); }
 
+// NVSM_INDEX_AUTO's rule for one round (DESIGN.md §22 "AUTO"): the postings fill costs about one binary search per (posting of a
+// query's distinct terms, entry of that query) — `work` — and the scan costs one workgroup visit per document whatever the queries
+// are: in the measurements its time went with D_c (x 20 for x 20 documents and x 5 tokens), so N dropped out of the rule. The
+// slab's -inf fill, selection and sort are the same on both sides. The constants — how many searches one scanned document is worth,
+// the TF-IDF scan being the cheaper one (no log per pair) — are fitted to the cells of tools/bench_index.py
+// (profiles/index_bench.jsonl): below them the postings won every measured cell, above them the first cell they lost.
+constexpr double kIndexAutoSearchesPerDocument = 200.0, kIndexAutoSearchesPerDocumentTfidf = 100.0;
+bool index_auto_takes_postings(double work, int64_t num_documents, bool tfidf) {
+    return work <= (tfidf ? kIndexAutoSearchesPerDocumentTfidf : kIndexAutoSearchesPerDocument) * static_cast<double>(num_documents);
+}
+
 }  // namespace
 
 // ---- the layout of a round (DESIGN.md §9 "Dispatch by Q and k"): host arithmetic only -------------------------------------------
@@ -495,17 +506,23 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
     std::vector<int> terms, qoff, tslot;
     std::vector<double> c0, base, wt;
     std::vector<std::pair<int64_t, int>> slot_of;      // (term, slot) of the round, kept sorted by term
+    // an indexed corpus: every entry's query and whether it is the first of its term there, the round's postings work
+    const bool indexed = c.indexed && c.index_use != NVSM_INDEX_NEVER;
+    std::vector<int> entry_query, entry_first;
 
     for (int64_t q0 = 0; q0 < Q;) {
         RankLayout l = rank_layout(Dc, k, Q - q0, score_floats());
         // ---- the round's queries: as many of the l.qn as their distinct remaining terms leave room for (at least one: lexical_check);
         // the slabs stay those of the layout, the scratch is sized by the queries taken
-        terms.clear(); tslot.clear(); c0.clear(); base.clear(); wt.clear(); slot_of.clear();
+        terms.clear(); tslot.clear(); c0.clear(); base.clear(); wt.clear(); slot_of.clear(); entry_query.clear(); entry_first.clear();
         qoff.assign(1, 0);
         int64_t taken = 0;
+        double postings_work = 0.0;      // Σ over the queries of (Σ df of the query's distinct terms) · (its entries): the searches of the fill
+        int64_t round_max_df = 0;
         for (; taken < l.qn; ++taken) {
             const size_t terms_before = terms.size(), entries_before = tslot.size();
             bool fits = true;
+            double query_df = 0.0;
             for (int64_t j = q.offsets[q0 + taken]; j < q.offsets[q0 + taken + 1]; ++j) {
                 const int64_t t = q.word_ids[j];
                 if (t < 0 || t >= V) { bad_word = true; continue; }      // the index contract: matches nothing, reported at the end
@@ -521,8 +538,17 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
                     slot_of.insert(it, std::make_pair(t, slot));
                     terms.push_back(static_cast<int>(t));
                 }
+                if (indexed) {
+                    const bool first = std::find(tslot.begin() + static_cast<std::ptrdiff_t>(entries_before), tslot.end(), slot) == tslot.end();
+                    entry_query.push_back(static_cast<int>(taken));
+                    entry_first.push_back(first ? 1 : 0);
+                    if (first) {
+                        query_df += static_cast<double>(c.df[static_cast<size_t>(t)]);
+                        round_max_df = std::max(round_max_df, c.df[static_cast<size_t>(t)]);
+                    }
+                }
                 tslot.push_back(slot);
-                if (tfidf) {      // the term's idf, once per term by the host, where the lexical scorer has c0 (base is not read)
+                if (tfidf) {    // the term's idf, once per term by the host, where the lexical scorer has c0 (base is not read)
                     const double df = static_cast<double>(c.df[static_cast<size_t>(t)]), docs = static_cast<double>(Dc);
                     c0.push_back(tfidf->idf == NVSM_IDF_OKAPI ? std::log((docs - df + 0.5) / (df + 0.5)) : std::log((docs + 1.0) / (df + 0.5)));
                     base.push_back(0.0);
@@ -540,8 +566,10 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
                 }
                 terms.resize(terms_before); tslot.resize(entries_before); c0.resize(entries_before); base.resize(entries_before);
                 if (weights) wt.resize(entries_before);
+                if (indexed) { entry_query.resize(entries_before); entry_first.resize(entries_before); }
                 break;
             }
+            postings_work += query_df * static_cast<double>(tslot.size() - entries_before);
             qoff.push_back(static_cast<int>(tslot.size()));
         }
         const int64_t qn = l.qn = taken;
@@ -575,7 +603,33 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
             ta.Q = a.Q; ta.num_slots = nslots; ta.k1 = tfidf->k1; ta.b = tfidf->b; ta.avgdl = tfidf->avgdl;
             ta.qoff = a.qoff; ta.tslot = a.tslot; ta.idf = a.c0; ta.weight = a.weight; ta.ld = l.ld;
         }
+        // the fill of this round's slabs: the arena scan, or the postings of the round's terms. Both give the same bits, so the
+        // choice — the caller's, or under NVSM_INDEX_AUTO index_auto_takes_postings' — is invisible in the results
+        const bool postings = indexed && (c.index_use == NVSM_INDEX_ALWAYS || index_auto_takes_postings(postings_work, Dc, tfidf != nullptr));
+        PostingsArgs pa{};
+        if (postings) {
+            grow(r.post_query, std::max<size_t>(nent, 1));
+            grow(r.post_first, std::max<size_t>(nent, 1));
+            grow(r.post_lo, static_cast<size_t>(kLexSlots));
+            grow(r.post_hi, static_cast<size_t>(kLexSlots));
+            if (nent > 0) {
+                NVSM_HIP_CHECK(hipMemcpy(r.post_query.p, entry_query.data(), nent * sizeof(int), hipMemcpyHostToDevice));
+                NVSM_HIP_CHECK(hipMemcpy(r.post_first.p, entry_first.data(), nent * sizeof(int), hipMemcpyHostToDevice));
+            }
+            pa.post_off = c.post_off.p; pa.post_doc = c.post_doc.p; pa.post_tf = c.post_tf.p; pa.doc_offsets = c.offsets.p;
+            pa.terms = r.lex_terms.p; pa.num_slots = nslots; pa.lo = r.post_lo.p; pa.hi = r.post_hi.p;
+            pa.Q = static_cast<int>(qn); pa.num_entries = static_cast<int>(nent); pa.method = lex.method; pa.param = param;
+            if (tfidf) { pa.k1 = tfidf->k1; pa.b = tfidf->b; pa.avgdl = tfidf->avgdl; }
+            pa.qoff = r.lex_qoff.p; pa.tslot = r.lex_tslot.p; pa.entry_query = r.post_query.p; pa.first = r.post_first.p;
+            pa.c0 = r.lex_c0.p; pa.base = r.lex_base.p; pa.weight = a.weight; pa.ld = l.ld;
+        }
         round_slabs(l, Dc, k, [&](int64_t d0, int Ss) {
+            if (postings) {
+                pa.scores = r.scores.p; pa.d0 = d0; pa.S = Ss;
+                RankProf scope(prof, tfidf ? "tfidf_postings" : (weights ? "lex_postings_weighted" : "lex_postings"), stream_);
+                launch_postings_fill(pa, round_max_df, tfidf != nullptr, stream_);
+                return;
+            }
             if (d0 == 0) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);      // (behind round_slabs' grows)
             if (tfidf) {
                 ta.scores = r.scores.p; ta.d0 = d0; ta.S = Ss;
@@ -587,7 +641,7 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
             RankProf scope(prof, weights ? "lex_score_weighted" : "lex_score", stream_);
             launch_lex_score(a, stream_);
         });
-        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
+        if (!postings) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
         round_sort(l, [&] { launch_lex_write(r.keys.p, l.npad, static_cast<int>(qn), k, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_); });
         round_results(q0, qn, k, doc_ids, scores, counts);
         if (hand) hand->take(*this, l, counts + q0, qn);      // (the round's sorted keys still lie in r.keys)
@@ -644,6 +698,120 @@ void Model::corpus_df() {
     NVSM_HIP_CHECK(hipMemcpyAsync(host.data(), df.p, static_cast<size_t>(V) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
     NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
     c.df.swap(host);
+}
+
+// ---- the inverted index of the uploaded corpus (include/cunvsm_amd.h nvsm_corpus_index; kernels: index.hip) ---------
+// The arena is in document order and sort_pairs is stable: sorted by token with the positions as values, every term's positions
+// ascend, hence its documents. Heads — where (term, document) changes — are the postings; their scan is three launches. All the
+// build's scratch is local to this function: freed before the call returns.
+void Model::index_build(Corpus& c) {
+    const int64_t N = c.num_tokens, Dc = c.num_documents, V = cfg_.num_words;
+    if (N >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "the inverted index supports fewer than 2^31 tokens");
+    RankProf scope(prof, "index_build", stream_);
+    c.post_off.alloc(static_cast<size_t>(V) + 1, true);
+    std::vector<int64_t> post_off(static_cast<size_t>(V) + 1, 0), tok_off(static_cast<size_t>(V) + 1, 0);
+    int64_t P = 0;
+    if (N > 0) {
+        int bits = 1;
+        while (bits < 31 && (int64_t(1) << bits) < V) ++bits;
+        DevBuf<int> term, doc, sums;
+        term.alloc(static_cast<size_t>(N));
+        doc.alloc(static_cast<size_t>(N));
+        {
+            DevBuf<char> temp;
+            const size_t temp_bytes = sort_pairs_temp_bytes(N, bits);
+            temp.alloc(temp_bytes, true);
+            sort_pairs(temp.p, temp_bytes, nullptr, c.tokens.p, term.p, nullptr, doc.p, N, bits, nullptr, stream_);
+            launch_index_docs(doc.p, N, c.offsets.p, Dc, stream_);
+            NVSM_HIP_CHECK(hipStreamSynchronize(stream_));      // (the sort's workspace goes before the postings come)
+        }
+        const int64_t tiles = index_tiles(N);
+        sums.alloc(static_cast<size_t>(tiles) + 1);
+        launch_index_scan(term.p, doc.p, N, sums.p, stream_);
+        int total = 0;
+        NVSM_HIP_CHECK(hipMemcpyAsync(&total, sums.p + tiles, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        P = total;
+        DevBuf<int> head;
+        DevBuf<int64_t> tok;
+        head.alloc(static_cast<size_t>(P) + 1);
+        tok.alloc(static_cast<size_t>(V) + 1);
+        c.post_doc.alloc(static_cast<size_t>(P));
+        c.post_tf.alloc(static_cast<size_t>(P));
+        launch_index_write(term.p, doc.p, N, V, sums.p, head.p, c.post_doc.p, c.post_off.p, tok.p, stream_);
+        launch_index_tf(head.p, P, c.post_tf.p, stream_);
+        NVSM_HIP_CHECK(hipMemcpyAsync(post_off.data(), c.post_off.p, post_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipMemcpyAsync(tok_off.data(), tok.p, tok_off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    } else {
+        c.post_doc.alloc(1, true);
+        c.post_tf.alloc(1, true);
+    }
+    c.max_df = 0;
+    for (int64_t t = 0; t < V; ++t) c.max_df = std::max(c.max_df, post_off[static_cast<size_t>(t) + 1] - post_off[static_cast<size_t>(t)]);
+    if (c.cf.empty()) {      // what lex_cf_kernel counts: a term's sorted entries
+        c.cf.resize(static_cast<size_t>(V));
+        for (int64_t t = 0; t < V; ++t) c.cf[static_cast<size_t>(t)] = tok_off[static_cast<size_t>(t) + 1] - tok_off[static_cast<size_t>(t)];
+    }
+    if (c.df.empty()) {      // what lex_df_kernel counts: a term's postings
+        c.df.resize(static_cast<size_t>(V));
+        for (int64_t t = 0; t < V; ++t) c.df[static_cast<size_t>(t)] = post_off[static_cast<size_t>(t) + 1] - post_off[static_cast<size_t>(t)];
+    }
+    c.host_post_off.swap(post_off);
+    c.num_postings = P;
+    c.index_bytes = static_cast<int64_t>(c.post_off.n * sizeof(int64_t) + (c.post_doc.n + c.post_tf.n) * sizeof(int));
+    c.indexed = true;
+}
+
+void Model::corpus_index(const nvsm_index_options& opt, nvsm_index_info* info) {
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the inverted index needs a corpus: call nvsm_corpus_upload first");
+    if (opt.use != NVSM_INDEX_AUTO && opt.use != NVSM_INDEX_ALWAYS && opt.use != NVSM_INDEX_NEVER)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown index use (NVSM_INDEX_AUTO, NVSM_INDEX_ALWAYS or NVSM_INDEX_NEVER)");
+    if (cfg_.world_size > 1) throw Error(NVSM_ERR_UNSUPPORTED, "the inverted index is not implemented under data parallelism (world_size > 1)");
+    Corpus& c = *corpus_;
+    if (!c.indexed) {
+        rank_join();
+        try {
+            index_build(c);
+        } catch (...) {      // a refused or failed build leaves the corpus without an index
+            c.post_off.release(); c.post_doc.release(); c.post_tf.release();
+            throw;
+        }
+    }
+    c.index_use = opt.use;
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->num_postings = c.num_postings; info->bytes = c.index_bytes; info->max_df = c.max_df; info->use = c.index_use;
+    }
+}
+
+void Model::corpus_index_free() {
+    if (!corpus_ || !corpus_->indexed) return;
+    rank_join();      // whatever is queued may still read the postings
+    Corpus& c = *corpus_;
+    c.post_off.release(); c.post_doc.release(); c.post_tf.release();
+    c.host_post_off.clear();
+    c.indexed = false; c.index_use = NVSM_INDEX_AUTO;
+    c.num_postings = c.index_bytes = c.max_df = 0;
+}
+
+void Model::corpus_postings(int64_t word_id, int64_t capacity, int64_t* doc_ids, int32_t* tfs, int64_t* count) {
+    *count = 0;
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the inverted index needs a corpus: call nvsm_corpus_upload first");
+    if (!corpus_->indexed) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the corpus has no inverted index: call nvsm_corpus_index first");
+    if (word_id < 0 || word_id >= cfg_.num_words) throw Error(NVSM_ERR_INVALID_ARGUMENT, "word_id is outside [0, num_words)");
+    const Corpus& c = *corpus_;
+    const int64_t lo = c.host_post_off[static_cast<size_t>(word_id)], n = c.host_post_off[static_cast<size_t>(word_id) + 1] - lo;
+    *count = n;
+    if (capacity < n) throw Error(NVSM_ERR_INVALID_ARGUMENT, "capacity is below the word's document frequency (returned in count)");
+    if (n == 0) return;
+    if (!doc_ids) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: doc_ids");
+    if (!tfs) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: tfs");
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    std::vector<int> docs(static_cast<size_t>(n));
+    NVSM_HIP_CHECK(hipMemcpy(docs.data(), c.post_doc.p + lo, static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToHost));
+    NVSM_HIP_CHECK(hipMemcpy(tfs, c.post_tf.p + lo, static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) doc_ids[i] = docs[static_cast<size_t>(i)];
 }
 
 void Model::tfidf_rank(const nvsm_queries& q, const nvsm_tfidf_options& opt, int64_t* doc_ids, float* scores, int64_t* counts) {

@@ -46,7 +46,7 @@ using namespace nvsm_host;
 namespace {
 
 std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs, FLAGS_qlm, FLAGS_qlm_param, FLAGS_qlm_run_out,
-    FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure, FLAGS_rerank, FLAGS_tfidf_run_out;
+    FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure, FLAGS_rerank, FLAGS_tfidf_run_out, FLAGS_lexical_index;
 bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
     FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf;
 double FLAGS_bias_coefficient, FLAGS_qlm_fb_orig_weight, FLAGS_alpha_stepsize;
@@ -110,6 +110,9 @@ void define_flags(Flags* f) {
     f->define_int64("rerank_depth", &FLAGS_rerank_depth, 1000, "With --rerank: candidates per topic, clipped to the collection; at most 4096.");
     f->define_string("tfidf_run_out", &FLAGS_tfidf_run_out, "", "Prefix of the TF-IDF runs (Robertson's idf; Okapi's with --rerank okapi), written as "
                      "<prefix>-<topic file> in TREC format, --top_k documents per topic (with --rerank: the --rerank_depth candidates).");
+    f->define_string("lexical_index", &FLAGS_lexical_index, "", "auto | always | never, with --qlm or --rerank: build the inverted index of the uploaded "
+                     "collection and let the lexical rankings fill their scores from its postings (always), from the token arena (never) or "
+                     "whichever is cheaper per round (auto). Every run file is byte for byte the one written without the flag.");
     f->define_bool("help", &FLAGS_help, false, "Print the options and exit.");
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
     f->define_int64("v", &FLAGS_v, 0, "Verbosity of VLOG messages.");
@@ -285,6 +288,17 @@ int run(int argc, char** argv) {
         NVSM_CHECK(FLAGS_rerank_depth == 1000) << "--rerank_depth needs --rerank.";
     }
     const bool with_collection = with_qlm || with_rerank || with_tfidf_run;      // the token arena goes to the device
+    // ---- --lexical_index: the inverted index of that arena
+    nvsm_index_options index_opt;
+    nvsm_index_options_default(&index_opt);
+    const bool with_index = !FLAGS_lexical_index.empty();
+    if (with_index) {
+        NVSM_CHECK(with_qlm || with_rerank) << "--lexical_index needs --qlm or --rerank.";
+        if (FLAGS_lexical_index == "auto") index_opt.use = NVSM_INDEX_AUTO;
+        else if (FLAGS_lexical_index == "always") index_opt.use = NVSM_INDEX_ALWAYS;
+        else if (FLAGS_lexical_index == "never") index_opt.use = NVSM_INDEX_NEVER;
+        else NVSM_LOG(FATAL) << "--lexical_index: '" << FLAGS_lexical_index << "' is none of auto, always, never.";
+    }
 
     // ---- --top_k (py/query.py:118-139)
     int64_t top_k = 1000;
@@ -377,6 +391,11 @@ int run(int argc, char** argv) {
         corpus.num_tokens = static_cast<int64_t>(arena.tokens.size()); corpus.num_documents = num_entities;
         NVSM_CALL(nvsm_corpus_upload(model, &corpus));
         NVSM_LOG(INFO) << "<collection of " << corpus.num_documents << " documents and " << corpus.num_tokens << " in-vocabulary tokens>";
+        if (with_index) {
+            nvsm_index_info info;
+            NVSM_CALL(nvsm_corpus_index(model, &index_opt, &info));
+            NVSM_LOG(INFO) << "<inverted index of " << info.num_postings << " postings, " << info.bytes << " bytes, longest list " << info.max_df << ">";
+        }
     }
 
     nvsm_rank_options opt;

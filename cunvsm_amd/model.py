@@ -513,6 +513,7 @@ def feedback_options(fb_docs=10, fb_terms=10, orig_weight=0.5):
 
 IDFS = {"robertson": _lib.IDF_ROBERTSON, "okapi": _lib.IDF_OKAPI}
 FIRST_STAGES = {"tfidf": _lib.STAGE_TFIDF, "lexical": _lib.STAGE_LEXICAL}
+INDEX_USES = {"auto": _lib.INDEX_AUTO, "always": _lib.INDEX_ALWAYS, "never": _lib.INDEX_NEVER}
 
 
 def tfidf_options(k1=None, b=None, idf="robertson", top_k=1000):
@@ -960,6 +961,39 @@ class Model:
             raise ValueError("term_weights holds %d values, expected num_words = %d" % (corpus.term_weights.size, self.cfg.num_words))
         st = corpus.as_struct()
         check(lib().nvsm_corpus_upload(self._h, C.byref(st)))
+
+    # -- the inverted index of the uploaded corpus ------------------------------------------------
+    def index_corpus(self, use="auto"):
+        """nvsm_corpus_index: builds the postings of the uploaded corpus in HBM (once; a later call only sets `use`) and says
+        which fill the lexical rounds take: "never" the arena scan, "always" the postings, "auto" chosen per round. Results do
+        not depend on it. Returns {"num_postings", "bytes", "max_df", "use"}."""
+        if isinstance(use, str):
+            if use not in INDEX_USES:
+                raise ValueError("unknown index use %r (one of %s)" % (use, sorted(INDEX_USES)))
+            use = INDEX_USES[use]
+        opt = _lib.NvsmIndexOptions()
+        lib().nvsm_index_options_default(C.byref(opt))
+        opt.use = int(use)
+        info = _lib.NvsmIndexInfo()
+        check(lib().nvsm_corpus_index(self._h, C.byref(opt), C.byref(info)))
+        names = {v: k for k, v in INDEX_USES.items()}
+        return {"num_postings": info.num_postings, "bytes": info.bytes, "max_df": info.max_df, "use": names[info.use]}
+
+    def postings(self, word):
+        """nvsm_corpus_postings: (doc ids int64 [df], tfs int32 [df]) of one word, documents ascending."""
+        n = C.c_int64()
+        st = lib().nvsm_corpus_postings(self._h, int(word), 0, None, None, C.byref(n))
+        if n.value == 0:
+            check(st)      # an empty list is a success; a refusal (no corpus, no index, word out of range) is raised
+        ids = np.empty(n.value, dtype=np.int64)
+        tfs = np.empty(n.value, dtype=np.int32)
+        if n.value:
+            check(lib().nvsm_corpus_postings(self._h, int(word), n.value, ids.ctypes.data, tfs.ctypes.data, C.byref(n)))
+        return ids, tfs
+
+    def drop_index(self):
+        """nvsm_corpus_index_free: frees the index, the corpus stays (no index: nothing happens)."""
+        check(lib().nvsm_corpus_index_free(self._h))
 
     def _checked_windows(self, windows, entity_ids):
         if not isinstance(windows, WindowBatch):

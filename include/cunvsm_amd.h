@@ -766,6 +766,45 @@ int nvsm_rerank(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_opti
                 const nvsm_judgments* judgments, double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
 
 /*
+ * INVERTED INDEX OF THE UPLOADED CORPUS (nvsm_corpus_index) — DESIGN.md §22
+ *
+ * A CSR of postings in HBM: per word its documents, ascending and each once, with the word's count in each. Once it exists, the
+ * lexical rounds — nvsm_lexical_rank, its weighted form, nvsm_tfidf_rank, the first stage of nvsm_rerank, both passes of the
+ * feedback calls, list B of the fused calls — may fill their score slabs from the postings of the query words instead of
+ * re-reading the whole token arena. Both fills return THE SAME BITS: ids, scores and counts do not depend on `use`.
+ *   NVSM_INDEX_NEVER   the arena scan           NVSM_INDEX_ALWAYS  the postings, in every lexical round
+ *   NVSM_INDEX_AUTO    chosen per round on the host from the round's Σ df, its entries per query and the corpus size
+ * nvsm_corpus_index is synchronous, runs behind everything queued and touches no parameter, optimiser state, RNG state or lazy
+ * bookkeeping. On a corpus that is indexed already it only sets `use` and refills `info`. The layout is a function of the corpus
+ * alone: a second build gives the same bytes. nvsm_corpus_upload, with a new corpus or NULL, drops the index with the corpus. A
+ * handle that never calls it allocates and launches exactly what it did before, and its nvsm_describe text is unchanged.
+ * NVSM_ERR_INVALID_ARGUMENT, each with a sentence, the handle staying usable: no corpus; no index (nvsm_corpus_postings); a null
+ * argument, by name; an unknown `use`; a word id outside [0, num_words). NVSM_ERR_UNSUPPORTED: a corpus of 2^31 tokens or more;
+ * world_size > 1. The index describes the corpus as uploaded; there are no incremental updates.
+ */
+enum { NVSM_INDEX_AUTO = 0, NVSM_INDEX_ALWAYS = 1, NVSM_INDEX_NEVER = 2 };
+typedef struct {
+    int32_t use;                  /* NVSM_INDEX_* */
+    int32_t reserved[7];
+} nvsm_index_options;
+typedef struct {
+    int64_t num_postings;         /* P = Σ_t df(t) */
+    int64_t bytes;                /* HBM the index holds */
+    int64_t max_df;               /* the longest list */
+    int32_t use;                  /* NVSM_INDEX_* in force */
+    int32_t reserved[9];
+} nvsm_index_info;
+/* NVSM_INDEX_AUTO */
+void nvsm_index_options_default(nvsm_index_options* opt);
+/* info may be NULL */
+int nvsm_corpus_index(nvsm_model* m, const nvsm_index_options* opt, nvsm_index_info* info);
+/* frees the index (the corpus stays); no index: success */
+int nvsm_corpus_index_free(nvsm_model* m);
+/* one word's list to the host: *count = df(word_id), always written; doc_ids / tfs [capacity] receive the list when
+ * capacity >= *count, else nothing else is written and the call returns NVSM_ERR_INVALID_ARGUMENT */
+int nvsm_corpus_postings(nvsm_model* m, int64_t word_id, int64_t capacity, int64_t* doc_ids, int32_t* tfs, int64_t* count);
+
+/*
  * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query
  * library does with the same parameters (py/nvsm/base.py). Semantics, pinned by the reference:
  *   space        NVSM_SPACE_WORDS: the rows of W, dimension word_repr_size — NVSM.related_terms (base.py:325-342) and

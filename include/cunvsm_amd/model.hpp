@@ -280,6 +280,27 @@ class Model {
         r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
         return r;
     }
+    // the inverted index of the uploaded corpus (cunvsm_amd.h nvsm_corpus_index): built once, a later call only sets `use`; the
+    // lexical rankings return the same bits whichever fill they take
+    nvsm_index_info index_corpus(int32_t use = NVSM_INDEX_AUTO) {
+        nvsm_index_options opt;
+        nvsm_index_options_default(&opt);
+        opt.use = use;
+        nvsm_index_info info;
+        check(nvsm_corpus_index(h_, &opt, &info));
+        return info;
+    }
+    void free_index() { check(nvsm_corpus_index_free(h_)); }
+    struct Postings { std::vector<int64_t> doc_ids; std::vector<int32_t> tfs; };
+    Postings postings(int64_t word_id) {      // one word's list, documents ascending
+        Postings p;
+        int64_t n = 0;
+        const int st = nvsm_corpus_postings(h_, word_id, 0, nullptr, nullptr, &n);
+        if (n == 0) { check(st); return p; }      // (an empty list is a success; a refusal leaves the count 0)
+        p.doc_ids.resize(static_cast<size_t>(n)); p.tfs.resize(static_cast<size_t>(n));
+        check(nvsm_corpus_postings(h_, word_id, n, p.doc_ids.data(), p.tfs.data(), &n));
+        return p;
+    }
     // nvsm_rerank: rank() over the candidates the first stage retrieves at top_k = rr.depth, handed over on the device. judgments
     // null: no metrics (width 0).
     Evaluation rerank(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
