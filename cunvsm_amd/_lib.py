@@ -238,6 +238,42 @@ class LossArgs(C.Structure):
     ]
 
 
+class BnDxArgs(C.Structure):
+    """nvsm_debug_bn_dx_args (include/cunvsm_amd_test_hooks.h)."""
+    _fields_ = [
+        ("rows", C.c_int64), ("dim", C.c_int),
+        ("dy", C.c_void_p), ("pre", C.c_void_p), ("mean", C.c_void_p), ("inv_std", C.c_void_p),
+        ("sums", C.c_void_p), ("n_global", C.c_double),
+        ("dy_out", C.c_void_p), ("dbeta", C.c_void_p), ("dgamma", C.c_void_p), ("grad_bias", C.c_void_p),
+    ]
+
+
+ROW_MEANSQ, ROW_L2_FORWARD, ROW_L2_BACKWARD, ROW_MATERIALIZE, ROW_MATERIALIZE_L2 = range(5)
+
+
+class RowOpArgs(C.Structure):
+    """nvsm_debug_row_op_args (include/cunvsm_amd_test_hooks.h)."""
+    _fields_ = [
+        ("op", C.c_int), ("rows", C.c_int64), ("dim", C.c_int),
+        ("x", C.c_void_p), ("g", C.c_void_p), ("norms", C.c_void_p), ("coef", C.c_void_p),
+        ("E", C.c_void_p), ("table_rows", C.c_int64), ("ids", C.c_void_p), ("R", C.c_int),
+        ("scale", C.c_float), ("in_place", C.c_int),
+        ("out", C.c_void_p), ("out_scalar", C.c_void_p),
+    ]
+
+
+class TransformUpdateArgs(C.Structure):
+    """nvsm_debug_transform_update_args (include/cunvsm_amd_test_hooks.h)."""
+    _fields_ = [
+        ("method", C.c_int), ("dw", C.c_int), ("de", C.c_int),
+        ("lr", C.c_float), ("lambda_", C.c_float), ("t_transform", C.c_uint64),
+        ("T", C.c_void_p), ("b", C.c_void_p), ("gT", C.c_void_p), ("gb", C.c_void_p),
+        ("s0T", C.c_void_p), ("s0b", C.c_void_p), ("s1T", C.c_void_p), ("s1b", C.c_void_p),
+        ("partial", C.c_void_p), ("slabs", C.c_int),
+        ("plane_kind", C.c_int * 2), ("planes", C.c_void_p * 2), ("fresh", C.c_void_p * 2),
+    ]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_void_p)
 
 
@@ -310,6 +346,13 @@ class _Library:
                 "nvsm_debug_tsne_gradient": (C.c_int, [vp, vp, i64, C.c_float, vp, P(C.c_double)]),
                 "nvsm_debug_tsne_pca": (C.c_int, [vp, i64, C.c_int, vp]),
                 "nvsm_debug_tsne_descent": (C.c_int, [vp, vp, i64, P(NvsmTsneOptions), C.c_int, P(C.c_double), P(C.c_int32)]),
+                "nvsm_debug_adam_u": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, C.c_float, C.c_float, vp]),
+                "nvsm_debug_adagrad_scale": (C.c_int, [i64, vp, vp, C.c_int, i64, C.c_float, vp]),
+                "nvsm_debug_bn_dx": (C.c_int, [P(BnDxArgs)]),
+                "nvsm_debug_row_op": (C.c_int, [P(RowOpArgs)]),
+                "nvsm_debug_slab_sum": (C.c_int, [C.c_int, vp, C.c_int, i64, i64, vp]),
+                "nvsm_debug_plane_sizes": (C.c_int, [C.c_int, C.c_int, C.c_int, P(i64), P(i64)]),
+                "nvsm_debug_transform_update": (C.c_int, [P(TransformUpdateArgs)]),
             }.items():
                 fn = getattr(H, hook)
                 fn.restype = res

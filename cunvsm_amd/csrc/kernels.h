@@ -532,6 +532,10 @@ struct TransformUpdateArgs {
     float lr, lambda, eps, one_m_b1, s_m, one_m_b2, s_v, bc;
 };
 void launch_transform_update(const TransformUpdateArgs& a, hipStream_t s);
+// the scalars of the launch (method, lr, lambda, eps, the Adam factors and the bias correction at step count t) as
+// Model::update_transform hands them over; model.cpp
+float adam_bias_correction(uint64_t t);
+void fill_transform_consts(TransformUpdateArgs& a, int method, float lr, float sl, uint64_t t);
 
 // ---- ranking: query inference and top-k documents (rank.hip; Model::infer, cpp/model.cu:105-133; py/nvsm/base.py:297-430) ----
 // query side: ragged weighted gather-mean (ids / wts / offsets on the device; `lazy` as launch_gather_mean), then f(pre + c·b) in place

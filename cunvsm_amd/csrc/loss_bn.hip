@@ -712,10 +712,11 @@ void launch_l2_rows_forward(const float* x, int64_t rows, int dim, float* y, flo
     if (rows > 0) hipLaunchKernelGGL(l2_rows_forward_kernel, dim3(stream_grid(rows * 64, 256)), dim3(256), 0, s, x, rows, dim, y, norms);
 }
 
-// gin = scale · (g·n² − x·(x·g)) / n³ (in place over g allowed), msq[b] = mean_t(gin²) when msq != null
-__global__ __launch_bounds__(256) void l2_rows_backward_kernel(const float* __restrict__ g, const float* __restrict__ x,
+// gin = scale · (g·n² − x·(x·g)) / n³, msq[b] = mean_t(gin²) when msq != null. In place over g allowed — Model::backward calls it
+// so —: g and gin carry no __restrict__, and a lane reads element t of g for the last time before it stores element t of gin.
+__global__ __launch_bounds__(256) void l2_rows_backward_kernel(const float* g, const float* __restrict__ x,
                                                                const float* __restrict__ norms, int64_t rows, int dim,
-                                                               float scale, float inv_dim, float* __restrict__ gin,
+                                                               float scale, float inv_dim, float* gin,
                                                                float* __restrict__ msq) {
     const int lane = threadIdx.x & 63;
     for (int64_t b = blockIdx.x * 4 + (threadIdx.x >> 6); b < rows; b += static_cast<int64_t>(gridDim.x) * 4) {

@@ -1746,10 +1746,11 @@ float Model::get_cost() {
 // ---------------------------------------------------------------------------------------------
 // update — cpp/model.cu:187-220: entities → words → transform
 // ---------------------------------------------------------------------------------------------
-float Model::adam_bc(uint64_t t) const {
+float adam_bias_correction(uint64_t t) {
     const double b1 = static_cast<double>(0.9f), b2 = static_cast<double>(0.999f);
     return static_cast<float>(std::sqrt(1.0 - std::pow(b2, static_cast<double>(t))) / (1.0 - std::pow(b1, static_cast<double>(t))));
 }
+float Model::adam_bc(uint64_t t) const { return adam_bias_correction(t); }
 
 // Entries per level-1 chunk of a long row. The small-batch steps of SGD and Adagrad on NARROW rows (the LSE recipe: batch 4 096,
 // 128-wide word rows, eight thread groups to a workgroup) end in the hottest row's chain of dependent round trips — a 64-entry chunk
@@ -2115,19 +2116,24 @@ void Model::update_words(float lr, float sl, hipStream_t untouched_stream) {
     lazy_end_update(t, c, stream_);
 }
 
+// the scalars of launch_transform_update (kernels.h): also what nvsm_debug_transform_update fills its launch with
+void fill_transform_consts(TransformUpdateArgs& a, int method, float lr, float sl, uint64_t t) {
+    a.method = method;
+    a.lr = lr; a.lambda = sl; a.eps = 1e-6f;
+    const double b1 = static_cast<double>(0.9f), b2 = static_cast<double>(0.999f);
+    a.one_m_b1 = static_cast<float>(1.0 - b1); a.one_m_b2 = static_cast<float>(1.0 - b2);
+    a.s_m = static_cast<float>(1.0 - 1.0 * static_cast<double>(a.one_m_b1));
+    a.s_v = static_cast<float>(1.0 - 1.0 * static_cast<double>(a.one_m_b2));
+    a.bc = adam_bias_correction(t);
+}
+
 void Model::update_transform(float lr, float sl, hipStream_t strm) {
     PROF_ON("transform_update", strm);
     TransformUpdateArgs a{};
     a.T = T_.p; a.b = b_.p; a.gT = gT_.p; a.gb = gb_.p;
     a.s0T = s0T_.p; a.s0b = s0b_.p; a.s1T = s1T_.p; a.s1b = s1b_.p;
     a.nT = cfg_.entity_repr_size * cfg_.word_repr_size; a.nb = cfg_.entity_repr_size;
-    a.method = cfg_.update_method;
-    a.lr = lr; a.lambda = sl; a.eps = 1e-6f;
-    const double b1 = static_cast<double>(0.9f), b2 = static_cast<double>(0.999f);
-    a.one_m_b1 = static_cast<float>(1.0 - b1); a.one_m_b2 = static_cast<float>(1.0 - b2);
-    a.s_m = static_cast<float>(1.0 - 1.0 * static_cast<double>(a.one_m_b1));
-    a.s_v = static_cast<float>(1.0 - 1.0 * static_cast<double>(a.one_m_b2));
-    a.bc = adam_bc(t_transform_);
+    fill_transform_consts(a, cfg_.update_method, lr, sl, t_transform_);
     if (cfg_.update_method == NVSM_ADAM) t_transform_ += 1;
     // T changes: its bf16 planes for the next step's two projection products are written by the update kernel itself (off the
     // critical path in the fused step: side stream 2, which the next projection GEMM joins anyway). Which layout: the kernels

@@ -939,3 +939,249 @@ int nvsm_debug_lex_df(const int32_t* tokens, int64_t num_tokens, const int64_t* 
 }
 
 }  // extern "C"
+
+// ---- the streaming kernels of a training step, one launcher each (cunvsm_amd_test_hooks.h) ----
+namespace {
+void step_bad(const char* who, const char* what) { throw Error(NVSM_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); }
+void step_fill(void* p, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemset(p, 0xFF, bytes)); }
+void step_up(void* d, const void* h, size_t bytes) { if (bytes) NVSM_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice)); }
+void step_down(void* h, const void* d, size_t bytes) { if (h && bytes) NVSM_HIP_CHECK(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost)); }
+// a device copy of n host floats
+void step_in(cunvsm::DevBuf<float>& d, const float* h, size_t n) { d.alloc(n); step_up(d.p, h, n * sizeof(float)); }
+// an output of n owned floats and `guard` more, all 0xFF
+void step_out(cunvsm::DevBuf<float>& d, size_t n, size_t guard) { d.alloc(n + guard); step_fill(d.p, (n + guard) * sizeof(float)); }
+void step_ids(const char* who, const int32_t* ids, int64_t n, int64_t limit) {
+    for (int64_t i = 0; i < n; ++i) if (ids[i] < 0 || ids[i] >= limit) step_bad(who, "id out of range");
+}
+// the work items of the kernels that count them in 32 bits (adam_u, bn_dx): rows * nvec
+void step_items32(const char* who, int64_t rows, int dim) {
+    const int64_t nvec = dim % 4 == 0 ? dim / 4 : dim;
+    if (rows > ((int64_t(1) << 32) - 1) / nvec) step_bad(who, "rows * vectors per row must stay below 2^32");
+}
+void step_sync() {
+    NVSM_HIP_CHECK(hipGetLastError());
+    NVSM_HIP_CHECK(hipDeviceSynchronize());
+}
+}  // namespace
+
+extern "C" {
+
+int nvsm_debug_adam_u(int64_t rows, int dim, const float* m, const float* v, const int32_t* idx, int window, int64_t B, float bc,
+                      float eps, float* U_out) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(v); NVSM_REQUIRE(idx); NVSM_REQUIRE(U_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        if (rows < 1 || rows >= (int64_t(1) << 31) || dim < 1 || window < 1 || B < 1 || B > (int64_t(1) << 40) / window) step_bad("adam_u", "bad sizes");
+        step_items32("adam_u", B, dim);
+        step_ids("adam_u", idx, B * window, rows);
+        DevBuf<float> M, V, U;
+        DevBuf<int> I;
+        step_in(M, m, static_cast<size_t>(rows) * dim); step_in(V, v, static_cast<size_t>(rows));
+        I.alloc(static_cast<size_t>(B) * window); step_up(I.p, idx, I.n * sizeof(int));
+        step_out(U, static_cast<size_t>(B) * dim, dim);
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        launch_adam_u(M.p, V.p, dim, I.p, window, B, bc, eps, U.p, nullptr);
+        step_sync();
+        step_down(U_out, U.p, U.n * sizeof(float));
+    });
+}
+
+int nvsm_debug_adagrad_scale(int64_t rows, const float* acc, const int32_t* idx, int window, int64_t B, float eps, float* scale_out) {
+    NVSM_REQUIRE(acc); NVSM_REQUIRE(idx); NVSM_REQUIRE(scale_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        if (rows < 1 || rows >= (int64_t(1) << 31) || window < 1 || B < 1 || B > (int64_t(1) << 40) / window) step_bad("adagrad_scale", "bad sizes");
+        step_ids("adagrad_scale", idx, B * window, rows);
+        DevBuf<float> A, S;
+        DevBuf<int> I;
+        step_in(A, acc, static_cast<size_t>(rows));
+        I.alloc(static_cast<size_t>(B) * window); step_up(I.p, idx, I.n * sizeof(int));
+        step_out(S, static_cast<size_t>(B), 1);
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        launch_adagrad_scale(A.p, I.p, window, B, eps, S.p, nullptr);
+        step_sync();
+        step_down(scale_out, S.p, S.n * sizeof(float));
+    });
+}
+
+int nvsm_debug_bn_dx(const nvsm_debug_bn_dx_args* a) {
+    NVSM_REQUIRE(a); NVSM_REQUIRE(a->sums); NVSM_REQUIRE(a->grad_bias);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        const int64_t rows = a->rows;
+        const int dim = a->dim;
+        const size_t sd = static_cast<size_t>(dim > 0 ? dim : 0);
+        if (dim < 1 || dim > (1 << 20)) step_bad("bn_dx", "bad sizes");
+        DevBuf<float> dy, pre, mean, inv_std, dbeta, dgamma, gbias;
+        DevBuf<double> sums;
+        sums.alloc(2 * sd); step_up(sums.p, a->sums, 2 * sd * sizeof(double));
+        step_out(dbeta, sd, 1); step_out(dgamma, sd, 1); step_out(gbias, sd, 1);
+        if (a->pre) {
+            if (rows < 1 || rows >= (int64_t(1) << 31) || !a->dy || !a->mean || !a->inv_std || !a->dy_out || !a->dbeta || !a->dgamma || !(a->n_global > 0))
+                step_bad("bn_dx", "the batch-norm backward needs rows, dy, pre, mean, inv_std, n_global > 0 and every output");
+            step_items32("bn_dx", rows, dim);
+            const size_t RD = static_cast<size_t>(rows) * dim;
+            step_out(dy, RD, sd); step_up(dy.p, a->dy, RD * sizeof(float));
+            step_in(pre, a->pre, RD); step_in(mean, a->mean, sd); step_in(inv_std, a->inv_std, sd);
+            NVSM_HIP_CHECK(hipDeviceSynchronize());
+            launch_bn_dx(dy.p, pre.p, mean.p, inv_std.p, sums.p, dbeta.p, dgamma.p, gbias.p, a->n_global, rows, dim, nullptr);
+            step_sync();
+            step_down(a->dy_out, dy.p, dy.n * sizeof(float));
+        } else {
+            NVSM_HIP_CHECK(hipDeviceSynchronize());
+            launch_colsum_finalize(sums.p, dim, gbias.p, nullptr);
+            step_sync();
+        }
+        step_down(a->dbeta, dbeta.p, dbeta.n * sizeof(float));
+        step_down(a->dgamma, dgamma.p, dgamma.n * sizeof(float));
+        step_down(a->grad_bias, gbias.p, gbias.n * sizeof(float));
+    });
+}
+
+int nvsm_debug_row_op(const nvsm_debug_row_op_args* a) {
+    NVSM_REQUIRE(a); NVSM_REQUIRE(a->x);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        const int64_t rows = a->rows;
+        const int dim = a->dim, op = a->op;
+        if (op < NVSM_DEBUG_ROW_MEANSQ || op > NVSM_DEBUG_ROW_MATERIALIZE_L2) step_bad("row_op", "op 0 .. 4");
+        if (rows < 1 || rows >= (int64_t(1) << 24) || dim < 1 || dim > (1 << 16)) step_bad("row_op", "bad sizes");
+        const size_t RD = static_cast<size_t>(rows) * dim, sd = static_cast<size_t>(dim), R1 = static_cast<size_t>(rows);
+        DevBuf<float> x, g, norms, coef, E, out, sc;
+        DevBuf<int> ids;
+        const bool wants_out = op != NVSM_DEBUG_ROW_MEANSQ;
+        const bool wants_sc = op == NVSM_DEBUG_ROW_MEANSQ || op == NVSM_DEBUG_ROW_L2_FORWARD || a->out_scalar != nullptr;
+        if (wants_out && !a->out) step_bad("row_op", "out is required");
+        if (op == NVSM_DEBUG_ROW_MATERIALIZE && a->out_scalar) step_bad("row_op", "the plain materialise has no scalar output");
+        if (wants_sc && !a->out_scalar) step_bad("row_op", "out_scalar is required");
+        if (wants_out) step_out(out, RD, sd);
+        if (wants_sc) step_out(sc, R1, 1);
+        switch (op) {
+        case NVSM_DEBUG_ROW_MEANSQ:
+            step_in(x, a->x, RD);
+            NVSM_HIP_CHECK(hipDeviceSynchronize());
+            launch_row_meansq(x.p, rows, dim, a->scale, sc.p, nullptr);
+            break;
+        case NVSM_DEBUG_ROW_L2_FORWARD:
+            step_in(x, a->x, RD);
+            NVSM_HIP_CHECK(hipDeviceSynchronize());
+            launch_l2_rows_forward(x.p, rows, dim, out.p, sc.p, nullptr);
+            break;
+        case NVSM_DEBUG_ROW_L2_BACKWARD:
+            if (!a->g || !a->norms) step_bad("row_op", "the normaliser's backward needs g and norms");
+            step_in(x, a->x, RD); step_in(norms, a->norms, R1);
+            if (a->in_place) step_up(out.p, a->g, RD * sizeof(float));      // (the guard row behind it stays 0xFF)
+            else step_in(g, a->g, RD);
+            NVSM_HIP_CHECK(hipDeviceSynchronize());
+            launch_l2_rows_backward(a->in_place ? out.p : g.p, x.p, norms.p, rows, dim, a->scale, out.p, sc.p, nullptr);
+            break;
+        default: {
+            const int R = a->R;
+            if (R < 1 || !a->coef) step_bad("row_op", "the materialise ops need coef and R >= 1");
+            const size_t prows = static_cast<size_t>((rows + R - 1) / R);
+            step_in(x, a->x, prows * sd); step_in(coef, a->coef, R1);
+            if (op == NVSM_DEBUG_ROW_MATERIALIZE_L2) {
+                if (!a->E || !a->ids || a->table_rows < 1 || a->table_rows >= (int64_t(1) << 31)) step_bad("row_op", "the normalised materialise needs E, ids and table_rows");
+                step_ids("row_op", a->ids, rows, a->table_rows);
+                step_in(E, a->E, static_cast<size_t>(a->table_rows) * sd);
+                ids.alloc(R1); step_up(ids.p, a->ids, R1 * sizeof(int));
+                NVSM_HIP_CHECK(hipDeviceSynchronize());
+                launch_materialize_grad_entity_l2(coef.p, x.p, E.p, ids.p, rows, R, dim, out.p, sc.p, nullptr);
+            } else {
+                NVSM_HIP_CHECK(hipDeviceSynchronize());
+                launch_materialize_grad_entity(coef.p, x.p, rows, R, dim, out.p, nullptr);
+            }
+        }
+        }
+        step_sync();
+        if (wants_out) step_down(a->out, out.p, out.n * sizeof(float));
+        if (wants_sc) step_down(a->out_scalar, sc.p, sc.n * sizeof(float));
+    });
+}
+
+int nvsm_debug_slab_sum(int which, const float* parts, int nparts, int64_t stride, int64_t n, float* out) {
+    NVSM_REQUIRE(parts); NVSM_REQUIRE(out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        if ((which != 0 && which != 1) || nparts < 1 || nparts > 4096 || n < 1 || stride < n || stride > (int64_t(1) << 32) / nparts)
+            step_bad("slab_sum", "which 0 / 1, 1 <= nparts <= 4096, 1 <= n <= stride");
+        DevBuf<float> P, O;
+        step_in(P, parts, static_cast<size_t>(nparts) * stride);
+        step_out(O, static_cast<size_t>(n), 1);
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        if (which == 0) launch_splitk_reduce(P.p, nparts, static_cast<size_t>(stride), O.p, n, nullptr);
+        else launch_sum_parts(P.p, nparts, stride, O.p, n, nullptr);
+        step_sync();
+        step_down(out, O.p, O.n * sizeof(float));
+    });
+}
+
+int nvsm_debug_plane_sizes(int kind, int N, int K, int64_t* bytes, int64_t* plane_stride) {
+    NVSM_REQUIRE(bytes); NVSM_REQUIRE(plane_stride);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        if ((kind != 1 && kind != 2) || N < 1 || K < 1 || N > (1 << 14) || K > (1 << 14)) step_bad("plane_sizes", "kind 1 / 2, 1 <= N, K <= 16384");
+        *bytes = static_cast<int64_t>(kind == 1 ? gemm_split_planes_bytes(N, K) : gemm_rsplit_planes_bytes(N, K));
+        const PlaneTarget t = kind == 1 ? gemm_split_plane_target(N, K, nullptr, 0) : gemm_rsplit_plane_target(N, K, nullptr, 0);
+        *plane_stride = static_cast<int64_t>(t.plane_stride);
+    });
+}
+
+int nvsm_debug_transform_update(const nvsm_debug_transform_update_args* a) {
+    NVSM_REQUIRE(a); NVSM_REQUIRE(a->T); NVSM_REQUIRE(a->b); NVSM_REQUIRE(a->gT); NVSM_REQUIRE(a->gb);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        const int dw = a->dw, de = a->de, method = a->method;
+        if (method != NVSM_SGD && method != NVSM_ADAGRAD && method != NVSM_ADAM) step_bad("transform_update", "method 0 SGD / 1 Adagrad / 2 Adam");
+        if (dw < 1 || de < 1 || dw > (1 << 12) || de > (1 << 12) || a->t_transform < 1) step_bad("transform_update", "bad sizes");
+        if (method != NVSM_SGD && (!a->s0T || !a->s0b)) step_bad("transform_update", "Adagrad and Adam need s0T and s0b");
+        if (method == NVSM_ADAM && (!a->s1T || !a->s1b)) step_bad("transform_update", "Adam needs s1T and s1b");
+        if (a->partial && (a->slabs < 1 || a->slabs > 4096)) step_bad("transform_update", "1 <= slabs <= 4096");
+        for (int i = 0; i < 2; ++i) {
+            if (a->plane_kind[i] < 0 || a->plane_kind[i] > 2) step_bad("transform_update", "plane_kind 0 / 1 / 2");
+            if (a->plane_kind[i] && (!a->planes[i] || !a->fresh[i])) step_bad("transform_update", "a plane target needs planes and fresh");
+        }
+        const size_t nT = static_cast<size_t>(dw) * de, nb = static_cast<size_t>(de);
+        DevBuf<float> T, b, gT, gb, s0T, s0b, s1T, s1b, partial;
+        auto inout = [](DevBuf<float>& d, const float* h, size_t n) { step_out(d, n, 1); step_up(d.p, h, n * sizeof(float)); };
+        inout(T, a->T, nT); inout(b, a->b, nb); inout(gT, a->gT, nT); inout(gb, a->gb, nb);
+        if (a->s0T) { inout(s0T, a->s0T, nT); inout(s0b, a->s0b, nb); }
+        if (a->s1T) { inout(s1T, a->s1T, nT); inout(s1b, a->s1b, nb); }
+        if (a->partial) step_in(partial, a->partial, static_cast<size_t>(a->slabs) * nT);
+
+        TransformUpdateArgs u{};
+        u.T = T.p; u.b = b.p; u.gT = gT.p; u.gb = gb.p;
+        u.s0T = s0T.p; u.s0b = s0b.p; u.s1T = s1T.p; u.s1b = s1b.p;
+        u.nT = static_cast<int>(nT); u.nb = de; u.de = de;
+        fill_transform_consts(u, method, a->lr, a->lambda, a->t_transform);
+        if (a->partial) { u.partial = partial.p; u.slabs = a->slabs; u.slab_stride = nT; }
+        // pt[0]: the forward product's B (N = de, K = dw), pt[1]: the backward one's (N = dw, K = de, transposed) - Model::update_transform
+        DevBuf<char> planes[2], fresh[2];
+        for (int i = 0; i < 2; ++i) {
+            const int kind = a->plane_kind[i], N = i == 0 ? de : dw, K = i == 0 ? dw : de;
+            if (!kind) continue;
+            const size_t bytes = kind == 1 ? gemm_split_planes_bytes(N, K) : gemm_rsplit_planes_bytes(N, K);
+            planes[i].alloc(bytes, true);                   // zero-filled, as Model's are
+            fresh[i].alloc(bytes); step_fill(fresh[i].p, bytes);
+            u.pt[i] = kind == 1 ? gemm_split_plane_target(N, K, planes[i].p, i) : gemm_rsplit_plane_target(N, K, planes[i].p, i);
+        }
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        launch_transform_update(u, nullptr);
+        step_sync();
+        for (int i = 0; i < 2; ++i) {      // Model::cut_transform_planes' arguments
+            const int kind = a->plane_kind[i];
+            if (!kind) continue;
+            if (kind == 1) { if (i == 0) launch_gemm_split_planes(0, T.p, de, dw, de, fresh[i].p, nullptr); else launch_gemm_split_planes(1, T.p, dw, de, de, fresh[i].p, nullptr); }
+            else { if (i == 0) launch_gemm_rsplit_planes(0, T.p, de, dw, de, fresh[i].p, nullptr); else launch_gemm_rsplit_planes(1, T.p, dw, de, de, fresh[i].p, nullptr); }
+        }
+        step_sync();
+        step_down(a->T, T.p, T.n * sizeof(float)); step_down(a->b, b.p, b.n * sizeof(float));
+        step_down(a->gT, gT.p, gT.n * sizeof(float)); step_down(a->gb, gb.p, gb.n * sizeof(float));
+        if (a->s0T) { step_down(a->s0T, s0T.p, s0T.n * sizeof(float)); step_down(a->s0b, s0b.p, s0b.n * sizeof(float)); }
+        if (a->s1T) { step_down(a->s1T, s1T.p, s1T.n * sizeof(float)); step_down(a->s1b, s1b.p, s1b.n * sizeof(float)); }
+        for (int i = 0; i < 2; ++i)
+            if (a->plane_kind[i]) { step_down(a->planes[i], planes[i].p, planes[i].n); step_down(a->fresh[i], fresh[i].p, fresh[i].n); }
+    });
+}
+
+}  // extern "C"

@@ -210,6 +210,73 @@ int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* args);
 int nvsm_debug_lex_df(const int32_t* tokens, int64_t num_tokens, const int64_t* doc_offsets, int64_t num_documents, int64_t num_words,
                       int64_t slab, int64_t* df_out);
 
+/* ---- the streaming kernels of a training step, one launcher each (tests/test_gpu_step_kernels.py) ----
+ * As nvsm_debug_loss and nvsm_debug_table_pass: host arrays go up, the product's own launcher runs once, everything comes back. Every
+ * output starts as 0xFF bytes and carries a guard behind what the kernel owns (one more row or element), which comes back too. Bad
+ * sizes and ids outside the table are refused with NVSM_ERR_INVALID_ARGUMENT on the host and never reach the device. */
+/* launch_adam_u (csrc/update.hip): m [rows][dim], v [rows], idx [B][window] each in [0, rows); U_out [B + 1][dim].
+ * B * (dim / 4 where dim is a multiple of 4, else dim) must stay below 2^32: the kernel counts its work items in 32 bits. */
+int nvsm_debug_adam_u(int64_t rows, int dim, const float* m, const float* v, const int32_t* idx, int window, int64_t B, float bc,
+                      float eps, float* U_out);
+/* launch_adagrad_scale: acc [rows], idx [B][window]; scale_out [B + 1] */
+int nvsm_debug_adagrad_scale(int64_t rows, const float* acc, const int32_t* idx, int window, int64_t B, float eps, float* scale_out);
+/* launch_bn_dx (csrc/loss_bn.hip) on dy, pre [rows][dim], mean, inv_std [dim], sums [2][dim] (column sums of dy and of dy * xhat) and
+ * n_global; with pre == NULL launch_colsum_finalize(sums, dim, grad_bias) instead, which reads the first row of sums only: dbeta and
+ * dgamma come back as the 0xFF bytes they started as, dy_out is not written. rows * (dim / 4 or dim, as above) below 2^32. */
+typedef struct nvsm_debug_bn_dx_args {
+    int64_t rows; int dim;
+    const float* dy; const float* pre; const float* mean; const float* inv_std;
+    const double* sums; double n_global;
+    float* dy_out;                               /* out [rows + 1][dim]: dy after the launch (dx) */
+    float* dbeta; float* dgamma; float* grad_bias;   /* out [dim + 1] */
+} nvsm_debug_bn_dx_args;
+int nvsm_debug_bn_dx(const nvsm_debug_bn_dx_args* args);
+/* ONE of the wave-per-row launchers of csrc/loss_bn.hip:
+ *   MEANSQ          launch_row_meansq(x, rows, dim, scale)                      -> out_scalar
+ *   L2_FORWARD      launch_l2_rows_forward(x, rows, dim)                        -> out (y), out_scalar (norms)
+ *   L2_BACKWARD     launch_l2_rows_backward(g, x, norms, rows, dim, scale)      -> out (gin), out_scalar (msq; NULL: the launcher gets none).
+ *                   in_place: ONE device buffer [rows + 1][dim] holding g is passed as g and as gin, as Model::backward does.
+ *   MATERIALIZE     launch_materialize_grad_entity(coef, x = proj, rows, R, dim)               -> out
+ *   MATERIALIZE_L2  launch_materialize_grad_entity_l2(coef, x = proj, E, ids, rows, R, dim)    -> out, out_scalar (msq; NULL: none)
+ * For the two materialise ops `rows` counts gathered rows (entries j), x is proj [(rows + R - 1) / R][dim], coef [rows], ids [rows]
+ * each in [0, table_rows), E [table_rows][dim]. out is [rows + 1][dim], out_scalar [rows + 1]. */
+enum { NVSM_DEBUG_ROW_MEANSQ = 0, NVSM_DEBUG_ROW_L2_FORWARD = 1, NVSM_DEBUG_ROW_L2_BACKWARD = 2, NVSM_DEBUG_ROW_MATERIALIZE = 3,
+       NVSM_DEBUG_ROW_MATERIALIZE_L2 = 4 };
+typedef struct nvsm_debug_row_op_args {
+    int op; int64_t rows; int dim;
+    const float* x; const float* g; const float* norms; const float* coef;
+    const float* E; int64_t table_rows; const int32_t* ids; int R;
+    float scale; int in_place;
+    float* out; float* out_scalar;
+} nvsm_debug_row_op_args;
+int nvsm_debug_row_op(const nvsm_debug_row_op_args* args);
+/* The two ordered sums of csrc/gather_gemm.hip over parts [nparts][stride], n <= stride elements of each: which 0 =
+ * launch_splitk_reduce, 1 = launch_sum_parts; out [n + 1]. Both buffers come from the device allocator (16-byte aligned), so
+ * launch_splitk_reduce takes its float4 kernel exactly where n and stride are multiples of 4. */
+int nvsm_debug_slab_sum(int which, const float* parts, int nparts, int64_t stride, int64_t n, float* out);
+/* Host-only (never touches the GPU): gemm_split_planes_bytes / gemm_rsplit_planes_bytes (kind 1 / 2) of an N x K operand and the
+ * plane_stride of its gemm_*_plane_target. */
+int nvsm_debug_plane_sizes(int kind, int N, int K, int64_t* bytes, int64_t* plane_stride);
+/* ONE launch_transform_update (csrc/update.hip) on T [dw][de] and b [de]. The kernel's scalars come from fill_transform_consts
+ * (kernels.h), the function Model::update_transform derives them by, from (method, lr, lambda, t_transform: the Adam step count the
+ * bias correction is taken at, 1 for the first update). T, gT, s0T, s1T are [dw * de + 1] and b, gb, s0b, s1b [de + 1]: all but the
+ * last element go up, all come back, the last one being the 0xFF guard. s0* are required by Adagrad and Adam, s1* by Adam.
+ * partial [slabs][dw * de] (or NULL): the dT product's slabs, added up by the update in place of gT's content.
+ * plane_kind[i] (0 none, 1 gemm_split_plane_target, 2 gemm_rsplit_plane_target) for pt[0] = (N = de, K = dw, transposed 0) and
+ * pt[1] = (N = dw, K = de, transposed 1): planes[i] receives the whole buffer (nvsm_debug_plane_sizes bytes; zero-filled in front
+ * of the launch, as the model's are) the update wrote its bf16 pieces into, and fresh[i] the buffer launch_gemm_split_planes /
+ * launch_gemm_rsplit_planes cut from the updated T with the model's arguments, into memory that started as 0xFF bytes. */
+typedef struct nvsm_debug_transform_update_args {
+    int method; int dw, de;
+    float lr, lambda; uint64_t t_transform;
+    float* T; float* b; float* gT; float* gb;
+    float* s0T; float* s0b; float* s1T; float* s1b;
+    const float* partial; int slabs;
+    int plane_kind[2];
+    unsigned char* planes[2]; unsigned char* fresh[2];
+} nvsm_debug_transform_update_args;
+int nvsm_debug_transform_update(const nvsm_debug_transform_update_args* args);
+
 #ifdef __cplusplus
 }
 #endif
