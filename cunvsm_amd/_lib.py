@@ -183,6 +183,18 @@ class NvsmTsneOptions(C.Structure):
     ]
 
 
+KMEANS_MAX_CLUSTERS = 4096
+KMEANS_INIT_PLUSPLUS, KMEANS_INIT_GIVEN = 0, 1
+
+
+class NvsmKmeansOptions(C.Structure):
+    _fields_ = [
+        ("space", C.c_int32), ("l2_normalize", C.c_int32), ("ids", C.c_void_p), ("num_rows", C.c_int64),
+        ("num_clusters", C.c_int32), ("max_iter", C.c_int32), ("tol", C.c_double), ("init", C.c_int32), ("reserved0", C.c_int32),
+        ("init_centers", C.c_void_p), ("seed", C.c_int64), ("reserved", C.c_int32 * 6),
+    ]
+
+
 class GemmEpilogueArgs(C.Structure):
     """nvsm_debug_gemm_epilogue_args (include/cunvsm_amd_test_hooks.h)."""
     _fields_ = [
@@ -346,6 +358,9 @@ class _Library:
                 "nvsm_debug_tsne_gradient": (C.c_int, [vp, vp, i64, C.c_float, vp, P(C.c_double)]),
                 "nvsm_debug_tsne_pca": (C.c_int, [vp, i64, C.c_int, vp]),
                 "nvsm_debug_tsne_descent": (C.c_int, [vp, vp, i64, P(NvsmTsneOptions), C.c_int, P(C.c_double), P(C.c_int32)]),
+                "nvsm_debug_kmeans_assign": (C.c_int, [vp, i64, C.c_int, vp, C.c_int, vp, vp]),
+                "nvsm_debug_kmeans_update": (C.c_int, [vp, i64, C.c_int, vp, vp, C.c_int, vp, vp, P(C.c_double)]),
+                "nvsm_debug_kmeans_plusplus": (C.c_int, [vp, i64, C.c_int, C.c_int, i64, vp, vp]),
                 "nvsm_debug_adam_u": (C.c_int, [i64, C.c_int, vp, vp, vp, C.c_int, i64, C.c_float, C.c_float, vp]),
                 "nvsm_debug_adagrad_scale": (C.c_int, [i64, vp, vp, C.c_int, i64, C.c_float, vp]),
                 "nvsm_debug_bn_dx": (C.c_int, [P(BnDxArgs)]),
@@ -447,6 +462,8 @@ def lib():
         "nvsm_ngram_search": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNgramOptions), vp, vp, vp, vp]),
         "nvsm_tsne_options_default": (None, [P(NvsmTsneOptions)]),
         "nvsm_tsne": (C.c_int, [vp, P(NvsmTsneOptions), vp, P(C.c_double), P(C.c_int32)]),
+        "nvsm_kmeans_options_default": (None, [P(NvsmKmeansOptions)]),
+        "nvsm_kmeans": (C.c_int, [vp, P(NvsmKmeansOptions), vp, vp, vp, vp, P(C.c_double), P(C.c_int32)]),
         "nvsm_set_stream": (C.c_int, [vp, vp]), "nvsm_synchronize": (C.c_int, [vp]),
         "nvsm_describe": (C.c_int, [vp, C.c_int64, C.c_char_p, C.c_int64]),
         "nvsm_comm_unique_id": (C.c_int, [vp]), "nvsm_comm_init": (C.c_int, [vp, vp]),

@@ -523,6 +523,18 @@ int nvsm_tsne(nvsm_model* m, const nvsm_tsne_options* opt, float* embedding, dou
     return guarded_on(m, [&] { m->impl.tsne(*opt, embedding, kl_divergence, n_iter); });
 }
 
+void nvsm_kmeans_options_default(nvsm_kmeans_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->space = NVSM_SPACE_ENTITIES;
+    o->num_clusters = 8; o->max_iter = 300; o->tol = 1e-4; o->init = NVSM_KMEANS_INIT_PLUSPLUS; o->seed = 1;
+}
+int nvsm_kmeans(nvsm_model* m, const nvsm_kmeans_options* opt, int32_t* labels, float* centers, int64_t* counts, float* distances,
+                double* inertia, int32_t* n_iter) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(opt); NVSM_REQUIRE(labels); NVSM_REQUIRE(centers); NVSM_REQUIRE(counts); NVSM_REQUIRE(inertia); NVSM_REQUIRE(n_iter);
+    return guarded_on(m, [&] { m->impl.kmeans(*opt, labels, centers, counts, distances, inertia, n_iter); });
+}
+
 int nvsm_set_stream(nvsm_model* m, void* s) { NVSM_REQUIRE(m); return guarded_on(m, [&] { m->impl.set_stream(static_cast<hipStream_t>(s)); }); }
 int nvsm_describe(nvsm_model* m, int64_t batch, char* buf, int64_t buf_bytes) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(buf);

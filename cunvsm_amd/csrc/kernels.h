@@ -614,6 +614,38 @@ void launch_tsne_check(const double* klrow, const float* gs, int n, double* out,
 void launch_tsne_covariance(const float* X, int n, int d, double* mean, double* cov, hipStream_t s);
 void launch_tsne_project(const float* X, int n, int d, const double* mean, const double* V, float* Y0, hipStream_t s);
 
+// ---- k-means of table rows (kmeans.hip; include/cunvsm_amd.h nvsm_kmeans) ----
+// Every pointer below is a device pointer; every floating-point sum has a fixed order (no float atomics).
+// The assignment pass runs on v_mfma_f32_16x16x4_f32 at every dimension (columns beyond d are zeros in LDS): always true today,
+// kept as a predicate so that a caller names the route it got, as nbr_scan_uses_mfma does.
+bool kmeans_assign_uses_mfma(int d);
+int kmeans_stat_slabs(int n);                  // row slabs of launch_kmeans_colstats (part: [slabs][d] doubles)
+int64_t kmeans_max_chunks(int64_t n, int k);   // an upper bound of the chunks of launch_kmeans_update (part: [chunks][d] doubles)
+int64_t kmeans_prefix_chunks(int64_t n);       // chunks of launch_kmeans_kpp_pick (part: [chunks] doubles)
+// mean64 / var [d]: fp64 column mean and population variance of X [n][d]; mean32 its fp32 rounding; *var_mean = mean of var
+void launch_kmeans_colstats(const float* X, int n, int d, double* part, double* mean64, float* mean32, double* var, double* var_mean, hipStream_t s);
+// cc [rows][d] (may be null) = fp32(x − mean); norm [rows] = the squared norms of those (fp64 sums rounded to fp32)
+void launch_kmeans_center_rows(const float* X, int64_t rows, int d, const float* mean, float* cc, float* norm, hipStream_t s);
+// label [n] = argmin_j |x_i − c_j|² by the centred expansion (Cc, cn: launch_kmeans_center_rows of the centres; xn: of the rows), the
+// lowest j on a tie; dist [n] = that minimum, clamped at 0
+void launch_kmeans_assign(const float* X, int n, int d, const float* mean, const float* Cc, const float* cn, const float* xn, int k,
+                          int* label, float* dist, hipStream_t s);
+// out64 [n] = direct fp64 |x_i − c|², c = C[label[i]] or (label null) the row X[fixed]; min_into: the minimum with what out64 holds;
+// out32 (may be null) its fp32 rounding
+void launch_kmeans_rowdist(const float* X, int n, int d, const float* C, const int* label, int64_t fixed, bool min_into, double* out64,
+                           float* out32, hipStream_t s);
+void launch_kmeans_sum(const double* v, int64_t n, double* out, hipStream_t s);      // *out = Σ v, one workgroup, fixed order
+void launch_kmeans_iota(int* v, int n, hipStream_t s);
+// from the labels sorted ascending: start [k + 1] segment bounds, choff [k + 1] chunk offsets, counts [k], *n_empty
+void launch_kmeans_segments(const int* sorted_label, int n, int k, int* start, int* choff, int64_t* counts, int* n_empty, hipStream_t s);
+// Cnew [k][d] = fp32 of the fp64 mean of each segment's rows (pos: row positions in sorted order), Cold's row where a segment is
+// empty; shift [k] and *shift_total = Σ (Cnew − Cold)² (fp64)
+void launch_kmeans_update(const float* X, int n, int d, const int* pos, const int* start, const int* choff, int k, double* part,
+                          const float* Cold, float* Cnew, double* shift, double* shift_total, hipStream_t s);
+void launch_kmeans_changed(const int* a, const int* b, int n, int* changed, hipStream_t s);      // *changed += 1 per workgroup with a moved label
+// out[0] = Σ dmin (two-level sequential prefix); out[1] = the lowest position whose inclusive prefix exceeds u · total, −1 if none
+void launch_kmeans_kpp_pick(const double* dmin, int n, double* part, double u, double* out, hipStream_t s);
+
 // ---- retrieval metrics of a round's ranking (eval.hip; include/cunvsm_amd.h nvsm_evaluate) ----
 // One wave per query of the round. ids [Q][k] / counts [Q]: what launch_rank_write left. Judged documents of ALL queries of the
 // call: jids ascending per query (no -1 entries), jgrades next to them, joff [queries of the call + 1]; consts

@@ -144,6 +144,31 @@ void tsne_pca_start(const float* X, int n, int d, TsneScratch& w, float* Y0, hip
 void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl, int32_t* n_iter,
                   Profiler* prof, hipStream_t s);
 
+// ---- k-means (ranking.cpp; kernels: kmeans.hip): the host side the product call and the test hooks share ----
+struct KmeansScratch {
+    DevBuf<float> x, mean32, xn, c, c2, cc, cn, dist32;
+    DevBuf<double> stats;      // column partials [slabs][d] | mean [d] | var [d] | mean variance, shift total, inertia, the draw's (total, position)
+    DevBuf<double> part, shift, dist64, kpp_part;
+    DevBuf<int> lab_a, lab_b, sorted_lab, pos, iota, start, choff, meta;      // meta: empty clusters, workgroups with a moved label
+    DevBuf<int64_t> counts, ids;
+    DevBuf<char> sort_temp;
+    size_t sort_temp_bytes = 0;
+    void grow_for(int64_t n, int d, int k);
+    double* mean64(int n, int d) { return stats.p + static_cast<size_t>(kmeans_stat_slabs(n)) * d; }
+    double* var(int n, int d) { return mean64(n, d) + d; }
+    double* scalars(int n, int d) { return var(n, d) + d; }      // [0] mean variance [1] shift total [2] inertia [3..4] the draw
+};
+// column statistics of w.x [n][d] (w.mean32, the variances) and the centred rows' norms w.xn; queued on s
+void kmeans_prepare(KmeansScratch& w, int n, int d, hipStream_t s);
+// label [n], w.dist32 [n]: one assignment pass of w.x against C [k][d] (both device); queued on s
+void kmeans_assign_pass(KmeansScratch& w, int n, int d, int k, const float* C, int* label, hipStream_t s);
+// one centre update from label [n] (device; relocated rows are rewritten): empty clusters settled by nvsm_kmeans' rule against Cold,
+// then Cnew [k][d], w.counts [k], the shift total in w.scalars()[1]. relocate false: empty clusters keep Cold's row (the final pass's
+// counts). Returns the number of clusters that were empty. Synchronises s once (twice when a cluster was empty).
+int kmeans_update_pass(KmeansScratch& w, int n, int d, int k, int* label, const float* Cold, float* Cnew, bool relocate, hipStream_t s);
+// the k-means++ start of w.x: C [k][d] (device) and rows [k] (host) the chosen positions. Synchronous on s.
+void kmeans_plusplus(KmeansScratch& w, int n, int d, int k, int64_t seed, float* C, int64_t* rows, hipStream_t s);
+
 class Model {
  public:
     explicit Model(const nvsm_config& cfg);
@@ -228,6 +253,8 @@ class Model {
     void similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out);
     // exact t-SNE of rows of E or W (py/visualize.py; nvsm_tsne): embedding [num_rows][2] host
     void tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_divergence, int32_t* n_iter);
+    // Lloyd's k-means of rows of E or W (nvsm_kmeans): labels [num_rows], centers [k][dim], counts [k], distances [num_rows] or null: host
+    void kmeans(const nvsm_kmeans_options& opt, int32_t* labels, float* centers, int64_t* counts, float* distances, double* inertia, int32_t* n_iter);
 
     void set_stream(hipStream_t s);
     int64_t step_deferred(const nvsm_batch& batch, const int64_t* entity_ids, float lr);
@@ -550,6 +577,7 @@ class Model {
     };
     RankScratch rank_;
     TsneScratch tsne_;      // allocated by the first nvsm_tsne, grown by a later call with more rows
+    KmeansScratch kmeans_;  // likewise for nvsm_kmeans
     int64_t score_floats() const { return static_cast<int64_t>(tune_.rank_slab_mb) << 18; }      // the score slab: 256 MB unless NVSM_RANK_SLAB_MB says otherwise
     // one round behind its layout (ranking.cpp): scratch, the slabs through the caller's fill step, sort + the caller's write, results
     void round_grow(const RankLayout& l, int k);

@@ -1797,4 +1797,211 @@ void Model::tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_dive
     raise_device_error();
 }
 
+// ---- k-means of table rows (include/cunvsm_amd.h nvsm_kmeans; kernels: kmeans.hip) ---------------------------------
+// sklearn's _kmeans_single_lloyd. The host keeps the control flow and reads a few words back per iteration (the number of empty
+// clusters behind the sort, then the moved-label count and the centre shift); rows, labels, centres and every sum stay on the
+// device. An empty cluster — rare — costs a round trip of the fp64 distances and the labels. The passes are free functions so
+// that the test hooks run the same code.
+void KmeansScratch::grow_for(int64_t n, int d, int k) {
+    const size_t nn = static_cast<size_t>(n), dd = static_cast<size_t>(d), kk = static_cast<size_t>(k);
+    grow(x, nn * dd); grow(mean32, dd); grow(xn, nn); grow(dist32, nn);
+    grow(c, kk * dd); grow(c2, kk * dd); grow(cc, kk * dd); grow(cn, kk);
+    grow(stats, static_cast<size_t>(kmeans_stat_slabs(static_cast<int>(n))) * dd + 2 * dd + 8);
+    grow(part, static_cast<size_t>(kmeans_max_chunks(n, k)) * dd);
+    grow(shift, kk); grow(dist64, nn); grow(kpp_part, static_cast<size_t>(kmeans_prefix_chunks(n)));
+    grow(lab_a, nn); grow(lab_b, nn); grow(sorted_lab, nn); grow(pos, nn);
+    grow(start, kk + 1); grow(choff, kk + 1); grow(meta, 4);
+    grow(counts, kk); grow(ids, nn);
+    if (iota.n < nn) {
+        iota.alloc(nn);
+        launch_kmeans_iota(iota.p, static_cast<int>(iota.n), nullptr);
+        NVSM_HIP_CHECK(hipStreamSynchronize(nullptr));
+    }
+    const size_t tb = sort_pairs_temp_bytes(n, 31);
+    if (sort_temp_bytes < tb) { sort_temp.alloc(tb, true); sort_temp_bytes = tb; }
+}
+
+void kmeans_prepare(KmeansScratch& w, int n, int d, hipStream_t s) {
+    double* sc = w.scalars(n, d);
+    launch_kmeans_colstats(w.x.p, n, d, w.stats.p, w.mean64(n, d), w.mean32.p, w.var(n, d), sc, s);
+    launch_kmeans_center_rows(w.x.p, n, d, w.mean32.p, nullptr, w.xn.p, s);
+}
+
+void kmeans_assign_pass(KmeansScratch& w, int n, int d, int k, const float* C, int* label, hipStream_t s) {
+    launch_kmeans_center_rows(C, k, d, w.mean32.p, w.cc.p, w.cn.p, s);
+    launch_kmeans_assign(w.x.p, n, d, w.mean32.p, w.cc.p, w.cn.p, w.xn.p, k, label, w.dist32.p, s);
+}
+
+namespace {
+// labels sorted (stable: positions ascend inside a label), segment bounds, chunk offsets, counts, the number of empty clusters
+int kmeans_sort_segments(KmeansScratch& w, int n, int k, const int* label, hipStream_t s) {
+    int bits = 1;
+    while (bits < 31 && (int64_t(1) << bits) < k) ++bits;
+    sort_pairs(w.sort_temp.p, w.sort_temp_bytes, nullptr, label, w.sorted_lab.p, w.iota.p, w.pos.p, n, bits, nullptr, s);
+    launch_kmeans_segments(w.sorted_lab.p, n, k, w.start.p, w.choff.p, w.counts.p, w.meta.p, s);
+    int empty = 0;
+    NVSM_HIP_CHECK(hipMemcpyAsync(&empty, w.meta.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    NVSM_HIP_CHECK(hipStreamSynchronize(s));
+    return empty;
+}
+}  // namespace
+
+int kmeans_update_pass(KmeansScratch& w, int n, int d, int k, int* label, const float* Cold, float* Cnew, bool relocate, hipStream_t s) {
+    const int empty = kmeans_sort_segments(w, n, k, label, s);
+    if (empty > 0 && relocate) {
+        // nvsm_kmeans' rule, on the host: the fp64 distances of the rows to the centres they are assigned to
+        launch_kmeans_rowdist(w.x.p, n, d, Cold, label, 0, false, w.dist64.p, nullptr, s);
+        std::vector<double> dist(static_cast<size_t>(n));
+        std::vector<int> lab(static_cast<size_t>(n));
+        std::vector<int64_t> cnt(static_cast<size_t>(k));
+        NVSM_HIP_CHECK(hipMemcpyAsync(dist.data(), w.dist64.p, dist.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        NVSM_HIP_CHECK(hipMemcpyAsync(lab.data(), label, lab.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        NVSM_HIP_CHECK(hipMemcpyAsync(cnt.data(), w.counts.p, cnt.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        NVSM_HIP_CHECK(hipStreamSynchronize(s));
+        for (int j = 0; j < k; ++j) {
+            if (cnt[static_cast<size_t>(j)] != 0) continue;
+            int far = -1;
+            for (int i = 0; i < n; ++i) {
+                if (cnt[static_cast<size_t>(lab[static_cast<size_t>(i)])] < 2) continue;
+                if (far < 0 || dist[static_cast<size_t>(i)] > dist[static_cast<size_t>(far)]) far = i;
+            }
+            if (far < 0) break;      // (k <= n: some cluster has two members while one is empty; only non-finite labels get here)
+            --cnt[static_cast<size_t>(lab[static_cast<size_t>(far)])];
+            lab[static_cast<size_t>(far)] = j;
+            cnt[static_cast<size_t>(j)] = 1;
+        }
+        NVSM_HIP_CHECK(hipMemcpyAsync(label, lab.data(), lab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        kmeans_sort_segments(w, n, k, label, s);      // (synchronises: `lab` is this frame's)
+    }
+    launch_kmeans_update(w.x.p, n, d, w.pos.p, w.start.p, w.choff.p, k, w.part.p, Cold, Cnew, w.shift.p, w.scalars(n, d) + 1, s);
+    return empty;
+}
+
+void kmeans_plusplus(KmeansScratch& w, int n, int d, int k, int64_t seed, float* C, int64_t* rows, hipStream_t s) {
+    std::minstd_rand0 gen(static_cast<std::minstd_rand0::result_type>(seed % 2147483647));
+    auto draw = [&] { return (static_cast<double>(gen()) - 1.0) / 2147483646.0; };
+    double* out = w.scalars(n, d) + 3;
+    std::vector<char> chosen(static_cast<size_t>(n), 0);
+    int64_t lowest_free = 0;
+    for (int t = 0; t < k; ++t) {
+        const double u = draw();
+        int64_t p;
+        if (t == 0) {
+            p = std::min<int64_t>(static_cast<int64_t>(std::floor(u * n)), n - 1);
+        } else {
+            double host[2];
+            launch_kmeans_kpp_pick(w.dist64.p, n, w.kpp_part.p, u, out, s);
+            NVSM_HIP_CHECK(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, s));
+            NVSM_HIP_CHECK(hipStreamSynchronize(s));
+            p = static_cast<int64_t>(host[1]);
+            if (p < 0 || p >= n) {      // total is 0 (or not finite): the lowest position not yet chosen (t < k <= n: there is one)
+                while (chosen[static_cast<size_t>(lowest_free)]) ++lowest_free;
+                p = lowest_free;
+            }
+        }
+        chosen[static_cast<size_t>(p)] = 1;
+        rows[t] = p;
+        NVSM_HIP_CHECK(hipMemcpyAsync(C + static_cast<size_t>(t) * d, w.x.p + static_cast<size_t>(p) * d, static_cast<size_t>(d) * sizeof(float),
+                                      hipMemcpyDeviceToDevice, s));
+        if (t + 1 < k) launch_kmeans_rowdist(w.x.p, n, d, nullptr, nullptr, p, t > 0, w.dist64.p, nullptr, s);
+    }
+    NVSM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void Model::kmeans(const nvsm_kmeans_options& opt, int32_t* labels, float* centers, int64_t* counts, float* distances, double* inertia,
+                   int32_t* n_iter) {
+    if (opt.space != NVSM_SPACE_ENTITIES && opt.space != NVSM_SPACE_WORDS)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space: k-means takes the rows of NVSM_SPACE_ENTITIES or NVSM_SPACE_WORDS");
+    const RowSpace sp = row_space(opt.space);
+    const int64_t n = (!opt.ids && opt.num_rows == 0) ? sp.count : opt.num_rows;
+    if (n < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_rows must be at least 1");
+    if (!opt.ids && n > sp.count) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_rows exceeds the rows of the space");
+    if (opt.ids)
+        for (int64_t i = 0; i < n; ++i)
+            if (opt.ids[i] < 0 || opt.ids[i] >= sp.count) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a row id is outside the space");
+    if (opt.num_clusters < 1 || opt.num_clusters > n) throw Error(NVSM_ERR_INVALID_ARGUMENT, "num_clusters must be in [1, num_rows]");
+    if (opt.num_clusters > NVSM_KMEANS_MAX_CLUSTERS) throw Error(NVSM_ERR_UNSUPPORTED, "k-means supports at most NVSM_KMEANS_MAX_CLUSTERS (4096) clusters");
+    if (n >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "k-means supports fewer than 2^31 rows");
+    if (opt.max_iter < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "max_iter must be at least 1");
+    if (!std::isfinite(opt.tol) || opt.tol < 0.0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tol must be finite and not negative");
+    if (opt.init != NVSM_KMEANS_INIT_PLUSPLUS && opt.init != NVSM_KMEANS_INIT_GIVEN) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown init");
+    const int d = sp.dim, rows = static_cast<int>(n), k = opt.num_clusters;
+    if (opt.init == NVSM_KMEANS_INIT_GIVEN) {
+        if (!opt.init_centers) throw Error(NVSM_ERR_INVALID_ARGUMENT, "NVSM_KMEANS_INIT_GIVEN needs init_centers");
+        for (int64_t i = 0; i < static_cast<int64_t>(k) * d; ++i)
+            if (!std::isfinite(opt.init_centers[i])) throw Error(NVSM_ERR_INVALID_ARGUMENT, "init_centers holds a value that is not finite");
+    } else if (opt.seed < 1) {
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "seed must be at least 1");
+    }
+    rank_join();
+    KmeansScratch& w = kmeans_;
+    w.grow_for(n, d, k);
+    if (opt.ids) NVSM_HIP_CHECK(hipMemcpy(w.ids.p, opt.ids, static_cast<size_t>(n) * sizeof(int64_t), hipMemcpyHostToDevice));
+    {
+        RankProf scope(prof, "kmeans_rows", stream_);
+        launch_rank_gather_rows(sp.rows, d, opt.ids ? w.ids.p : nullptr, 0, n, w.x.p, lazy_view(*sp.table), stream_);
+        if (opt.l2_normalize) launch_tsne_normalize(w.x.p, rows, d, stream_);
+        kmeans_prepare(w, rows, d, stream_);
+    }
+    float* C = w.c.p;
+    float* Cnext = w.c2.p;
+    if (opt.init == NVSM_KMEANS_INIT_GIVEN) {
+        NVSM_HIP_CHECK(hipMemcpyAsync(C, opt.init_centers, static_cast<size_t>(k) * d * sizeof(float), hipMemcpyHostToDevice, stream_));
+    } else {
+        RankProf scope(prof, "kmeans_plusplus", stream_);
+        std::vector<int64_t> chosen(static_cast<size_t>(k));
+        kmeans_plusplus(w, rows, d, k, opt.seed, C, chosen.data(), stream_);
+    }
+    double* sc = w.scalars(rows, d);
+    double var_mean = 0.0;
+    NVSM_HIP_CHECK(hipMemcpyAsync(&var_mean, sc, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    const double tol = opt.tol * var_mean;
+    int* lab = w.lab_a.p;
+    int* lab_old = w.lab_b.p;
+    NVSM_HIP_CHECK(hipMemsetAsync(lab_old, 0xFF, static_cast<size_t>(n) * sizeof(int), stream_));      // −1: no row keeps it
+    bool strict = false;
+    int iterations = 0;
+    prof.note(kmeans_assign_uses_mfma(d) ? "kmeans_assign_mfma" : "kmeans_assign_plain");
+    for (int it = 0; it < opt.max_iter; ++it) {
+        { RankProf scope(prof, "kmeans_assign", stream_); kmeans_assign_pass(w, rows, d, k, C, lab, stream_); }
+        double shift = 0.0;
+        int moved = 0;
+        {
+            RankProf scope(prof, "kmeans_update", stream_);
+            kmeans_update_pass(w, rows, d, k, lab, C, Cnext, true, stream_);
+            NVSM_HIP_CHECK(hipMemsetAsync(w.meta.p + 1, 0, sizeof(int), stream_));
+            launch_kmeans_changed(lab, lab_old, rows, w.meta.p + 1, stream_);
+            NVSM_HIP_CHECK(hipMemcpyAsync(&moved, w.meta.p + 1, sizeof(int), hipMemcpyDeviceToHost, stream_));
+            NVSM_HIP_CHECK(hipMemcpyAsync(&shift, sc + 1, sizeof(double), hipMemcpyDeviceToHost, stream_));
+            NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        }
+        std::swap(C, Cnext);
+        iterations = it + 1;
+        if (moved == 0) { strict = true; break; }
+        if (shift <= tol) break;
+        if (it + 1 < opt.max_iter) std::swap(lab, lab_old);
+    }
+    if (!strict) {      // sklearn: one more E-step against the final centres; counts are then plain member counts
+        RankProf scope(prof, "kmeans_assign", stream_);
+        kmeans_assign_pass(w, rows, d, k, C, lab, stream_);
+        kmeans_sort_segments(w, rows, k, lab, stream_);
+    }
+    {
+        RankProf scope(prof, "kmeans_inertia", stream_);
+        launch_kmeans_rowdist(w.x.p, rows, d, C, lab, 0, false, w.dist64.p, w.dist32.p, stream_);
+        launch_kmeans_sum(w.dist64.p, n, sc + 2, stream_);
+    }
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    raise_device_error();
+    static_assert(sizeof(int) == sizeof(int32_t), "labels are copied out as they are");
+    NVSM_HIP_CHECK(hipMemcpyAsync(labels, lab, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipMemcpyAsync(centers, C, static_cast<size_t>(k) * d * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipMemcpyAsync(counts, w.counts.p, static_cast<size_t>(k) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+    if (distances) NVSM_HIP_CHECK(hipMemcpyAsync(distances, w.dist32.p, static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipMemcpyAsync(inertia, sc + 2, sizeof(double), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    *n_iter = iterations;
+}
+
 }  // namespace cunvsm

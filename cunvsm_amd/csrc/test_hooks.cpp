@@ -853,6 +853,71 @@ int nvsm_debug_tsne_descent(const float* P, float* Y, int64_t n, const nvsm_tsne
     });
 }
 
+// ---- nvsm_kmeans' passes on caller-supplied inputs (cunvsm_amd_test_hooks.h): the product's launchers and host functions
+// (kernels.h launch_kmeans_*, model.h kmeans_*) on a scratch of the hook's own
+namespace {
+void kmeans_hook_sizes(int64_t n, int64_t d, int64_t k) {
+    if (n < 1 || n >= (int64_t(1) << 31) || d < 1 || d > 4096 || k < 1 || k > n || k > NVSM_KMEANS_MAX_CLUSTERS)
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "kmeans hook: bad sizes");
+}
+}  // namespace
+
+int nvsm_debug_kmeans_assign(const float* X, int64_t n, int d, const float* C, int k, int32_t* labels_out, float* dist_out) {
+    NVSM_REQUIRE(X); NVSM_REQUIRE(C); NVSM_REQUIRE(labels_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        kmeans_hook_sizes(n, d, k);
+        KmeansScratch w;
+        w.grow_for(n, d, k);
+        NVSM_HIP_CHECK(hipMemcpy(w.x.p, X, static_cast<size_t>(n) * d * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(w.c.p, C, static_cast<size_t>(k) * d * sizeof(float), hipMemcpyHostToDevice));
+        kmeans_prepare(w, static_cast<int>(n), d, nullptr);
+        kmeans_assign_pass(w, static_cast<int>(n), d, k, w.c.p, w.lab_a.p, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(labels_out, w.lab_a.p, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (dist_out) NVSM_HIP_CHECK(hipMemcpy(dist_out, w.dist32.p, static_cast<size_t>(n) * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int nvsm_debug_kmeans_update(const float* X, int64_t n, int d, int32_t* labels, const float* C_old, int k, float* C_new,
+                             int64_t* counts_out, double* shift_out) {
+    NVSM_REQUIRE(X); NVSM_REQUIRE(labels); NVSM_REQUIRE(C_old); NVSM_REQUIRE(C_new); NVSM_REQUIRE(counts_out); NVSM_REQUIRE(shift_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        kmeans_hook_sizes(n, d, k);
+        for (int64_t i = 0; i < n; ++i)
+            if (labels[i] < 0 || labels[i] >= k) throw Error(NVSM_ERR_INVALID_ARGUMENT, "kmeans hook: a label is outside [0, k)");
+        KmeansScratch w;
+        w.grow_for(n, d, k);
+        NVSM_HIP_CHECK(hipMemcpy(w.x.p, X, static_cast<size_t>(n) * d * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(w.c.p, C_old, static_cast<size_t>(k) * d * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(w.lab_a.p, labels, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyHostToDevice));
+        kmeans_update_pass(w, static_cast<int>(n), d, k, w.lab_a.p, w.c.p, w.c2.p, true, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(labels, w.lab_a.p, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(C_new, w.c2.p, static_cast<size_t>(k) * d * sizeof(float), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(counts_out, w.counts.p, static_cast<size_t>(k) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(shift_out, w.scalars(static_cast<int>(n), d) + 1, sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int nvsm_debug_kmeans_plusplus(const float* X, int64_t n, int d, int k, int64_t seed, int64_t* rows_out, float* centers_out) {
+    NVSM_REQUIRE(X); NVSM_REQUIRE(rows_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        kmeans_hook_sizes(n, d, k);
+        if (seed < 1) throw Error(NVSM_ERR_INVALID_ARGUMENT, "kmeans hook: seed must be at least 1");
+        KmeansScratch w;
+        w.grow_for(n, d, k);
+        NVSM_HIP_CHECK(hipMemcpy(w.x.p, X, static_cast<size_t>(n) * d * sizeof(float), hipMemcpyHostToDevice));
+        kmeans_plusplus(w, static_cast<int>(n), d, k, seed, w.c.p, rows_out, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        if (centers_out) NVSM_HIP_CHECK(hipMemcpy(centers_out, w.c.p, static_cast<size_t>(k) * d * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
 // One launch_lazy_refresh on caller-supplied inputs (cunvsm_amd_test_hooks.h): the arguments of Model::lazy_refresh /
 // Model::lazy_scalar_snapshot, the list and its count on the device as Csr::touched / num_touched are.
 int nvsm_debug_lazy_refresh(const nvsm_debug_lazy_refresh_args* a) {

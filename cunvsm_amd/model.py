@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmNgramOptions, NvsmTsneOptions, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmNgramOptions, NvsmTsneOptions, NvsmKmeansOptions, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -860,6 +860,103 @@ def grow_documents(params, new_rows, seed):
     return out
 
 
+# -- k-means of document or word rows (sklearn.cluster.KMeans(algorithm='lloyd', n_init=1); nvsm_kmeans) --------------------------
+def kmeans_arguments(cfg, space="entities", num_clusters=8, ids=None, limit=None, l2_normalize=False, max_iter=300, tol=1e-4,
+                     init="k-means++", seed=1):
+    """(nvsm_kmeans_options, number of rows, dimension, arrays to keep alive) from keywords; raises ValueError for what the ABI would
+    refuse, in its order (no device needed). ids: row ids in any order, duplicates allowed; limit: the first rows; neither: every
+    row. init: "k-means++" (one candidate per draw from std::minstd_rand0(seed)) or a [num_clusters][dim] array."""
+    space, rows, dim = space_shape(cfg, space)
+    if space == _lib.SPACE_PROJECTED_WORDS:
+        raise ValueError("unknown space for k-means: \"entities\" or \"words\" (projected words are not served)")
+    if ids is not None and limit is not None:
+        raise ValueError("at most one of ids and limit may be given")
+    id_array = None
+    if ids is not None:
+        if np.asarray(ids).ndim > 1:
+            raise ValueError("ids must be a flat list of row ids")
+        id_array = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).ravel())
+        n = int(id_array.size)
+    else:
+        n = rows if limit is None else int(limit)
+    if n < 1:
+        raise ValueError("num_rows = %d: k-means needs at least 1 row" % n)
+    if id_array is None and n > rows:
+        raise ValueError("limit = %d exceeds the rows of the space = %d" % (n, rows))
+    if id_array is not None and (id_array.min() < 0 or id_array.max() >= rows):
+        raise ValueError("a row id is outside [0, %d)" % rows)
+    k = int(num_clusters)
+    if k < 1 or k > n:
+        raise ValueError("num_clusters = %d must be in [1, num_rows = %d]" % (k, n))
+    if k > _lib.KMEANS_MAX_CLUSTERS:
+        raise ValueError("num_clusters = %d above the limit of %d clusters" % (k, _lib.KMEANS_MAX_CLUSTERS))
+    if int(max_iter) < 1:
+        raise ValueError("max_iter = %d must be at least 1" % int(max_iter))
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("tol = %r must be finite and not negative" % tol)
+    given = None
+    if isinstance(init, str):
+        if init != "k-means++":
+            raise ValueError("unknown init %r (\"k-means++\" or a [num_clusters][dim] array)" % init)
+        if int(seed) < 1:
+            raise ValueError("seed = %d must be at least 1" % int(seed))
+    else:
+        given = np.ascontiguousarray(init, dtype=np.float32)
+        if given.shape != (k, dim):
+            raise ValueError("init has shape %s, expected (%d, %d)" % (given.shape, k, dim))
+        if not np.isfinite(given).all():
+            raise ValueError("init holds a value that is not finite")
+    opt = NvsmKmeansOptions()
+    opt.space, opt.l2_normalize = space, int(bool(l2_normalize))
+    opt.ids, opt.num_rows = (None if id_array is None else id_array.ctypes.data), n
+    opt.num_clusters, opt.max_iter, opt.tol = k, int(max_iter), tol
+    opt.init = _lib.KMEANS_INIT_PLUSPLUS if given is None else _lib.KMEANS_INIT_GIVEN
+    opt.init_centers = None if given is None else given.ctypes.data
+    opt.seed = int(seed) if given is None else 0
+    return opt, n, dim, (id_array, given)
+
+
+def cluster_agreement(labels, classes):
+    """(purity, nmi, ari) of a clustering against a labelling of the same items, on the host: purity = Σ_j max_c n_jc / n; NMI with
+    arithmetic-mean normalisation and natural logarithms (sklearn's normalized_mutual_info_score); ARI as sklearn's
+    adjusted_rand_score. Labels and classes may be any values numpy can sort (strings included)."""
+    labels, classes = np.asarray(labels).ravel(), np.asarray(classes).ravel()
+    if labels.size != classes.size or labels.size == 0:
+        raise ValueError("labels and classes must have the same, non-zero length")
+    _, li = np.unique(labels, return_inverse=True)
+    _, ci = np.unique(classes, return_inverse=True)
+    t = np.zeros((int(li.max()) + 1, int(ci.max()) + 1), dtype=np.float64)
+    np.add.at(t, (li.ravel(), ci.ravel()), 1.0)
+    n = float(labels.size)
+    a, b = t.sum(axis=1), t.sum(axis=0)
+    purity = float(t.max(axis=1).sum() / n)
+
+    def entropy(c):
+        c = c[c > 0]
+        return float(-np.sum(c / n * (np.log(c) - np.log(n))))
+
+    eps = float(np.finfo(np.float64).eps)
+    if a.size == 1 and b.size == 1:
+        nmi = 1.0      # (one group on both sides: sklearn's special case)
+    else:
+        nz = t > 0
+        mi = float(np.sum(t[nz] / n * np.log(n * t[nz] / np.outer(a, b)[nz])))
+        mi = max(mi, 0.0)
+        nmi = 0.0 if mi < eps else mi / max(0.5 * (entropy(a) + entropy(b)), eps)
+    # pair counts, as sklearn's pair_confusion_matrix
+    sum_sq = float(np.sum(t * t))
+    n11 = sum_sq - n
+    n01 = float(np.sum(t.dot(b))) - sum_sq
+    n10 = float(np.sum(t.T.dot(a))) - sum_sq
+    n00 = n * n - n01 - n10 - sum_sq
+    if n10 == 0.0 and n01 == 0.0:
+        ari = 1.0
+    else:
+        ari = 2.0 * (n11 * n00 - n10 * n01) / ((n11 + n10) * (n10 + n00) + (n11 + n01) * (n01 + n00))
+    return purity, float(nmi), float(ari)
+
+
 class Model:
     def __init__(self, cfg):
         self.cfg = cfg
@@ -1465,6 +1562,25 @@ class Model:
         check(lib().nvsm_tsne(self._h, C.byref(opt), embedding.ctypes.data, C.byref(kl), C.byref(it)))
         del keep
         return embedding, kl.value, it.value
+
+    def kmeans(self, space="entities", num_clusters=8, ids=None, limit=None, l2_normalize=False, max_iter=300, tol=1e-4,
+               init="k-means++", seed=1, return_distances=False):
+        """sklearn.cluster.KMeans(n_clusters, n_init=1, algorithm='lloyd') of table rows on the device (nvsm_kmeans): the rows `ids` of
+        `space` ("entities" | "words"), its first `limit` rows, or all of them. Returns (labels [n] int32, centers [k, dim] float32,
+        counts [k] int64, inertia, n_iter) and, with return_distances, the rows' squared distances to their centres [n] float32."""
+        opt, n, dim, keep = kmeans_arguments(self.cfg, space, num_clusters, ids, limit, l2_normalize, max_iter, tol, init, seed)
+        k = int(opt.num_clusters)
+        labels = np.empty(n, dtype=np.int32)
+        centers = np.empty((k, dim), dtype=np.float32)
+        counts = np.empty(k, dtype=np.int64)
+        distances = np.empty(n, dtype=np.float32) if return_distances else None
+        inertia, it = C.c_double(0.0), C.c_int32(0)
+        check(lib().nvsm_kmeans(self._h, C.byref(opt), labels.ctypes.data, centers.ctypes.data, counts.ctypes.data,
+                                None if distances is None else distances.ctypes.data, C.byref(inertia), C.byref(it)))
+        del keep
+        if return_distances:
+            return labels, centers, counts, inertia.value, it.value, distances
+        return labels, centers, counts, inertia.value, it.value
 
     def related_documents(self, entity_ids, top_k=10, exclude_self=False):
         """Documents near documents (query_using_projected_query, base.py:362-430, with document rows as the queries)."""

@@ -963,6 +963,68 @@ void nvsm_tsne_options_default(nvsm_tsne_options* opt);
 /* embedding [num_rows][2] host; kl_divergence and n_iter as sklearn's kl_divergence_ and n_iter_ */
 int nvsm_tsne(nvsm_model* m, const nvsm_tsne_options* opt, float* embedding, double* kl_divergence, int32_t* n_iter);
 
+/*
+ * k-means (Lloyd's algorithm) of document or word rows on the device — what a caller would otherwise ask
+ * sklearn.cluster.KMeans(n_clusters=k, n_init=1, algorithm='lloyd') for after pulling the table to the host. Semantics, pinned by
+ * scikit-learn 1.7 where it specifies them:
+ *   rows         nvsm_tsne_options' selection: ids (num_rows host row ids of `space`, any order, duplicates allowed), or NULL: rows
+ *                0 .. num_rows − 1; num_rows 0 with ids NULL: every row. Gathered through the lazy view; with l2_normalize every
+ *                row is divided by its norm (a zero row stays zero). X below is these rows, fp32.
+ *   assignment   label[i] = the j that minimises |x_i − c_j|² in the kernel's arithmetic, the lowest j on a tie. The kernel evaluates
+ *                |x|² − 2 x·c + |c|² in fp32 on rows and centres centred by the column mean of X (an fp64 sum rounded to fp32), as
+ *                sklearn centres X: without that the cancellation is not fp32-accurate for rows far from the origin.
+ *   empty        settled before the sums are taken: empty clusters in ascending id each take the row with the largest squared
+ *                distance (direct fp64) to the centre it is assigned to, the lower row position on a tie, among rows whose cluster
+ *                has at least two members at that moment; counts are updated as it goes and the row's label CHANGES. (sklearn
+ *                relocates the same kind of rows but hands them out in argpartition's unspecified order and keeps the labels.)
+ *   update       c_j = fp32((Σ_{label i = j} x_i) / count_j), the sum in fp64 over the fp32 rows as gathered (not the centred
+ *                copy), in an order that depends on the member count and ascending row position alone. No float atomics.
+ *   stopping     sklearn's _kmeans_single_lloyd: stop at iteration i when its labels equal those of iteration i − 1 ("strict"),
+ *                or when the fp64 sum of squared centre shifts is <= tol · mean_c(var(X[:, c])) (fp64 population variances);
+ *                n_iter is the number of iterations run. After a stop that was not strict — max_iter included — one more
+ *                assignment pass runs against the final centres (no relocation). labels, counts, distances and inertia describe
+ *                that final assignment; centers are the last update's.
+ *   inertia      an fp64 sum in a fixed order of directly evaluated fp64 (x − c)²; distances[i] = the fp32 rounding of row i's.
+ *   k-means++    u_t = (x_t − 1) / 2147483646.0 in fp64, x_t the t-th output (t = 0, 1, …) of std::minstd_rand0(seed). Centre 0 is
+ *                row floor(u_0 · n). Centre t is the lowest row position p whose inclusive fp64 prefix sum, over ascending
+ *                positions, of min_{s<t} |x_p − c_s|² (direct fp64) exceeds u_t · total; where total is 0, the lowest position not
+ *                yet chosen. ONE candidate per draw: sklearn's greedy local trials (2 + log k candidates, the best kept) are NOT
+ *                reproduced, so a seed does not give sklearn's start.
+ *                NVSM_KMEANS_INIT_GIVEN: init_centers as they are.
+ * Out of scope: spherical k-means, mini-batches, n_init > 1 (loop over seeds and keep the lowest inertia),
+ * NVSM_SPACE_PROJECTED_WORDS, world_size > 1.
+ * Refused with a status code before anything runs, in this order, nothing written to the outputs, the handle usable afterwards:
+ * a space other than entities or words; num_rows < 1 (after the default is resolved) or, with ids NULL, beyond the space's rows;
+ * an id out of range; num_clusters < 1 or > num_rows; num_clusters > NVSM_KMEANS_MAX_CLUSTERS (NVSM_ERR_UNSUPPORTED); max_iter < 1;
+ * a tol that is negative or not finite; an unknown init; NVSM_KMEANS_INIT_GIVEN without an array or with an entry that is not
+ * finite; seed < 1 with NVSM_KMEANS_INIT_PLUSPLUS.
+ * Every dimension the model accepts is served by the same matrix-pipe kernel. The call is synchronous; it runs behind everything
+ * earlier steps have queued (the side streams' tails included), flushes nothing and moves no stamp of a lazily decayed table, and
+ * touches no parameter, optimiser state or RNG state: training goes on from exactly the same state. A repeated call returns the
+ * same bits. Device scratch (the gathered rows and a few arrays of n or k entries) is allocated by the first call and grown later.
+ */
+#define NVSM_KMEANS_MAX_CLUSTERS 4096     /* the chunk scan of the update is one workgroup and k-means++ costs a host round trip per centre */
+enum { NVSM_KMEANS_INIT_PLUSPLUS = 0, NVSM_KMEANS_INIT_GIVEN = 1 };
+typedef struct {
+    int32_t        space;                    /* NVSM_SPACE_ENTITIES or NVSM_SPACE_WORDS */
+    int32_t        l2_normalize;
+    const int64_t* ids;                      /* [num_rows] host row ids, any order, or NULL: rows 0 .. num_rows-1 */
+    int64_t        num_rows;
+    int32_t        num_clusters;             /* k: 1 .. min(num_rows, NVSM_KMEANS_MAX_CLUSTERS) */
+    int32_t        max_iter;                 /* 300 */
+    double         tol;                      /* 1e-4, relative to the mean column variance */
+    int32_t        init;                     /* NVSM_KMEANS_INIT_* */
+    int32_t        reserved0;
+    const float*   init_centers;             /* [num_clusters][dim] host, with NVSM_KMEANS_INIT_GIVEN */
+    int64_t        seed;                     /* >= 1 with NVSM_KMEANS_INIT_PLUSPLUS */
+    int32_t        reserved[6];
+} nvsm_kmeans_options;
+/* entities, no normalisation, ids NULL, num_rows 0 = every row, num_clusters 8, max_iter 300, tol 1e-4, k-means++, seed 1 */
+void nvsm_kmeans_options_default(nvsm_kmeans_options* opt);
+/* labels [num_rows], centers [k][dim], counts [k], distances [num_rows] (may be NULL): host */
+int nvsm_kmeans(nvsm_model* m, const nvsm_kmeans_options* opt, int32_t* labels, float* centers, int64_t* counts, float* distances,
+                double* inertia, int32_t* n_iter);
+
 /* Streams. A handle issues its work on FOUR HIP streams of its own device: the main stream (highest priority: the step's
  * critical chain), two side streams (lowest priority: the batch → row-order sorts, and — in nvsm_step — the documents
  * update and the ∂T GEMM + projection update, which keep running after nvsm_step has returned and are joined by the next

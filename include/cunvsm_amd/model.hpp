@@ -499,6 +499,29 @@ class Model {
         return tsne(opt);
     }
 
+    // Lloyd's k-means of document or word rows (nvsm_kmeans): opt.ids / opt.num_rows choose the rows (nvsm_kmeans_options_default: every
+    // document), opt.num_clusters the centres; labels [rows], centers [k][dim], counts [k], distances [rows] (squared, to the own centre)
+    struct Kmeans { std::vector<int32_t> labels; std::vector<float> centers; std::vector<int64_t> counts; std::vector<float> distances;
+                    double inertia; int32_t n_iter; };
+    Kmeans kmeans(const nvsm_kmeans_options& opt) {
+        int64_t n = opt.num_rows;
+        if (!opt.ids && n == 0) n = opt.space == NVSM_SPACE_WORDS ? cfg_.num_words : cfg_.num_entities;
+        const int64_t dim = opt.space == NVSM_SPACE_WORDS ? cfg_.word_repr_size : cfg_.entity_repr_size;
+        const size_t rows = static_cast<size_t>(n > 0 ? n : 0), k = static_cast<size_t>(opt.num_clusters > 0 ? opt.num_clusters : 0);
+        Kmeans r;
+        r.labels.resize(rows + 1); r.distances.resize(rows + 1);
+        r.centers.resize(k * static_cast<size_t>(dim) + 1); r.counts.resize(k + 1);
+        r.inertia = 0.0; r.n_iter = 0;
+        check(nvsm_kmeans(h_, &opt, r.labels.data(), r.centers.data(), r.counts.data(), r.distances.data(), &r.inertia, &r.n_iter));
+        r.labels.resize(rows); r.distances.resize(rows);
+        r.centers.resize(k * static_cast<size_t>(dim)); r.counts.resize(k);
+        return r;
+    }
+    Kmeans kmeans(const std::vector<int64_t>& row_ids, nvsm_kmeans_options opt) {
+        opt.ids = row_ids.data(); opt.num_rows = static_cast<int64_t>(row_ids.size());
+        return kmeans(opt);
+    }
+
     void synchronize() { check(nvsm_synchronize(h_)); }
     void comm_init(const char id[128]) { check(nvsm_comm_init(h_, id)); }
     nvsm_model* handle() { return h_; }

@@ -170,6 +170,18 @@ int nvsm_debug_tsne_gradient(const float* P, const float* Y, int64_t n, float ex
 int nvsm_debug_tsne_pca(const float* X, int64_t n, int d, float* Y0_out);
 int nvsm_debug_tsne_descent(const float* P, float* Y, int64_t n, const nvsm_tsne_options* opt, int exploration, double* kl_out,
                             int32_t* n_iter_out);
+/* nvsm_kmeans' passes on caller-supplied host inputs, through the product's own launchers (csrc/kmeans.hip) and host functions
+ * (csrc/ranking.cpp kmeans_prepare / kmeans_assign_pass / kmeans_update_pass / kmeans_plusplus). Sizes: 1 <= n < 2^31, 1 <= d <= 4096,
+ * 1 <= k <= min(n, NVSM_KMEANS_MAX_CLUSTERS), else NVSM_ERR_INVALID_ARGUMENT.
+ * assign: one assignment pass of X [n][d] against C [k][d]: labels_out [n], dist_out [n] (may be NULL) = the kernel's own fp32
+ *   squared distance of each row to its centre.
+ * update: one centre update from labels [n] (in: values in [0, k); out: relocated rows rewritten) with empty clusters settled against
+ *   C_old [k][d]: C_new [k][d], counts_out [k], *shift_out = Σ (C_new − C_old)².
+ * plusplus: the k-means++ start: rows_out [k] the chosen positions, centers_out [k][d] (may be NULL) their rows. seed >= 1. */
+int nvsm_debug_kmeans_assign(const float* X, int64_t n, int d, const float* C, int k, int32_t* labels_out, float* dist_out);
+int nvsm_debug_kmeans_update(const float* X, int64_t n, int d, int32_t* labels, const float* C_old, int k, float* C_new,
+                             int64_t* counts_out, double* shift_out);
+int nvsm_debug_kmeans_plusplus(const float* X, int64_t n, int d, int k, int64_t seed, int64_t* rows_out, float* centers_out);
 /* the stable (row, entry) radix sort alone: keys of `bits` significant bits in, sorted keys + their original positions out */
 /* average ms per launch of a batch-sized projection product on device operands (extras: 1 = column statistics, 2 = row sums of squares) */
 int nvsm_debug_gemm_time(int b_layout, int M, int N, int K, int extras, int repeats, float* avg_ms);
