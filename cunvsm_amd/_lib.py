@@ -123,6 +123,14 @@ class NvsmEnsembleOptions(C.Structure):
     _fields_ = [("alpha", C.c_float), ("normalizer", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
+SDM_MAX_WINDOW = 64
+
+
+class NvsmSdmOptions(C.Structure):
+    _fields_ = [("w_term", C.c_float), ("w_ordered", C.c_float), ("w_unordered", C.c_float), ("window", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
 class NvsmFeedbackOptions(C.Structure):
     _fields_ = [("fb_docs", C.c_int32), ("fb_terms", C.c_int32), ("orig_weight", C.c_float), ("reserved", C.c_int32 * 5)]
 
@@ -440,6 +448,11 @@ def lib():
         "nvsm_lexical_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), vp, vp, vp]),
         "nvsm_rank_ensemble": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmEnsembleOptions),
                                          P(NvsmJudgments), vp, vp, vp, vp]),
+        "nvsm_sdm_options_default": (None, [P(NvsmSdmOptions)]),
+        "nvsm_sdm_rank": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), P(NvsmSdmOptions), vp, vp, vp]),
+        "nvsm_sdm_pair_counts": (C.c_int, [vp, P(NvsmQueries), P(NvsmSdmOptions), vp, vp]),
+        "nvsm_rank_ensemble_sdm": (C.c_int, [vp, P(NvsmQueries), P(NvsmRankOptions), P(NvsmLexicalOptions), P(NvsmSdmOptions),
+                                             P(NvsmEnsembleOptions), P(NvsmJudgments), vp, vp, vp, vp]),
         "nvsm_feedback_options_default": (None, [P(NvsmFeedbackOptions)]),
         "nvsm_lexical_rank_weighted": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), vp, vp, vp]),
         "nvsm_relevance_model": (C.c_int, [vp, P(NvsmQueries), P(NvsmLexicalOptions), P(NvsmFeedbackOptions), vp, vp, vp]),

@@ -396,6 +396,31 @@ int nvsm_rank_ensemble(nvsm_model* m, const nvsm_queries* queries, const nvsm_ra
     return guarded_on(m, [&] { m->impl.rank_ensemble(*queries, *rank_opt, *lex, *ens, judgments, metrics, doc_ids, scores, counts); });
 }
 
+void nvsm_sdm_options_default(nvsm_sdm_options* o) {
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->w_term = 0.85f; o->w_ordered = 0.10f; o->w_unordered = 0.05f; o->window = 8;
+}
+int nvsm_sdm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, const nvsm_sdm_options* sdm, int64_t* doc_ids,
+                  float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(lex); NVSM_REQUIRE(sdm); NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores);
+    NVSM_REQUIRE(counts);
+    return guarded_on(m, [&] { m->impl.sdm_rank(*queries, *lex, *sdm, doc_ids, scores, counts); });
+}
+int nvsm_sdm_pair_counts(nvsm_model* m, const nvsm_queries* queries, const nvsm_sdm_options* sdm, uint64_t* ordered, uint64_t* unordered) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(sdm); NVSM_REQUIRE(ordered); NVSM_REQUIRE(unordered);
+    return guarded_on(m, [&] { m->impl.sdm_pair_counts(*queries, *sdm, ordered, unordered); });
+}
+int nvsm_rank_ensemble_sdm(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                           const nvsm_sdm_options* sdm, const nvsm_ensemble_options* ens, const nvsm_judgments* judgments, double* metrics,
+                           int64_t* doc_ids, float* scores, int64_t* counts) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(queries); NVSM_REQUIRE(rank_opt); NVSM_REQUIRE(lex); NVSM_REQUIRE(sdm); NVSM_REQUIRE(ens);
+    NVSM_REQUIRE(doc_ids); NVSM_REQUIRE(scores); NVSM_REQUIRE(counts);
+    if (judgments) NVSM_REQUIRE(metrics);
+    if (metrics) NVSM_REQUIRE(judgments);
+    return guarded_on(m, [&] { m->impl.rank_ensemble_sdm(*queries, *rank_opt, *lex, *sdm, *ens, judgments, metrics, doc_ids, scores, counts); });
+}
+
 void nvsm_feedback_options_default(nvsm_feedback_options* o) {
     if (!o) return;
     std::memset(o, 0, sizeof(*o));

@@ -768,5 +768,34 @@ struct PostingsArgs {
 };
 void launch_postings_fill(const PostingsArgs& a, int64_t max_df, bool tfidf, hipStream_t s);
 
+// ---- sequential dependence: ordered and unordered term pairs (sdm.hip; include/cunvsm_amd.h nvsm_sdm_rank) ----
+constexpr int kSdmTile = 256;              // positions of a document staged at a time: the workgroup
+constexpr int kSdmMaxWindow = 64;          // NVSM_SDM_MAX_WINDOW: the halo behind a tile is at most 63 positions
+constexpr int kSdmSlots = kLexSlots;       // distinct terms of a round: tf counters, 4 KiB of LDS
+constexpr int kSdmPairs = 1024;            // distinct (first, second) pairs of a round: od and uw counters, 8 KiB of LDS
+// What the counting reads of a round. slot_of [num_words]: as launch_lex_set_slots leaves it for the round's terms. The pair entries
+// of slot s are ent_off[s] .. ent_off[s + 1) (ent_off [num_slots + 1]): ent_other[e] the slot of the pair's other term, ent_pair[e] =
+// pair id << 1 | first, first = 1 where s is the pair's first term (the entry that also counts the ordered form). A pair (a, b),
+// a != b, has one entry under a (first) and one under b; a pair (a, a) has its first entry alone, so a position counts once.
+struct SdmCountArgs {
+    const int* tokens; const int64_t* doc_offsets; const int* slot_of;
+    const int* ent_off; const int* ent_other; const int* ent_pair;
+    int num_slots; int num_pairs; int window;
+};
+// cf_o[p] += od(pair p; d), cf_u[p] += uw(pair p; d) over every document d < num_documents; both zeroed by the caller
+void launch_sdm_collect(const SdmCountArgs& a, int64_t num_documents, unsigned long long* cf_o, unsigned long long* cf_u, hipStream_t s);
+// scores[q][d - d0] for q < Q, d in [d0, d0 + S), the layout of launch_lex_score. Group g (0 terms, 1 ordered, 2 unordered) of query q
+// has the members goff[g][q] .. goff[g][q + 1) (goff [3][Q + 1], indices into index / c0 / base, query order): index[j] a slot (g = 0)
+// or a pair id, c0[j] and base[j] = log(c0[j]) as LexScoreArgs'. score = Σ_g coef[q][g]·(Σ_j log term / members), the groups in the
+// order 0, 1, 2, over the groups with members and coef > 0; fp64, every operation rounded on its own, narrowed once; -inf when no
+// member of group 0 occurs in d.
+struct SdmScoreArgs {
+    SdmCountArgs count;
+    int64_t d0; int S; int Q; int method; double param;
+    const int* goff; const int* index; const double* c0; const double* base; const double* coef;
+    float* scores; int64_t ld;
+};
+void launch_sdm_score(const SdmScoreArgs& a, hipStream_t s);
+
 
 }  // namespace cunvsm

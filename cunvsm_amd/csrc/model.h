@@ -233,6 +233,13 @@ class Model {
                            int64_t* counts);
     void evaluate(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_judgments& j, double* metrics, int64_t* doc_ids,
                   float* scores, int64_t* counts);
+    // sequential dependence: terms, ordered pairs and unordered pairs in a window (include/cunvsm_amd.h; sdm.hip)
+    void sdm_rank(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_sdm_options& sdm, int64_t* doc_ids, float* scores,
+                  int64_t* counts);
+    void sdm_pair_counts(const nvsm_queries& q, const nvsm_sdm_options& sdm, uint64_t* ordered, uint64_t* unordered);
+    void rank_ensemble_sdm(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_sdm_options& sdm,
+                           const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
+                           int64_t* counts);
     // TF-IDF first stage over the resident corpus, and nvsm_rank over its candidates handed over on the device (include/cunvsm_amd.h;
     // lexical.hip); j and metrics both null or both given
     void tfidf_rank(const nvsm_queries& q, const nvsm_tfidf_options& opt, int64_t* doc_ids, float* scores, int64_t* counts);
@@ -565,6 +572,9 @@ class Model {
         DevBuf<double> jconst, metrics;            //           ... R / idcg / idcg@c per query, and the metric rows
         DevBuf<int> lex_slot_of, lex_terms, lex_qoff, lex_tslot;      // lexical: term -> slot [num_words] (-1 between rounds), a round's terms
         DevBuf<double> lex_c0, lex_base, lex_weight;                  //          ... and their constants (lex_weight: weighted queries only)
+        DevBuf<int> sdm_ent_off, sdm_ent_other, sdm_ent_pair, sdm_goff, sdm_index;      // sequential dependence: a round's pair entries by slot, its groups
+        DevBuf<double> sdm_c0, sdm_base, sdm_coef;                    //          ... their members' constants, every query's group coefficients
+        DevBuf<unsigned long long> sdm_cf;                            //          ... and the round's collection counts [2][kSdmPairs]
         DevBuf<int> post_query, post_first;                           // postings fill (indexed corpora only): an entry's query, first-of-its-term flag
         DevBuf<int64_t> post_lo, post_hi;                             //          ... and a term's postings inside the slab
         DevBuf<double> rm_acc, rm_sum;                                // relevance model: acc [round][num_words] and cnt likewise (zero between
@@ -600,7 +610,13 @@ class Model {
                         const TfidfPlan* tfidf = nullptr, Handover* hand = nullptr);
     void tfidf_check(const nvsm_queries& q, const nvsm_tfidf_options& opt) const;          // the refusals of nvsm_tfidf_rank, before anything runs
     TfidfPlan tfidf_plan(const nvsm_tfidf_options& opt) const;
+    void corpus_cf();                       // the cf table of the corpus, made once (lex_cf_kernel)
     void corpus_df();                       // the df table of the corpus, made once (lex_df_kernel)
+    // the refusals of the sequential-dependence calls that are their own (behind lexical_check where there is a ranking), and their
+    // rounds: lex null: the pair counts alone into ordered / unordered; given: the ranking (ordered / unordered may still be given)
+    void sdm_check(const nvsm_queries& q, const nvsm_sdm_options& sdm) const;
+    void sdm_rounds(const nvsm_queries& q, const nvsm_lexical_options* lex, const nvsm_sdm_options& sdm, int64_t* doc_ids, float* scores,
+                    int64_t* counts, uint64_t* ordered, uint64_t* unordered);
     void index_build(Corpus& c);            // the postings of the corpus and, where still empty, its cf and df (ranking.cpp; index.hip)
     // one round of nvsm_rank over candidate lists that lie on the device as launch_rank_scan_candidates reads them
     void rank_candidates_round(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, const RankLayout& l, const int* cand,
@@ -616,14 +632,14 @@ class Model {
     void expand_queries(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_feedback_options& fb, ExpandedQueries& out);
     void ensemble_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
                          const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
-                         int64_t* counts);
+                         int64_t* counts, const nvsm_sdm_options* sdm = nullptr);      // sdm given (fb null): list B is nvsm_sdm_rank's
     // what the fused calls share (ranking.cpp): the refusals of nvsm_rank_ensemble(_prf) for every alpha of the call, both rankings
     // once, a round's lists on the device, and the fusion of the call's queries at one alpha or at one alpha per query
     struct EnsembleLists;
     void ensemble_check(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
-                        int normalizer, const float* alphas, int64_t num_alphas);
+                        int normalizer, const float* alphas, int64_t num_alphas, const nvsm_sdm_options* sdm = nullptr);
     void ensemble_lists(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
-                        EnsembleLists& l);
+                        EnsembleLists& l, const nvsm_sdm_options* sdm = nullptr);
     FuseArgs ensemble_upload(const EnsembleLists& l, int64_t q0, int64_t qn, int normalizer);
     void fuse_rounds(const nvsm_queries& q, const EnsembleLists& l, int normalizer, float alpha, const float* query_alpha, const EvalPlan* plan,
                      int64_t* doc_ids, float* scores, int64_t* counts);

@@ -478,6 +478,20 @@ void Model::lexical_rank(const nvsm_queries& q, const nvsm_lexical_options& lex,
     lexical_rounds(q, lex, nullptr, doc_ids, scores, counts);
 }
 
+// the cf table of the corpus: one histogram pass over the arena, kept with the corpus (a new upload is a new Corpus)
+void Model::corpus_cf() {
+    Corpus& c = *corpus_;
+    if (!c.cf.empty()) return;
+    const int64_t V = cfg_.num_words;
+    DevBuf<unsigned long long> cf;
+    cf.alloc(static_cast<size_t>(V), true);
+    { RankProf scope(prof, "lex_cf", stream_); launch_lex_cf(c.tokens.p, c.num_tokens, cf.p, stream_); }
+    std::vector<int64_t> host(static_cast<size_t>(V));
+    NVSM_HIP_CHECK(hipMemcpyAsync(host.data(), cf.p, static_cast<size_t>(V) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    c.cf.swap(host);
+}
+
 void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& lex, const float* weights, int64_t* doc_ids, float* scores,
                            int64_t* counts, const TfidfPlan* tfidf, Handover* hand) {
     Corpus& c = *corpus_;
@@ -486,14 +500,8 @@ void Model::lexical_rounds(const nvsm_queries& q, const nvsm_lexical_options& le
     RankScratch& r = rank_;
     if (tfidf) {
         corpus_df();
-    } else if (c.cf.empty()) {      // one histogram pass over the arena, kept with the corpus (a new upload is a new Corpus)
-        DevBuf<unsigned long long> cf;
-        cf.alloc(static_cast<size_t>(V), true);
-        { RankProf scope(prof, "lex_cf", stream_); launch_lex_cf(c.tokens.p, N, cf.p, stream_); }
-        std::vector<int64_t> host(static_cast<size_t>(V));
-        NVSM_HIP_CHECK(hipMemcpyAsync(host.data(), cf.p, static_cast<size_t>(V) * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
-        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
-        c.cf.swap(host);
+    } else {
+        corpus_cf();
     }
     if (r.lex_slot_of.n < static_cast<size_t>(V)) {
         r.lex_slot_of.alloc(static_cast<size_t>(V));
@@ -1083,9 +1091,10 @@ struct Model::EnsembleLists {
 
 // the refusals of nvsm_rank_ensemble(_prf), in their order, for every fused call; alphas [num_alphas]: the weights the call fuses with
 void Model::ensemble_check(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
-                           int normalizer, const float* alphas, int64_t num_alphas) {
+                           int normalizer, const float* alphas, int64_t num_alphas, const nvsm_sdm_options* sdm) {
     lexical_check(q, lex);
     if (fb) feedback_check(*fb);
+    if (sdm) sdm_check(q, *sdm);
     if (normalizer != NVSM_NORM_STANDARDIZE && normalizer != NVSM_NORM_MINMAX && normalizer != NVSM_NORM_NONE)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown score normalizer");
     for (int64_t i = 0; i < num_alphas; ++i)
@@ -1100,7 +1109,7 @@ void Model::ensemble_check(const nvsm_queries& q, const nvsm_rank_options& opt, 
 
 // list A: nvsm_rank's; list B: nvsm_lexical_rank's (fb null) or nvsm_lexical_rank_prf's — once per call
 void Model::ensemble_lists(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
-                           EnsembleLists& l) {
+                           EnsembleLists& l, const nvsm_sdm_options* sdm) {
     const int64_t Q = q.num_queries;
     l.k = opt.top_k;
     const size_t cells = static_cast<size_t>(std::max<int64_t>(Q, 1)) * l.k;
@@ -1111,6 +1120,8 @@ void Model::ensemble_lists(const nvsm_queries& q, const nvsm_rank_options& opt, 
         ExpandedQueries x;
         expand_queries(q, lex, *fb, x);
         lexical_rounds(x.view(), lex, x.weights.data(), l.ids_b.data(), l.sc_b.data(), l.cnt_b.data());
+    } else if (sdm) {
+        sdm_rounds(q, &lex, *sdm, l.ids_b.data(), l.sc_b.data(), l.cnt_b.data(), nullptr, nullptr);
     } else {
         lexical_rounds(q, lex, nullptr, l.ids_b.data(), l.sc_b.data(), l.cnt_b.data());
     }
@@ -1186,13 +1197,281 @@ void Model::fuse_rounds(const nvsm_queries& q, const EnsembleLists& l, int norma
 // fb null: list B is nvsm_lexical_rank's; given: nvsm_lexical_rank_prf's
 void Model::ensemble_rounds(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_feedback_options* fb,
                             const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
-                            int64_t* counts) {
-    ensemble_check(q, opt, lex, fb, ens.normalizer, &ens.alpha, 1);
+                            int64_t* counts, const nvsm_sdm_options* sdm) {
+    ensemble_check(q, opt, lex, fb, ens.normalizer, &ens.alpha, 1, sdm);
     EvalPlan plan;
     if (j) { plan.request = j; plan.metrics = metrics; eval_plan(plan, q.num_queries); }
     EnsembleLists l;
-    ensemble_lists(q, opt, lex, fb, l);
+    ensemble_lists(q, opt, lex, fb, l, sdm);
     fuse_rounds(q, l, ens.normalizer, ens.alpha, nullptr, j ? &plan : nullptr, doc_ids, scores, counts);
+}
+
+// ---- sequential dependence: terms, ordered pairs, unordered pairs in a window (include/cunvsm_amd.h nvsm_sdm_rank / nvsm_sdm_pair_counts
+// / nvsm_rank_ensemble_sdm; kernels: sdm.hip) ---------------------------------------------------------------------------
+// lexical_rounds' frame: a round takes queries while their distinct remaining terms fit kSdmSlots counters AND their distinct pairs
+// fit kSdmPairs; the terms go into the slot table, the pairs into a small CSR by slot. One counting pass over ALL documents gives the
+// round's collection counts (integers, read back: the host drops what has none and evaluates log(c0) once per member), then the
+// slabs are filled by launch_sdm_score and selection, sort, write and results are those of every other round.
+void Model::sdm_check(const nvsm_queries& q, const nvsm_sdm_options& sdm) const {
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "lexical ranking needs a corpus: call nvsm_corpus_upload first");
+    check_row_count(corpus_->num_documents, "ranking supports fewer than 2^31 documents");
+    check_queries(q);
+    const float w[3] = {sdm.w_term, sdm.w_ordered, sdm.w_unordered};
+    for (float x : w)
+        if (!std::isfinite(x) || x < 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "an sdm weight (w_term, w_ordered, w_unordered) is negative or not finite");
+    if (w[0] == 0.f && w[1] == 0.f && w[2] == 0.f) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the three sdm weights are all zero");
+    if (sdm.window < 2 || sdm.window > kSdmMaxWindow) throw Error(NVSM_ERR_INVALID_ARGUMENT, "sdm->window must be in [2, NVSM_SDM_MAX_WINDOW]");
+    std::vector<int64_t> one;
+    std::vector<std::pair<int64_t, int64_t>> two;
+    for (int64_t i = 0; i < q.num_queries; ++i) {
+        const int64_t L = q.offsets[i + 1] - q.offsets[i];
+        if (L <= kSdmSlots && L - 1 <= kSdmPairs) continue;
+        one.assign(q.word_ids + q.offsets[i], q.word_ids + q.offsets[i + 1]);
+        two.clear();
+        for (int64_t j = 0; j + 1 < L; ++j) two.emplace_back(one[static_cast<size_t>(j)], one[static_cast<size_t>(j) + 1]);
+        std::sort(one.begin(), one.end());
+        if (std::unique(one.begin(), one.end()) - one.begin() > kSdmSlots)
+            throw Error(NVSM_ERR_UNSUPPORTED, "a query has more than NVSM_LEXICAL_MAX_QUERY_TERMS distinct terms");
+        std::sort(two.begin(), two.end());
+        if (std::unique(two.begin(), two.end()) - two.begin() > kSdmPairs)
+            throw Error(NVSM_ERR_UNSUPPORTED, "a query has more than NVSM_SDM_MAX_QUERY_PAIRS distinct term pairs");
+    }
+}
+
+void Model::sdm_rank(const nvsm_queries& q, const nvsm_lexical_options& lex, const nvsm_sdm_options& sdm, int64_t* doc_ids, float* scores,
+                     int64_t* counts) {
+    lexical_check(q, lex);
+    sdm_check(q, sdm);
+    rank_join();
+    sdm_rounds(q, &lex, sdm, doc_ids, scores, counts, nullptr, nullptr);
+}
+
+void Model::sdm_pair_counts(const nvsm_queries& q, const nvsm_sdm_options& sdm, uint64_t* ordered, uint64_t* unordered) {
+    sdm_check(q, sdm);
+    rank_join();
+    sdm_rounds(q, nullptr, sdm, nullptr, nullptr, nullptr, ordered, unordered);
+}
+
+void Model::rank_ensemble_sdm(const nvsm_queries& q, const nvsm_rank_options& opt, const nvsm_lexical_options& lex, const nvsm_sdm_options& sdm,
+                              const nvsm_ensemble_options& ens, const nvsm_judgments* j, double* metrics, int64_t* doc_ids, float* scores,
+                              int64_t* counts) {
+    ensemble_rounds(q, opt, lex, nullptr, ens, j, metrics, doc_ids, scores, counts, &sdm);
+}
+
+void Model::sdm_rounds(const nvsm_queries& q, const nvsm_lexical_options* lex, const nvsm_sdm_options& sdm, int64_t* doc_ids, float* scores,
+                       int64_t* counts, uint64_t* ordered, uint64_t* unordered) {
+    Corpus& c = *corpus_;
+    const int64_t Dc = c.num_documents, N = c.num_tokens, Q = q.num_queries, V = cfg_.num_words;
+    const int k = lex ? lex->top_k : 1;
+    RankScratch& r = rank_;
+    corpus_cf();
+    if (r.lex_slot_of.n < static_cast<size_t>(V)) {
+        r.lex_slot_of.alloc(static_cast<size_t>(V));
+        launch_lex_fill_int(r.lex_slot_of.p, V, -1, stream_);
+    }
+    double param = 0.0;
+    if (lex)
+        param = lex->method == NVSM_LEX_JM ? (lex->param == 0.f ? 0.5 : static_cast<double>(lex->param))
+                                           : (lex->param == 0.f ? static_cast<double>(N) / static_cast<double>(Dc) : static_cast<double>(lex->param));
+    const double w[3] = {static_cast<double>(sdm.w_term), static_cast<double>(sdm.w_ordered), static_cast<double>(sdm.w_unordered)};
+    bool bad_word = false;
+    std::vector<int> terms, pair_a, pair_b;              // the round's distinct terms by slot, its distinct pairs by id (slots)
+    std::vector<std::pair<int64_t, int>> slot_of;        // (term, slot), sorted by term
+    std::vector<std::pair<int64_t, int>> pair_of;        // (first slot · kSdmSlots + second slot, pair id), sorted
+    std::vector<int> qslot, qpair, qfirst;               // every query position's slot, the pair id of (position, position + 1); -1: dropped
+    std::vector<int> ent_off, ent_other, ent_pair, goff, index;
+    std::vector<double> c0, base, coef;
+    std::vector<unsigned long long> cf(2 * static_cast<size_t>(kSdmPairs));
+    int64_t pairs_out = 0;                               // pairs of the queries before this round, in the layout of ordered / unordered
+
+    for (int64_t q0 = 0; q0 < Q;) {
+        RankLayout l{};
+        if (lex) l = rank_layout(Dc, k, Q - q0, score_floats());
+        else l.qn = std::min(kRankChunk, Q - q0);
+        terms.clear(); pair_a.clear(); pair_b.clear(); slot_of.clear(); pair_of.clear(); qslot.clear(); qpair.clear();
+        qfirst.assign(1, 0);
+        int64_t taken = 0;
+        for (; taken < l.qn; ++taken) {
+            const size_t terms_before = terms.size(), pairs_before = pair_a.size(), cells_before = qslot.size();
+            bool fits = true;
+            const int64_t j0 = q.offsets[q0 + taken], j1 = q.offsets[q0 + taken + 1];
+            for (int64_t j = j0; j < j1 && fits; ++j) {
+                const int64_t t = q.word_ids[j];
+                int slot = -1;
+                if (t < 0 || t >= V) {
+                    bad_word = true;      // the index contract: matches nothing, reported at the end
+                } else if (c.cf[static_cast<size_t>(t)] != 0) {
+                    auto it = std::lower_bound(slot_of.begin(), slot_of.end(), std::make_pair(t, -1));
+                    if (it != slot_of.end() && it->first == t) {
+                        slot = it->second;
+                    } else if (terms.size() == static_cast<size_t>(kSdmSlots)) {
+                        fits = false;
+                    } else {
+                        slot = static_cast<int>(terms.size());
+                        slot_of.insert(it, std::make_pair(t, slot));
+                        terms.push_back(static_cast<int>(t));
+                    }
+                }
+                qslot.push_back(slot);
+            }
+            // the pairs of the query as given: qpair[cell] is the pair (cell, cell + 1), -1 at the query's last position
+            for (size_t i = cells_before; fits && i < qslot.size(); ++i) {
+                int pair = -1;
+                if (i + 1 < qslot.size() && qslot[i] >= 0 && qslot[i + 1] >= 0) {      // (a pair with a term nobody holds has no occurrence: dropped)
+                    const int64_t key = static_cast<int64_t>(qslot[i]) * kSdmSlots + qslot[i + 1];
+                    auto it = std::lower_bound(pair_of.begin(), pair_of.end(), std::make_pair(key, -1));
+                    if (it != pair_of.end() && it->first == key) {
+                        pair = it->second;
+                    } else if (pair_a.size() == static_cast<size_t>(kSdmPairs)) {
+                        fits = false;
+                    } else {
+                        pair = static_cast<int>(pair_a.size());
+                        pair_of.insert(it, std::make_pair(key, pair));
+                        pair_a.push_back(qslot[i]); pair_b.push_back(qslot[i + 1]);
+                    }
+                }
+                qpair.push_back(pair);
+            }
+            if (!fits) {      // this query opens the next round (alone it fits: sdm_check): take back what it added
+                slot_of.erase(std::remove_if(slot_of.begin(), slot_of.end(), [&](const std::pair<int64_t, int>& e) { return e.second >= static_cast<int>(terms_before); }),
+                              slot_of.end());
+                pair_of.erase(std::remove_if(pair_of.begin(), pair_of.end(), [&](const std::pair<int64_t, int>& e) { return e.second >= static_cast<int>(pairs_before); }),
+                              pair_of.end());
+                terms.resize(terms_before); pair_a.resize(pairs_before); pair_b.resize(pairs_before);
+                qslot.resize(cells_before);
+                qpair.resize(cells_before);
+                break;
+            }
+            qfirst.push_back(static_cast<int>(qslot.size()));
+        }
+        const int64_t qn = l.qn = taken;
+        const int nslots = static_cast<int>(terms.size()), npairs = static_cast<int>(pair_a.size());
+
+        // ---- the pair entries by slot, the slot table, the collection counts of the round's pairs
+        ent_off.assign(static_cast<size_t>(nslots) + 1, 0);
+        for (int p = 0; p < npairs; ++p) {
+            ++ent_off[static_cast<size_t>(pair_a[p]) + 1];
+            if (pair_b[p] != pair_a[p]) ++ent_off[static_cast<size_t>(pair_b[p]) + 1];
+        }
+        for (int s = 0; s < nslots; ++s) ent_off[static_cast<size_t>(s) + 1] += ent_off[static_cast<size_t>(s)];
+        const size_t nentries = static_cast<size_t>(ent_off[static_cast<size_t>(nslots)]);
+        ent_other.assign(std::max<size_t>(nentries, 1), 0);
+        ent_pair.assign(std::max<size_t>(nentries, 1), 0);
+        {
+            std::vector<int> at(ent_off.begin(), ent_off.end() - 1);
+            for (int p = 0; p < npairs; ++p) {
+                const int a = pair_a[p], b = pair_b[p];
+                ent_other[static_cast<size_t>(at[a])] = b; ent_pair[static_cast<size_t>(at[a]++)] = (p << 1) | 1;
+                if (b != a) { ent_other[static_cast<size_t>(at[b])] = a; ent_pair[static_cast<size_t>(at[b]++)] = p << 1; }
+            }
+        }
+        grow(r.lex_terms, static_cast<size_t>(kLexSlots));
+        grow(r.sdm_ent_off, static_cast<size_t>(kSdmSlots) + 1);
+        grow(r.sdm_ent_other, static_cast<size_t>(2 * kSdmPairs));
+        grow(r.sdm_ent_pair, static_cast<size_t>(2 * kSdmPairs));
+        grow(r.sdm_cf, cf.size());
+        // (the main stream is idle here: every round ends with a wait)
+        if (nslots > 0) NVSM_HIP_CHECK(hipMemcpy(r.lex_terms.p, terms.data(), static_cast<size_t>(nslots) * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.sdm_ent_off.p, ent_off.data(), ent_off.size() * sizeof(int), hipMemcpyHostToDevice));
+        if (nentries > 0) {
+            NVSM_HIP_CHECK(hipMemcpy(r.sdm_ent_other.p, ent_other.data(), nentries * sizeof(int), hipMemcpyHostToDevice));
+            NVSM_HIP_CHECK(hipMemcpy(r.sdm_ent_pair.p, ent_pair.data(), nentries * sizeof(int), hipMemcpyHostToDevice));
+        }
+        SdmScoreArgs a{};
+        a.count.tokens = c.tokens.p; a.count.doc_offsets = c.offsets.p; a.count.slot_of = r.lex_slot_of.p;
+        a.count.ent_off = r.sdm_ent_off.p; a.count.ent_other = r.sdm_ent_other.p; a.count.ent_pair = r.sdm_ent_pair.p;
+        a.count.num_slots = nslots; a.count.num_pairs = npairs; a.count.window = sdm.window;
+        std::fill(cf.begin(), cf.end(), 0ull);
+        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);
+        if (npairs > 0) {
+            NVSM_HIP_CHECK(hipMemsetAsync(r.sdm_cf.p, 0, cf.size() * sizeof(unsigned long long), stream_));
+            { RankProf scope(prof, "sdm_collect", stream_); launch_sdm_collect(a.count, Dc, r.sdm_cf.p, r.sdm_cf.p + kSdmPairs, stream_); }
+            NVSM_HIP_CHECK(hipMemcpyAsync(cf.data(), r.sdm_cf.p, cf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+            NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        }
+        const unsigned long long* cf_o = cf.data();
+        const unsigned long long* cf_u = cf.data() + kSdmPairs;
+        if (ordered || unordered) {
+            for (int64_t i = 0; i < qn; ++i) {
+                for (int cell = qfirst[static_cast<size_t>(i)]; cell + 1 < qfirst[static_cast<size_t>(i) + 1]; ++cell) {
+                    const int p = qpair[static_cast<size_t>(cell)];
+                    if (ordered) ordered[pairs_out] = p >= 0 ? cf_o[p] : 0;
+                    if (unordered) unordered[pairs_out] = p >= 0 ? cf_u[p] : 0;
+                    ++pairs_out;
+                }
+            }
+        }
+        if (!lex) {
+            launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
+            NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+            q0 += qn;
+            continue;
+        }
+
+        // ---- the members of every query's three groups, in query order, and the queries' group coefficients
+        goff.assign(3 * (static_cast<size_t>(qn) + 1), 0);
+        index.clear(); c0.clear(); base.clear();
+        coef.assign(3 * static_cast<size_t>(std::max<int64_t>(qn, 1)), 0.0);
+        auto member = [&](int idx, double held) {
+            const double v = param * (held / static_cast<double>(N));
+            index.push_back(idx); c0.push_back(v); base.push_back(std::log(v));
+        };
+        for (int g = 0; g < 3; ++g) {
+            int* off = goff.data() + static_cast<size_t>(g) * (static_cast<size_t>(qn) + 1);
+            for (int64_t i = 0; i < qn; ++i) {
+                off[i] = static_cast<int>(index.size());
+                for (int cell = qfirst[static_cast<size_t>(i)]; cell < qfirst[static_cast<size_t>(i) + 1]; ++cell) {
+                    if (g == 0) {
+                        const int s = qslot[static_cast<size_t>(cell)];
+                        if (s >= 0) member(s, static_cast<double>(c.cf[static_cast<size_t>(terms[static_cast<size_t>(s)])]));
+                    } else {
+                        const int p = qpair[static_cast<size_t>(cell)];
+                        const unsigned long long held = p >= 0 ? (g == 1 ? cf_o[p] : cf_u[p]) : 0ull;
+                        if (held > 0) member(p, static_cast<double>(held));
+                    }
+                }
+            }
+            off[qn] = static_cast<int>(index.size());
+        }
+        for (int64_t i = 0; i < qn; ++i) {
+            double total = 0.0;
+            bool present[3];
+            for (int g = 0; g < 3; ++g) {
+                const int* off = goff.data() + static_cast<size_t>(g) * (static_cast<size_t>(qn) + 1);
+                present[g] = off[i + 1] > off[i] && w[g] > 0.0;
+                if (present[g]) total += w[g];
+            }
+            for (int g = 0; g < 3; ++g) coef[static_cast<size_t>(i) * 3 + g] = present[g] ? w[g] / total : 0.0;
+        }
+        const size_t nmem = index.size();
+        grow(r.sdm_goff, 3 * (static_cast<size_t>(kRankChunk) + 1));
+        grow(r.sdm_coef, 3 * static_cast<size_t>(kRankChunk));
+        grow(r.sdm_index, std::max<size_t>(nmem, 1));
+        grow(r.sdm_c0, std::max<size_t>(nmem, 1));
+        grow(r.sdm_base, std::max<size_t>(nmem, 1));
+        NVSM_HIP_CHECK(hipMemcpy(r.sdm_goff.p, goff.data(), goff.size() * sizeof(int), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(r.sdm_coef.p, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (nmem > 0) {
+            NVSM_HIP_CHECK(hipMemcpy(r.sdm_index.p, index.data(), nmem * sizeof(int), hipMemcpyHostToDevice));
+            NVSM_HIP_CHECK(hipMemcpy(r.sdm_c0.p, c0.data(), nmem * sizeof(double), hipMemcpyHostToDevice));
+            NVSM_HIP_CHECK(hipMemcpy(r.sdm_base.p, base.data(), nmem * sizeof(double), hipMemcpyHostToDevice));
+        }
+        round_grow(l, k);
+        a.Q = static_cast<int>(qn); a.method = lex->method; a.param = param;
+        a.goff = r.sdm_goff.p; a.index = r.sdm_index.p; a.c0 = r.sdm_c0.p; a.base = r.sdm_base.p; a.coef = r.sdm_coef.p;
+        a.ld = l.ld;
+        round_slabs(l, Dc, k, [&](int64_t d0, int Ss) {
+            a.scores = r.scores.p; a.d0 = d0; a.S = Ss;
+            RankProf scope(prof, "sdm_score", stream_);
+            launch_sdm_score(a, stream_);
+        });
+        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
+        round_sort(l, [&] { launch_lex_write(r.keys.p, l.npad, static_cast<int>(qn), k, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_); });
+        round_results(q0, qn, k, doc_ids, scores, counts);
+        q0 += qn;
+    }
+    raise_device_error();
+    if (bad_word) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a query word id is outside [0, num_words)");
 }
 
 // ---- supervised fusion: the alpha sweep and the k-fold choice (include/cunvsm_amd.h nvsm_ensemble_sweep / nvsm_rank_ensemble_cv;

@@ -16,7 +16,8 @@
 // --alpha) — is --qlm / --ensemble_alpha: the collection goes to HBM as the token arena the trainer would upload (token_arena.hpp:
 // IndexSource's term mapping and out-of-vocabulary rule, documents in model id order) and nvsm_lexical_rank / nvsm_rank_ensemble do
 // the rest. The lexical model is over the MODEL's vocabulary, not Indri's. --qlm_prf makes the lexical run, and with it
-// the fusion, the reference's "QLM w/ PRF": nvsm_lexical_rank_prf / nvsm_rank_ensemble_prf (RM3).
+// the fusion, the reference's "QLM w/ PRF": nvsm_lexical_rank_prf / nvsm_rank_ensemble_prf (RM3). --qlm_sdm makes it the
+// sequential dependence model's — terms, exact adjacent pairs, pairs in a window: nvsm_sdm_rank / nvsm_rank_ensemble_sdm.
 // py/combine_runs.py's supervised mode (--qrel --num_folds --alpha_stepsize) is --ensemble_qrel: the fusion's weight is chosen per fold
 // of the topics on a grid by nvsm_rank_ensemble_cv.
 // py/query.py's --rerank_exact_matching_documents — a lexical first stage names each topic's candidates and the model ranks only those —
@@ -46,12 +47,12 @@ using namespace nvsm_host;
 namespace {
 
 std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs, FLAGS_qlm, FLAGS_qlm_param, FLAGS_qlm_run_out,
-    FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure, FLAGS_rerank, FLAGS_tfidf_run_out, FLAGS_lexical_index;
+    FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure, FLAGS_rerank, FLAGS_tfidf_run_out, FLAGS_lexical_index, FLAGS_sdm_weights;
 bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
-    FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf;
+    FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf, FLAGS_qlm_sdm;
 double FLAGS_bias_coefficient, FLAGS_qlm_fb_orig_weight, FLAGS_alpha_stepsize;
 int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers, FLAGS_qlm_fb_docs, FLAGS_qlm_fb_terms, FLAGS_num_folds, FLAGS_ensemble_seed,
-    FLAGS_rerank_depth;
+    FLAGS_rerank_depth, FLAGS_sdm_window;
 
 void define_flags(Flags* f) {
     f->define_string("index", &FLAGS_index, "", "TREC-text collection file or Indri repository directory, as given to cuNVSMTrainModel.");
@@ -110,6 +111,12 @@ void define_flags(Flags* f) {
     f->define_int64("rerank_depth", &FLAGS_rerank_depth, 1000, "With --rerank: candidates per topic, clipped to the collection; at most 4096.");
     f->define_string("tfidf_run_out", &FLAGS_tfidf_run_out, "", "Prefix of the TF-IDF runs (Robertson's idf; Okapi's with --rerank okapi), written as "
                      "<prefix>-<topic file> in TREC format, --top_k documents per topic (with --rerank: the --rerank_depth candidates).");
+    f->define_bool("qlm_sdm", &FLAGS_qlm_sdm, false, "With --qlm: the sequential dependence model. Every topic is ranked by its terms, its adjacent pairs "
+                   "of terms as exact phrases and those pairs within a window; the --qlm_run_out runs and the --ensemble_alpha fusion use that ranking. "
+                   "Not together with --qlm_prf or --ensemble_qrel.");
+    f->define_string("sdm_weights", &FLAGS_sdm_weights, "0.85,0.10,0.05", "With --qlm_sdm: t,o,u, the weights of the terms, the ordered pairs and the unordered "
+                     "pairs; not negative, not all zero.");
+    f->define_int64("sdm_window", &FLAGS_sdm_window, 8, "With --qlm_sdm: the window of the unordered pairs, in [2, 64].");
     f->define_string("lexical_index", &FLAGS_lexical_index, "", "auto | always | never, with --qlm or --rerank: build the inverted index of the uploaded "
                      "collection and let the lexical rankings fill their scores from its postings (always), from the token arena (never) or "
                      "whichever is cheaper per round (auto). Every run file is byte for byte the one written without the flag.");
@@ -255,6 +262,31 @@ int run(int argc, char** argv) {
     } else {
         NVSM_CHECK(FLAGS_qlm_fb_docs == 10 && FLAGS_qlm_fb_terms == 10 && FLAGS_qlm_fb_orig_weight == 0.5)
             << "--qlm_fb_docs, --qlm_fb_terms and --qlm_fb_orig_weight need --qlm_prf.";
+    }
+    nvsm_sdm_options sdm;
+    nvsm_sdm_options_default(&sdm);
+    const bool with_sdm = FLAGS_qlm_sdm;
+    if (with_sdm) {
+        NVSM_CHECK(with_qlm) << "--qlm_sdm needs --qlm.";
+        NVSM_CHECK(!with_prf) << "--qlm_sdm and --qlm_prf are mutually exclusive: the lexical run is either the dependence model's or the expanded query's.";
+        NVSM_CHECK(!with_cv) << "--qlm_sdm is not offered with --ensemble_qrel: the cross-validated fusion takes the query-likelihood run.";
+        float w[3];
+        size_t n = 0;
+        std::istringstream in(FLAGS_sdm_weights);
+        bool good = !FLAGS_sdm_weights.empty() && FLAGS_sdm_weights.back() != ',';
+        for (std::string item; good && std::getline(in, item, ',');) {
+            char* end = nullptr;
+            const double v = std::strtod(item.c_str(), &end);
+            good = !item.empty() && *end == '\0' && v >= 0.0 && v <= 3.0e38 && n < 3;
+            if (good) w[n++] = static_cast<float>(v);
+        }
+        if (!good || n != 3 || (w[0] == 0.f && w[1] == 0.f && w[2] == 0.f))
+            NVSM_LOG(FATAL) << "--sdm_weights: '" << FLAGS_sdm_weights << "' is not three weights t,o,u that are not negative and not all zero.";
+        NVSM_CHECK(FLAGS_sdm_window >= 2 && FLAGS_sdm_window <= NVSM_SDM_MAX_WINDOW) << "--sdm_window must be in [2, " << NVSM_SDM_MAX_WINDOW << "].";
+        sdm.w_term = w[0]; sdm.w_ordered = w[1]; sdm.w_unordered = w[2];
+        sdm.window = static_cast<int32_t>(FLAGS_sdm_window);
+    } else {
+        NVSM_CHECK(FLAGS_sdm_weights == "0.85,0.10,0.05" && FLAGS_sdm_window == 8) << "--sdm_weights and --sdm_window need --qlm_sdm.";
     }
     if (with_ensemble) {
         char* end = nullptr;
@@ -511,6 +543,7 @@ int run(int argc, char** argv) {
                 std::vector<int64_t> lex_ids(static_cast<size_t>(Q * k) + 1), lex_counts(static_cast<size_t>(Q) + 1);
                 std::vector<float> lex_scores(static_cast<size_t>(Q * k) + 1);
                 if (with_prf) NVSM_CALL(nvsm_lexical_rank_prf(model, &queries, &lex, &fb, lex_ids.data(), lex_scores.data(), lex_counts.data()));
+                else if (with_sdm) NVSM_CALL(nvsm_sdm_rank(model, &queries, &lex, &sdm, lex_ids.data(), lex_scores.data(), lex_counts.data()));
                 else NVSM_CALL(nvsm_lexical_rank(model, &queries, &lex, lex_ids.data(), lex_scores.data(), lex_counts.data()));
                 write_run(qlm_path, lex_ids, lex_scores, lex_counts, k);
             }
@@ -565,6 +598,9 @@ int run(int argc, char** argv) {
             judgments.cutoffs = cutoffs.data(); judgments.num_cutoffs = static_cast<int32_t>(cutoffs.size());
             if (with_prf)
                 NVSM_CALL(nvsm_rank_ensemble_prf(model, &queries, &opt, &lex, &fb, &ens, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr,
+                                                 doc_ids.data(), scores.data(), counts.data()));
+            else if (with_sdm)
+                NVSM_CALL(nvsm_rank_ensemble_sdm(model, &queries, &opt, &lex, &sdm, &ens, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr,
                                                  doc_ids.data(), scores.data(), counts.data()));
             else
                 NVSM_CALL(nvsm_rank_ensemble(model, &queries, &opt, &lex, &ens, qrels ? &judgments : nullptr, qrels ? metrics.data() : nullptr,

@@ -449,6 +449,29 @@ def lexical_options(method="jm", param=None, top_k=1000):
     return opt
 
 
+def sdm_options(weights=(0.85, 0.10, 0.05), window=8):
+    """nvsm_sdm_options from keywords: weights = (terms, ordered pairs, unordered pairs); raises ValueError for what the ABI would
+    refuse. An NvsmSdmOptions, a dict of these keywords or True (the defaults) are taken as they are."""
+    if isinstance(weights, _lib.NvsmSdmOptions):
+        return weights
+    if weights is True:
+        weights = (0.85, 0.10, 0.05)
+    if isinstance(weights, dict):
+        return sdm_options(**weights)
+    w = [float(x) for x in weights]
+    if len(w) != 3:
+        raise ValueError("sdm weights are (terms, ordered, unordered), got %d values" % len(w))
+    if any(not np.isfinite(x) or x < 0.0 for x in w):
+        raise ValueError("an sdm weight in %r is negative or not finite" % (tuple(w),))
+    if not any(np.float32(x) > 0 for x in w):
+        raise ValueError("the three sdm weights are all zero")
+    if not 2 <= int(window) <= _lib.SDM_MAX_WINDOW:
+        raise ValueError("window = %d outside [2, %d]" % (int(window), _lib.SDM_MAX_WINDOW))
+    opt = _lib.NvsmSdmOptions()
+    opt.w_term, opt.w_ordered, opt.w_unordered, opt.window = w[0], w[1], w[2], int(window)
+    return opt
+
+
 def ensemble_options(alpha=0.5, normalizer="standardize"):
     """nvsm_ensemble_options from keywords; raises ValueError for what the ABI would refuse."""
     opt = _lib.NvsmEnsembleOptions()
@@ -1293,18 +1316,53 @@ class Model:
         check(lib().nvsm_lexical_rank_prf(self._h, C.byref(st), C.byref(opt), C.byref(fb), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         return ids, scores, counts
 
+    # -- sequential dependence: terms, ordered pairs, unordered pairs in a window --------
+    def sdm_rank(self, queries, method="jm", param=None, top_k=1000, weights=(0.85, 0.10, 0.05), window=8):
+        """nvsm_sdm_rank: lexical_rank()'s retrieved set ranked by the sequential dependence model — the mean log term of the query's
+        words, of its adjacent pairs as exact phrases, and of those pairs co-occurring within `window` positions, mixed with
+        weights = (terms, ordered, unordered) normalised over the groups that have members (include/cunvsm_amd.h has the formula).
+        Returns what lexical_rank does."""
+        q = queries if isinstance(queries, Queries) else Queries(queries)
+        opt = lexical_options(method, param, top_k)
+        sopt = sdm_options(weights, window)
+        k = opt.top_k
+        ids = np.empty((q.num_queries, k), dtype=np.int64)
+        scores = np.empty((q.num_queries, k), dtype=np.float32)
+        counts = np.empty(q.num_queries, dtype=np.int64)
+        st = q.as_struct()
+        check(lib().nvsm_sdm_rank(self._h, C.byref(st), C.byref(opt), C.byref(sopt), ids.ctypes.data, scores.ctypes.data, counts.ctypes.data))
+        return ids, scores, counts
+
+    def sdm_pair_counts(self, queries, window=8):
+        """nvsm_sdm_pair_counts: (ordered, unordered) collection counts, uint64, of every adjacent pair of every query, concatenated in
+        query order: a query of L words holds max(L - 1, 0) pairs."""
+        q = queries if isinstance(queries, Queries) else Queries(queries)
+        sopt = sdm_options(window=window)
+        sizes = np.asarray([max(len(row) - 1, 0) for row in q.rows()], dtype=np.int64)
+        n = int(sizes.sum())
+        ordered = np.zeros(max(n, 1), dtype=np.uint64)
+        unordered = np.zeros(max(n, 1), dtype=np.uint64)
+        st = q.as_struct()
+        check(lib().nvsm_sdm_pair_counts(self._h, C.byref(st), C.byref(sopt), ordered.ctypes.data, unordered.ctypes.data))
+        return ordered[:n], unordered[:n]
+
     def rank_ensemble(self, queries, alpha=0.5, normalizer="standardize", judgments=None, top_k=1000, method="jm", param=None,
-                      cutoffs=(5, 10, 20, 100, 1000), weights=None, feedback=None, **opts):
+                      cutoffs=(5, 10, 20, 100, 1000), weights=None, feedback=None, dependence=None, **opts):
         """nvsm_rank_ensemble: rank()'s list and lexical_rank()'s list of every query, each normalised over its returned
         entries ("standardize" | "minmax" | "none") and fused with weights alpha and 1 - alpha (include/cunvsm_amd.h has the
         formula). Returns (ids [Q, 2k], scores [Q, 2k], counts [Q]); with judgments, (metrics, ids, scores, counts) where
         metrics is evaluate()'s dict computed on the fused list. feedback (True, a dict of fb_docs / fb_terms / orig_weight, such a
-        tuple, or an NvsmFeedbackOptions): nvsm_rank_ensemble_prf, the lexical list is lexical_rank_prf()'s. opts: as rank()."""
+        tuple, or an NvsmFeedbackOptions): nvsm_rank_ensemble_prf, the lexical list is lexical_rank_prf()'s. dependence (True, a
+        (terms, ordered, unordered) tuple, a dict of weights / window, or an NvsmSdmOptions): nvsm_rank_ensemble_sdm, the lexical list
+        is sdm_rank()'s; not together with feedback. opts: as rank()."""
         q = queries if isinstance(queries, Queries) else Queries(queries, weights)
         ropt = rank_options(self.cfg.num_entities, top_k, **opts)
         lopt = lexical_options(method, param, top_k)
         eopt = ensemble_options(alpha, normalizer)
         fopt = None if feedback is None or feedback is False else as_feedback_options(feedback)
+        sopt = None if dependence is None or dependence is False else sdm_options(dependence)
+        if fopt is not None and sopt is not None:
+            raise ValueError("feedback and dependence cannot be combined: list B is either lexical_rank_prf()'s or sdm_rank()'s")
         k = ropt.top_k
         ids = np.empty((q.num_queries, 2 * k), dtype=np.int64)
         scores = np.empty((q.num_queries, 2 * k), dtype=np.float32)
@@ -1324,7 +1382,9 @@ class Model:
         tail = (C.byref(eopt), None if js is None else C.byref(js),
                 None if js is None else (metrics.ctypes.data if metrics.size else _EMPTY_F64.ctypes.data),
                 ids.ctypes.data, scores.ctypes.data, counts.ctypes.data)
-        if fopt is None:
+        if sopt is not None:
+            check(lib().nvsm_rank_ensemble_sdm(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), C.byref(sopt), *tail))
+        elif fopt is None:
             check(lib().nvsm_rank_ensemble(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), *tail))
         else:
             check(lib().nvsm_rank_ensemble_prf(self._h, C.byref(st), C.byref(ropt), C.byref(lopt), C.byref(fopt), *tail))

@@ -637,6 +637,66 @@ int nvsm_rank_ensemble_prf(nvsm_model* m, const nvsm_queries* queries, const nvs
                            double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
 
 /*
+ * SEQUENTIAL DEPENDENCE (nvsm_sdm_rank, nvsm_sdm_pair_counts, nvsm_rank_ensemble_sdm) — Metzler & Croft's sequential dependence model,
+ * the Indri query #weight(w_T #combine(t_1 .. t_L) w_O #combine(#1(t_1 t_2) ..) w_U #combine(#uwW(t_1 t_2) ..)): the unigram score,
+ * plus exact adjacent pairs of query terms, plus pairs that co-occur inside a small window. The reference has no program text for it;
+ * the contract is this one. It is defined over the corpus AS UPLOADED: where the arena's builder dropped out-of-vocabulary positions,
+ * adjacency means adjacency in the arena. cf, p(t), len(d), tf, N, the smoothing methods and "auto" mean what they mean for
+ * nvsm_lexical_rank. For a query t_1 .. t_L as given and a window W, 2 <= W <= NVSM_SDM_MAX_WINDOW:
+ *   pairs           (t_j, t_{j+1}), j = 1 .. L − 1, from the query as given (before any term is dropped); a repeated pair counts once per
+ *                   occurrence. A query of one term has no pairs and ranks as its T group alone.
+ *   ordered count   od(a, b; d) = #{i : tok_i = a and tok_{i+1} = b}, both positions inside d.
+ *   unordered count uw(a, b; d) = #{i : tok_i in {a, b} and there is a j, i < j < i + W, j inside d, with tok_j = the OTHER term}; for
+ *                   a = b the other term is a. Every position counts at most once per pair: an existence test, not a count of matches.
+ *                   uw(a, b) = uw(b, a).
+ *   collection      cf_o(a, b) and cf_u(a, b) are those counts summed over all documents, as integers.
+ *   dropped         a term with cf = 0 is dropped from T, as in nvsm_lexical_rank; an ordered pair with cf_o = 0 is dropped from O; an
+ *                   unordered pair with cf_u = 0 is dropped from U. (A pair with a term of cf = 0, or out of range, has no occurrence.)
+ *   features        the unigram term a_j(d) is the log term of nvsm_lexical_rank. A pair feature uses the same formula with its count c
+ *                   in place of tf and cf_x / N in place of p: Dirichlet log((c + μ·cf_x / N) / (len + μ)), JM log((1 − λ)·c / len +
+ *                   λ·cf_x / N).
+ *   score           three groups: T (terms), O (ordered pairs), U (unordered pairs), each in query order. With n_G remaining members
+ *                   g_G = (Σ members in order, fp64) / n_G (Indri's #combine is a mean), and s(q, d) = Σ_G (w_G / Σ_{present G'} w_G')·g_G
+ *                   over the PRESENT groups, those with n_G > 0 and w_G > 0 (Indri's #weight normalises). The weights are float32
+ *                   widened to fp64 and added in the order T, O, U; every product and quotient is rounded on its own; the groups are
+ *                   added in the order T, O, U; the sum is narrowed to float32 ONCE. With no group present (w_T = 0 and no pair left)
+ *                   the score of a retrieved document is 0.
+ *   retrieved set, order, ties, empty queries, counts   exactly nvsm_lexical_rank's: a document is retrieved if it holds at least one
+ *                   remaining TERM, whatever the weights are.
+ *   accuracy        every log term is <= 0 and every coefficient >= 0, so nothing cancels: |score − the fp64 value| <= 2^-23·|the fp64
+ *                   value|, the weighted call's bound.
+ *   reproducibility a repeated call returns the same bits (integer atomics only).
+ * nvsm_sdm_pair_counts writes cf_o and cf_u of every pair (t_j, t_{j+1}) of every query, laid out [Σ_q max(L_q − 1, 0)] in query order:
+ * exact integers, 0 for a pair that holds a term nobody holds. Only sdm->window is looked at beyond the refusals.
+ * nvsm_rank_ensemble_sdm is nvsm_rank_ensemble with list B taken from nvsm_sdm_rank; everything behind list B is the same code path.
+ * The postings of nvsm_corpus_index hold counts and no positions: these calls always scan the arena, whatever nvsm_corpus_index_use says.
+ * All three calls are synchronous, touch no parameter, optimiser state, RNG state or lazy bookkeeping, allocate on first use and leave
+ * nvsm_describe unchanged. NVSM_ERR_INVALID_ARGUMENT before anything runs, each with a sentence: what nvsm_lexical_rank refuses (and
+ * nvsm_rank_ensemble, for the fused call); null arguments, by name; a weight that is negative or not finite, or all three weights
+ * zero; a window outside [2, NVSM_SDM_MAX_WINDOW]. A round whose distinct terms or distinct pairs exceed the LDS counters is split by
+ * the driver; a single query of more than NVSM_LEXICAL_MAX_QUERY_TERMS distinct terms or NVSM_SDM_MAX_QUERY_PAIRS distinct pairs is
+ * NVSM_ERR_UNSUPPORTED. A word id out of range follows the index contract, as in nvsm_lexical_rank.
+ */
+#define NVSM_SDM_MAX_WINDOW 64
+#define NVSM_SDM_MAX_QUERY_PAIRS 1024
+typedef struct {
+    float   w_term, w_ordered, w_unordered;      /* >= 0, not all zero; normalised over the groups that are present */
+    int32_t window;               /* W of the unordered pairs: 2 .. NVSM_SDM_MAX_WINDOW */
+    int32_t reserved[4];
+} nvsm_sdm_options;
+/* 0.85, 0.10, 0.05, window 8: Metzler & Croft's weights with #uw8 for pairs */
+void nvsm_sdm_options_default(nvsm_sdm_options* opt);
+/* results as nvsm_lexical_rank */
+int nvsm_sdm_rank(nvsm_model* m, const nvsm_queries* queries, const nvsm_lexical_options* lex, const nvsm_sdm_options* sdm,
+                  int64_t* doc_ids, float* scores, int64_t* counts);
+/* ordered, unordered [Σ_q max(L_q − 1, 0)], host */
+int nvsm_sdm_pair_counts(nvsm_model* m, const nvsm_queries* queries, const nvsm_sdm_options* sdm, uint64_t* ordered, uint64_t* unordered);
+/* arguments and results as nvsm_rank_ensemble */
+int nvsm_rank_ensemble_sdm(nvsm_model* m, const nvsm_queries* queries, const nvsm_rank_options* rank_opt, const nvsm_lexical_options* lex,
+                           const nvsm_sdm_options* sdm, const nvsm_ensemble_options* ens, const nvsm_judgments* judgments,
+                           double* metrics, int64_t* doc_ids, float* scores, int64_t* counts);
+
+/*
  * SUPERVISED FUSION (nvsm_ensemble_sweep, nvsm_rank_ensemble_cv) — py/combine_runs.py --qrel --num_folds --alpha_stepsize, the mode
  * rank-cranfield-collection.sh takes its "NVSM + QLM" figures from: the fusion is evaluated on a grid of weights alpha, and for each of
  * k folds of the queries the alpha with the best training measure fuses the held-out queries.

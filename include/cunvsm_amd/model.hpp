@@ -378,6 +378,50 @@ class Model {
         return e;
     }
 
+    // nvsm_sdm_rank: lexical_rank's retrieved set ranked by the sequential dependence model (cunvsm_amd.h has the formula)
+    Ranking sdm_rank(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_lexical_options& lex,
+                     const nvsm_sdm_options& sdm) {
+        const nvsm_queries q = queries_of(word_ids, offsets, nullptr);
+        Ranking r;
+        r.top_k = lex.top_k;
+        const size_t n = static_cast<size_t>(q.num_queries) * static_cast<size_t>(lex.top_k > 0 ? lex.top_k : 0);
+        r.doc_ids.resize(n ? n : 1); r.scores.resize(n ? n : 1); r.counts.resize(static_cast<size_t>(q.num_queries) + 1);
+        check(nvsm_sdm_rank(h_, &q, &lex, &sdm, r.doc_ids.data(), r.scores.data(), r.counts.data()));
+        r.doc_ids.resize(n); r.scores.resize(n); r.counts.resize(static_cast<size_t>(q.num_queries));
+        return r;
+    }
+    // nvsm_sdm_pair_counts: the collection counts of every adjacent pair of every query, concatenated in query order
+    struct PairCounts { std::vector<uint64_t> ordered, unordered; };
+    PairCounts sdm_pair_counts(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_sdm_options& sdm) {
+        const nvsm_queries q = queries_of(word_ids, offsets, nullptr);
+        size_t n = 0;
+        for (size_t i = 0; i + 1 < offsets.size(); ++i)
+            if (offsets[i + 1] - offsets[i] > 1) n += static_cast<size_t>(offsets[i + 1] - offsets[i] - 1);
+        PairCounts p;
+        p.ordered.resize(n + 1); p.unordered.resize(n + 1);
+        check(nvsm_sdm_pair_counts(h_, &q, &sdm, p.ordered.data(), p.unordered.data()));
+        p.ordered.resize(n); p.unordered.resize(n);
+        return p;
+    }
+    // nvsm_rank_ensemble_sdm: rank_ensemble with the lexical list taken from sdm_rank
+    Evaluation rank_ensemble_sdm(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
+                                 const nvsm_lexical_options& lex, const nvsm_sdm_options& sdm, const nvsm_ensemble_options& ens,
+                                 const nvsm_judgments* judgments = nullptr, const std::vector<float>* word_weights = nullptr) {
+        const nvsm_queries q = queries_of(word_ids, offsets, word_weights);
+        Evaluation e;
+        e.width = judgments ? NVSM_EVAL_FIXED + 3 * (judgments->num_cutoffs > 0 ? judgments->num_cutoffs : 0) : 0;
+        e.ranking.top_k = 2 * opt.top_k;
+        const size_t Q = static_cast<size_t>(q.num_queries);
+        const size_t n = Q * 2 * static_cast<size_t>(opt.top_k > 0 ? opt.top_k : 0);
+        e.metrics.resize(Q * static_cast<size_t>(e.width) + 1);
+        e.ranking.doc_ids.resize(n ? n : 1); e.ranking.scores.resize(n ? n : 1); e.ranking.counts.resize(Q + 1);
+        check(nvsm_rank_ensemble_sdm(h_, &q, &opt, &lex, &sdm, &ens, judgments, judgments ? e.metrics.data() : nullptr, e.ranking.doc_ids.data(),
+                                     e.ranking.scores.data(), e.ranking.counts.data()));
+        e.metrics.resize(Q * static_cast<size_t>(e.width));
+        e.ranking.doc_ids.resize(n); e.ranking.scores.resize(n); e.ranking.counts.resize(Q);
+        return e;
+    }
+
     // nvsm_ensemble_sweep: both rankings once, then the metric rows [alphas][num_queries][width] of their fusion at every alpha over
     // the first `depth` entries of the fused lists (0: all). fb null: the lexical list is lexical_rank's, else lexical_rank_prf's.
     struct Sweep { std::vector<double> metrics; int32_t width; int32_t num_alphas; };
