@@ -12,7 +12,7 @@ from ._lib import (  # noqa: F401
     NvsmQueries, NvsmRankOptions, NvsmJudgments, EVAL_MAX_CUTOFFS, NvsmPairBatch, NvsmMixture, NvsmCorpus, NvsmWindowBatch, NvsmError, abi_symbols, build_library,
     bind_host_thread, device_count, lib, library_path,
     NvsmLexicalOptions, NvsmEnsembleOptions, NvsmFeedbackOptions, FEEDBACK_MAX_DOCS, LEX_JM, LEX_DIRICHLET, NORM_STANDARDIZE, NORM_MINMAX, NORM_NONE,
-    NvsmSweepOptions, NvsmCvOptions, SWEEP_MAX_ALPHAS, NvsmNgramOptions, NvsmTsneOptions, TSNE_MAX_ROWS, TSNE_INIT_PCA, TSNE_INIT_GIVEN,
+    NvsmSweepOptions, NvsmCvOptions, SWEEP_MAX_ALPHAS, NvsmNgramOptions, NvsmTsneOptions, NvsmTsneSparseOptions, TSNE_MAX_ROWS, TSNE_SPARSE_MAX_ROWS, TSNE_SPARSE_MAX_NEIGHBORS, TSNE_INIT_PCA, TSNE_INIT_GIVEN,
     NvsmSdmOptions, SDM_MAX_WINDOW,
     NvsmKmeansOptions, KMEANS_MAX_CLUSTERS, KMEANS_INIT_PLUSPLUS, KMEANS_INIT_GIVEN,
     NvsmIndexOptions, NvsmIndexInfo, INDEX_AUTO, INDEX_ALWAYS, INDEX_NEVER,

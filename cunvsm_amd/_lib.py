@@ -191,6 +191,14 @@ class NvsmTsneOptions(C.Structure):
     ]
 
 
+TSNE_SPARSE_MAX_ROWS = 1048576
+TSNE_SPARSE_MAX_NEIGHBORS = 1024
+
+
+class NvsmTsneSparseOptions(C.Structure):
+    _fields_ = [("n_neighbors", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 KMEANS_MAX_CLUSTERS = 4096
 KMEANS_INIT_PLUSPLUS, KMEANS_INIT_GIVEN = 0, 1
 
@@ -366,6 +374,10 @@ class _Library:
                 "nvsm_debug_tsne_gradient": (C.c_int, [vp, vp, i64, C.c_float, vp, P(C.c_double)]),
                 "nvsm_debug_tsne_pca": (C.c_int, [vp, i64, C.c_int, vp]),
                 "nvsm_debug_tsne_descent": (C.c_int, [vp, vp, i64, P(NvsmTsneOptions), C.c_int, P(C.c_double), P(C.c_int32)]),
+                "nvsm_debug_tsne_knn": (C.c_int, [vp, i64, C.c_int, C.c_int, i64, vp, vp]),
+                "nvsm_debug_tsne_sparse_affinities": (C.c_int, [vp, i64, C.c_int, C.c_float, C.c_int, vp, vp, vp, vp]),
+                "nvsm_debug_tsne_sparse_gradient": (C.c_int, [vp, vp, vp, vp, i64, C.c_float, C.c_int, vp, P(C.c_double)]),
+                "nvsm_debug_tsne_sparse_descent": (C.c_int, [vp, vp, vp, vp, i64, P(NvsmTsneOptions), C.c_int, P(C.c_double), P(C.c_int32)]),
                 "nvsm_debug_kmeans_assign": (C.c_int, [vp, i64, C.c_int, vp, C.c_int, vp, vp]),
                 "nvsm_debug_kmeans_update": (C.c_int, [vp, i64, C.c_int, vp, vp, C.c_int, vp, vp, P(C.c_double)]),
                 "nvsm_debug_kmeans_plusplus": (C.c_int, [vp, i64, C.c_int, C.c_int, i64, vp, vp]),
@@ -475,6 +487,8 @@ def lib():
         "nvsm_ngram_search": (C.c_int, [vp, P(NvsmNeighborQueries), P(NvsmNgramOptions), vp, vp, vp, vp]),
         "nvsm_tsne_options_default": (None, [P(NvsmTsneOptions)]),
         "nvsm_tsne": (C.c_int, [vp, P(NvsmTsneOptions), vp, P(C.c_double), P(C.c_int32)]),
+        "nvsm_tsne_sparse_options_default": (None, [P(NvsmTsneSparseOptions)]),
+        "nvsm_tsne_sparse": (C.c_int, [vp, P(NvsmTsneOptions), P(NvsmTsneSparseOptions), vp, P(C.c_double), P(C.c_int32)]),
         "nvsm_kmeans_options_default": (None, [P(NvsmKmeansOptions)]),
         "nvsm_kmeans": (C.c_int, [vp, P(NvsmKmeansOptions), vp, vp, vp, vp, P(C.c_double), P(C.c_int32)]),
         "nvsm_set_stream": (C.c_int, [vp, vp]), "nvsm_synchronize": (C.c_int, [vp]),

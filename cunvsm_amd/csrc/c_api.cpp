@@ -547,6 +547,16 @@ int nvsm_tsne(nvsm_model* m, const nvsm_tsne_options* opt, float* embedding, dou
     NVSM_REQUIRE(m); NVSM_REQUIRE(opt); NVSM_REQUIRE(embedding); NVSM_REQUIRE(kl_divergence); NVSM_REQUIRE(n_iter);
     return guarded_on(m, [&] { m->impl.tsne(*opt, embedding, kl_divergence, n_iter); });
 }
+void nvsm_tsne_sparse_options_default(nvsm_tsne_sparse_options* o) {
+    if (o) std::memset(o, 0, sizeof(*o));
+}
+int nvsm_tsne_sparse(nvsm_model* m, const nvsm_tsne_options* opt, const nvsm_tsne_sparse_options* sparse, float* embedding,
+                     double* kl_divergence, int32_t* n_iter) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(opt); NVSM_REQUIRE(embedding); NVSM_REQUIRE(kl_divergence); NVSM_REQUIRE(n_iter);
+    nvsm_tsne_sparse_options defaults;
+    nvsm_tsne_sparse_options_default(&defaults);
+    return guarded_on(m, [&] { m->impl.tsne_sparse(*opt, sparse ? *sparse : defaults, embedding, kl_divergence, n_iter); });
+}
 
 void nvsm_kmeans_options_default(nvsm_kmeans_options* o) {
     if (!o) return;

@@ -614,6 +614,34 @@ void launch_tsne_check(const double* klrow, const float* gs, int n, double* out,
 void launch_tsne_covariance(const float* X, int n, int d, double* mean, double* cov, hipStream_t s);
 void launch_tsne_project(const float* X, int n, int d, const double* mean, const double* V, float* Y0, hipStream_t s);
 
+// ---- sparse-affinity t-SNE (tsne_sparse.hip; include/cunvsm_amd.h nvsm_tsne_sparse) ----
+// sklearn's method='barnes_hut' at angle 0: k neighbours a row, P a CSR matrix (indptr [n + 1] int64, indices / data [nnz]), the
+// repulsion over all pairs from Y alone. Every pointer is a device pointer and every sum has a fixed order (no float atomics).
+// the column ranges of tsne_sp_repulsion_kernel at n rows: width wr, LDS tile tw (a multiple of 256, at most 4096) and their number, a
+// function of n alone; forced_ranges > 0 (the test hooks) asks for that many ranges. Host arithmetic.
+void tsne_sparse_layout(int n, int forced_ranges, int* wr, int* tw, int* ranges);
+// scores [qn][ld]: row q0 + i against rows j0 .. j0 + S: −fp32(fp64 Σ_t (x_it − x_jt)²), never −0; −inf at the row itself
+void launch_tsne_nn_scores(const float* X, int n, int d, int q0, int qn, int j0, int S, float* scores, int64_t ld, hipStream_t s);
+// the round's sorted selection keys -> nbr_id / nbr_d2 [n][k] rows q0 .. q0 + qn, nearest first, ties by ascending id
+void launch_tsne_nn_write(const unsigned long long* keys, int64_t npad, int qn, int k, int q0, int* nbr_id, float* nbr_d2, hipStream_t s);
+// sklearn's perplexity search over each row's k distances (fp64): cond [n][k] (fp32), rowsum [n] their sums (fp64)
+void launch_tsne_nn_conditionals(const float* nbr_d2, int n, int k, float perplexity, float* cond, double* rowsum, hipStream_t s);
+// out [2nk]: the row (row = true) or column of directed entry perm[t] (perm null: t); entry e < nk is edge e as (i, j), e >= nk as (j, i)
+void launch_tsne_sym_keys(const int* nbr_id, int n, int k, const int* perm, bool row, int* out, hipStream_t s);
+// data[p] = fp32(Σ cond of the entries head_pos[p] .. head_pos[p + 1] of perm / max(2·total, eps)); total [1] = Σ rowsum
+void launch_tsne_sym_values(const int* head_pos, const int* perm, const float* cond, int64_t nnz, int n, int k, const double* total, float* data,
+                            hipStream_t s);
+// attr [n][2] = Σ_{stored j} P q (y_i − y_j); part [n][ranges][3] = (Σ q² dx, Σ q² dy, Σ q) over the range's j != i; z [1] = Σ q
+void launch_tsne_sparse_forces(const int64_t* indptr, const int* indices, const float* data, const float* Y, int n, int forced_ranges, float* attr,
+                               float* part, double* z, hipStream_t s);
+// launch_tsne_update on attr and part
+void launch_tsne_sparse_update(const float* attr, const float* part, int n, int forced_ranges, const double* z, float exaggeration, float momentum,
+                               float learning_rate, float* Y, float* upd, float* gains, float* gs, float* graw, hipStream_t s);
+// klrow [n] = Σ_{stored j} e·P·log(max(e·P, tiny) / max(q / Z, tiny)), fp64 throughout, with a Z of their own in z64 [1] (scratch: one
+// more pass over all pairs, in fp64); launch_tsne_check adds them up
+void launch_tsne_sparse_kl_rows(const int64_t* indptr, const int* indices, const float* data, const float* Y, int n, double* z64,
+                                float exaggeration, double* klrow, hipStream_t s);
+
 // ---- k-means of table rows (kmeans.hip; include/cunvsm_amd.h nvsm_kmeans) ----
 // Every pointer below is a device pointer; every floating-point sum has a fixed order (no float atomics).
 // The assignment pass runs on v_mfma_f32_16x16x4_f32 at every dimension (columns beyond d are zeros in LDS): always true today,

@@ -144,6 +144,29 @@ void tsne_pca_start(const float* X, int n, int d, TsneScratch& w, float* Y0, hip
 void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl, int32_t* n_iter,
                   Profiler* prof, hipStream_t s);
 
+// ---- sparse-affinity t-SNE (ranking.cpp; kernels: tsne_sparse.hip): the host side nvsm_tsne_sparse and the test hooks share
+struct TsneSparseScratch {
+    TsneScratch base;                      // x, y, upd, gains, gs, rows, pca, ids as nvsm_tsne uses them; its p and part stay empty
+    DevBuf<int> nbr_id, indices;           // [n][k]; [nnz]
+    DevBuf<float> nbr_d2, cond, data, attr, part;      // [n][k] twice; [nnz]; [n][2]; [n][ranges][3]
+    DevBuf<int64_t> indptr;                // [n + 1]
+    DevBuf<float> scores;                  // a neighbour round's slab
+    DevBuf<unsigned long long> keys;
+    DevBuf<char> sel_ws;
+    int64_t nnz = 0;
+    int forced_ranges = 0;                 // > 0 (test hooks): that many column ranges in the repulsion
+    void grow_rows(int64_t n, int d);      // everything sized by n and d alone
+};
+// w.nbr_id / w.nbr_d2 [n][k]: every row's k nearest other rows of X [n][d] (device), nearest first, ties by ascending id; rounds of
+// query rows as the retrieval calls run them (score slab of score_floats floats; round_rows > 0: that many rows a round)
+void tsne_sparse_knn(const float* X, int n, int d, int k, int64_t round_rows, int64_t score_floats, TsneSparseScratch& w, Profiler* prof,
+                     hipStream_t s);
+// w.cond [n][k] and the CSR matrix P (w.indptr, w.indices, w.data, w.nnz) from w.nbr_id / w.nbr_d2. Synchronous on s.
+void tsne_sparse_affinities(int n, int k, float perplexity, TsneSparseScratch& w, Profiler* prof, hipStream_t s);
+// tsne_descent on the CSR matrix in w and w.base.y
+void tsne_sparse_descent(TsneSparseScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl,
+                         int32_t* n_iter, Profiler* prof, hipStream_t s);
+
 // ---- k-means (ranking.cpp; kernels: kmeans.hip): the host side the product call and the test hooks share ----
 struct KmeansScratch {
     DevBuf<float> x, mean32, xn, c, c2, cc, cn, dist32;
@@ -260,6 +283,9 @@ class Model {
     void similarity(int space, const int64_t* a, const int64_t* b, int64_t n, int similarity, float* out);
     // exact t-SNE of rows of E or W (py/visualize.py; nvsm_tsne): embedding [num_rows][2] host
     void tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_divergence, int32_t* n_iter);
+    // the same picture from sparse affinities (nvsm_tsne_sparse): sklearn's barnes_hut at angle 0, no n × n memory
+    void tsne_sparse(const nvsm_tsne_options& opt, const nvsm_tsne_sparse_options& sparse, float* embedding, double* kl_divergence,
+                     int32_t* n_iter);
     // Lloyd's k-means of rows of E or W (nvsm_kmeans): labels [num_rows], centers [k][dim], counts [k], distances [num_rows] or null: host
     void kmeans(const nvsm_kmeans_options& opt, int32_t* labels, float* centers, int64_t* counts, float* distances, double* inertia, int32_t* n_iter);
 
@@ -587,6 +613,8 @@ class Model {
     };
     RankScratch rank_;
     TsneScratch tsne_;      // allocated by the first nvsm_tsne, grown by a later call with more rows
+    TsneSparseScratch tsne_sparse_;      // likewise for nvsm_tsne_sparse
+    void tsne_check(const nvsm_tsne_options& opt, int64_t max_rows, const char* too_many, int64_t* n_out) const;      // the refusals both calls share
     KmeansScratch kmeans_;  // likewise for nvsm_kmeans
     int64_t score_floats() const { return static_cast<int64_t>(tune_.rank_slab_mb) << 18; }      // the score slab: 256 MB unless NVSM_RANK_SLAB_MB says otherwise
     // one round behind its layout (ranking.cpp): scratch, the slabs through the caller's fill step, sort + the caller's write, results

@@ -1980,8 +1980,13 @@ void tsne_pca_start(const float* X, int n, int d, TsneScratch& w, float* Y0, hip
     NVSM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl, int32_t* n_iter,
-                  Profiler* prof, hipStream_t s) {
+namespace {
+// sklearn's two-phase _gradient_descent over the device steps of one method (exact: tsne.hip; sparse: tsne_sparse.hip). w holds y, upd,
+// gains, gs and rows = rowsum [n] | klrow [n] | total, z, kl, |g|, a z of the check's own. forces(z): the iteration's sums and its Z;
+// kl_rows(z, z64, e, klrow): the rows of the error; update(z, e, momentum): the step.
+template <typename Forces, typename KlRows, typename Update>
+void tsne_descent_loop(TsneScratch& w, int n, const nvsm_tsne_options& opt, int exploration, double* kl, int32_t* n_iter, Profiler* prof,
+                       hipStream_t s, Forces forces, KlRows kl_rows, Update update) {
     double* klrow = w.rows.p + n;
     double* z = w.rows.p + 2 * static_cast<size_t>(n) + 1;
     double* out = z + 1;
@@ -1996,12 +2001,9 @@ void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float lea
         for (int i = it0; i < max_iter; ++i) {
             last = i;
             const bool check = (i + 1) % 50 == 0, compute = check || i == max_iter - 1;
-            { RankProf scope(prof, "tsne_forces", s); launch_tsne_forces(w.p.p, w.y.p, n, w.part.p, z, s); }
-            if (compute) { RankProf scope(prof, "tsne_kl", s); launch_tsne_kl_rows(w.p.p, w.y.p, n, out + 2, exaggeration, klrow, s); }
-            {
-                RankProf scope(prof, "tsne_update", s);
-                launch_tsne_update(w.part.p, n, z, exaggeration, momentum, learning_rate, w.y.p, w.upd.p, w.gains.p, w.gs.p, nullptr, s);
-            }
+            { RankProf scope(prof, "tsne_forces", s); forces(z); }
+            if (compute) { RankProf scope(prof, "tsne_kl", s); kl_rows(z, out + 2, exaggeration, klrow); }
+            { RankProf scope(prof, "tsne_update", s); update(z, exaggeration, momentum); }
             if (!compute) continue;
             double host[2];
             { RankProf scope(prof, "tsne_kl", s); launch_tsne_check(klrow, w.gs.p, n, out, s); }
@@ -2021,8 +2023,19 @@ void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float lea
     *kl = error;
     *n_iter = it;
 }
+}  // namespace
 
-void Model::tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_divergence, int32_t* n_iter) {
+void tsne_descent(TsneScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl, int32_t* n_iter,
+                  Profiler* prof, hipStream_t s) {
+    tsne_descent_loop(
+        w, n, opt, exploration, kl, n_iter, prof, s, [&](double* z) { launch_tsne_forces(w.p.p, w.y.p, n, w.part.p, z, s); },
+        [&](double*, double* z64, float e, double* klrow) { launch_tsne_kl_rows(w.p.p, w.y.p, n, z64, e, klrow, s); },
+        [&](double* z, float e, float momentum) {
+            launch_tsne_update(w.part.p, n, z, e, momentum, learning_rate, w.y.p, w.upd.p, w.gains.p, w.gs.p, nullptr, s);
+        });
+}
+
+void Model::tsne_check(const nvsm_tsne_options& opt, int64_t max_rows, const char* too_many, int64_t* n_out) const {
     if (opt.space != NVSM_SPACE_ENTITIES && opt.space != NVSM_SPACE_WORDS)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown space: t-SNE takes the rows of NVSM_SPACE_ENTITIES or NVSM_SPACE_WORDS");
     const RowSpace sp = row_space(opt.space);
@@ -2032,7 +2045,7 @@ void Model::tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_dive
     if (opt.ids)
         for (int64_t i = 0; i < n; ++i)
             if (opt.ids[i] < 0 || opt.ids[i] >= sp.count) throw Error(NVSM_ERR_INVALID_ARGUMENT, "a row id is outside the space");
-    if (n > NVSM_TSNE_MAX_ROWS) throw Error(NVSM_ERR_UNSUPPORTED, "t-SNE supports at most NVSM_TSNE_MAX_ROWS (32768) rows");
+    if (n > max_rows) throw Error(NVSM_ERR_UNSUPPORTED, too_many);
     if (!std::isfinite(opt.perplexity) || !(opt.perplexity > 0.f) || !(opt.perplexity < static_cast<float>(n)))
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "perplexity must be finite, positive and below num_rows");
     if (!std::isfinite(opt.early_exaggeration) || !(opt.early_exaggeration > 0.f))
@@ -2047,6 +2060,13 @@ void Model::tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_dive
     if (opt.init != NVSM_TSNE_INIT_PCA && opt.init != NVSM_TSNE_INIT_GIVEN) throw Error(NVSM_ERR_INVALID_ARGUMENT, "unknown init");
     if (opt.init == NVSM_TSNE_INIT_GIVEN && !opt.init_embedding)
         throw Error(NVSM_ERR_INVALID_ARGUMENT, "NVSM_TSNE_INIT_GIVEN needs init_embedding");
+    *n_out = n;
+}
+
+void Model::tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_divergence, int32_t* n_iter) {
+    int64_t n;
+    tsne_check(opt, NVSM_TSNE_MAX_ROWS, "t-SNE supports at most NVSM_TSNE_MAX_ROWS (32768) rows", &n);
+    const RowSpace sp = row_space(opt.space);
     const int d = sp.dim, rows = static_cast<int>(n);
     rank_join();
     TsneScratch& w = tsne_;
@@ -2072,6 +2092,151 @@ void Model::tsne(const nvsm_tsne_options& opt, float* embedding, double* kl_dive
     const float lr = opt.learning_rate > 0.f ? opt.learning_rate : std::max(static_cast<float>(n) / opt.early_exaggeration / 4.f, 50.f);
     tsne_descent(w, rows, opt, lr, std::min(250, opt.max_iter), kl_divergence, n_iter, &prof, stream_);
     NVSM_HIP_CHECK(hipMemcpyAsync(embedding, w.y.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    raise_device_error();
+}
+
+// ---- sparse-affinity t-SNE (include/cunvsm_amd.h nvsm_tsne_sparse; kernels: tsne_sparse.hip) -----------------------
+// sklearn's method='barnes_hut' at angle 0. Neighbour rounds as the retrieval calls run them (a block of query rows against all
+// rows, slab by slab, then the selection and the sort of rank.hip); the symmetrisation on index.hip's scan behind two passes of
+// the stable pair sort; the descent is tsne_descent's loop over the sparse kernels. Free functions, so the test hooks run them.
+void TsneSparseScratch::grow_rows(int64_t n, int d) {
+    int wr, tw, ranges;
+    tsne_sparse_layout(static_cast<int>(n), forced_ranges, &wr, &tw, &ranges);
+    const size_t n2 = static_cast<size_t>(2 * n);
+    grow(base.x, static_cast<size_t>(n) * d);
+    grow(base.y, n2); grow(base.upd, n2); grow(base.gains, n2); grow(base.gs, n2); grow(attr, n2);
+    grow(part, static_cast<size_t>(n) * ranges * 3);
+    grow(base.rows, n2 + 5);
+    grow(base.pca, static_cast<size_t>(d) * (d + 3));
+    grow(base.ids, static_cast<size_t>(n));
+    grow(indptr, static_cast<size_t>(n) + 1);
+}
+
+void tsne_sparse_knn(const float* X, int n, int d, int k, int64_t round_rows, int64_t score_floats, TsneSparseScratch& w, Profiler* prof,
+                     hipStream_t s) {
+    grow(w.nbr_id, static_cast<size_t>(n) * k);
+    grow(w.nbr_d2, static_cast<size_t>(n) * k);
+    for (int64_t q0 = 0; q0 < n;) {
+        const int64_t left = round_rows > 0 ? std::min<int64_t>(round_rows, n - q0) : n - q0;
+        const RankLayout l = rank_layout(n, k, left, score_floats);
+        const int qn = static_cast<int>(l.qn);
+        grow(w.scores, static_cast<size_t>(l.qn * l.ld));
+        grow(w.sel_ws, rank_select_ws_bytes(qn, static_cast<int>(l.S)));
+        grow(w.keys, static_cast<size_t>(l.qn * l.npad));
+        int64_t key_off = 0;
+        for (int64_t j0 = 0; j0 < n; j0 += l.S) {
+            const int Ss = static_cast<int>(std::min<int64_t>(l.S, n - j0));
+            { RankProf scope(prof, "tsne_nn_scan", s); launch_tsne_nn_scores(X, n, d, static_cast<int>(q0), qn, static_cast<int>(j0), Ss, w.scores.p, l.ld, s); }
+            RankProf scope(prof, "rank_select", s);
+            launch_rank_select(w.scores.p, l.ld, Ss, j0, qn, k, w.sel_ws.p, w.keys.p, l.npad, key_off, s);
+            key_off += std::min<int64_t>(k, Ss);
+        }
+        launch_rank_fill_keys(w.keys.p, l.npad, l.n_keys, l.npad, qn, s);
+        RankProf scope(prof, "rank_sort", s);
+        launch_rank_sort(w.keys.p, l.npad, qn, s);
+        launch_tsne_nn_write(w.keys.p, l.npad, qn, k, static_cast<int>(q0), w.nbr_id.p, w.nbr_d2.p, s);
+        q0 += qn;
+    }
+}
+
+void tsne_sparse_affinities(int n, int k, float perplexity, TsneSparseScratch& w, Profiler* prof, hipStream_t s) {
+    const int64_t nk = static_cast<int64_t>(n) * k, n2 = 2 * nk;
+    double* rowsum = w.base.rows.p;
+    double* total = rowsum + 2 * static_cast<size_t>(n);
+    grow(w.cond, static_cast<size_t>(nk));
+    {
+        RankProf scope(prof, "tsne_conditionals", s);
+        launch_tsne_nn_conditionals(w.nbr_d2.p, n, k, perplexity, w.cond.p, rowsum, s);
+        launch_kmeans_sum(rowsum, n, total, s);
+    }
+    RankProf scope(prof, "tsne_symmetrize", s);
+    // the directed entries by (row, column): the stable sort by column, then by row; a row id has at most 20 bits
+    int bits = 1;
+    while (bits < 31 && (int64_t(1) << bits) < n) ++bits;
+    DevBuf<int> a, b, perm, sums, head;
+    DevBuf<int64_t> tok;
+    a.alloc(static_cast<size_t>(n2)); b.alloc(static_cast<size_t>(n2)); perm.alloc(static_cast<size_t>(n2));
+    {
+        DevBuf<int> perm1;
+        DevBuf<char> temp;
+        perm1.alloc(static_cast<size_t>(n2));
+        const size_t temp_bytes = sort_pairs_temp_bytes(n2, bits);
+        temp.alloc(temp_bytes, true);
+        launch_tsne_sym_keys(w.nbr_id.p, n, k, nullptr, false, a.p, s);
+        sort_pairs(temp.p, temp_bytes, nullptr, a.p, b.p, nullptr, perm1.p, n2, bits, nullptr, s);
+        launch_tsne_sym_keys(w.nbr_id.p, n, k, perm1.p, true, a.p, s);
+        sort_pairs(temp.p, temp_bytes, nullptr, a.p, b.p, perm1.p, perm.p, n2, bits, nullptr, s);      // b: the rows, sorted
+        launch_tsne_sym_keys(w.nbr_id.p, n, k, perm.p, false, a.p, s);                                   // a: their columns
+        NVSM_HIP_CHECK(hipStreamSynchronize(s));      // (the sort's workspace goes before the matrix comes)
+    }
+    // heads = entries whose (row, column) differs from their predecessor's: one per stored cell, both directions of an edge merged
+    const int64_t tiles = index_tiles(n2);
+    sums.alloc(static_cast<size_t>(tiles) + 1);
+    launch_index_scan(b.p, a.p, n2, sums.p, s);
+    int nnz = 0;
+    NVSM_HIP_CHECK(hipMemcpyAsync(&nnz, sums.p + tiles, sizeof(int), hipMemcpyDeviceToHost, s));
+    NVSM_HIP_CHECK(hipStreamSynchronize(s));
+    w.nnz = nnz;
+    head.alloc(static_cast<size_t>(nnz) + 1);
+    tok.alloc(static_cast<size_t>(n) + 1);
+    grow(w.indices, static_cast<size_t>(nnz));
+    grow(w.data, static_cast<size_t>(nnz));
+    grow(w.indptr, static_cast<size_t>(n) + 1);
+    launch_index_write(b.p, a.p, n2, n, sums.p, head.p, w.indices.p, w.indptr.p, tok.p, s);
+    launch_tsne_sym_values(head.p, perm.p, w.cond.p, nnz, n, k, total, w.data.p, s);
+    NVSM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void tsne_sparse_descent(TsneSparseScratch& w, int n, const nvsm_tsne_options& opt, float learning_rate, int exploration, double* kl,
+                         int32_t* n_iter, Profiler* prof, hipStream_t s) {
+    TsneScratch& b = w.base;
+    tsne_descent_loop(
+        b, n, opt, exploration, kl, n_iter, prof, s,
+        [&](double* z) { launch_tsne_sparse_forces(w.indptr.p, w.indices.p, w.data.p, b.y.p, n, w.forced_ranges, w.attr.p, w.part.p, z, s); },
+        [&](double*, double* z64, float e, double* klrow) { launch_tsne_sparse_kl_rows(w.indptr.p, w.indices.p, w.data.p, b.y.p, n, z64, e, klrow, s); },
+        [&](double* z, float e, float momentum) {
+            launch_tsne_sparse_update(w.attr.p, w.part.p, n, w.forced_ranges, z, e, momentum, learning_rate, b.y.p, b.upd.p, b.gains.p, b.gs.p,
+                                      nullptr, s);
+        });
+}
+
+void Model::tsne_sparse(const nvsm_tsne_options& opt, const nvsm_tsne_sparse_options& sparse, float* embedding, double* kl_divergence,
+                        int32_t* n_iter) {
+    int64_t n;
+    tsne_check(opt, NVSM_TSNE_SPARSE_MAX_ROWS, "sparse t-SNE supports at most NVSM_TSNE_SPARSE_MAX_ROWS (1048576) rows", &n);
+    int64_t k = sparse.n_neighbors;
+    if (k == 0) {      // TSNE._fit: n_neighbors = min(n_samples - 1, int(3.0 * self.perplexity + 1))
+        k = std::min<int64_t>(n - 1, static_cast<int64_t>(3.0 * static_cast<double>(opt.perplexity) + 1.0));
+        if (k > NVSM_TSNE_SPARSE_MAX_NEIGHBORS)
+            throw Error(NVSM_ERR_UNSUPPORTED, "the perplexity asks for more than NVSM_TSNE_SPARSE_MAX_NEIGHBORS (1024) neighbours");
+    } else if (k < 1 || k > std::min<int64_t>(n - 1, NVSM_TSNE_SPARSE_MAX_NEIGHBORS)) {
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "n_neighbors must be in [1, min(num_rows - 1, NVSM_TSNE_SPARSE_MAX_NEIGHBORS)]");
+    }
+    if (2 * n * k >= (int64_t(1) << 31)) throw Error(NVSM_ERR_UNSUPPORTED, "sparse t-SNE supports fewer than 2^31 directed entries (2 * num_rows * n_neighbors)");
+    const RowSpace sp = row_space(opt.space);
+    const int d = sp.dim, rows = static_cast<int>(n), kk = static_cast<int>(k);
+    rank_join();
+    TsneSparseScratch& w = tsne_sparse_;
+    w.grow_rows(n, d);
+    TsneScratch& b = w.base;
+    if (opt.ids) NVSM_HIP_CHECK(hipMemcpy(b.ids.p, opt.ids, static_cast<size_t>(n) * sizeof(int64_t), hipMemcpyHostToDevice));
+    {
+        RankProf scope(prof, "tsne_rows", stream_);
+        launch_rank_gather_rows(sp.rows, d, opt.ids ? b.ids.p : nullptr, 0, n, b.x.p, lazy_view(*sp.table), stream_);
+        if (opt.l2_normalize) launch_tsne_normalize(b.x.p, rows, d, stream_);
+    }
+    tsne_sparse_knn(b.x.p, rows, d, kk, 0, score_floats(), w, &prof, stream_);
+    tsne_sparse_affinities(rows, kk, opt.perplexity, w, &prof, stream_);
+    if (opt.init == NVSM_TSNE_INIT_GIVEN) {
+        NVSM_HIP_CHECK(hipMemcpyAsync(b.y.p, opt.init_embedding, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyHostToDevice, stream_));
+    } else {
+        RankProf scope(prof, "tsne_pca", stream_);
+        tsne_pca_start(b.x.p, rows, d, b, b.y.p, stream_);
+    }
+    const float lr = opt.learning_rate > 0.f ? opt.learning_rate : std::max(static_cast<float>(n) / opt.early_exaggeration / 4.f, 50.f);
+    tsne_sparse_descent(w, rows, opt, lr, std::min(250, opt.max_iter), kl_divergence, n_iter, &prof, stream_);
+    NVSM_HIP_CHECK(hipMemcpyAsync(embedding, b.y.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost, stream_));
     NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
     raise_device_error();
 }

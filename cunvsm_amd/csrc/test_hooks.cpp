@@ -853,6 +853,126 @@ int nvsm_debug_tsne_descent(const float* P, float* Y, int64_t n, const nvsm_tsne
     });
 }
 
+// ---- nvsm_tsne_sparse's stages on caller-supplied inputs (cunvsm_amd_test_hooks.h): the product's launchers (kernels.h
+// launch_tsne_nn_* / launch_tsne_sparse_*) and host functions (model.h tsne_sparse_*) on a scratch of the hook's own
+namespace {
+constexpr int64_t kTsneHookScoreFloats = int64_t(256) << 18;      // the default score slab of a retrieval round: 256 MB
+void tsne_sparse_hook_sizes(int64_t n, int64_t d, int64_t k) {
+    if (n < 2 || n > NVSM_TSNE_SPARSE_MAX_ROWS || d < 1 || d > 4096 || k < 1 || k > n - 1 || k > NVSM_TSNE_SPARSE_MAX_NEIGHBORS ||
+        2 * n * k >= (int64_t(1) << 31))
+        throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: bad sizes");
+}
+// the caller's CSR matrix (indptr [n + 1], indices / data [nnz]) into the scratch, checked: the kernels trust what they index with
+void tsne_sparse_hook_csr(cunvsm::TsneSparseScratch& w, const int64_t* indptr, const int32_t* indices, const float* data, int64_t n) {
+    if (indptr[0] != 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: indptr[0] must be 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (indptr[i + 1] < indptr[i]) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: indptr decreases");
+    const int64_t nnz = indptr[n];
+    if (nnz >= (int64_t(1) << 31)) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: too many entries");
+    for (int64_t p = 0; p < nnz; ++p)
+        if (indices[p] < 0 || indices[p] >= n) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: a column is outside the matrix");
+    w.nnz = nnz;
+    w.indices.alloc(static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+    w.data.alloc(static_cast<size_t>(std::max<int64_t>(nnz, 1)));
+    NVSM_HIP_CHECK(hipMemcpy(w.indptr.p, indptr, static_cast<size_t>(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (nnz > 0) {
+        NVSM_HIP_CHECK(hipMemcpy(w.indices.p, indices, static_cast<size_t>(nnz) * sizeof(int32_t), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemcpy(w.data.p, data, static_cast<size_t>(nnz) * sizeof(float), hipMemcpyHostToDevice));
+    }
+}
+}  // namespace
+
+int nvsm_debug_tsne_knn(const float* X, int64_t n, int d, int k, int64_t round_rows, int32_t* ids_out, float* d2_out) {
+    NVSM_REQUIRE(X); NVSM_REQUIRE(ids_out); NVSM_REQUIRE(d2_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_sparse_hook_sizes(n, d, k);
+        if (round_rows < 0) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: round_rows is negative");
+        TsneSparseScratch w;
+        w.grow_rows(n, d);
+        NVSM_HIP_CHECK(hipMemcpy(w.base.x.p, X, static_cast<size_t>(n) * d * sizeof(float), hipMemcpyHostToDevice));
+        tsne_sparse_knn(w.base.x.p, static_cast<int>(n), d, k, round_rows, kTsneHookScoreFloats, w, nullptr, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(ids_out, w.nbr_id.p, static_cast<size_t>(n) * k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(d2_out, w.nbr_d2.p, static_cast<size_t>(n) * k * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int nvsm_debug_tsne_sparse_affinities(const float* X, int64_t n, int d, float perplexity, int k, int64_t* indptr_out, int32_t* indices_out,
+                                      float* data_out, float* cond_out) {
+    NVSM_REQUIRE(X); NVSM_REQUIRE(indptr_out); NVSM_REQUIRE(indices_out); NVSM_REQUIRE(data_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_sparse_hook_sizes(n, d, k);
+        if (!(perplexity > 0.f) || !(perplexity < static_cast<float>(n))) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: bad perplexity");
+        TsneSparseScratch w;
+        w.grow_rows(n, d);
+        NVSM_HIP_CHECK(hipMemcpy(w.base.x.p, X, static_cast<size_t>(n) * d * sizeof(float), hipMemcpyHostToDevice));
+        tsne_sparse_knn(w.base.x.p, static_cast<int>(n), d, k, 0, kTsneHookScoreFloats, w, nullptr, nullptr);
+        tsne_sparse_affinities(static_cast<int>(n), k, perplexity, w, nullptr, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(indptr_out, w.indptr.p, static_cast<size_t>(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(indices_out, w.indices.p, static_cast<size_t>(w.nnz) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(data_out, w.data.p, static_cast<size_t>(w.nnz) * sizeof(float), hipMemcpyDeviceToHost));
+        if (cond_out) NVSM_HIP_CHECK(hipMemcpy(cond_out, w.cond.p, static_cast<size_t>(n) * k * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int nvsm_debug_tsne_sparse_gradient(const int64_t* indptr, const int32_t* indices, const float* data, const float* Y, int64_t n,
+                                    float exaggeration, int ranges, float* grad_out, double* kl_out) {
+    NVSM_REQUIRE(indptr); NVSM_REQUIRE(indices); NVSM_REQUIRE(data); NVSM_REQUIRE(Y); NVSM_REQUIRE(grad_out); NVSM_REQUIRE(kl_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_sparse_hook_sizes(n, 1, 1);
+        if (ranges < 0 || ranges > 4096) throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: bad ranges");
+        TsneSparseScratch w;
+        w.forced_ranges = ranges;
+        w.grow_rows(n, 1);
+        tsne_sparse_hook_csr(w, indptr, indices, data, n);
+        TsneScratch& b = w.base;
+        DevBuf<float> graw;
+        graw.alloc(static_cast<size_t>(2 * n));
+        const int rows = static_cast<int>(n);
+        double* klrow = b.rows.p + n;
+        double* z = b.rows.p + 2 * n + 1;
+        NVSM_HIP_CHECK(hipMemcpy(b.y.p, Y, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyHostToDevice));
+        NVSM_HIP_CHECK(hipMemset(b.upd.p, 0, static_cast<size_t>(2 * n) * sizeof(float)));
+        NVSM_HIP_CHECK(hipMemset(b.gains.p, 0, static_cast<size_t>(2 * n) * sizeof(float)));
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        launch_tsne_sparse_forces(w.indptr.p, w.indices.p, w.data.p, b.y.p, rows, ranges, w.attr.p, w.part.p, z, nullptr);
+        launch_tsne_sparse_kl_rows(w.indptr.p, w.indices.p, w.data.p, b.y.p, rows, z + 3, exaggeration, klrow, nullptr);
+        // a step of learning rate 0 on zero gains and updates: Y stays, graw is the gradient
+        launch_tsne_sparse_update(w.attr.p, w.part.p, rows, ranges, z, exaggeration, 0.f, 0.f, b.y.p, b.upd.p, b.gains.p, b.gs.p, graw.p, nullptr);
+        launch_tsne_check(klrow, b.gs.p, rows, z + 1, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipDeviceSynchronize());
+        NVSM_HIP_CHECK(hipMemcpy(grad_out, graw.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost));
+        NVSM_HIP_CHECK(hipMemcpy(kl_out, z + 1, sizeof(double), hipMemcpyDeviceToHost));
+    });
+}
+
+int nvsm_debug_tsne_sparse_descent(const int64_t* indptr, const int32_t* indices, const float* data, float* Y, int64_t n,
+                                   const nvsm_tsne_options* opt, int exploration, double* kl_out, int32_t* n_iter_out) {
+    NVSM_REQUIRE(indptr); NVSM_REQUIRE(indices); NVSM_REQUIRE(data); NVSM_REQUIRE(Y); NVSM_REQUIRE(opt); NVSM_REQUIRE(kl_out);
+    NVSM_REQUIRE(n_iter_out);
+    return guarded_hook([&] {
+        using namespace cunvsm;
+        tsne_sparse_hook_sizes(n, 1, 1);
+        if (opt->max_iter < 1 || opt->max_iter > 100000 || exploration < 1 || exploration > opt->max_iter || !(opt->learning_rate > 0.f) ||
+            !(opt->early_exaggeration > 0.f) || opt->n_iter_without_progress < 0)
+            throw Error(NVSM_ERR_INVALID_ARGUMENT, "tsne sparse hook: bad options");
+        TsneSparseScratch w;
+        w.grow_rows(n, 1);
+        tsne_sparse_hook_csr(w, indptr, indices, data, n);
+        NVSM_HIP_CHECK(hipMemcpy(w.base.y.p, Y, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyHostToDevice));
+        tsne_sparse_descent(w, static_cast<int>(n), *opt, opt->learning_rate, exploration, kl_out, n_iter_out, nullptr, nullptr);
+        NVSM_HIP_CHECK(hipGetLastError());
+        NVSM_HIP_CHECK(hipMemcpy(Y, w.base.y.p, static_cast<size_t>(2 * n) * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
 // ---- nvsm_kmeans' passes on caller-supplied inputs (cunvsm_amd_test_hooks.h): the product's launchers and host functions
 // (kernels.h launch_kmeans_*, model.h kmeans_*) on a scratch of the hook's own
 namespace {

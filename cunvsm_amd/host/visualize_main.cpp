@@ -1,9 +1,11 @@
 // cuNVSMVisualize — the reference's py/visualize.py (the body of visualize-reuters-collection.sh) on top of libcunvsm_amd.so's
 // C ABI: the document rows of a checkpoint, restricted to the classified documents, as a two-dimensional t-SNE picture
-// (nvsm_tsne: sklearn's exact method on the device) or as TSV files for the embedding projector.
+// (nvsm_tsne: sklearn's exact method on the device; --tsne_method sparse: nvsm_tsne_sparse, sklearn's barnes_hut method at angle 0,
+// for more than NVSM_TSNE_MAX_ROWS documents) or as TSV files for the embedding projector.
 //
 //   cuNVSMVisualize --object_classification f1 [f2 ...] --filter_unclassified [--limit N] [--l2_normalize]
-//                   [--mode tsne|embedding_projector] --plot_out PATH  <model>_<epoch>.hdf5  <index>
+//                   [--mode tsne|embedding_projector] [--tsne_method exact|sparse] [--tsne_neighbors N]
+//                   --plot_out PATH  <model>_<epoch>.hdf5  <index>
 //
 // Each classification file has lines "<docno> <class>". The rows are the ascending model indices of the classified documents
 // the model knows. Differences from py/visualize.py:
@@ -31,9 +33,9 @@ using namespace nvsm_host;
 
 namespace {
 
-std::string FLAGS_object_classification, FLAGS_mode, FLAGS_plot_out, FLAGS_stopwords;
+std::string FLAGS_object_classification, FLAGS_mode, FLAGS_plot_out, FLAGS_stopwords, FLAGS_tsne_method;
 bool FLAGS_filter_unclassified, FLAGS_l2_normalize, FLAGS_help, FLAGS_logtostderr;
-int64_t FLAGS_limit, FLAGS_device, FLAGS_v, FLAGS_max_iter;
+int64_t FLAGS_limit, FLAGS_device, FLAGS_v, FLAGS_max_iter, FLAGS_tsne_neighbors;
 double FLAGS_perplexity;
 
 void define_flags(Flags* f) {
@@ -48,6 +50,9 @@ void define_flags(Flags* f) {
     f->define_string("stopwords", &FLAGS_stopwords, "", "Stop list applied while indexing a TREC-text collection: the training run's.");
     f->define_double("perplexity", &FLAGS_perplexity, 30.0, "t-SNE perplexity (sklearn's default); must be below the number of rows.");
     f->define_int64("max_iter", &FLAGS_max_iter, 1000, "t-SNE iterations (sklearn's default).");
+    f->define_string("tsne_method", &FLAGS_tsne_method, "exact", "exact | sparse: sparse keeps --tsne_neighbors affinities per document "
+                     "(sklearn's barnes_hut method at angle 0) and serves more than 32768 documents.");
+    f->define_int64("tsne_neighbors", &FLAGS_tsne_neighbors, 0, "Neighbours per document with --tsne_method sparse (0: sklearn's 3 * perplexity + 1).");
     f->define_int64("device", &FLAGS_device, 0, "HIP device ordinal.");
     f->define_bool("help", &FLAGS_help, false, "Print the options and exit.");
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
@@ -81,6 +86,11 @@ int run(int argc, char** argv) {
                                              "handle either: pass --filter_unclassified.";
     NVSM_CHECK(FLAGS_limit >= 0) << "--limit must not be negative.";
     NVSM_CHECK(FLAGS_max_iter >= 1 && FLAGS_max_iter <= 2147483647) << "--max_iter must be at least 1.";
+    const bool sparse = FLAGS_tsne_method == "sparse";
+    if (!sparse && FLAGS_tsne_method != "exact") NVSM_LOG(FATAL) << "--tsne_method: '" << FLAGS_tsne_method << "' is neither exact nor sparse.";
+    NVSM_CHECK(FLAGS_tsne_neighbors >= 0 && FLAGS_tsne_neighbors <= NVSM_TSNE_SPARSE_MAX_NEIGHBORS)
+        << "--tsne_neighbors must be in [0, " << NVSM_TSNE_SPARSE_MAX_NEIGHBORS << "].";
+    NVSM_CHECK(sparse || FLAGS_tsne_neighbors == 0) << "--tsne_neighbors belongs to --tsne_method sparse.";
     std::vector<std::string> class_paths = {FLAGS_object_classification};
     for (size_t i = 1; i + 2 < args.size(); ++i) class_paths.push_back(args[i]);
     const std::string model_path = args[args.size() - 2], index_path = args[args.size() - 1];
@@ -156,7 +166,14 @@ int run(int argc, char** argv) {
         std::vector<float> Y(2 * ids.size());
         double kl = 0.0;
         int32_t n_iter = 0;
-        NVSM_CALL(nvsm_tsne(model, &opt, Y.data(), &kl, &n_iter));
+        if (sparse) {
+            nvsm_tsne_sparse_options sp;
+            nvsm_tsne_sparse_options_default(&sp);
+            sp.n_neighbors = static_cast<int32_t>(FLAGS_tsne_neighbors);
+            NVSM_CALL(nvsm_tsne_sparse(model, &opt, &sp, Y.data(), &kl, &n_iter));
+        } else {
+            NVSM_CALL(nvsm_tsne(model, &opt, Y.data(), &kl, &n_iter));
+        }
         NVSM_LOG(INFO) << "t-SNE of " << ids.size() << " documents: KL divergence " << kl << " after " << (n_iter + 1) << " iterations.";
         const std::string out_path = tsne_out_path(FLAGS_plot_out, class_path);
         std::ofstream out(out_path);

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmNgramOptions, NvsmTsneOptions, NvsmKmeansOptions, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
+from ._lib import NvsmBatch, NvsmConfig, NvsmCorpus, NvsmWindowBatch, NvsmMixture, NvsmPairBatch, NvsmNeighborOptions, NvsmNeighborQueries, NvsmNgramOptions, NvsmTsneOptions, NvsmTsneSparseOptions, NvsmKmeansOptions, NvsmJudgments, NvsmQueries, NvsmRankOptions, check, lib
 
 # --update_method of the reference CLI (cpp/main.cu:479-485)
 UPDATE_METHODS = {
@@ -764,10 +764,19 @@ def ngram_arguments(cfg, entity_ids=None, word_ids=None, vectors=None, vocabular
 
 # -- exact t-SNE of document or word rows (py/visualize.py's sklearn.manifold.TSNE; nvsm_tsne) ----------------------------------
 def tsne_arguments(cfg, space="entities", ids=None, limit=None, l2_normalize=False, perplexity=30.0, early_exaggeration=12.0,
-                   learning_rate="auto", max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=0):
+                   learning_rate="auto", max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=0,
+                   method="exact", n_neighbors=None):
     """(nvsm_tsne_options, number of rows, arrays to keep alive) from keywords; raises ValueError for what the ABI would refuse, in
     its order (no device needed). ids: row ids in any order (visualize.py --filter_unclassified); limit: the first rows (--limit);
-    neither: every row. init: "pca", "random" (sklearn's 1e-4 · RandomState(random_state).standard_normal((n, 2))) or an [n][2] array."""
+    neither: every row. init: "pca", "random" (sklearn's 1e-4 · RandomState(random_state).standard_normal((n, 2))) or an [n][2] array.
+    method: "exact" (nvsm_tsne) or "sparse" (nvsm_tsne_sparse: sklearn's barnes_hut at angle 0, up to TSNE_SPARSE_MAX_ROWS rows, with
+    n_neighbors per row — None: sklearn's min(n − 1, int(3·perplexity + 1))); with "sparse" the kept arrays end with the
+    nvsm_tsne_sparse_options."""
+    if method not in ("exact", "sparse"):
+        raise ValueError("unknown method %r (\"exact\" or \"sparse\")" % (method,))
+    if method == "exact" and n_neighbors is not None:
+        raise ValueError("n_neighbors belongs to method=\"sparse\"")
+    max_rows = _lib.TSNE_MAX_ROWS if method == "exact" else _lib.TSNE_SPARSE_MAX_ROWS
     space, rows, _ = space_shape(cfg, space)
     if space == _lib.SPACE_PROJECTED_WORDS:
         raise ValueError("unknown space for t-SNE: \"entities\" or \"words\" (projected words are not served)")
@@ -787,8 +796,8 @@ def tsne_arguments(cfg, space="entities", ids=None, limit=None, l2_normalize=Fal
         raise ValueError("limit = %d exceeds the rows of the space = %d" % (n, rows))
     if id_array is not None and (id_array.min() < 0 or id_array.max() >= rows):
         raise ValueError("a row id is outside [0, %d)" % rows)
-    if n > _lib.TSNE_MAX_ROWS:
-        raise ValueError("num_rows = %d above the limit of %d rows" % (n, _lib.TSNE_MAX_ROWS))
+    if n > max_rows:
+        raise ValueError("num_rows = %d above the limit of %d rows" % (n, max_rows))
     perplexity = float(np.float32(perplexity))
     if not (np.isfinite(perplexity) and 0.0 < perplexity < n):
         raise ValueError("perplexity = %r must be finite, positive and below num_rows = %d" % (perplexity, n))
@@ -826,7 +835,21 @@ def tsne_arguments(cfg, space="entities", ids=None, limit=None, l2_normalize=Fal
     opt.max_iter, opt.n_iter_without_progress = int(max_iter), int(n_iter_without_progress)
     opt.init = _lib.TSNE_INIT_PCA if given is None else _lib.TSNE_INIT_GIVEN
     opt.init_embedding = None if given is None else given.ctypes.data
-    return opt, n, (id_array, given)
+    if method == "exact":
+        return opt, n, (id_array, given)
+    sparse = NvsmTsneSparseOptions()
+    if n_neighbors is None:
+        if min(n - 1, int(3.0 * perplexity + 1.0)) > _lib.TSNE_SPARSE_MAX_NEIGHBORS:
+            raise ValueError("perplexity = %r asks for more than the limit of %d neighbours" % (perplexity, _lib.TSNE_SPARSE_MAX_NEIGHBORS))
+        k = min(n - 1, int(3.0 * perplexity + 1.0))
+    else:
+        k = int(n_neighbors)
+        if not 1 <= k <= min(n - 1, _lib.TSNE_SPARSE_MAX_NEIGHBORS):
+            raise ValueError("n_neighbors = %d outside [1, min(num_rows - 1, %d)]" % (k, _lib.TSNE_SPARSE_MAX_NEIGHBORS))
+        sparse.n_neighbors = k
+    if 2 * n * k >= 2 ** 31:
+        raise ValueError("2 * num_rows * n_neighbors = %d: sparse t-SNE numbers fewer than 2^31 directed entries" % (2 * n * k))
+    return opt, n, (id_array, given, sparse)
 
 
 def fold_summation():
@@ -1611,15 +1634,21 @@ class Model:
         return rows, terms, scores, counts
 
     def tsne(self, space="entities", ids=None, limit=None, l2_normalize=False, perplexity=30.0, early_exaggeration=12.0,
-             learning_rate="auto", max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=0):
+             learning_rate="auto", max_iter=1000, n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=0,
+             method="exact", n_neighbors=None):
         """py/visualize.py's sklearn.manifold.TSNE(n_components=2, init='pca', random_state=0) with the exact gradient, on the device
         (nvsm_tsne): the rows `ids` of `space` ("entities" | "words"), its first `limit` rows, or all of them. Returns
-        (embedding [n, 2] float32, kl_divergence, n_iter) as sklearn's embedding_, kl_divergence_ and n_iter_."""
+        (embedding [n, 2] float32, kl_divergence, n_iter) as sklearn's embedding_, kl_divergence_ and n_iter_.
+        method="sparse" (nvsm_tsne_sparse): sklearn's default barnes_hut method at angle 0 — n_neighbors affinities per row (None:
+        sklearn's 3·perplexity + 1) and the exact repulsion, no n × n memory: up to TSNE_SPARSE_MAX_ROWS rows."""
         opt, n, keep = tsne_arguments(self.cfg, space, ids, limit, l2_normalize, perplexity, early_exaggeration, learning_rate, max_iter,
-                                      n_iter_without_progress, min_grad_norm, init, random_state)
+                                      n_iter_without_progress, min_grad_norm, init, random_state, method, n_neighbors)
         embedding = np.empty((n, 2), dtype=np.float32)
         kl, it = C.c_double(0.0), C.c_int32(0)
-        check(lib().nvsm_tsne(self._h, C.byref(opt), embedding.ctypes.data, C.byref(kl), C.byref(it)))
+        if method == "sparse":
+            check(lib().nvsm_tsne_sparse(self._h, C.byref(opt), C.byref(keep[2]), embedding.ctypes.data, C.byref(kl), C.byref(it)))
+        else:
+            check(lib().nvsm_tsne(self._h, C.byref(opt), embedding.ctypes.data, C.byref(kl), C.byref(it)))
         del keep
         return embedding, kl.value, it.value
 

@@ -1024,6 +1024,39 @@ void nvsm_tsne_options_default(nvsm_tsne_options* opt);
 int nvsm_tsne(nvsm_model* m, const nvsm_tsne_options* opt, float* embedding, double* kl_divergence, int32_t* n_iter);
 
 /*
+ * Sparse-affinity t-SNE of document or word rows, for collections beyond NVSM_TSNE_MAX_ROWS: sklearn.manifold.TSNE with its
+ * default method='barnes_hut' at angle = 0, where the tree summarises nothing and the repulsion is the exact sum over all
+ * pairs. No n × n values are held: the affinities take O(n · n_neighbors) memory and the repulsion reads the embedding alone.
+ * Rows, normalisation, start, descent, results and synchrony are nvsm_tsne's (same options struct). What differs, pinned by
+ * scikit-learn 1.7 (sklearn/manifold/_t_sne.py):
+ *   neighbours   k = n_neighbors, or with 0 sklearn's min(n − 1, int(3 · perplexity + 1)) (TSNE._fit). Per row the k OTHER rows of
+ *                smallest squared Euclidean distance (nvsm_tsne's distance: an fp64 sum rounded to fp32), ties by ascending row
+ *                id. A row is never its own neighbour; a duplicate of it is one, at distance 0.
+ *   affinities   _binary_search_perplexity over each row's k distances in fp64, stored as fp32; _joint_probabilities_nn:
+ *                P = (C + Cᵀ) / max(ΣC + ΣCᵀ, eps) as a CSR matrix over the union of both directions of every edge, with no
+ *                clamp per cell (the sparse path has none), no diagonal, columns ascending, P_ij and P_ji the same bits.
+ *   gradient     _kl_divergence_bh at angle 0: g_i = 4·(e·Σ_{j stored} P_ij q_ij (y_i − y_j) − Σ_{j != i} q_ij² (y_i − y_j) / Z),
+ *                q = 1 / (1 + |y_i − y_j|²), Z = Σ_{i != j} q_ij over all pairs.
+ *   error        Σ_{stored} e·P_ij · log(max(e·P_ij, tiny) / max(q_ij / Z, tiny)), tiny = FLT_MIN (_barnes_hut_tsne.pyx), in fp64
+ *                throughout and with an fp64 Z of its own, as nvsm_tsne's: a check costs one more pass over all pairs.
+ * Refused as nvsm_tsne refuses and in its order, with these changes: the row limit is NVSM_TSNE_SPARSE_MAX_ROWS
+ * (NVSM_ERR_UNSUPPORTED); behind all of nvsm_tsne's checks, n_neighbors outside [1, min(num_rows − 1, NVSM_TSNE_SPARSE_MAX_NEIGHBORS)]
+ * is NVSM_ERR_INVALID_ARGUMENT, a default k above NVSM_TSNE_SPARSE_MAX_NEIGHBORS is NVSM_ERR_UNSUPPORTED, and so is
+ * 2 · num_rows · k >= 2^31 (the directed entries are numbered in 32 bits).
+ * A repeated call returns the same bits. Device scratch is allocated by the first call and grown by a later, larger one.
+ */
+#define NVSM_TSNE_SPARSE_MAX_ROWS 1048576     /* row ids fit 20 bits: two passes of the 32-bit pair sort order (row, column) */
+#define NVSM_TSNE_SPARSE_MAX_NEIGHBORS 1024   /* perplexity up to 341 */
+typedef struct {
+    int32_t n_neighbors;                     /* 0: sklearn's min(n - 1, int(3 * perplexity + 1)) */
+    int32_t reserved[7];
+} nvsm_tsne_sparse_options;
+void nvsm_tsne_sparse_options_default(nvsm_tsne_sparse_options* opt);      /* n_neighbors 0 */
+/* sparse: NULL = the defaults; embedding, kl_divergence and n_iter as nvsm_tsne's */
+int nvsm_tsne_sparse(nvsm_model* m, const nvsm_tsne_options* opt, const nvsm_tsne_sparse_options* sparse, float* embedding,
+                     double* kl_divergence, int32_t* n_iter);
+
+/*
  * k-means (Lloyd's algorithm) of document or word rows on the device — what a caller would otherwise ask
  * sklearn.cluster.KMeans(n_clusters=k, n_init=1, algorithm='lloyd') for after pulling the table to the host. Semantics, pinned by
  * scikit-learn 1.7 where it specifies them:

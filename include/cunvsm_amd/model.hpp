@@ -542,6 +542,25 @@ class Model {
         opt.ids = row_ids.data(); opt.num_rows = static_cast<int64_t>(row_ids.size());
         return tsne(opt);
     }
+    // sparse-affinity t-SNE (nvsm_tsne_sparse: sklearn's barnes_hut at angle 0) for collections beyond NVSM_TSNE_MAX_ROWS; n_neighbors 0:
+    // sklearn's min(n − 1, int(3·perplexity + 1))
+    Tsne tsne_sparse(const nvsm_tsne_options& opt, int32_t n_neighbors = 0) {
+        int64_t n = opt.num_rows;
+        if (!opt.ids && n == 0) n = opt.space == NVSM_SPACE_WORDS ? cfg_.num_words : cfg_.num_entities;
+        nvsm_tsne_sparse_options sp;
+        nvsm_tsne_sparse_options_default(&sp);
+        sp.n_neighbors = n_neighbors;
+        Tsne r;
+        r.embedding.resize(static_cast<size_t>(n > 0 ? 2 * n : 0) + 1);
+        r.kl_divergence = 0.0; r.n_iter = 0;
+        check(nvsm_tsne_sparse(h_, &opt, &sp, r.embedding.data(), &r.kl_divergence, &r.n_iter));
+        r.embedding.resize(static_cast<size_t>(2 * n));
+        return r;
+    }
+    Tsne tsne_sparse(const std::vector<int64_t>& row_ids, nvsm_tsne_options opt, int32_t n_neighbors = 0) {
+        opt.ids = row_ids.data(); opt.num_rows = static_cast<int64_t>(row_ids.size());
+        return tsne_sparse(opt, n_neighbors);
+    }
 
     // Lloyd's k-means of document or word rows (nvsm_kmeans): opt.ids / opt.num_rows choose the rows (nvsm_kmeans_options_default: every
     // document), opt.num_clusters the centres; labels [rows], centers [k][dim], counts [k], distances [rows] (squared, to the own centre)

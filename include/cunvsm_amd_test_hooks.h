@@ -170,6 +170,27 @@ int nvsm_debug_tsne_gradient(const float* P, const float* Y, int64_t n, float ex
 int nvsm_debug_tsne_pca(const float* X, int64_t n, int d, float* Y0_out);
 int nvsm_debug_tsne_descent(const float* P, float* Y, int64_t n, const nvsm_tsne_options* opt, int exploration, double* kl_out,
                             int32_t* n_iter_out);
+/* nvsm_tsne_sparse's stages on caller-supplied host inputs, through the product's own launchers (csrc/tsne_sparse.hip) and host
+ * functions (csrc/ranking.cpp tsne_sparse_knn / tsne_sparse_affinities / tsne_sparse_descent). Sizes: 2 <= n <=
+ * NVSM_TSNE_SPARSE_MAX_ROWS, 1 <= d <= 4096, 1 <= k <= min(n − 1, NVSM_TSNE_SPARSE_MAX_NEIGHBORS), 2·n·k < 2^31, else
+ * NVSM_ERR_INVALID_ARGUMENT.
+ * knn: ids_out / d2_out [n][k] = every row's k nearest other rows of X [n][d] and their squared distances, nearest first, ties by
+ *   ascending id. round_rows > 0 forces that many query rows per round (0: the product's layout), so that a small n crosses
+ *   several rounds.
+ * sparse_affinities: knn, then the perplexity search and the symmetrisation: the CSR matrix P as indptr_out [n + 1], indices_out /
+ *   data_out [indptr_out[n]] — give both room for 2·n·k entries — and cond_out [n][k] (may be NULL), the conditional probabilities
+ *   beside the neighbour lists.
+ * sparse_gradient: for a CSR matrix P (columns inside [0, n) or the hook refuses) and Y [n][2], grad_out [n][2] = 4·(e·attractive −
+ *   repulsive / Z) and *kl_out = the error as the convergence check evaluates it; Y is left as it is. ranges > 0 forces the number
+ *   of column ranges of the repulsion (0: the product's layout; at most 4096).
+ * sparse_descent: nvsm_debug_tsne_descent on a CSR matrix. */
+int nvsm_debug_tsne_knn(const float* X, int64_t n, int d, int k, int64_t round_rows, int32_t* ids_out, float* d2_out);
+int nvsm_debug_tsne_sparse_affinities(const float* X, int64_t n, int d, float perplexity, int k, int64_t* indptr_out, int32_t* indices_out,
+                                      float* data_out, float* cond_out);
+int nvsm_debug_tsne_sparse_gradient(const int64_t* indptr, const int32_t* indices, const float* data, const float* Y, int64_t n,
+                                    float exaggeration, int ranges, float* grad_out, double* kl_out);
+int nvsm_debug_tsne_sparse_descent(const int64_t* indptr, const int32_t* indices, const float* data, float* Y, int64_t n,
+                                   const nvsm_tsne_options* opt, int exploration, double* kl_out, int32_t* n_iter_out);
 /* nvsm_kmeans' passes on caller-supplied host inputs, through the product's own launchers (csrc/kmeans.hip) and host functions
  * (csrc/ranking.cpp kmeans_prepare / kmeans_assign_pass / kmeans_update_pass / kmeans_plusplus). Sizes: 1 <= n < 2^31, 1 <= d <= 4096,
  * 1 <= k <= min(n, NVSM_KMEANS_MAX_CLUSTERS), else NVSM_ERR_INVALID_ARGUMENT.
