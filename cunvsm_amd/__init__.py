@@ -15,11 +15,11 @@ from ._lib import (  # noqa: F401
     NvsmSweepOptions, NvsmCvOptions, SWEEP_MAX_ALPHAS, NvsmNgramOptions, NvsmTsneOptions, NvsmTsneSparseOptions, TSNE_MAX_ROWS, TSNE_SPARSE_MAX_ROWS, TSNE_SPARSE_MAX_NEIGHBORS, TSNE_INIT_PCA, TSNE_INIT_GIVEN,
     NvsmSdmOptions, SDM_MAX_WINDOW,
     NvsmKmeansOptions, KMEANS_MAX_CLUSTERS, KMEANS_INIT_PLUSPLUS, KMEANS_INIT_GIVEN,
-    NvsmIndexOptions, NvsmIndexInfo, INDEX_AUTO, INDEX_ALWAYS, INDEX_NEVER,
+    NvsmIndexOptions, NvsmIndexInfo, NvsmPositionsInfo, INDEX_AUTO, INDEX_ALWAYS, INDEX_NEVER,
     NvsmTfidfOptions, NvsmRerankOptions, NvsmFoldOptions, IDF_ROBERTSON, IDF_OKAPI, STAGE_TFIDF, STAGE_LEXICAL, RERANK_MAX_DEPTH,
 )
 from . import dp  # noqa: F401
 from .model import Batch, Corpus, WindowBatch, expand_windows, Judgments, Model, PairBatch, Queries, UPDATE_METHODS, default_config, self_information_weights, alpha_grid, ngram_rows, ngram_encode, ngram_decode, ngram_arguments, tsne_arguments, kmeans_arguments, cluster_agreement, grow_documents, fold_summation  # noqa: F401
 
-__all__ = ["Model", "Batch", "Corpus", "WindowBatch", "expand_windows", "NvsmCorpus", "NvsmWindowBatch", "PairBatch", "NvsmPairBatch", "NvsmMixture", "Queries", "Judgments", "self_information_weights", "NvsmQueries", "NvsmRankOptions", "NvsmJudgments", "NvsmNeighborQueries", "NvsmNeighborOptions", "NvsmLexicalOptions", "NvsmEnsembleOptions", "NvsmFeedbackOptions", "NvsmSdmOptions", "NvsmSweepOptions", "NvsmCvOptions", "NvsmNgramOptions", "NvsmTsneOptions", "NvsmTfidfOptions", "NvsmRerankOptions", "NvsmFoldOptions", "NvsmIndexOptions", "NvsmIndexInfo", "grow_documents", "fold_summation", "tsne_arguments", "NvsmKmeansOptions", "kmeans_arguments", "cluster_agreement", "alpha_grid", "ngram_rows", "ngram_encode", "ngram_decode", "ngram_arguments", "default_config", "UPDATE_METHODS", "NvsmConfig", "NvsmBatch", "NvsmError", "lib",
+__all__ = ["Model", "Batch", "Corpus", "WindowBatch", "expand_windows", "NvsmCorpus", "NvsmWindowBatch", "PairBatch", "NvsmPairBatch", "NvsmMixture", "Queries", "Judgments", "self_information_weights", "NvsmQueries", "NvsmRankOptions", "NvsmJudgments", "NvsmNeighborQueries", "NvsmNeighborOptions", "NvsmLexicalOptions", "NvsmEnsembleOptions", "NvsmFeedbackOptions", "NvsmSdmOptions", "NvsmSweepOptions", "NvsmCvOptions", "NvsmNgramOptions", "NvsmTsneOptions", "NvsmTfidfOptions", "NvsmRerankOptions", "NvsmFoldOptions", "NvsmIndexOptions", "NvsmIndexInfo", "NvsmPositionsInfo", "grow_documents", "fold_summation", "tsne_arguments", "NvsmKmeansOptions", "kmeans_arguments", "cluster_agreement", "alpha_grid", "ngram_rows", "ngram_encode", "ngram_decode", "ngram_arguments", "default_config", "UPDATE_METHODS", "NvsmConfig", "NvsmBatch", "NvsmError", "lib",
            "library_path", "build_library", "device_count", "bind_host_thread", "abi_symbols"]

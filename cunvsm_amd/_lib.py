@@ -73,6 +73,10 @@ class NvsmIndexInfo(C.Structure):
     _fields_ = [("num_postings", C.c_int64), ("bytes", C.c_int64), ("max_df", C.c_int64), ("use", C.c_int32), ("reserved", C.c_int32 * 9)]
 
 
+class NvsmPositionsInfo(C.Structure):
+    _fields_ = [("num_positions", C.c_int64), ("bytes", C.c_int64), ("reserved", C.c_int32 * 12)]
+
+
 class NvsmPairBatch(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("weights", C.c_void_p), ("num_pairs", C.c_int64), ("on_device", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
@@ -445,6 +449,9 @@ def lib():
         "nvsm_corpus_index": (C.c_int, [vp, P(NvsmIndexOptions), P(NvsmIndexInfo)]),
         "nvsm_corpus_index_free": (C.c_int, [vp]),
         "nvsm_corpus_postings": (C.c_int, [vp, i64, i64, vp, vp, P(i64)]),
+        "nvsm_corpus_index_positions": (C.c_int, [vp, P(NvsmPositionsInfo)]),
+        "nvsm_corpus_index_positions_free": (C.c_int, [vp]),
+        "nvsm_corpus_positions": (C.c_int, [vp, i64, i64, i64, vp, P(i64)]),
         "nvsm_compute_cost_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp]),
         "nvsm_step_windows": (C.c_int, [vp, P(NvsmWindowBatch), vp, C.c_float, P(C.c_float)]),
         "nvsm_step_windows_deferred": (C.c_int, [vp, P(NvsmWindowBatch), vp, C.c_float, P(i64)]),

@@ -330,6 +330,18 @@ int nvsm_corpus_postings(nvsm_model* m, int64_t word_id, int64_t capacity, int64
     NVSM_REQUIRE(m); NVSM_REQUIRE(count);
     return guarded_on(m, [&] { m->impl.corpus_postings(word_id, capacity, doc_ids, tfs, count); });
 }
+int nvsm_corpus_index_positions(nvsm_model* m, nvsm_positions_info* info) {
+    NVSM_REQUIRE(m);
+    return guarded_on(m, [&] { m->impl.corpus_index_positions(info); });
+}
+int nvsm_corpus_index_positions_free(nvsm_model* m) {
+    NVSM_REQUIRE(m);
+    return guarded_on(m, [&] { m->impl.corpus_index_positions_free(); });
+}
+int nvsm_corpus_positions(nvsm_model* m, int64_t word_id, int64_t doc_id, int64_t capacity, int64_t* positions, int64_t* count) {
+    NVSM_REQUIRE(m); NVSM_REQUIRE(count);
+    return guarded_on(m, [&] { m->impl.corpus_positions(word_id, doc_id, capacity, positions, count); });
+}
 int nvsm_compute_cost_windows(nvsm_model* m,const nvsm_window_batch* windows, const int64_t* entity_ids) {
     NVSM_REQUIRE(m); NVSM_REQUIRE(windows);
     return guarded_on(m, [&] { m->impl.compute_cost_windows(*windows, entity_ids); });

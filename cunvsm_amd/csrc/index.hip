@@ -21,12 +21,15 @@
 // the later entries the same way, adds the terms in query order and stores scores[q][d − d0] once. No two lanes write one address
 // and nothing is accumulated in memory. A wave's lanes hold consecutive postings of one list, so their searches in another list
 // walk the same upper levels and part only near the leaves.
+// The positional layer (nvsm_corpus_index_positions) is the same build with the sorted positions kept:
+// index_positions_kernel writes every entry's document and its offset inside it, and the heads index_write_kernel finds are post_first.
 // The term expressions are lex_score_kernel's and tfidf_score_kernel's (lexical.hip), operation for operation: the same bits.
 #include <algorithm>
 #include <cstdint>
 #include "../../include/cunvsm_amd.h"
 #include "kernels.h"
 #include "device_utils.h"
+#include "index_search.h"
 
 namespace cunvsm {
 
@@ -34,16 +37,6 @@ namespace {
 
 constexpr int kIndexItems = 8;                                // consecutive entries per lane
 constexpr int kIndexTile = 256 * kIndexItems;                 // entries per workgroup
-
-// first index in [lo, hi) whose value is >= key; hi when there is none
-template <typename T, typename K>
-__device__ __forceinline__ int64_t index_lower_bound(const T* __restrict__ a, int64_t lo, int64_t hi, K key) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (static_cast<K>(a[mid]) < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // pos[i]: arena position -> its document: the last d with doc_offsets[d] <= position (empty documents hold nothing)
 __global__ __launch_bounds__(256) void index_docs_kernel(int* __restrict__ pos, int64_t n, const int64_t* __restrict__ doc_offsets, int64_t num_documents) {
@@ -56,6 +49,21 @@ __global__ __launch_bounds__(256) void index_docs_kernel(int* __restrict__ pos, 
             if (doc_offsets[mid] <= p) lo = mid + 1; else hi = mid;
         }
         pos[i] = static_cast<int>(lo - 1);
+    }
+}
+
+// the positional layer: pos[i] an arena position -> doc[i] its document (index_docs_kernel's search), pos[i] the offset inside it
+__global__ __launch_bounds__(256) void index_positions_kernel(int* __restrict__ pos, int* __restrict__ doc, int64_t n,
+                                                              const int64_t* __restrict__ doc_offsets, int64_t num_documents) {
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
+        const int64_t p = pos[i];
+        int64_t lo = 1, hi = num_documents;
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (doc_offsets[mid] <= p) lo = mid + 1; else hi = mid;
+        }
+        doc[i] = static_cast<int>(lo - 1);
+        pos[i] = static_cast<int>(p - doc_offsets[lo - 1]);
     }
 }
 
@@ -250,6 +258,19 @@ int64_t index_tiles(int64_t n) { return (n + kIndexTile - 1) / kIndexTile; }
 
 void launch_index_docs(int* pos, int64_t n, const int64_t* doc_offsets, int64_t num_documents, hipStream_t s) {
     if (n > 0) NVSM_LAUNCH(index_docs_kernel, dim3(index_grid(n)), dim3(256), 0, s, pos, n, doc_offsets, num_documents);
+}
+
+void launch_index_positions(int* pos, int* doc, int64_t n, const int64_t* doc_offsets, int64_t num_documents, hipStream_t s) {
+    if (n > 0) NVSM_LAUNCH(index_positions_kernel, dim3(index_grid(n)), dim3(256), 0, s, pos, doc, n, doc_offsets, num_documents);
+}
+
+void launch_index_fill(float* p, int64_t n, hipStream_t s) {
+    if (n > 0) NVSM_LAUNCH(index_fill_kernel, dim3(index_grid(n)), dim3(256), 0, s, p, n);
+}
+
+void launch_index_bounds(const int64_t* post_off, const int* post_doc, const int* terms, int n, int64_t d0, int S, int64_t* lo, int64_t* hi,
+                         hipStream_t s) {
+    if (n > 0) NVSM_LAUNCH(index_bounds_kernel, dim3((n + 255) / 256), dim3(256), 0, s, post_off, post_doc, terms, n, d0, S, lo, hi);
 }
 
 void launch_index_scan(const int* term, const int* doc, int64_t n, int* tile_sums, hipStream_t s) {

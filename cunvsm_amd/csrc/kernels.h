@@ -825,5 +825,31 @@ struct SdmScoreArgs {
 };
 void launch_sdm_score(const SdmScoreArgs& a, hipStream_t s);
 
+// ---- the positional layer of the index, and the SDM rounds served from it (index.hip, sdm.hip; include/cunvsm_amd.h
+// nvsm_corpus_index_positions) ----
+// Behind sort_pairs(keys = tokens, vals_in = nullptr): pos [n] the sorted entries' arena positions -> doc[i] their document, pos[i] the
+// offset inside it (position − doc_offsets[document]). One writer per element.
+void launch_index_positions(int* pos, int* doc, int64_t n, const int64_t* doc_offsets, int64_t num_documents, hipStream_t s);
+// what launch_postings_fill does before its scorer: p[0 .. n) = -inf; lo / hi [n]: the postings of terms[s] inside [d0, d0 + S)
+void launch_index_fill(float* p, int64_t n, hipStream_t s);
+void launch_index_bounds(const int64_t* post_off, const int* post_doc, const int* terms, int n, int64_t d0, int S, int64_t* lo, int64_t* hi,
+                         hipStream_t s);
+// The postings with positions: post_first [P + 1] a posting's first entry of pos [N], its in-document offsets, ascending.
+// pair_a / pair_b [num_pairs]: the slots of a pair's first and second term; terms [num_slots]: the round's terms by slot.
+struct SdmPostingsArgs {
+    const int64_t* post_off; const int* post_doc; const int* post_tf; const int* post_first; const int* pos;
+    const int* terms; const int* pair_a; const int* pair_b; int num_slots; int num_pairs; int window;
+};
+// launch_sdm_collect's sums from the postings: cf_o[p] += Σ_d od(pair p; d), cf_u[p] += Σ_d uw(pair p; d); both zeroed by the caller
+void launch_sdm_postings_collect(const SdmPostingsArgs& a, int64_t max_df, unsigned long long* cf_o, unsigned long long* cf_u, hipStream_t s);
+// launch_sdm_score's slab from the postings, the same bits. `score` as launch_sdm_score reads it (of score.count only doc_offsets);
+// entry_query / first [goff[0][Q]]: the query of a member of group 0, and 1 where it is the first of its slot in its query;
+// lo / hi [num_slots]: scratch, a term's postings inside the slab. max_df: the longest list among the round's terms.
+struct SdmPostingsScoreArgs {
+    SdmScoreArgs score; SdmPostingsArgs post;
+    const int* entry_query; const int* first; int num_entries; int64_t* lo; int64_t* hi;
+};
+void launch_sdm_postings_score(const SdmPostingsScoreArgs& a, int64_t max_df, hipStream_t s);
+
 
 }  // namespace cunvsm

@@ -312,6 +312,10 @@ class Model {
     void corpus_index(const nvsm_index_options& opt, nvsm_index_info* info);
     void corpus_index_free();
     void corpus_postings(int64_t word_id, int64_t capacity, int64_t* doc_ids, int32_t* tfs, int64_t* count);
+    // its positional layer (include/cunvsm_amd.h nvsm_corpus_index_positions; ranking.cpp)
+    void corpus_index_positions(nvsm_positions_info* info);
+    void corpus_index_positions_free();
+    void corpus_positions(int64_t word_id, int64_t doc_id, int64_t capacity, int64_t* positions, int64_t* count);
     std::string describe(int64_t batch) const;      // which kernel each product of a step takes at `batch` windows, table modes, switches off their defaults
 
  private:
@@ -576,6 +580,11 @@ class Model {
         DevBuf<int> post_doc, post_tf;
         std::vector<int64_t> host_post_off; // post_off on the host: df, and the bounds nvsm_corpus_postings copies between
         int64_t num_postings = 0, index_bytes = 0, max_df = 0;
+        // the positional layer of the index, made by nvsm_corpus_index_positions and dropped with the index:
+        // post_first [P + 1], a posting's first entry of pos [N] (at least one element), its in-document offsets, ascending
+        bool positional = false;
+        DevBuf<int> post_first, pos;
+        int64_t positions_bytes = 0;
     };
     Corpus* corpus_ = nullptr;
     DevBuf<uint32_t> in_refs_[2];               // host references, one per staging set
@@ -603,6 +612,7 @@ class Model {
         DevBuf<unsigned long long> sdm_cf;                            //          ... and the round's collection counts [2][kSdmPairs]
         DevBuf<int> post_query, post_first;                           // postings fill (indexed corpora only): an entry's query, first-of-its-term flag
         DevBuf<int64_t> post_lo, post_hi;                             //          ... and a term's postings inside the slab
+        DevBuf<int> sdm_pair_a, sdm_pair_b;                           // SDM from positional postings: a round's pairs as slots
         DevBuf<double> rm_acc, rm_sum;                                // relevance model: acc [round][num_words] and cnt likewise (zero between
         DevBuf<int> rm_cnt, rm_ids, rm_counts;                        //   rounds), Σω [round], a round's feedback lists [round][fb_docs]
         DevBuf<float> rm_scores;
@@ -646,6 +656,7 @@ class Model {
     void sdm_rounds(const nvsm_queries& q, const nvsm_lexical_options* lex, const nvsm_sdm_options& sdm, int64_t* doc_ids, float* scores,
                     int64_t* counts, uint64_t* ordered, uint64_t* unordered);
     void index_build(Corpus& c);            // the postings of the corpus and, where still empty, its cf and df (ranking.cpp; index.hip)
+    void positions_build(Corpus& c);        // the positional layer of an indexed corpus (ranking.cpp; index.hip)
     // one round of nvsm_rank over candidate lists that lie on the device as launch_rank_scan_candidates reads them
     void rank_candidates_round(const nvsm_queries& q, const nvsm_rank_options& opt, int64_t q0, const RankLayout& l, const int* cand,
                                const int64_t* cand_off, EvalArgs* ea, int64_t* doc_ids, float* scores, int64_t* counts);

@@ -60,6 +60,14 @@ bool index_auto_takes_postings(double work, int64_t num_documents, bool tfidf) {
     return work <= (tfidf ? kIndexAutoSearchesPerDocumentTfidf : kIndexAutoSearchesPerDocument) * static_cast<double>(num_documents);
 }
 
+// NVSM_INDEX_AUTO's rule for one SDM round over positional postings (DESIGN.md §26 "AUTO"): `work`, the entries the postings form
+// searches and merges, against the tokens the scan reads (both of its passes walk the whole arena whatever the queries are). The
+// constant comes from the cells of tools/bench_sdm_index.py (profiles/sdm_index_bench_fit.jsonl): the postings won every measured
+// cell, up to 79.8 entries per token (256 queries of five words on 2·10⁶ documents), so no losing cell bounds it from above; it
+// stands at the edge of what was measured, and a round beyond it — queries far longer than five words — keeps the scan.
+constexpr double kSdmAutoEntriesPerToken = 80.0;
+bool sdm_auto_takes_postings(double work, int64_t num_tokens) { return work <= kSdmAutoEntriesPerToken * static_cast<double>(num_tokens); }
+
 }  // namespace
 
 // ---- the layout of a round (DESIGN.md §9 "Dispatch by Q and k"): host arithmetic only -------------------------------------------
@@ -798,9 +806,107 @@ void Model::corpus_index_free() {
     rank_join();      // whatever is queued may still read the postings
     Corpus& c = *corpus_;
     c.post_off.release(); c.post_doc.release(); c.post_tf.release();
+    c.post_first.release(); c.pos.release();
     c.host_post_off.clear();
-    c.indexed = false; c.index_use = NVSM_INDEX_AUTO;
-    c.num_postings = c.index_bytes = c.max_df = 0;
+    c.indexed = c.positional = false; c.index_use = NVSM_INDEX_AUTO;
+    c.num_postings = c.index_bytes = c.max_df = c.positions_bytes = 0;
+}
+
+// ---- the positional layer of the index (include/cunvsm_amd.h nvsm_corpus_index_positions; kernels: index.hip) -------
+// index_build's sort once more, in a call of its own so that a plain nvsm_corpus_index keeps its scratch and its launches: the sorted
+// entries' arena positions ARE the layer once every one is taken relative to its document, and the heads of index_build's scan are
+// post_first. The scan's other outputs (post_doc, post_off, tok_off, rewritten with the values they hold already) go to scratch.
+void Model::positions_build(Corpus& c) {
+    const int64_t N = c.num_tokens, Dc = c.num_documents, V = cfg_.num_words, P = c.num_postings;
+    RankProf scope(prof, "index_positions", stream_);
+    c.post_first.alloc(static_cast<size_t>(P) + 1, true);      // (no token: post_first[0] = 0 = N)
+    c.pos.alloc(static_cast<size_t>(std::max<int64_t>(N, 1)), true);
+    if (N > 0) {
+        int bits = 1;
+        while (bits < 31 && (int64_t(1) << bits) < V) ++bits;
+        DevBuf<int> term, doc, sums, post_doc;
+        DevBuf<int64_t> post_off, tok;
+        term.alloc(static_cast<size_t>(N));
+        doc.alloc(static_cast<size_t>(N));
+        {
+            DevBuf<char> temp;
+            const size_t temp_bytes = sort_pairs_temp_bytes(N, bits);
+            temp.alloc(temp_bytes, true);
+            sort_pairs(temp.p, temp_bytes, nullptr, c.tokens.p, term.p, nullptr, c.pos.p, N, bits, nullptr, stream_);
+            launch_index_positions(c.pos.p, doc.p, N, c.offsets.p, Dc, stream_);
+            NVSM_HIP_CHECK(hipStreamSynchronize(stream_));      // (the sort's workspace goes before the scan's comes)
+        }
+        const int64_t tiles = index_tiles(N);
+        sums.alloc(static_cast<size_t>(tiles) + 1);
+        post_doc.alloc(static_cast<size_t>(P));
+        post_off.alloc(static_cast<size_t>(V) + 1);
+        tok.alloc(static_cast<size_t>(V) + 1);
+        launch_index_scan(term.p, doc.p, N, sums.p, stream_);
+        int total = 0;
+        NVSM_HIP_CHECK(hipMemcpyAsync(&total, sums.p + tiles, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+        if (total != P) throw Error(NVSM_ERR_STATE,"the positional layer counted other postings than the index holds");
+        launch_index_write(term.p, doc.p, N, V, sums.p, c.post_first.p, post_doc.p, post_off.p, tok.p, stream_);
+        NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    c.positions_bytes = static_cast<int64_t>((c.post_first.n + c.pos.n) * sizeof(int));
+    c.positional = true;
+}
+
+void Model::corpus_index_positions(nvsm_positions_info* info) {
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the positional layer needs a corpus: call nvsm_corpus_upload first");
+    if (cfg_.world_size > 1) throw Error(NVSM_ERR_UNSUPPORTED, "the inverted index is not implemented under data parallelism (world_size > 1)");
+    Corpus& c = *corpus_;
+    if (!c.indexed) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the positional layer needs an inverted index: call nvsm_corpus_index first");
+    if (!c.positional) {
+        rank_join();
+        try {
+            positions_build(c);
+        } catch (...) {      // a failed build leaves the index without the layer
+            c.post_first.release(); c.pos.release();
+            throw;
+        }
+    }
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->num_positions = c.num_tokens; info->bytes = c.positions_bytes;
+    }
+}
+
+void Model::corpus_index_positions_free() {
+    if (!corpus_ || !corpus_->positional) return;
+    rank_join();      // whatever is queued may still read the layer
+    Corpus& c = *corpus_;
+    c.post_first.release(); c.pos.release();
+    c.positional = false;
+    c.positions_bytes = 0;
+}
+
+void Model::corpus_positions(int64_t word_id, int64_t doc_id, int64_t capacity, int64_t* positions, int64_t* count) {
+    *count = 0;
+    if (!corpus_) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the positional layer needs a corpus: call nvsm_corpus_upload first");
+    if (!corpus_->indexed) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the corpus has no inverted index: call nvsm_corpus_index first");
+    if (!corpus_->positional) throw Error(NVSM_ERR_INVALID_ARGUMENT, "the index has no positional layer: call nvsm_corpus_index_positions first");
+    if (word_id < 0 || word_id >= cfg_.num_words) throw Error(NVSM_ERR_INVALID_ARGUMENT, "word_id is outside [0, num_words)");
+    const Corpus& c = *corpus_;
+    if (doc_id < 0 || doc_id >= c.num_documents) throw Error(NVSM_ERR_INVALID_ARGUMENT, "doc_id is outside [0, num_documents of the corpus)");
+    const int64_t lo = c.host_post_off[static_cast<size_t>(word_id)], n = c.host_post_off[static_cast<size_t>(word_id) + 1] - lo;
+    if (n == 0) return;
+    NVSM_HIP_CHECK(hipSetDevice(cfg_.device));
+    std::vector<int> docs(static_cast<size_t>(n));
+    NVSM_HIP_CHECK(hipMemcpy(docs.data(), c.post_doc.p + lo, static_cast<size_t>(n) * sizeof(int), hipMemcpyDeviceToHost));
+    const auto it = std::lower_bound(docs.begin(), docs.end(), static_cast<int>(doc_id));
+    if (it == docs.end() || *it != doc_id) return;
+    const int64_t p = lo + (it - docs.begin());
+    int first[2];
+    NVSM_HIP_CHECK(hipMemcpy(first, c.post_first.p + p, sizeof(first), hipMemcpyDeviceToHost));
+    const int64_t tf = first[1] - first[0];
+    *count = tf;
+    if (capacity < tf) throw Error(NVSM_ERR_INVALID_ARGUMENT, "capacity is below the word's count in the document (returned in count)");
+    if (!positions) throw Error(NVSM_ERR_INVALID_ARGUMENT, "null argument: positions");
+    std::vector<int> run(static_cast<size_t>(tf));
+    NVSM_HIP_CHECK(hipMemcpy(run.data(), c.pos.p + first[0], static_cast<size_t>(tf) * sizeof(int), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < tf; ++i) positions[i] = run[static_cast<size_t>(i)];
 }
 
 void Model::corpus_postings(int64_t word_id, int64_t capacity, int64_t* doc_ids, int32_t* tfs, int64_t* count) {
@@ -1283,6 +1389,7 @@ void Model::sdm_rounds(const nvsm_queries& q, const nvsm_lexical_options* lex, c
     std::vector<double> c0, base, coef;
     std::vector<unsigned long long> cf(2 * static_cast<size_t>(kSdmPairs));
     int64_t pairs_out = 0;                               // pairs of the queries before this round, in the layout of ordered / unordered
+    const bool layered = c.indexed && c.positional && c.index_use != NVSM_INDEX_NEVER;      // the rounds may be served from the postings
 
     for (int64_t q0 = 0; q0 < Q;) {
         RankLayout l{};
@@ -1381,11 +1488,55 @@ void Model::sdm_rounds(const nvsm_queries& q, const nvsm_lexical_options* lex, c
         a.count.tokens = c.tokens.p; a.count.doc_offsets = c.offsets.p; a.count.slot_of = r.lex_slot_of.p;
         a.count.ent_off = r.sdm_ent_off.p; a.count.ent_other = r.sdm_ent_other.p; a.count.ent_pair = r.sdm_ent_pair.p;
         a.count.num_slots = nslots; a.count.num_pairs = npairs; a.count.window = sdm.window;
+        // both phases of this round: the arena scan, or the positional postings of the round's terms. Both give the
+        // same bits, so the choice — the caller's, or under NVSM_INDEX_AUTO sdm_auto_takes_postings' — is invisible in the results
+        bool postings = layered && c.index_use == NVSM_INDEX_ALWAYS;
+        int64_t round_max_df = 0;
+        SdmPostingsScoreArgs pa{};
+        if (layered) {
+            // the fill's searched and merged entries: every pair merges at most the occurrences of its two terms, and every posting of
+            // a query's distinct terms searches once per member of that query
+            double work = 0.0;
+            for (int p = 0; p < npairs; ++p)
+                work += static_cast<double>(c.cf[static_cast<size_t>(terms[static_cast<size_t>(pair_a[p])])] + c.cf[static_cast<size_t>(terms[static_cast<size_t>(pair_b[p])])]);
+            std::vector<char> seen(static_cast<size_t>(std::max(nslots, 1)));
+            for (int64_t i = 0; i < qn; ++i) {
+                std::fill(seen.begin(), seen.end(), 0);
+                double query_df = 0.0, members = 0.0;
+                for (int cell = qfirst[static_cast<size_t>(i)]; cell < qfirst[static_cast<size_t>(i) + 1]; ++cell) {
+                    const int s = qslot[static_cast<size_t>(cell)];
+                    if (s < 0) continue;
+                    members += qpair[static_cast<size_t>(cell)] >= 0 ? 3.0 : 1.0;      // the term, and its pair in O and in U
+                    if (!seen[static_cast<size_t>(s)]) { seen[static_cast<size_t>(s)] = 1; query_df += static_cast<double>(c.df[static_cast<size_t>(terms[static_cast<size_t>(s)])]); }
+                }
+                work += query_df * members;
+            }
+            for (int s = 0; s < nslots; ++s) round_max_df = std::max(round_max_df, c.df[static_cast<size_t>(terms[static_cast<size_t>(s)])]);
+            if (c.index_use == NVSM_INDEX_AUTO) postings = sdm_auto_takes_postings(work, N);
+        }
+        if (postings) {
+            grow(r.sdm_pair_a, static_cast<size_t>(kSdmPairs));
+            grow(r.sdm_pair_b, static_cast<size_t>(kSdmPairs));
+            if (npairs > 0) {
+                NVSM_HIP_CHECK(hipMemcpy(r.sdm_pair_a.p, pair_a.data(), static_cast<size_t>(npairs) * sizeof(int), hipMemcpyHostToDevice));
+                NVSM_HIP_CHECK(hipMemcpy(r.sdm_pair_b.p, pair_b.data(), static_cast<size_t>(npairs) * sizeof(int), hipMemcpyHostToDevice));
+            }
+            pa.post.post_off = c.post_off.p; pa.post.post_doc = c.post_doc.p; pa.post.post_tf = c.post_tf.p;
+            pa.post.post_first = c.post_first.p; pa.post.pos = c.pos.p;
+            pa.post.terms = r.lex_terms.p; pa.post.pair_a = r.sdm_pair_a.p; pa.post.pair_b = r.sdm_pair_b.p;
+            pa.post.num_slots = nslots; pa.post.num_pairs = npairs; pa.post.window = sdm.window;
+        }
         std::fill(cf.begin(), cf.end(), 0ull);
-        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);
+        if (!postings) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, true, stream_);
         if (npairs > 0) {
             NVSM_HIP_CHECK(hipMemsetAsync(r.sdm_cf.p, 0, cf.size() * sizeof(unsigned long long), stream_));
-            { RankProf scope(prof, "sdm_collect", stream_); launch_sdm_collect(a.count, Dc, r.sdm_cf.p, r.sdm_cf.p + kSdmPairs, stream_); }
+            if (postings) {
+                RankProf scope(prof, "sdm_postings_collect", stream_);
+                launch_sdm_postings_collect(pa.post, round_max_df, r.sdm_cf.p, r.sdm_cf.p + kSdmPairs, stream_);
+            } else {
+                RankProf scope(prof, "sdm_collect", stream_);
+                launch_sdm_collect(a.count, Dc, r.sdm_cf.p, r.sdm_cf.p + kSdmPairs, stream_);
+            }
             NVSM_HIP_CHECK(hipMemcpyAsync(cf.data(), r.sdm_cf.p, cf.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
             NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
         }
@@ -1402,7 +1553,7 @@ void Model::sdm_rounds(const nvsm_queries& q, const nvsm_lexical_options* lex, c
             }
         }
         if (!lex) {
-            launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
+            if (!postings) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
             NVSM_HIP_CHECK(hipStreamSynchronize(stream_));
             q0 += qn;
             continue;
@@ -1460,12 +1611,38 @@ void Model::sdm_rounds(const nvsm_queries& q, const nvsm_lexical_options* lex, c
         a.Q = static_cast<int>(qn); a.method = lex->method; a.param = param;
         a.goff = r.sdm_goff.p; a.index = r.sdm_index.p; a.c0 = r.sdm_c0.p; a.base = r.sdm_base.p; a.coef = r.sdm_coef.p;
         a.ld = l.ld;
+        if (postings) {      // every member of group 0: its query, and whether it is the first of its slot there (index.hip's ownership)
+            const size_t nent = static_cast<size_t>(goff[static_cast<size_t>(qn)]);
+            std::vector<int> entry_query(nent), entry_first(nent);
+            for (int64_t i = 0; i < qn; ++i)
+                for (int j = goff[static_cast<size_t>(i)]; j < goff[static_cast<size_t>(i) + 1]; ++j) {
+                    entry_query[static_cast<size_t>(j)] = static_cast<int>(i);
+                    entry_first[static_cast<size_t>(j)] =
+                        std::find(index.begin() + goff[static_cast<size_t>(i)], index.begin() + j, index[static_cast<size_t>(j)]) == index.begin() + j ? 1 : 0;
+                }
+            grow(r.post_query, std::max<size_t>(nent, 1));
+            grow(r.post_first, std::max<size_t>(nent, 1));
+            grow(r.post_lo, static_cast<size_t>(kLexSlots));
+            grow(r.post_hi, static_cast<size_t>(kLexSlots));
+            if (nent > 0) {
+                NVSM_HIP_CHECK(hipMemcpy(r.post_query.p, entry_query.data(), nent * sizeof(int), hipMemcpyHostToDevice));
+                NVSM_HIP_CHECK(hipMemcpy(r.post_first.p, entry_first.data(), nent * sizeof(int), hipMemcpyHostToDevice));
+            }
+            pa.entry_query = r.post_query.p; pa.first = r.post_first.p; pa.num_entries = static_cast<int>(nent);
+            pa.lo = r.post_lo.p; pa.hi = r.post_hi.p;
+        }
         round_slabs(l, Dc, k, [&](int64_t d0, int Ss) {
             a.scores = r.scores.p; a.d0 = d0; a.S = Ss;
+            if (postings) {
+                pa.score = a;
+                RankProf scope(prof, "sdm_postings_score", stream_);
+                launch_sdm_postings_score(pa, round_max_df, stream_);
+                return;
+            }
             RankProf scope(prof, "sdm_score", stream_);
             launch_sdm_score(a, stream_);
         });
-        launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
+        if (!postings) launch_lex_set_slots(r.lex_slot_of.p, r.lex_terms.p, nslots, false, stream_);
         round_sort(l, [&] { launch_lex_write(r.keys.p, l.npad, static_cast<int>(qn), k, l.n_keys, r.out_ids.p, r.out_scores.p, r.out_counts.p, stream_); });
         round_results(q0, qn, k, doc_ids, scores, counts);
         q0 += qn;

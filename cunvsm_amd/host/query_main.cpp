@@ -49,7 +49,7 @@ namespace {
 std::string FLAGS_index, FLAGS_topics, FLAGS_stopwords, FLAGS_top_k, FLAGS_qrels, FLAGS_cutoffs, FLAGS_qlm, FLAGS_qlm_param, FLAGS_qlm_run_out,
     FLAGS_ensemble_alpha, FLAGS_score_normalizer, FLAGS_ensemble_qrel, FLAGS_ensemble_measure, FLAGS_rerank, FLAGS_tfidf_run_out, FLAGS_lexical_index, FLAGS_sdm_weights;
 bool FLAGS_linear, FLAGS_self_information, FLAGS_strict, FLAGS_per_query, FLAGS_logtostderr, FLAGS_rerank_exact_matching_documents,
-    FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf, FLAGS_qlm_sdm;
+    FLAGS_l2norm_phrase, FLAGS_help, FLAGS_qlm_prf, FLAGS_qlm_sdm, FLAGS_lexical_positions;
 double FLAGS_bias_coefficient, FLAGS_qlm_fb_orig_weight, FLAGS_alpha_stepsize;
 int64_t FLAGS_num_queries, FLAGS_device, FLAGS_v, FLAGS_num_workers, FLAGS_qlm_fb_docs, FLAGS_qlm_fb_terms, FLAGS_num_folds, FLAGS_ensemble_seed,
     FLAGS_rerank_depth, FLAGS_sdm_window;
@@ -120,6 +120,9 @@ void define_flags(Flags* f) {
     f->define_string("lexical_index", &FLAGS_lexical_index, "", "auto | always | never, with --qlm or --rerank: build the inverted index of the uploaded "
                      "collection and let the lexical rankings fill their scores from its postings (always), from the token arena (never) or "
                      "whichever is cheaper per round (auto). Every run file is byte for byte the one written without the flag.");
+    f->define_bool("lexical_positions", &FLAGS_lexical_positions, false, "With --lexical_index and --qlm_sdm: build the positional layer of the inverted "
+                   "index behind it, so that the dependence model's rounds may be served from the postings. Every run file is byte for byte the "
+                   "one written without the flag.");
     f->define_bool("help", &FLAGS_help, false, "Print the options and exit.");
     f->define_bool("logtostderr", &FLAGS_logtostderr, true, "Log to stderr (there is no log-file sink).");
     f->define_int64("v", &FLAGS_v, 0, "Verbosity of VLOG messages.");
@@ -331,6 +334,10 @@ int run(int argc, char** argv) {
         else if (FLAGS_lexical_index == "never") index_opt.use = NVSM_INDEX_NEVER;
         else NVSM_LOG(FATAL) << "--lexical_index: '" << FLAGS_lexical_index << "' is none of auto, always, never.";
     }
+    if (FLAGS_lexical_positions) {      // the positional layer of that index
+        NVSM_CHECK(with_index) << "--lexical_positions needs --lexical_index.";
+        NVSM_CHECK(with_sdm) << "--lexical_positions needs --qlm_sdm: only the dependence model reads positions.";
+    }
 
     // ---- --top_k (py/query.py:118-139)
     int64_t top_k = 1000;
@@ -427,6 +434,11 @@ int run(int argc, char** argv) {
             nvsm_index_info info;
             NVSM_CALL(nvsm_corpus_index(model, &index_opt, &info));
             NVSM_LOG(INFO) << "<inverted index of " << info.num_postings << " postings, " << info.bytes << " bytes, longest list " << info.max_df << ">";
+            if (FLAGS_lexical_positions) {
+                nvsm_positions_info layer;
+                NVSM_CALL(nvsm_corpus_index_positions(model, &layer));
+                NVSM_LOG(INFO) << "<positional layer of " << layer.num_positions << " positions, " << layer.bytes << " bytes>";
+            }
         }
     }
 

@@ -1106,10 +1106,11 @@ class Model:
         check(lib().nvsm_corpus_upload(self._h, C.byref(st)))
 
     # -- the inverted index of the uploaded corpus ------------------------------------------------
-    def index_corpus(self, use="auto"):
+    def index_corpus(self, use="auto", positions=False):
         """nvsm_corpus_index: builds the postings of the uploaded corpus in HBM (once; a later call only sets `use`) and says
         which fill the lexical rounds take: "never" the arena scan, "always" the postings, "auto" chosen per round. Results do
-        not depend on it. Returns {"num_postings", "bytes", "max_df", "use"}."""
+        not depend on it. Returns {"num_postings", "bytes", "max_df", "use"}; with positions=True the positional layer is built
+        behind the index (index_positions) and its dictionary is returned under "positions"."""
         if isinstance(use, str):
             if use not in INDEX_USES:
                 raise ValueError("unknown index use %r (one of %s)" % (use, sorted(INDEX_USES)))
@@ -1120,7 +1121,32 @@ class Model:
         info = _lib.NvsmIndexInfo()
         check(lib().nvsm_corpus_index(self._h, C.byref(opt), C.byref(info)))
         names = {v: k for k, v in INDEX_USES.items()}
-        return {"num_postings": info.num_postings, "bytes": info.bytes, "max_df": info.max_df, "use": names[info.use]}
+        out = {"num_postings": info.num_postings, "bytes": info.bytes, "max_df": info.max_df, "use": names[info.use]}
+        if positions:
+            out["positions"] = self.index_positions()
+        return out
+
+    def index_positions(self):
+        """nvsm_corpus_index_positions: builds the positional layer of the index (once): every posting's in-document offsets.
+        With it the SDM rounds may be served from the postings (the same bits). Returns {"num_positions", "bytes"}."""
+        info = _lib.NvsmPositionsInfo()
+        check(lib().nvsm_corpus_index_positions(self._h, C.byref(info)))
+        return {"num_positions": info.num_positions, "bytes": info.bytes}
+
+    def positions(self, word, document):
+        """nvsm_corpus_positions: the 0-based offsets of `word` inside `document`, ascending, int64 [tf] (empty: not held)."""
+        n = C.c_int64()
+        st = lib().nvsm_corpus_positions(self._h, int(word), int(document), 0, None, C.byref(n))
+        if n.value == 0:
+            check(st)      # an empty run is a success; a refusal (no layer, an id out of range) is raised
+        out = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            check(lib().nvsm_corpus_positions(self._h, int(word), int(document), n.value, out.ctypes.data, C.byref(n)))
+        return out
+
+    def drop_positions(self):
+        """nvsm_corpus_index_positions_free: frees the positional layer, the index stays (no layer: nothing happens)."""
+        check(lib().nvsm_corpus_index_positions_free(self._h))
 
     def postings(self, word):
         """nvsm_corpus_postings: (doc ids int64 [df], tfs int32 [df]) of one word, documents ascending."""

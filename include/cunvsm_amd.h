@@ -669,7 +669,8 @@ int nvsm_rank_ensemble_prf(nvsm_model* m, const nvsm_queries* queries, const nvs
  * nvsm_sdm_pair_counts writes cf_o and cf_u of every pair (t_j, t_{j+1}) of every query, laid out [Σ_q max(L_q − 1, 0)] in query order:
  * exact integers, 0 for a pair that holds a term nobody holds. Only sdm->window is looked at beyond the refusals.
  * nvsm_rank_ensemble_sdm is nvsm_rank_ensemble with list B taken from nvsm_sdm_rank; everything behind list B is the same code path.
- * The postings of nvsm_corpus_index hold counts and no positions: these calls always scan the arena, whatever nvsm_corpus_index_use says.
+ * The postings of nvsm_corpus_index hold counts and no positions: without the positional layer (nvsm_corpus_index_positions, below)
+ * these calls scan the arena whatever `use` says; with it their rounds may be served from the postings, the same bits either way.
  * All three calls are synchronous, touch no parameter, optimiser state, RNG state or lazy bookkeeping, allocate on first use and leave
  * nvsm_describe unchanged. NVSM_ERR_INVALID_ARGUMENT before anything runs, each with a sentence: what nvsm_lexical_rank refuses (and
  * nvsm_rank_ensemble, for the fused call); null arguments, by name; a weight that is negative or not finite, or all three weights
@@ -863,6 +864,38 @@ int nvsm_corpus_index_free(nvsm_model* m);
 /* one word's list to the host: *count = df(word_id), always written; doc_ids / tfs [capacity] receive the list when
  * capacity >= *count, else nothing else is written and the call returns NVSM_ERR_INVALID_ARGUMENT */
 int nvsm_corpus_postings(nvsm_model* m, int64_t word_id, int64_t capacity, int64_t* doc_ids, int32_t* tfs, int64_t* count);
+
+/*
+ * POSITIONAL LAYER OF THE INVERTED INDEX (nvsm_corpus_index_positions) — DESIGN.md §26
+ *
+ * Beside every posting (word, document) of nvsm_corpus_index, the word's positions in that document: in-document offsets, 0-based
+ * from the document's first token, ascending, tf of them; N int32 in all plus a posting's first entry (P + 1 int32). It replaces no
+ * reference function: the reference has no program text for an index; the contract is this one. With the layer, an index and a
+ * `use` other than NVSM_INDEX_NEVER, the rounds of nvsm_sdm_rank, nvsm_sdm_pair_counts and list B of nvsm_rank_ensemble_sdm may count
+ * their pairs and fill their slabs from the postings of the query words instead of scanning the arena; both forms return THE SAME
+ * BITS (NVSM_INDEX_ALWAYS: the postings in every such round; NVSM_INDEX_AUTO: a host rule per round).
+ * nvsm_corpus_index_positions needs an index, is synchronous, runs behind everything queued and touches no parameter, optimiser
+ * state, RNG state or lazy bookkeeping. On a corpus that has the layer already it only refills `info`. The layout is a function of
+ * the corpus alone: a second build gives the same bytes. nvsm_corpus_index_free and nvsm_corpus_upload (a new corpus or NULL) drop
+ * the layer with the index; nvsm_corpus_index_positions_free drops the layer alone. nvsm_index_info and nvsm_describe are unchanged
+ * by it, and a handle that never calls it allocates and launches exactly what it did before.
+ * NVSM_ERR_INVALID_ARGUMENT, each with a sentence, the handle staying usable: a null handle or `count`; no corpus; no index; no
+ * layer (nvsm_corpus_positions); a word id outside [0, num_words); a document id outside [0, num_documents).
+ * NVSM_ERR_UNSUPPORTED: world_size > 1.
+ */
+typedef struct {
+    int64_t num_positions;        /* N: one per token of the corpus */
+    int64_t bytes;                /* HBM the layer holds beyond nvsm_index_info.bytes */
+    int32_t reserved[12];
+} nvsm_positions_info;
+/* info may be NULL */
+int nvsm_corpus_index_positions(nvsm_model* m, nvsm_positions_info* info);
+/* frees the layer (the index stays); no layer: success */
+int nvsm_corpus_index_positions_free(nvsm_model* m);
+/* the in-document offsets of word_id in doc_id to the host: *count = tf, 0 when the document does not hold the word, always
+ * written; positions [capacity] receives them when capacity >= *count, else nothing else is written and the call returns
+ * NVSM_ERR_INVALID_ARGUMENT */
+int nvsm_corpus_positions(nvsm_model* m, int64_t word_id, int64_t doc_id, int64_t capacity, int64_t* positions, int64_t* count);
 
 /*
  * Nearest-neighbour search in word, projected-word and document space — the three other things the reference's query

@@ -301,6 +301,23 @@ class Model {
         check(nvsm_corpus_postings(h_, word_id, n, p.doc_ids.data(), p.tfs.data(), &n));
         return p;
     }
+    // the positional layer of the index (cunvsm_amd.h nvsm_corpus_index_positions): built once behind index_corpus(); with it the
+    // SDM rankings may be served from the postings, the same bits
+    nvsm_positions_info index_positions() {
+        nvsm_positions_info info;
+        check(nvsm_corpus_index_positions(h_, &info));
+        return info;
+    }
+    void drop_positions() { check(nvsm_corpus_index_positions_free(h_)); }
+    std::vector<int64_t> positions(int64_t word_id, int64_t doc_id) {      // the word's offsets inside the document, ascending
+        std::vector<int64_t> p;
+        int64_t n = 0;
+        const int st = nvsm_corpus_positions(h_, word_id, doc_id, 0, nullptr, &n);
+        if (n == 0) { check(st); return p; }      // (an empty run is a success; a refusal leaves the count 0)
+        p.resize(static_cast<size_t>(n));
+        check(nvsm_corpus_positions(h_, word_id, doc_id, n, p.data(), &n));
+        return p;
+    }
     // nvsm_rerank: rank() over the candidates the first stage retrieves at top_k = rr.depth, handed over on the device. judgments
     // null: no metrics (width 0).
     Evaluation rerank(const std::vector<int64_t>& word_ids, const std::vector<int64_t>& offsets, const nvsm_rank_options& opt,
